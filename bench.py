@@ -7,8 +7,15 @@ north-star workload of BASELINE.md section 4 ("NS"): synthetic jittered HEX8 46^
 elements, 512^3 grid (N_max = 505), rho_t = 0.5.  Inputs are resident in HBM before the
 timed region; the output SDF stays in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 512] [--mesh 46]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 512] [--mesh 46] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, and the
+stage times, work counts and roofline figures derived from the timed steps themselves).  --full adds what takes work
+of its own: the host-pointer end-to-end leg (N = 1), the CPU oracle baseline and the `max|err| vs ref` check below.
+--dump-outputs DIR writes the volume of the last timed step as float64 samples: DIR/sdf_planes.npy (every
+`stride`-th Z plane in full, at most 32 MB) and DIR/sdf_sample.npy (voxels at sorted indices drawn with
+numpy.random.default_rng(DUMP_SEED) over the flat x-fastest volume, 2^21 of them).
 
 With N > 1 the fixed 512^3 grid is partitioned along Z (one rank per GPU; default: interleaved
 4-plane tile layers, balanced) and stitched over RCCL/xGMI so that every rank holds the whole volume
@@ -16,7 +23,7 @@ With N > 1 the fixed 512^3 grid is partitioned along Z (one rank per GPU; defaul
 (one padded all_gather_into_tensor of counts + tile payloads + ids per step; --stitch dense
 gathers the full Float64 volume instead).
 
-At N = 1 rank 0 also times the CPU oracle ("cpu_baseline", kind "port") on a plane sample of the same workload:
+With --full, at N = 1 rank 0 also times the CPU oracle ("cpu_baseline", kind "port") on a plane sample of the same workload:
 up to 16 single-thread worker processes, worker w on the Z planes k % --cpu-stride == w (about 25 s of CPU work);
 --check compares worker 0's planes with the GPU result bit for bit.
 """
@@ -45,6 +52,32 @@ ALG_BYTES_PER_VOXEL = 8.0      # one Float64 store per voxel; +
 FP64_VALU_PEAK_TFLOPS = 78.6   # MI355X FP64 vector peak (256 CUs x 4 SIMDs x 16 lanes x 2 FLOP x 2.4 GHz)
 DOMINANT_KERNEL = {"HEX8": "iso_project_hex_pl_kernel", "TET4": "iso_project_kernel"}
 PROFILE_ROUND = "r04"          # profiles/<round>_traffic.json, <round>_valu_counters.json (tools/collect_traffic.py)
+DUMP_SEED = 20241015           # --dump-outputs: the voxel sample is the same for every build and run of a workload
+DUMP_SAMPLE = 1 << 21          # sampled voxels (16 MB of float64)
+DUMP_PLANES_BYTES = 32 << 20   # full Z planes, at most this many bytes
+
+
+def dump_outputs(vol, out_dir):
+    """write the stitched (nz, ny, nx) float64 volume of the last timed step as two fixed samples (whole volume > 64 MB):
+    every stride-th Z plane (contiguous surface band; k % stride == 0 are all first planes of a 4-plane tile layer) and
+    seeded scattered voxels (every plane and tile position).  Returns {name: shape}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    nz, ny, nx = vol.shape
+    row_bytes = nx * vol.element_size()
+    n_planes = max(1, min(nz, DUMP_PLANES_BYTES // (ny * row_bytes)))
+    stride = -(-nz // n_planes)                               # ceil: at most n_planes planes
+    rows = min(ny, max(1, DUMP_PLANES_BYTES // row_bytes))    # (a single plane over the budget: its first rows)
+    planes = vol[::stride, :rows].cpu().numpy()
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.integers(0, vol.numel(), size=min(DUMP_SAMPLE, vol.numel()), dtype=np.int64))
+    sample = vol.reshape(-1)[torch.from_numpy(idx).to(vol.device)].cpu().numpy()
+    res = {}
+    for name, a in (("sdf_planes", planes), ("sdf_sample", sample)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        res[name] = list(a.shape)
+    res["plane_stride"] = stride
+    return res
 
 
 def load_committed_profile(kernel):
@@ -238,9 +271,13 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline processes (0: host cores available, at most 16)")
     ap.add_argument("--cpu-worker", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-save", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle leg (and with it the check)")
-    ap.add_argument("--check", action="store_true", help="(kept for compatibility: the check runs whenever the oracle planes exist)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-pointer end-to-end leg (r2s_sdf: H2D + kernels + D2H)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the host-pointer end-to-end leg, the CPU oracle baseline and the check against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write samples of the last timed step's volume to DIR/*.npy (float64, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle leg (and with it the check)")
+    ap.add_argument("--check", action="store_true", help="(kept for compatibility: with --full the check runs whenever the oracle planes exist)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-pointer end-to-end leg (r2s_sdf: H2D + kernels + D2H)")
     ap.add_argument("--no-build", action="store_true",
                     help="load the built library as it is and exit non-zero when it is missing or stale (runs under "
                          "rocprofv3 must not spawn make / hipcc: the profiler's preloaded library has initialised the GPU)")
@@ -250,6 +287,8 @@ def main():
                     help="N > 1: all-gather only the non-sentinel 4x4x4 tiles (sparse, interleaved partition) "
                          "or the whole Float64 volume (dense)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not args.cpu_stride:
         args.cpu_stride = {"ns": 32, "tet5": 64, "chapadlo256": 16}[args.workload]
     if args.cpu_worker is not None:
@@ -335,6 +374,7 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = ngp / (elapsed / args.steps) / 1e6
+    dumped = dump_outputs(sg.volume(), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         sts = [s for s in stats_acc if s]
@@ -394,7 +434,9 @@ def main():
                             if avg["ms_fill"] > 0 else None},
             "work": {k: int(st0[k]) for k in ("n_items", "n_band_entries", "n_sign_entries", "n_tiles", "n_active_tiles", "n_active_sign_tiles")},
         }
-        if world == 1 and not args.no_e2e:
+        if dumped:
+            out["outputs"] = {"dir": args.dump_outputs, "dtype": "float64", "seed": DUMP_SEED, **dumped}
+        if args.full and world == 1 and not args.no_e2e:
             out["e2e"] = e2e_leg(pkg, X, IEN, rho_n, rho_t, grid, dev_index, sg)
             # SURVEY 8(d)'s contract figure (H2D of the mesh + kernels + D2H of the volume) beside `value` (kernels only,
             # inputs and output resident in HBM, steady state with the sizes of the previous identical call)
@@ -405,7 +447,7 @@ def main():
                                  "r2s_sdf on host pointers into an ordinary (pageable) array - what the Julia binding allocates by "
                                  "default - PCIe-inclusive (SURVEY 8(d)), MEDIAN of 8 calls (e2e_Mvoxels_per_s_best: the fastest; "
                                  "e2e.*.host_phases_ms_*: where a call's time went); e2e.rho2sdf_default_options = the whole rho2sdf()")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             threads = args.cpu_threads or min(16, len(os.sched_getaffinity(0)))
             cb, ref = cpu_baseline(args, threads)
             if world == 1:

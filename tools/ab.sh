@@ -26,12 +26,13 @@ case $MODE in
           bench_line "$v" "R2S_LIB_OVERRIDE=$lib" ${BENCH_ARGS:-}
           R2S_LIB_OVERRIDE=$lib WORLDS=8 timeout -k 10 200 python tools/rank_share.py 2>> gpurun_out/ab.err | tail -1 | cut -c1-220
         done; done ;;
-  e2e)  for v in "$@"; do
-          env $v R2S_HOST_TIMING=1 timeout -k 10 300 python bench.py --no-build --no-cpu-baseline --steps 5 > gpurun_out/b.json 2> gpurun_out/b.err \
-            || { echo "$v failed"; tail -5 gpurun_out/b.err; exit 1; }
-          echo "== $v"; grep -a "r2s host" gpurun_out/b.err | tail -2 | cut -c1-200
+  e2e)  T=$(mktemp -d); trap 'rm -rf "$T"' EXIT
+        for v in "$@"; do
+          env $v R2S_HOST_TIMING=1 timeout -k 10 300 python bench.py --no-build --full --no-cpu-baseline --steps 5 > "$T/b.json" 2> "$T/b.err" \
+            || { echo "$v failed"; tail -5 "$T/b.err"; exit 1; }
+          echo "== $v"; grep -a "r2s host" "$T/b.err" | tail -2 | cut -c1-200
           python -c "
-import json; d=json.load(open('gpurun_out/b.json'))['e2e']
+import json; d=json.load(open('$T/b.json'))['e2e']
 for k in ('pageable', 'pinned'): print(k, '%.2f ms best, %.2f median' % (d[k]['ms_per_call'], d[k]['ms_per_call_median']), d[k]['host_phases_ms_median'])
 print(d['rho2sdf_default_options']['stages_ms'])"
         done ;;

@@ -14,9 +14,9 @@ step() {   # label, command...: stop at the first failure (after a GPU step time
   "$@" || { echo "$label failed (rc $?)"; tail -5 $O/bench.err 2>/dev/null; exit 1; }
   echo "$label done"
 }
-step bench        bash -c "timeout -k 10 600 python bench.py > $O/${TAG}_bench_driver_style.json 2> $O/bench.err"
-step chapadlo256  bash -c "timeout -k 10 300 python bench.py --no-build --workload chapadlo256 --no-e2e > $O/${TAG}_bench_chapadlo256.json 2>> $O/bench.err"
-step tet5         bash -c "timeout -k 10 300 python bench.py --no-build --workload tet5 --no-e2e > $O/${TAG}_bench_tet5.json 2>> $O/bench.err"
+step bench        bash -c "timeout -k 10 600 python bench.py --full > $O/${TAG}_bench_driver_style.json 2> $O/bench.err"
+step chapadlo256  bash -c "timeout -k 10 300 python bench.py --no-build --full --workload chapadlo256 --no-e2e > $O/${TAG}_bench_chapadlo256.json 2>> $O/bench.err"
+step tet5         bash -c "timeout -k 10 300 python bench.py --no-build --full --workload tet5 --no-e2e > $O/${TAG}_bench_tet5.json 2>> $O/bench.err"
 if [ -f diag/stats.so ]; then
   step phase_stats bash -c "R2S_LIB_OVERRIDE=diag/stats.so timeout -k 10 300 python tools/iso_phase_stats.py > $O/${TAG}_iso_phase_stats.txt 2> $O/diag.err"
 fi
