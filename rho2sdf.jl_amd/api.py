@@ -460,7 +460,7 @@ class Rho2sdfOptions:
 
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
-            info=None, pinned_results=False):
+            info=None, pinned_results=False, fine_out=None, dists_out=None):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -469,7 +469,9 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     `sdf_grid` replaces the interactive prompt of sdf_grid_setup = :manual (Grid_setup.jl:111-154 is out of scope).
     fine_grid is returned as (origin, spacing, dims) instead of one heap vector per voxel.  export_results=True
     writes the final `.vti` like RhoToSDF.jl:230-238 (the .jld2 dumps stay in the Julia package).  `info` (a dict)
-    receives V_domain, V_frac, rho_t, n_flipped, level_shift, cg_iters, per-stage milliseconds and rho_n."""
+    receives V_domain, V_frac, rho_t, n_flipped, level_shift, cg_iters, per-stage milliseconds and rho_n.
+    `fine_out` (Float32, one value per fine grid point) / `dists_out` (Float64, one per sdf_grid point): result arrays
+    to fill instead of new ones (e.g. from host_array); fine_sdf is then a view of fine_out."""
     options = options or Rho2sdfOptions()
     mesh = Mesh(X, IEN, options.element_type)
     rho = np.ascontiguousarray(rho, dtype=np.float64)
@@ -494,8 +496,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     dims = tuple(int(nn) * smooth + 1 for nn in sdf_grid.c.N)
     nfine = dims[0] * dims[1] * dims[2]
     alloc = host_array if pinned_results else (lambda n, dt=np.float64: np.empty(n, dtype=dt))
-    sdf_dists = alloc(sdf_grid.ngp)
-    fine = alloc(nfine, np.float32)
+    sdf_dists = alloc(sdf_grid.ngp) if dists_out is None else _out(dists_out, sdf_grid.ngp)
+    fine = alloc(nfine, np.float32) if fine_out is None else _out(fine_out, nfine, np.float32)
     rho_n = np.empty(mesh.nnp)
     ri = L.R2SRunInfo()
     L.check(L.lib().r2s_rho2sdf(_d(mesh.X), mesh.nnp, _i(mesh.IEN), mesh.nel, _d(rho), ctypes.byref(o),

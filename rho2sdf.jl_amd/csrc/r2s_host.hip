@@ -1071,11 +1071,19 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     // plain DMA, pageable ones the staged copy.
     bool dists_in_flight = false;
     std::thread dl_thread;
-    int dl_rc = 0;
+    std::atomic<int> dl_rc{0};   // (set by the download thread under qmu, read by this one)
     std::string dl_err;
     struct Chunk { int64_t t0, t1; hipEvent_t ev; };
     std::mutex qmu;
     std::condition_variable qcv;
+    auto dl_fail = [&](int code, const std::string& msg) {   // (download thread: the error, then a signal for the level-shift wait)
+        {
+            std::lock_guard<std::mutex> lk(qmu);
+            dl_err = msg;
+            dl_rc = code;
+        }
+        qcv.notify_all();
+    };
     std::vector<Chunk> queue;   // chunks of the smoothed field whose kernels have been launched
     std::vector<std::pair<int64_t, int64_t>> landed;   // early: chunks that have arrived in pinned memory (guarded by qmu)
     bool q_done = false;
@@ -1103,11 +1111,10 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     if (!o.skip_rbf) {
         const bool dists_here = sdf_dists_out && !pin_d;
         dl_thread = std::thread([&, dists_here]() {
-            if (hipSetDevice(dev0) != hipSuccess) { dl_rc = R2S_ERR_HIP; dl_err = "hipSetDevice failed"; return; }
+            if (hipSetDevice(dev0) != hipSuccess) { dl_fail(R2S_ERR_HIP, "hipSetDevice failed"); return; }
             if (dists_here) {
                 std::vector<Segment> segs{{(char*)sdf_dists_out, (const char*)S->out[2].p, sizeof(double) * (size_t)ngp}};
-                dl_rc = download(S, segs, false);
-                if (dl_rc) { dl_err = g_err; return; }
+                if (const int rc2 = download(S, segs, false)) { dl_fail(rc2, g_err); return; }
             }
             size_t next = 0;
             for (;;) {
@@ -1118,13 +1125,12 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
                     if (next >= queue.size()) return;
                     c = queue[next++];
                 }
-                if (hipEventSynchronize(c.ev) != hipSuccess) { dl_rc = R2S_ERR_HIP; dl_err = "hipEventSynchronize failed"; return; }
+                if (hipEventSynchronize(c.ev) != hipSuccess) { dl_fail(R2S_ERR_HIP, "hipEventSynchronize failed"); return; }
                 // (early: the chunk lands in pinned memory - the caller's array if it is pinned, else the landing zone - and gets its
                 //  level shift from the host threads once the level is known)
                 float* land = early ? (pin_f ? fine_sdf_out : (float*)S->fine_host) : fine_sdf_out;
                 std::vector<Segment> segs{{(char*)(land + c.t0), (const char*)(S->fine.as<float>() + c.t0), sizeof(float) * (size_t)(c.t1 - c.t0)}};
-                dl_rc = download(S, segs, early ? true : pin_f);
-                if (dl_rc) { dl_err = g_err; return; }
+                if (const int rc2 = download(S, segs, early ? true : pin_f)) { dl_fail(rc2, g_err); return; }
                 if (early) {
                     {
                         std::lock_guard<std::mutex> lk(qmu);
@@ -1143,7 +1149,7 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
         }
         qcv.notify_all();
         if (dl_thread.joinable()) dl_thread.join();
-        return dl_rc ? fail(dl_rc, "%s", dl_err.c_str()) : 0;
+        return dl_rc ? fail(dl_rc.load(), "%s", dl_err.c_str()) : 0;
     };
     // ---- RBF smoothing (:222-224) ----
     if (!o.skip_rbf) {
@@ -1194,7 +1200,7 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
             std::pair<int64_t, int64_t> ch;
             {
                 std::unique_lock<std::mutex> lk(qmu);
-                // (polling wait: the download thread sets dl_rc and leaves without a signal when a copy fails)
+                // (the download thread signals every landed chunk and its failure; the timeout only bounds a lost wake-up)
                 while (!qcv.wait_for(lk, std::chrono::milliseconds(20), [&] { return next < landed.size() || dl_rc != 0; })) {}
                 if (dl_rc) break;
                 ch = landed[next++];

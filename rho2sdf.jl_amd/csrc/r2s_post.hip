@@ -274,14 +274,18 @@ __global__ void __launch_bounds__(256) ccl_count_kernel(const uint32_t* __restri
     }
     if (cnt && lane == 0) atomicAdd(&size[cur], cnt);
 }
-// counters: [0] largest size, [1] smallest root having it, [3] interior count - from the list of roots (one workgroup)
+// counters: [0] largest size, [1] smallest root having it, [3] interior count - from the list of roots (one workgroup).
+// *nroots counts every root, also those the list had no room for: with more than roots_cap the list is incomplete (and
+// entries past roots_cap were never written), so the kernel leaves the counters alone and the host runs the sweeps.
 __global__ void __launch_bounds__(1024) ccl_roots_max_kernel(const uint32_t* __restrict__ size, const uint32_t* __restrict__ roots,
-                                                            const uint32_t* __restrict__ nroots, uint32_t* __restrict__ counters)
+                                                            const uint32_t* __restrict__ nroots, uint32_t roots_cap,
+                                                            uint32_t* __restrict__ counters)
 {
+    const uint32_t m = *nroots;
+    if (m > roots_cap) return;   // (block-uniform)
     __shared__ uint32_t s_max, s_arg, s_sum;
     if (threadIdx.x == 0) { s_max = 0u; s_arg = NOLABEL; s_sum = 0u; }
     __syncthreads();
-    const uint32_t m = *nroots;
     uint32_t mx = 0, sum = 0;
     for (uint32_t q = threadIdx.x; q < m; q += blockDim.x) {
         const uint32_t sz = size[roots[q]];
@@ -370,7 +374,8 @@ static int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double thresho
         ccl_compress_heads_sizes_kernel<<<(nb < 8192u ? nb : 8192u), 256, 0, st>>>(L.as<uint32_t>(), n, nx, size.as<uint32_t>(), roots.as<uint32_t>(),
                                                                                   roots_cap, cnt.as<uint32_t>() + 4);
     }
-    ccl_roots_max_kernel<<<1, 1024, 0, st>>>(size.as<uint32_t>(), roots.as<uint32_t>(), cnt.as<uint32_t>() + 4, cnt.as<uint32_t>());
+    ccl_roots_max_kernel<<<1, 1024, 0, st>>>(size.as<uint32_t>(), roots.as<uint32_t>(), cnt.as<uint32_t>() + 4, roots_cap,
+                                             cnt.as<uint32_t>());
     HIP_TRY(hipMemcpyAsync(h, cnt.p, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h[4] > roots_cap) {   // (noise at the voxel scale: more components than the list holds - the sweeps over all counters)

@@ -50,6 +50,20 @@ def test_argument_errors(pkg):
         pkg.Grid([0, 0, 0], [1, 1, 1], 0)
 
 
+def test_rho2sdf_output_arrays_are_checked(pkg):
+    """rho2sdf's fine_out / dists_out are checked like sdf_fused's `out` before anything runs"""
+    X, IEN, rho = load_fixture("sphere")
+    grid = pkg.Grid(X.min(0), X.max(0), 5, 3)
+    opts = pkg.Rho2sdfOptions(threshold_density=0.5, rbf_grid="fine")
+    nfine = int(np.prod(grid.N * 2 + 1))
+    bad = {"fine_out": [np.empty(nfine), np.empty(nfine - 1, np.float32), np.empty(2 * nfine, np.float32)[::2]],
+           "dists_out": [np.empty(grid.ngp, np.float32), np.empty(grid.ngp + 1), np.empty((grid.ngp, 2))[:, 0]]}
+    for name, arrays in bad.items():
+        for a in arrays:
+            with pytest.raises(pkg._lib.R2SError, match="contiguous"):
+                pkg.rho2sdf("t", X, IEN, rho, options=opts, sdf_grid=grid, **{name: a})
+
+
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="a GPU is present")
 def test_no_cpu_fallback(pkg):
     """without a GPU the compute entry points must fail loudly"""

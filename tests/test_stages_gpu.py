@@ -117,6 +117,7 @@ def test_remove_artifacts_many_components(pkg, oracle, monkeypatch, cap):
     pieces of the labelling; with a short list of roots (R2S_CCL_ROOTS_CAP) the sweeps over all counters take over"""
     if cap:
         monkeypatch.setenv("R2S_CCL_ROOTS_CAP", cap)
+        pkg._lib.lib().r2s_release_cache()               # a fresh list of roots: nothing left by an earlier case
     rng = np.random.default_rng(23)
     pg = pkg.Grid(np.zeros(3), np.array([2.0, 1.3, 0.9]), 70, 1)
     og = oracle.grid_make(np.zeros(3), np.array([2.0, 1.3, 0.9]), 70, 1)
