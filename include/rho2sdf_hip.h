@@ -155,7 +155,7 @@ typedef struct {
     double threshold_density;            /* NaN = nothing: find_threshold_for_volume (TET4: the TET4 iso-volume) */
     double band_factor;                  /* 1.1 */
     double artifact_min_component_ratio; /* 0.01 */
-    double rbf_kernel_threshold;         /* 1e-3 (RBFs4Smoothing.jl:328) */
+    double rbf_kernel_threshold;         /* 1e-3 (RBFs4Smoothing.jl:328); [R2S_RBF_MIN_KERNEL_THRESHOLD, 1) */
     int32_t elem_type;                   /* R2S_HEX8 / R2S_TET4 */
     int32_t rbf_interp;                  /* 1 */
     int32_t rbf_smooth;                  /* 1 = rbf_grid :same, 2 = :fine */
@@ -304,7 +304,13 @@ int r2s_volume_from_sdf(const float *sdf, int64_t nx, int64_t ny, int64_t nz, fl
  *                                                src/SdfSmoothing/RBFs4Smoothing.jl:321-377
  * target_volume = mesh.V_frac*mesh.V_domain; fine_sdf_out has prod(N*smooth+1) Float32 values
  * (x fastest); fine_grid is origin AABB_min + spacing (AABB_max[1]-AABB_min[1])/(N[1]*smooth) and is
- * materialised by the caller.  Optional outputs: level shift `th`, CG iterations, coarse LSF. */
+ * materialised by the caller.  Optional outputs: level shift `th`, CG iterations, coarse LSF.
+ * Every evaluation of the field sums over at most the 124 nearest in-bounds coarse nodes within the support
+ * (knn(kdtree, p, 124) at :238, ties by lattice distance^2 then dz, dy, dx); the CG matrix has no such cap.  The cap
+ * binds from kernel_threshold 1e-4 on refined grids and from about 1e-5 on the same grid.
+ * kernel_threshold must lie in [R2S_RBF_MIN_KERNEL_THRESHOLD, 1): smaller values give neighbour stencils beyond the
+ * 512 entries the kernels hold and fail with R2S_ERR_ARG. */
+#define R2S_RBF_MIN_KERNEL_THRESHOLD 1e-10
 int r2s_rbf_smooth(const double *sdf, const r2s_grid *grid, int32_t is_interp, int32_t smooth,
                    double kernel_threshold, double target_volume, int32_t device, float *fine_sdf_out,
                    float *level_shift_out, int32_t *cg_iters_out, float *lsf_out);

@@ -294,8 +294,10 @@ def rbf_smoothing(sdf, g, is_interp, smooth, target_volume, kthr=1e-3):
                                  ctypes.c_double(kthr), ctypes.c_double(target_volume),
                                  fine.ctypes.data_as(_fp), ctypes.byref(th), ctypes.byref(its),
                                  lsf.ctypes.data_as(_fp))
-    if rc:
+    if rc == -1:
         raise ValueError("every SDF value is a sentinel")
+    if rc:
+        raise ValueError(f"kernel threshold {kthr}: the neighbour stencil exceeds 512 entries")
     return fine.reshape(dims[2], dims[1], dims[0]), th.value, its.value, lsf.reshape(g.dims[2], g.dims[1], g.dims[0])
 
 

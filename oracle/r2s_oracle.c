@@ -2073,19 +2073,27 @@ typedef struct {
     int off[512][3]; /* coarse offsets (dx,dy,dz) relative to the base coarse index */
 } rbf_stencil;
 
-/* neighbours of a target point with sub-index frac (0..s-1 per axis) in a lattice refined s times */
-static void rbf_build_stencil(int s, const int frac[3], rbf_stencil *st)
+#define RBF_KNN 124 /* knn(kdtree, p, 124, true) (:238): the 124 nearest in-bounds nodes at most */
+
+/* neighbours of a target point with sub-index frac (0..s-1 per axis) in a lattice refined s times: lattice
+ * distance^2 (in 1/s cells) up to 5 % beyond the support radius R = sqrt(R2) cells, from offsets within
+ * ceil(R') + 1 cells on both sides; returns -1 when they do not fit */
+static int rbf_build_stencil(int s, const int frac[3], rbf_stencil *st, double R2)
 {
-    int cand[512][4], n = 0;
-    for (int dz = -3; dz <= 4; ++dz)
-        for (int dy = -3; dy <= 4; ++dy)
-            for (int dx = -3; dx <= 4; ++dx) {
+    const int d2max = (int)floor(R2 * 1.05 * s * s + 0.25);
+    const int B = (int)ceil(sqrt(R2 * 1.05)) + 1;
+    int (*cand)[4] = (int (*)[4])malloc(sizeof(int[4]) * (size_t)(2 * B + 1) * (2 * B + 1) * (2 * B + 1));
+    int n = 0;
+    for (int dz = -B; dz <= B; ++dz)
+        for (int dy = -B; dy <= B; ++dy)
+            for (int dx = -B; dx <= B; ++dx) {
                 int ex = dx * s - frac[0], ey = dy * s - frac[1], ez = dz * s - frac[2];
                 int d2 = ex * ex + ey * ey + ez * ez;
-                if (d2 > 9 * s * s) continue; /* > 3 cells: far beyond the 2.63-cell support */
+                if (d2 > d2max) continue;
                 cand[n][0] = d2; cand[n][1] = dz; cand[n][2] = dy; cand[n][3] = dx;
                 n++;
             }
+    if (n > 512) { free(cand); return -1; }
     for (int i = 1; i < n; ++i) { /* insertion sort by (d2, dz, dy, dx) */
         int t[4] = {cand[i][0], cand[i][1], cand[i][2], cand[i][3]}, j = i - 1;
         while (j >= 0 && (cand[j][0] > t[0] || (cand[j][0] == t[0] && (cand[j][1] > t[1] ||
@@ -2097,6 +2105,8 @@ static void rbf_build_stencil(int s, const int frac[3], rbf_stencil *st)
     }
     st->n = n;
     for (int i = 0; i < n; ++i) { st->off[i][0] = cand[i][3]; st->off[i][1] = cand[i][2]; st->off[i][2] = cand[i][1]; }
+    free(cand);
+    return 0;
 }
 
 /* create_grid (:36-46): Float32 `range(min, max, length)` */
@@ -2113,18 +2123,19 @@ typedef struct {
     double sigma;
     float max_distance;
     double thr;
+    int tap_r; /* matrix rows reach this many cells per axis */
 } rbf_ctx;
 
 /* rbf_interpolation_kdtree (:219-248): targets tx/ty/tz, refined s times w.r.t. the coarse lattice */
-static void rbf_apply(const rbf_ctx *c, const float *w, int s, int64_t tnx, int64_t tny, int64_t tnz,
-                      const float *tx, const float *ty, const float *tz, float *out)
+static int rbf_apply(const rbf_ctx *c, const float *w, int s, int64_t tnx, int64_t tny, int64_t tnz,
+                     const float *tx, const float *ty, const float *tz, float *out)
 {
     rbf_stencil *st = (rbf_stencil *)malloc(sizeof(rbf_stencil) * (size_t)(s * s * s));
     for (int fz = 0; fz < s; ++fz)
         for (int fy = 0; fy < s; ++fy)
             for (int fx = 0; fx < s; ++fx) {
                 int fr[3] = {fx, fy, fz};
-                rbf_build_stencil(s, fr, &st[(fz * s + fy) * s + fx]);
+                if (rbf_build_stencil(s, fr, &st[(fz * s + fy) * s + fx], -log(c->thr))) { free(st); return -1; }
             }
     for (int64_t k = 0; k < tnz; ++k)
         for (int64_t j = 0; j < tny; ++j)
@@ -2132,9 +2143,11 @@ static void rbf_apply(const rbf_ctx *c, const float *w, int s, int64_t tnx, int6
                 const rbf_stencil *S = &st[((k % s) * s + (j % s)) * s + (i % s)];
                 int64_t bi = i / s, bj = j / s, bk = k / s;
                 float acc = 0.0f;
+                int seen = 0;
                 for (int q = 0; q < S->n; ++q) {
                     int64_t ci = bi + S->off[q][0], cj = bj + S->off[q][1], ck = bk + S->off[q][2];
                     if (ci < 0 || cj < 0 || ck < 0 || ci >= c->nx || cj >= c->ny || ck >= c->nz) continue;
+                    if (++seen > RBF_KNN) break;
                     float dx = tx[i] - c->cx[ci], dy = ty[j] - c->cy[cj], dz = tz[k] - c->cz[ck];
                     float dist = sqrtf(dx * dx + dy * dy + dz * dz);
                     if (dist <= c->max_distance) {
@@ -2145,6 +2158,7 @@ static void rbf_apply(const rbf_ctx *c, const float *w, int s, int64_t tnx, int6
                 out[(k * tny + j) * tnx + i] = acc;
             }
     free(st);
+    return 0;
 }
 
 /* y = K x with K from compute_sparse_kernel_matrix (:142-176): Float32 entries
@@ -2156,9 +2170,9 @@ static void rbf_matvec(const rbf_ctx *c, const float *x, float *y)
         for (int64_t j = 0; j < c->ny; ++j)
             for (int64_t i = 0; i < c->nx; ++i) {
                 float acc = 0.0f;
-                for (int64_t ck = k - 3; ck <= k + 3; ++ck)
-                    for (int64_t cj = j - 3; cj <= j + 3; ++cj)
-                        for (int64_t ci = i - 3; ci <= i + 3; ++ci) {
+                for (int64_t ck = k - c->tap_r; ck <= k + c->tap_r; ++ck)
+                    for (int64_t cj = j - c->tap_r; cj <= j + c->tap_r; ++cj)
+                        for (int64_t ci = i - c->tap_r; ci <= i + c->tap_r; ++ci) {
                             if (ci < 0 || cj < 0 || ck < 0 || ci >= c->nx || cj >= c->ny || ck >= c->nz) continue;
                             float dx = c->cx[i] - c->cx[ci], dy = c->cy[j] - c->cy[cj], dz = c->cz[k] - c->cz[ck];
                             float r = sqrtf(dx * dx + dy * dy + dz * dz);
@@ -2243,13 +2257,17 @@ int orc_rbf_smoothing(const double *sdf, const orc_grid *g, int is_interp, int s
     c.sigma = g->cell;                                        /* :346 */
     c.thr = kthr;
     c.max_distance = (float)sqrt(-log(kthr) * c.sigma * c.sigma); /* :221 */
+    c.tap_r = (int)floor(sqrt(-log(kthr) * 1.05 + 0.25)); /* support radius + 5 %: nothing beyond passes `> thr` */
     float *w = (float *)malloc(sizeof(float) * (size_t)n);
     int its = 0;
     if (is_interp) its = rbf_cg(&c, dm, w, n);                /* :351-352 */
     else memcpy(w, dm, sizeof(float) * (size_t)n);            /* :353 */
     if (cg_iters) *cg_iters = its;
     float *lsf = (float *)malloc(sizeof(float) * (size_t)n);
-    rbf_apply(&c, w, 1, c.nx, c.ny, c.nz, c.cx, c.cy, c.cz, lsf); /* :357 */
+    if (rbf_apply(&c, w, 1, c.nx, c.ny, c.nz, c.cx, c.cy, c.cz, lsf)) { /* :357 */
+        free(dm); free(w); free(lsf); free(c.cx); free(c.cy); free(c.cz);
+        return -2;
+    }
     if (lsf_out) memcpy(lsf_out, lsf, sizeof(float) * (size_t)n);
     /* calculate_volume_from_sdf takes the edge from the coarse grid (CalcVolumeFromSDF.jl:38-40) */
     float ex = c.cx[1] - c.cx[0], ey = 0.0f, ez = 0.0f;
@@ -2265,7 +2283,10 @@ int orc_rbf_smoothing(const double *sdf, const orc_grid *g, int is_interp, int s
     for (int64_t i = 0; i < fx; ++i) tx[i] = xmin + (float)i * dx;
     for (int64_t i = 0; i < fy; ++i) ty[i] = ymin + (float)i * dx;
     for (int64_t i = 0; i < fz; ++i) tz[i] = zmin + (float)i * dx;
-    rbf_apply(&c, w, smooth, fx, fy, fz, tx, ty, tz, fine_out); /* :363 */
+    if (rbf_apply(&c, w, smooth, fx, fy, fz, tx, ty, tz, fine_out)) { /* :363 */
+        free(dm); free(w); free(lsf); free(tx); free(ty); free(tz); free(c.cx); free(c.cy); free(c.cz);
+        return -2;
+    }
     for (int64_t i = 0; i < fx * fy * fz; ++i) fine_out[i] = fine_out[i] + th; /* :366 */
     free(dm); free(w); free(lsf); free(tx); free(ty); free(tz); free(c.cx); free(c.cy); free(c.cz);
     return 0;

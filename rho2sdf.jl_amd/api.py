@@ -438,7 +438,7 @@ class Rho2sdfOptions:
     def __init__(self, threshold_density=None, sdf_grid_setup="manual", export_input_data=False,
                  export_nodal_densities=False, export_raw_sdf=False, rbf_interp=True, rbf_grid="same",
                  remove_artifacts=True, artifact_min_component_ratio=0.01, export_analysis=False,
-                 element_type=None):
+                 element_type=None, rbf_kernel_threshold=None):
         import warnings
         if threshold_density is not None and not (0.0 <= threshold_density <= 1.0):
             warnings.warn(f"Threshold density {threshold_density} is outside the valid range [0.0, 1.0]. "
@@ -457,6 +457,7 @@ class Rho2sdfOptions:
         self.remove_artifacts = remove_artifacts
         self.artifact_min_component_ratio = artifact_min_component_ratio
         self.element_type = element_type
+        self.rbf_kernel_threshold = rbf_kernel_threshold   # None: the library's default (1e-3, RBFs4Smoothing.jl:328)
 
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
@@ -491,6 +492,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     o.rbf_smooth = smooth
     o.remove_artifacts = int(bool(options.remove_artifacts))
     o.artifact_min_component_ratio = float(options.artifact_min_component_ratio)
+    if getattr(options, "rbf_kernel_threshold", None) is not None:
+        o.rbf_kernel_threshold = float(options.rbf_kernel_threshold)
     o.device = int(device)
     o.n_gpus = int(n_gpus)
     dims = tuple(int(nn) * smooth + 1 for nn in sdf_grid.c.N)

@@ -933,7 +933,11 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
         std::vector<double> h_rn((size_t)nnp);
         HIP_TRY(hipMemcpy(h_rn.data(), S->dR.p, sizeof(double) * (size_t)nnp, hipMemcpyDeviceToHost));
         const int64_t nz = grid->N[2] + 1, plane = (grid->N[0] + 1) * (grid->N[1] + 1), layers = (nz + 3) / 4;
-        const int H = 4;   // planes a smoothing stencil can reach beyond a slab (build_stencil: offsets -3..4)
+        // planes a smoothing stencil can reach beyond a slab (build_stencil: ceil(R') + 1 cells, 4 at the default threshold;
+        // a threshold out of range is rejected by the smoothing itself)
+        const double kthr = o.rbf_kernel_threshold;
+        const int H = (kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0)
+                          ? std::max(4, (int)std::ceil(std::sqrt(-std::log(kthr) * 1.05)) + 1) : 4;
         std::vector<HostSession*> T((size_t)G, nullptr);
         std::vector<r2s_int::Slab> slabs((size_t)G);
         for (int r = 0; r < G; ++r)

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -930,34 +931,63 @@ struct Stencil {
     signed char off[512][3];
 };
 
-static void build_stencil(int s, const int frac[3], Stencil* st, double R2)
+// knn(kdtree, p, 124, true) (RBFs4Smoothing.jl:238): every evaluation sums over the 124 nearest in-bounds coarse nodes
+// at most, counted in stencil order; the CG matrix (inrange, :156) has no cap
+#define RBF_KNN 124
+
+// returns the number of entries inside the support (lattice distance <= R), or -1 when the stencil would not fit
+static int build_stencil(int s, const int frac[3], Stencil* st, double R2)
 {
     // candidates: lattice distance^2 (in 1/s cells) up to 5 % beyond the support radius; the run-time
-    // `dist <= max_distance` test (RBFs4Smoothing.jl:240) decides
+    // `dist <= max_distance` test (RBFs4Smoothing.jl:240) decides.  Offsets reach ceil(R') + 1 cells (the target lies up
+    // to one cell beyond its base node), on both sides.
     const int d2max = (int)std::floor(R2 * 1.05 * s * s + 0.25);
-    int cand[512][4], n = 0;
-    for (int dz = -3; dz <= 4; ++dz)
-        for (int dy = -3; dy <= 4; ++dy)
-            for (int dx = -3; dx <= 4; ++dx) {
+    const int B = (int)std::ceil(std::sqrt(R2 * 1.05)) + 1;
+    std::vector<std::array<int, 4>> cand;
+    int n_in = 0;
+    for (int dz = -B; dz <= B; ++dz)
+        for (int dy = -B; dy <= B; ++dy)
+            for (int dx = -B; dx <= B; ++dx) {
                 const int ex = dx * s - frac[0], ey = dy * s - frac[1], ez = dz * s - frac[2];
                 const int d2 = ex * ex + ey * ey + ez * ez;
                 if (d2 > d2max) continue;
-                cand[n][0] = d2; cand[n][1] = dz; cand[n][2] = dy; cand[n][3] = dx;
-                n++;
+                if (d2 <= R2 * s * s * (1.0 + 1e-4)) n_in++;
+                cand.push_back({d2, dz, dy, dx});
             }
-    std::vector<int> idx(n);
-    for (int i = 0; i < n; ++i) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](int a, int b) {
-        for (int q = 0; q < 4; ++q)
-            if (cand[a][q] != cand[b][q]) return cand[a][q] < cand[b][q];
-        return false;
-    });
-    st->n = n;
-    for (int i = 0; i < n; ++i) {
-        st->off[i][0] = (signed char)cand[idx[i]][3];
-        st->off[i][1] = (signed char)cand[idx[i]][2];
-        st->off[i][2] = (signed char)cand[idx[i]][1];
+    if (cand.size() > sizeof st->off / sizeof st->off[0]) return -1;
+    std::sort(cand.begin(), cand.end());   // (d2, dz, dy, dx) lexicographic
+    st->n = (int)cand.size();
+    for (int i = 0; i < st->n; ++i) {
+        st->off[i][0] = (signed char)cand[(size_t)i][3];
+        st->off[i][1] = (signed char)cand[(size_t)i][2];
+        st->off[i][2] = (signed char)cand[(size_t)i][1];
     }
+    return n_in;
+}
+
+// stencils for smooth = 1 (sts[0]) and for the fine grid (sts[1 + class], smooth^3 parity classes); *capped: some class
+// holds more than RBF_KNN nodes inside the support, so the knn cap can bind - only rbf_apply_kernel counts it, every
+// table-driven evaluation must stand aside
+static int build_stencils(int smooth, double kthr, std::vector<Stencil>& sts, bool* capped)
+{
+    if (!(kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0))
+        return fail(R2S_ERR_ARG, "kernel threshold must be in [%g, 1): got %g", R2S_RBF_MIN_KERNEL_THRESHOLD, kthr);
+    sts.assign(1 + (size_t)smooth * smooth * smooth, Stencil{});
+    const double R2 = -std::log(kthr);
+    int most = 0;
+    int fr0[3] = {0, 0, 0};
+    int n_in = build_stencil(1, fr0, &sts[0], R2);
+    most = n_in;
+    for (int a = 0; a < smooth && n_in >= 0; ++a)
+        for (int b = 0; b < smooth && n_in >= 0; ++b)
+            for (int c = 0; c < smooth && n_in >= 0; ++c) {
+                int fr[3] = {c, b, a};
+                n_in = build_stencil(smooth, fr, &sts[1 + (a * smooth + b) * smooth + c], R2);
+                most = std::max(most, n_in);
+            }
+    if (n_in < 0) return fail(R2S_ERR_ARG, "kernel threshold %g: the neighbour stencil exceeds %d entries", kthr, (int)(sizeof sts[0].off / sizeof sts[0].off[0]));
+    *capped = most > RBF_KNN;
+    return 0;
 }
 
 struct RbfGeom {
@@ -1039,9 +1069,11 @@ __device__ __forceinline__ float rbf_apply_point(const RbfGeom& G, const float* 
     const int bi = i / s, bj = j / s, bk = k / s;
     const float px = tx[i], py = ty[j], pz = tz[k];
     float acc = 0.0f;
+    int seen = 0;   // in-bounds nodes so far: the knn cap (RBF_KNN)
     for (int q = 0; q < S.n; ++q) {
         const int ci = bi + S.off[q][0], cj = bj + S.off[q][1], ck = bk + S.off[q][2];
         if (ci < 0 || cj < 0 || ck < 0 || ci >= G.nx || cj >= G.ny || ck >= G.nz) continue;
+        if (++seen > RBF_KNN) break;
         const float dx = px - G.cx[ci], dy = py - G.cy[cj], dz = pz - G.cz[ck];
         const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
         if (dist <= G.max_distance) {
@@ -2189,7 +2221,8 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
 {
     if (!sdf || !g || !fine_out) return fail(R2S_ERR_ARG, "null argument");
     if (smooth < 1 || smooth > 4) return fail(R2S_ERR_ARG, "smooth must be 1..4");
-    if (!(kthr > 0.0 && kthr < 1.0)) return fail(R2S_ERR_ARG, "kernel threshold must be in (0,1)");
+    if (!(kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0))
+        return fail(R2S_ERR_ARG, "kernel threshold must be in [%g, 1): got %g", R2S_RBF_MIN_KERNEL_THRESHOLD, kthr);
     const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
     const int64_t n = (int64_t)nx * ny * nz;
     const int fx = (int)g->N[0] * smooth + 1, fy = (int)g->N[1] * smooth + 1, fz = (int)g->N[2] * smooth + 1;
@@ -2263,17 +2296,9 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     TRY_C(up(d_cx, cx)); TRY_C(up(d_cy, cy)); TRY_C(up(d_cz, cz));
     TRY_C(up(d_tx, tx)); TRY_C(up(d_ty, ty)); TRY_C(up(d_tz, tz));
     // stencils for smooth = 1 (one class) and for the fine grid (smooth^3 classes)
-    std::vector<Stencil> sts(1 + (size_t)smooth * smooth * smooth);
-    {
-        int fr0[3] = {0, 0, 0};
-        build_stencil(1, fr0, &sts[0], -std::log(kthr));
-        for (int a = 0; a < smooth; ++a)
-            for (int b = 0; b < smooth; ++b)
-                for (int c = 0; c < smooth; ++c) {
-                    int fr[3] = {c, b, a};
-                    build_stencil(smooth, fr, &sts[1 + (a * smooth + b) * smooth + c], -std::log(kthr));
-                }
-    }
+    std::vector<Stencil> sts;
+    bool capped = false;
+    TRY_C(build_stencils(smooth, kthr, sts, &capped));
     ENSURE_C(d_st, sizeof(Stencil) * sts.size());
     HIP_C(hipMemcpy(d_st.p, sts.data(), sizeof(Stencil) * sts.size(), hipMemcpyHostToDevice));
     RbfGeom G;
@@ -2290,7 +2315,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     // ---- refined output grid: the tables of its parity classes (R2S_RBF_APPLY=fly: on the fly, the tests compare) ----
     FineLut FL;
     memset(&FL, 0, sizeof FL);
-    if (smooth >= 2 && !(getenv("R2S_RBF_APPLY") && getenv("R2S_RBF_APPLY")[0] == 'f')) {
+    if (smooth >= 2 && !capped && !(getenv("R2S_RBF_APPLY") && getenv("R2S_RBF_APPLY")[0] == 'f')) {
         const int ncls = smooth * smooth * smooth;
         std::vector<uint64_t> pkx, pky, pkz;
         std::vector<float> vlx, vly, vlz;
@@ -2371,7 +2396,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     const char* mv_env = getenv("R2S_RBF_MATVEC");   // (read per call: the tests switch)
     const char* ap_env = getenv("R2S_RBF_APPLY");
     const bool want_mv_lut = is_interp && !(mv_env && (mv_env[0] == 'k' || mv_env[0] == 'f'));
-    const bool want_ap_lut = !(ap_env && ap_env[0] == 'f');
+    const bool want_ap_lut = !(ap_env && ap_env[0] == 'f') && !capped;   // (the tables cannot count the knn cap)
     RbfLutGeom LG, LGF;   // LGF: the evaluation of the output field at smooth = 1 (its grid is rounded separately)
     memset(&LG, 0, sizeof LG);
     memset(&LGF, 0, sizeof LGF);
@@ -2957,7 +2982,8 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
 {
     if (!g || !fine_out_host) return fail(R2S_ERR_ARG, "null argument");
     if (smooth < 1 || smooth > 4) return fail(R2S_ERR_ARG, "smooth must be 1..4");
-    if (!(kthr > 0.0 && kthr < 1.0)) return fail(R2S_ERR_ARG, "kernel threshold must be in (0,1)");
+    if (!(kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0))
+        return fail(R2S_ERR_ARG, "kernel threshold must be in [%g, 1): got %g", R2S_RBF_MIN_KERNEL_THRESHOLD, kthr);
     const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
     const int64_t plane = (int64_t)nx * ny;
     const int fx = (int)g->N[0] * smooth + 1, fy = (int)g->N[1] * smooth + 1, fz = (int)g->N[2] * smooth + 1;
@@ -2981,17 +3007,9 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         for (int i = 0; i < fy; ++i) ty[i] = ymin + (float)i * dx;
         for (int i = 0; i < fz; ++i) tz[i] = zmin + (float)i * dx;
     }
-    std::vector<Stencil> sts(1 + (size_t)smooth * smooth * smooth);
-    {
-        int fr0[3] = {0, 0, 0};
-        build_stencil(1, fr0, &sts[0], -std::log(kthr));
-        for (int a = 0; a < smooth; ++a)
-            for (int b = 0; b < smooth; ++b)
-                for (int c = 0; c < smooth; ++c) {
-                    int fr[3] = {c, b, a};
-                    build_stencil(smooth, fr, &sts[1 + (a * smooth + b) * smooth + c], -std::log(kthr));
-                }
-    }
+    std::vector<Stencil> sts;
+    bool capped = false;
+    if ((rc = build_stencils(smooth, kthr, sts, &capped))) return rc;
     RbfGeom G0;
     memset(&G0, 0, sizeof G0);
     G0.nx = nx; G0.ny = ny; G0.nz = nz;
@@ -3016,7 +3034,7 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
     std::vector<uint8_t> ix, iy, iz;
     bool lut_axes = false, mv_fits = false;
     const char* ap_env = getenv("R2S_RBF_APPLY");
-    const bool want_ap_lut = !(ap_env && ap_env[0] == 'f');
+    const bool want_ap_lut = !(ap_env && ap_env[0] == 'f') && !capped;   // (the tables cannot count the knn cap)
     if ((is_interp || want_ap_lut) && G0.tap_r >= 1 && G0.tap_r <= 3) {
         LV.R = G0.tap_r; LV.sigma = G0.sigma; LV.thr = G0.thr; LV.max_distance = G0.max_distance;
         const int m0 = rbf_lut_axis(cx, cx, G0.tap_r, LV.v[0], ix), m1 = rbf_lut_axis(cy, cy, G0.tap_r, LV.v[1], iy),

@@ -93,3 +93,59 @@ def test_rbf_pipeline_volume_preserved(oracle):
     # same field on the :same grid; coarse and fine coordinates are generated differently in the
     # reference (range vs explicit arithmetic), hence Float32 round-off differences
     assert np.allclose(fine, lsf + np.float32(th), rtol=0, atol=1e-5 * np.abs(lsf).max())
+
+
+def _rbf_case_grid(oracle, dims, dyadic=True):
+    """an oracle grid of `dims` points: dyadic bounds (exact cell count), or a non-dyadic box"""
+    dims = np.array(dims)
+    if dyadic:
+        lo = np.array([0.375, -0.25, 0.125])
+        g = oracle.grid_make(lo, lo + 0.125 * (dims - 1.0), int(dims.max()) - 1, 0)
+    else:
+        lo = np.array([0.013, -0.2, 0.07])
+        g = oracle.grid_make(lo, lo + 0.1037 * (dims - 1.0), int(dims.max()) - 1, 0)
+    return g
+
+
+@pytest.mark.parametrize("thr,smooth,dyadic", [(1e-3, 1, True), (1e-3, 2, False), (1e-4, 3, True), (1e-5, 1, True),
+                                                (1e-5, 2, False)])
+def test_rbf_oracle_matches_float64_restatement(oracle, thr, smooth, dyadic):
+    """approximation mode of oracle.rbf_smoothing against the float64 restatement of RBFs4Smoothing.jl (rbf_ref64):
+    the coarse LSF and the fine field minus the level shift, for impulses (the output is the stencil itself: an extra
+    or a missing tap shows) and for a small banded field with sentinels.  At 1e-4 with smooth 3 and at 1e-5 the knn cap
+    of 124 neighbours binds, and below exp(-9) the support reaches beyond 3 cells."""
+    import rbf_ref64 as ref
+    g = _rbf_case_grid(oracle, (11, 9, 10), dyadic)
+    nx, ny, nz = g.dims
+    caxes = ref.coarse_axes(g.amin, g.amax, g.N)
+    taxes = ref.fine_axes(g.amin, g.amax, g.N, smooth)
+    worst = 0.0
+    fields = []
+    for spike in [(5, 4, 5), (0, 0, 0), (nx - 1, 0, 4), (1, ny - 2, 5), (nx - 2, 3, nz - 1)]:
+        f = np.zeros((nz, ny, nx))
+        f[spike[2], spike[1], spike[0]] = 1.0
+        fields.append((f, spike))
+    ax = [g.amin[a] + g.cell * np.arange(n) for a, n in enumerate((nx, ny, nz))]
+    r = np.sqrt((ax[0][None, None, :] - ax[0].mean()) ** 2 + (ax[1][None, :, None] - ax[1].mean()) ** 2
+                + (ax[2][:, None, None] - ax[2].mean()) ** 2)
+    band = 3.0 * g.cell - r
+    fields.append((np.where(np.abs(band) < 2.5 * g.cell, band, np.sign(band) * 1e10), None))
+    for f, spike in fields:
+        fine, th, its, lsf = oracle.rbf_smoothing(f.ravel(), g, False, smooth, 1.0 * g.cell ** 3, kthr=thr)
+        w = ref.process_vector(f.ravel()).reshape(nz, ny, nx)
+        for got, axes, s, shift in ((lsf, caxes, 1, 0.0), (fine, taxes, smooth, th)):
+            e = ref.evaluate(w, caxes, axes, s, g.cell, thr)
+            if shift == 0.0:
+                err, b = np.abs(got - e["val"]), ref.bound(e, thr)
+            else:
+                err = np.abs(got.astype(np.float64) - (e["val"] + shift).astype(np.float32))
+                b = ref.fine_bound(e, shift, thr)
+            ok = e["tie_d2"] < 0
+            if spike is not None:   # a tie at the cap only matters where it involves the spike
+                kk, jj, ii = np.meshgrid(*[np.arange(n) for n in got.shape], indexing="ij")
+                d2 = (ii - spike[0] * s) ** 2 + (jj - spike[1] * s) ** 2 + (kk - spike[2] * s) ** 2
+                ok |= d2 != e["tie_d2"]
+            assert (err[ok] <= b[ok]).all(), (spike, s, float(np.max(err[ok] - b[ok])))
+            worst = max(worst, float(np.max(np.where(ok & (b > 0), err / np.where(b > 0, b, 1.0), 0.0))))
+            assert (err[b == 0] == 0).all()
+    print(f"oracle vs float64 thr={thr} smooth={smooth}: largest fraction of the bound {worst:.3g}")
