@@ -166,7 +166,10 @@ typedef struct {
     int32_t skip_rbf;                    /* 1: stop after artifact removal (fine_sdf_out may be NULL) */
     int32_t true_min;                    /* r2s_params.true_min for the raw SDF */
     int32_t sign_no_inner;               /* r2s_params.sign_no_inner for the raw SDF */
-    int32_t reserved[3];
+    int32_t analyze_components;          /* 1 (with remove_artifacts): keep the component table of the labelling that artifact
+                                            removal computes on the raw field at threshold 0 (analyze_sdf_components before the
+                                            cleanup, RhoToSDF.jl:177-179); read it with r2s_last_components.  0 = no change */
+    int32_t reserved[2];
 } r2s_options;
 
 typedef struct {
@@ -293,6 +296,25 @@ int r2s_remove_artifacts(double *sdf_inout, const r2s_grid *grid, double thresho
                          int32_t device, int64_t *n_flipped);
 int r2s_remove_artifacts_dev(double *d_sdf, const r2s_grid *grid, double threshold, double min_ratio,
                              void *stream, int64_t *n_flipped);
+
+/* analyze_sdf_components(sdf, grid; threshold)   src/SignedDistances/SdfArtifactRemoval.jl:256-311
+ * The 6-connected components of {sdf >= threshold} (NaN is never interior) as a table with one entry per component in
+ * ascending root order: roots_out = the component's 0-based x-fastest linear index of its first (= smallest) voxel,
+ * sizes_out = its voxel count.  *n_components is always the full count; the first min(capacity, n) entries are
+ * written.  roots_out / sizes_out may be NULL only with capacity == 0 (otherwise R2S_ERR_ARG).  sdf is only read.
+ * Differences from the reference: it keys each component by its union-find root (union by rank,
+ * SdfArtifactRemoval.jl:41-60), which depends on the union order; here the key is canonical, the component's first
+ * voxel.  The partition into components and the multiset of sizes are the same.  An all-exterior field gives n = 0
+ * (:263-266); nothing is printed.  Grid limits as for removal (ngp < 2^32 - 1).
+ * The _dev variant reads a device field on the current device after the work queued on `stream`; its output pointers
+ * are host pointers (like n_flipped of r2s_remove_artifacts_dev).  Every call replaces the calling thread's last table. */
+int r2s_analyze_components(const double *sdf, const r2s_grid *grid, double threshold, int32_t device,
+                           int64_t *roots_out, int64_t *sizes_out, int64_t capacity, int64_t *n_components);
+int r2s_analyze_components_dev(const double *d_sdf, const r2s_grid *grid, double threshold, void *stream,
+                               int64_t *roots_out, int64_t *sizes_out, int64_t capacity, int64_t *n_components);
+/* the calling thread's last component table (from either call above, or from r2s_rho2sdf with analyze_components and
+ * remove_artifacts set), same conventions: ask for the count with capacity 0, then copy without labelling again */
+int r2s_last_components(int64_t *roots_out, int64_t *sizes_out, int64_t capacity, int64_t *n_components);
 
 /* calculate_volume_from_sdf(sdf::Array{Float32,3}, grid; iso_threshold, detailed_quad_order)
  *                                                src/SdfSmoothing/CalcVolumeFromSDF.jl:26-125

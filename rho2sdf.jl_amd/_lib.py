@@ -34,7 +34,7 @@ class R2SOptions(ctypes.Structure):
                 ("elem_type", ctypes.c_int32), ("rbf_interp", ctypes.c_int32), ("rbf_smooth", ctypes.c_int32),
                 ("remove_artifacts", ctypes.c_int32), ("device", ctypes.c_int32), ("n_gpus", ctypes.c_int32),
                 ("skip_rbf", ctypes.c_int32), ("true_min", ctypes.c_int32), ("sign_no_inner", ctypes.c_int32),
-                ("reserved", ctypes.c_int32 * 3)]
+                ("analyze_components", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
 class R2SRunInfo(ctypes.Structure):
@@ -119,6 +119,11 @@ SYMBOLS = [
                                             ctypes.c_int32, c_int64_p]),
     ("r2s_remove_artifacts_dev", ctypes.c_int, [_P, ctypes.POINTER(R2SGrid), ctypes.c_double, ctypes.c_double, _P,
                                                 c_int64_p]),
+    ("r2s_analyze_components", ctypes.c_int, [c_double_p, ctypes.POINTER(R2SGrid), ctypes.c_double, ctypes.c_int32,
+                                              c_int64_p, c_int64_p, ctypes.c_int64, c_int64_p]),
+    ("r2s_analyze_components_dev", ctypes.c_int, [_P, ctypes.POINTER(R2SGrid), ctypes.c_double, _P, c_int64_p, c_int64_p,
+                                                  ctypes.c_int64, c_int64_p]),
+    ("r2s_last_components", ctypes.c_int, [c_int64_p, c_int64_p, ctypes.c_int64, c_int64_p]),
     ("r2s_volume_from_sdf", ctypes.c_int, [c_float_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
                                            ctypes.c_float, ctypes.c_int32, ctypes.c_int32, c_float_p]),
     ("r2s_rbf_smooth", ctypes.c_int, [c_double_p, ctypes.POINTER(R2SGrid), ctypes.c_int32, ctypes.c_int32,

@@ -330,6 +330,30 @@ def remove_sdf_artifacts(sdf, grid, *, threshold=0.0, min_component_ratio=0.01, 
     return int(n.value)
 
 
+def _components_dict(analyze):
+    """the table of one analysis call through the thread's last table: count (capacity 0), then copy -> {root + 1: size}"""
+    n = ctypes.c_int64()
+    L.check(analyze(None, None, 0, ctypes.byref(n)))
+    roots, sizes = np.empty(n.value, np.int64), np.empty(n.value, np.int64)
+    if n.value:
+        L.check(L.lib().r2s_last_components(_i(roots), _i(sizes), n.value, ctypes.byref(n)))
+    return dict(zip((roots + 1).tolist(), sizes.tolist()))
+
+
+def analyze_sdf_components(sdf, grid, *, threshold=0.0, device=-1):
+    """analyze_sdf_components(sdf, grid; threshold) -> Dict{Int,Int}  src/SignedDistances/SdfArtifactRemoval.jl:256-311
+    One entry per 6-connected component of {sdf >= threshold} (NaN is never interior), in ascending key order:
+    key = the 1-based (Julia) linear index of the component's first voxel, value = its voxel count.  The reference keys
+    each component by its union-find root (union by rank, :41-60), which depends on the union order; here the key is
+    canonical.  The partition and the sizes are the same.  An all-exterior field gives {}.  sdf is not modified and
+    nothing is printed."""
+    sdf = np.ascontiguousarray(sdf, dtype=np.float64)
+    if sdf.size != grid.ngp:
+        raise L.R2SError(f"SDF values length ({sdf.size}) doesn't match grid points ({grid.ngp})")
+    return _components_dict(lambda r, s, cap, n: L.lib().r2s_analyze_components(
+        _d(sdf), ctypes.byref(grid.c), float(threshold), int(device), r, s, cap, n))
+
+
 def calculate_volume_from_sdf(fine_sdf, edge, *, iso_threshold=0.0, detailed_quad_order=9, device=-1):
     """calculate_volume_from_sdf(fine_sdf, fine_grid; iso_threshold, detailed_quad_order) -> Float32
     src/SdfSmoothing/CalcVolumeFromSDF.jl:26-125; fine_sdf is (nz, ny, nx) float32, `edge` the grid spacing."""
@@ -456,6 +480,7 @@ class Rho2sdfOptions:
         self.rbf_grid = rbf_grid
         self.remove_artifacts = remove_artifacts
         self.artifact_min_component_ratio = artifact_min_component_ratio
+        self.export_analysis = export_analysis
         self.element_type = element_type
         self.rbf_kernel_threshold = rbf_kernel_threshold   # None: the library's default (1e-3, RBFs4Smoothing.jl:328)
 
@@ -470,7 +495,9 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     `sdf_grid` replaces the interactive prompt of sdf_grid_setup = :manual (Grid_setup.jl:111-154 is out of scope).
     fine_grid is returned as (origin, spacing, dims) instead of one heap vector per voxel.  export_results=True
     writes the final `.vti` like RhoToSDF.jl:230-238 (the .jld2 dumps stay in the Julia package).  `info` (a dict)
-    receives V_domain, V_frac, rho_t, n_flipped, level_shift, cg_iters, per-stage milliseconds and rho_n.
+    receives V_domain, V_frac, rho_t, n_flipped, level_shift, cg_iters, per-stage milliseconds and rho_n; with
+    options.export_analysis and remove_artifacts also "components_before": analyze_sdf_components of the raw field
+    (RhoToSDF.jl:177-179), taken from the labelling the artifact removal runs anyway.
     `fine_out` (Float32, one value per fine grid point) / `dists_out` (Float64, one per sdf_grid point): result arrays
     to fill instead of new ones (e.g. from host_array); fine_sdf is then a view of fine_out."""
     options = options or Rho2sdfOptions()
@@ -492,6 +519,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     o.rbf_smooth = smooth
     o.remove_artifacts = int(bool(options.remove_artifacts))
     o.artifact_min_component_ratio = float(options.artifact_min_component_ratio)
+    analysis = info is not None and bool(getattr(options, "export_analysis", False)) and bool(options.remove_artifacts)
+    o.analyze_components = int(analysis)
     if getattr(options, "rbf_kernel_threshold", None) is not None:
         o.rbf_kernel_threshold = float(options.rbf_kernel_threshold)
     o.device = int(device)
@@ -508,6 +537,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     if info is not None:
         info.update(ri.as_dict())
         info["rho_n"] = rho_n
+        if analysis:
+            info["components_before"] = _components_dict(lambda r, s, cap, n: L.lib().r2s_last_components(r, s, cap, n))
     fine_sdf = fine.reshape(dims[2], dims[1], dims[0])
     xmin, xmax = np.float32(sdf_grid.AABB_min[0]), np.float32(sdf_grid.AABB_max[0])
     spacing = (xmax - xmin) / np.float32(fine_sdf.shape[2] - 1)

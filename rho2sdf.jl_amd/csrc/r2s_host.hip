@@ -1029,7 +1029,11 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
         };
         if (sdf_raw_out && (rc = slabs_to_host(sdf_raw_out))) return rc;
         if (o.remove_artifacts) {
-            if ((rc = r2s_int::remove_artifacts_slabs(slabs, grid, 0.0, o.artifact_min_component_ratio, &ri.n_flipped))) return rc;
+            r2s_int::ComponentTable tab;
+            if ((rc = r2s_int::remove_artifacts_slabs(slabs, grid, 0.0, o.artifact_min_component_ratio, &ri.n_flipped,
+                                                      o.analyze_components ? &tab : nullptr)))
+                return rc;
+            if (o.analyze_components) r2s_int::set_last_components(std::move(tab));
             std::vector<void*> base((size_t)G);
             for (int r = 0; r < G; ++r) base[(size_t)r] = slabs[(size_t)r].d_sdf;
             if ((rc = r2s_int::exchange_halo_slabs(slabs, base, sizeof(double), plane, H))) return rc;   // flipped voxels reach the halos
@@ -1063,9 +1067,11 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     }
     // ---- artifact removal (:174-208) ----
     if (o.remove_artifacts) {
+        r2s_int::ComponentTable tab;
         if ((rc = r2s_int::remove_artifacts_dev(S->out[2].as<double>(), grid, 0.0, o.artifact_min_component_ratio, nullptr,
-                                                &ri.n_flipped)))
+                                                &ri.n_flipped, o.analyze_components ? &tab : nullptr)))
             return rc;
+        if (o.analyze_components) r2s_int::set_last_components(std::move(tab));
     }
     double t4 = now_ms();
     ri.ms_artifacts = t4 - t3;

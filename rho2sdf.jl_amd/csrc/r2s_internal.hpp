@@ -28,9 +28,18 @@ int find_threshold_dev(const double* dX, const int64_t* dIEN, int64_t nel, int e
 int isocontour_volume_dev(const double* dX, const int64_t* dIEN, int64_t nel, int elem_type, const double* d_rho_n,
                           double thr, double* volume_out);
 
-// remove_sdf_artifacts! on a device-resident field (SdfArtifactRemoval.jl:134-245)
+// analyze_sdf_components (SdfArtifactRemoval.jl:256-311): one entry per 6-connected component of {sdf >= threshold},
+// in ascending root order; root = the component's smallest 0-based linear index
+struct ComponentTable {
+    std::vector<int64_t> root, size;
+};
+// replaces the calling thread's last table (r2s_last_components)
+void set_last_components(ComponentTable&& t);
+
+// remove_sdf_artifacts! on a device-resident field (SdfArtifactRemoval.jl:134-245); table != nullptr: also the component
+// table of the same labelling (of the field before the flip)
 int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double threshold, double min_ratio, hipStream_t st,
-                         int64_t* n_flipped);
+                         int64_t* n_flipped, ComponentTable* table = nullptr);
 
 // RBFs_smoothing with device-resident input / output (RBFs4Smoothing.jl:321-377)
 // fine_chunk (optional): the output field is evaluated in a few Z chunks; after the launch of each one (default stream)
@@ -61,7 +70,9 @@ struct Slab {
 int exchange_halo_slabs(const std::vector<Slab>& S, const std::vector<void*>& base, size_t elem, int64_t plane, int radius);
 // remove_sdf_artifacts! with the components labelled per slab and merged across the slab interfaces on the host
 // (boundary-plane labels only); owned planes of d_sdf are modified, halos are NOT refreshed
-int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double threshold, double min_ratio, int64_t* n_flipped);
+// (table != nullptr: also the whole grid's component table, equal to remove_artifacts_dev's)
+int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double threshold, double min_ratio, int64_t* n_flipped,
+                           ComponentTable* table = nullptr);
 // RBFs_smoothing on slabs: halo exchanges of the CG direction / weights / LSF, plane-wise dot products summed in k
 // order on the host, volume row sums reduced on slab 0 - bit-identical to rbf_smooth_dev on one device.
 // fine_out_host: the caller's (host) array of the whole fine grid, filled slab by slab.

@@ -323,10 +323,121 @@ __global__ void ccl_flip_l_kernel(double* __restrict__ sdf, const uint32_t* __re
     if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(&counters[2], (uint32_t)__popcll(m));
 }
 
-// the work arrays of remove_artifacts_dev, kept between calls per device (r2s_release_cache frees them): allocating and
-// freeing 1.6 GB per call cost as much as a kernel of the stage
+// ---- the component table (analyze_sdf_components, SdfArtifactRemoval.jl:256-311) ----------------------------------
+// After a labelling, an interior voxel v is a root iff L[v] == v (other voxels of a run piece point at its head, heads
+// that are not roots at their root, exterior voxels hold NOLABEL), and size[root] is the component's size.  The table
+// (root, size) comes out in root order with no atomics and no sort: (a) roots per block of CT_TILE voxels, (b) one
+// workgroup scans the block counts, (c) each root's slot = its block's offset + the counts of the waves before its own
+// (LDS) + the roots of its wave before it (mbcnt).  A wavefront covers CT_CHUNKS consecutive 64-voxel chunks; the
+// scatter keeps their ballots in scalar registers, so L is read once by (a) and once by (c).
+#define CT_WAVES 4
+#define CT_CHUNKS 16
+#define CT_TILE (CT_WAVES * CT_CHUNKS * 64)
+
+__device__ __forceinline__ unsigned long long ct_roots(const uint32_t* __restrict__ L, uint32_t n, uint64_t v)
+{
+    return __ballot(v < n && L[v] == (uint32_t)v);   // (NOLABEL is no index: n < 2^32 - 1)
+}
+
+__global__ void __launch_bounds__(256) ccl_table_count_kernel(const uint32_t* __restrict__ L, uint32_t n, uint32_t* __restrict__ blk)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t base = (uint64_t)blockIdx.x * CT_TILE + (uint64_t)wave * (CT_CHUNKS * 64) + lane;
+    uint32_t c = 0;
+#pragma unroll
+    for (int ch = 0; ch < CT_CHUNKS; ++ch) c += (uint32_t)__popcll(ct_roots(L, n, base + 64 * ch));
+    __shared__ uint32_t s[CT_WAVES];
+    if (lane == 0) s[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+}
+
+// exclusive scan of the block counts in place, the number of roots in *total (one workgroup)
+__global__ void __launch_bounds__(1024) ccl_table_scan_kernel(uint32_t* __restrict__ blk, uint32_t nblk, uint32_t* __restrict__ total)
+{
+    const uint32_t per = (nblk + 1023u) / 1024u, b0 = threadIdx.x * per, b1 = min(b0 + per, nblk);
+    uint32_t s = 0;
+    for (uint32_t b = b0; b < b1; ++b) s += blk[b];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t x = s;   // inclusive scan over the wavefront
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    __shared__ uint32_t ws[16];
+    if (lane == 63) ws[wave] = x;
+    __syncthreads();
+    uint32_t off = 0;
+    for (int w = 0; w < wave; ++w) off += ws[w];
+    if (threadIdx.x == 1023) *total = off + x;
+    uint32_t run = off + x - s;
+    for (uint32_t b = b0; b < b1; ++b) {
+        const uint32_t c = blk[b];
+        blk[b] = run;
+        run += c;
+    }
+}
+
+__global__ void __launch_bounds__(256) ccl_table_scatter_kernel(const uint32_t* __restrict__ L, const uint32_t* __restrict__ size, uint32_t n,
+                                                               const uint32_t* __restrict__ blk_off, int64_t* __restrict__ root_out,
+                                                               int64_t* __restrict__ size_out)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t base = (uint64_t)blockIdx.x * CT_TILE + (uint64_t)wave * (CT_CHUNKS * 64) + lane;
+    unsigned long long m[CT_CHUNKS];
+    uint32_t c = 0;
+#pragma unroll
+    for (int ch = 0; ch < CT_CHUNKS; ++ch) {
+        m[ch] = ct_roots(L, n, base + 64 * ch);
+        c += (uint32_t)__popcll(m[ch]);
+    }
+    __shared__ uint32_t s[CT_WAVES];
+    if (lane == 0) s[wave] = c;
+    __syncthreads();
+    uint32_t at = blk_off[blockIdx.x];
+    for (int w = 0; w < wave; ++w) at += s[w];
+#pragma unroll
+    for (int ch = 0; ch < CT_CHUNKS; ++ch) {
+        if ((m[ch] >> lane) & 1ull) {
+            const uint32_t pos = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(m[ch] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[ch], 0u));
+            const uint64_t v = base + 64 * ch;
+            root_out[pos] = (int64_t)v;
+            size_out[pos] = (int64_t)size[v];
+        }
+        at += (uint32_t)__popcll(m[ch]);
+    }
+}
+
+// the table of the labelling in (L, size) of n voxels on `st`, read back into `out`.  blk / tab: work buffers of the
+// current device; d_total: one device word.  The table's buffer is sized from the count, not from n.
+static int ccl_table(const uint32_t* L, const uint32_t* size, uint32_t n, DevBuf& blk, DevBuf& tab, uint32_t* d_total,
+                     hipStream_t st, r2s_int::ComponentTable& out)
+{
+    const uint32_t nblk = (uint32_t)(((uint64_t)n + CT_TILE - 1) / CT_TILE);
+    ENSURE(blk, sizeof(uint32_t) * (size_t)nblk);
+    ccl_table_count_kernel<<<nblk, 256, 0, st>>>(L, n, blk.as<uint32_t>());
+    ccl_table_scan_kernel<<<1, 1024, 0, st>>>(blk.as<uint32_t>(), nblk, d_total);
+    uint32_t m = 0;
+    HIP_TRY(hipMemcpyAsync(&m, d_total, sizeof m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out.root.resize(m);
+    out.size.resize(m);
+    if (m == 0) return 0;
+    ENSURE(tab, 2 * sizeof(int64_t) * (size_t)m);
+    int64_t* d_root = tab.as<int64_t>();
+    int64_t* d_size = d_root + m;
+    ccl_table_scatter_kernel<<<nblk, 256, 0, st>>>(L, size, n, blk.as<uint32_t>(), d_root, d_size);
+    HIP_TRY(hipMemcpyAsync(out.root.data(), d_root, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out.size.data(), d_size, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the work arrays of remove_artifacts_dev / analyze_components_dev, kept between calls per device (r2s_release_cache
+// frees them): allocating and freeing 1.6 GB per call cost as much as a kernel of the stage
 struct CclWork {
-    DevBuf L, size, roots, cnt;
+    DevBuf L, size, roots, cnt, blk, tab;
 };
 static std::mutex g_ccl_mutex;
 static std::map<int, CclWork> g_ccl_work;
@@ -336,21 +447,18 @@ static void release_ccl_work()
     for (auto& kv : g_ccl_work) {
         (void)hipSetDevice(kv.first);
         kv.second.L.release(); kv.second.size.release(); kv.second.roots.release(); kv.second.cnt.release();
+        kv.second.blk.release(); kv.second.tab.release();
     }
     g_ccl_work.clear();
 }
 
-static int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double threshold, double min_ratio,
-                                hipStream_t st, int64_t* n_flipped)
+// The labelling of {sdf >= threshold} shared by removal and analysis, on the device's work arrays (the caller holds
+// g_ccl_mutex): afterwards L[v] is v's head (or root, or NOLABEL) and size[r] the size of every root r.  h[8] comes back
+// with [4] = number of roots and, when `counters`, [0] largest size, [1] smallest root having it, [3] interior count
+// (from the list of roots, or from the sweeps over all counters when the list overflowed).
+static int ccl_label(const double* d_sdf, uint32_t n, int nx, int ny, int nz, double threshold, hipStream_t st, CclWork& Wk,
+                     bool counters, uint32_t h[8])
 {
-    const int64_t n64 = g->ngp;
-    if (n64 <= 0 || n64 >= 0xFFFFFFFFll) return fail(R2S_ERR_ARG, "grid too large for 32-bit labels");
-    const uint32_t n = (uint32_t)n64;
-    const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_ccl_mutex);   // (one call at a time uses the device's work arrays)
-    CclWork& Wk = g_ccl_work[dev];
     DevBuf &L = Wk.L, &size = Wk.size, &roots = Wk.roots, &cnt = Wk.cnt;
     // roots_cap: a component has a head that is its own root; more roots than this (noise at the voxel scale) -> the counters
     // of the overflow are still zeroed, only the list is short: the sweeps over all counters take over (below)
@@ -362,8 +470,9 @@ static int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double thresho
     ENSURE(roots, sizeof(uint32_t) * (size_t)roots_max);
     ENSURE(cnt, 64);
     const unsigned nb = (n + 255) / 256;
-    uint32_t h[8] = {0, NOLABEL, 0, 0, 0, 0, 0, 0};   // [4]: number of roots
-    HIP_TRY(hipMemcpyAsync(cnt.p, h, sizeof h, hipMemcpyHostToDevice, st));
+    const uint32_t h0[8] = {0, NOLABEL, 0, 0, 0, 0, 0, 0};
+    std::memcpy(h, h0, sizeof h0);
+    HIP_TRY(hipMemcpyAsync(cnt.p, h, 8 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     static const bool split_env = getenv("R2S_CCL_SPLIT") && atoi(getenv("R2S_CCL_SPLIT"));   // (tests / A-B: sizes in a pass of their own)
     ccl_init_kernel<<<nb, 256, 0, st>>>(d_sdf, n, nx, threshold, L.as<uint32_t>(), split_env ? nullptr : size.as<uint32_t>());
     ccl_union_kernel<<<nb, 256, 0, st>>>(L.as<uint32_t>(), nx, ny, nz);
@@ -375,33 +484,77 @@ static int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double thresho
         ccl_compress_heads_sizes_kernel<<<(nb < 8192u ? nb : 8192u), 256, 0, st>>>(L.as<uint32_t>(), n, nx, size.as<uint32_t>(), roots.as<uint32_t>(),
                                                                                   roots_cap, cnt.as<uint32_t>() + 4);
     }
-    ccl_roots_max_kernel<<<1, 1024, 0, st>>>(size.as<uint32_t>(), roots.as<uint32_t>(), cnt.as<uint32_t>() + 4, roots_cap,
-                                             cnt.as<uint32_t>());
-    HIP_TRY(hipMemcpyAsync(h, cnt.p, sizeof h, hipMemcpyDeviceToHost, st));
+    if (counters)
+        ccl_roots_max_kernel<<<1, 1024, 0, st>>>(size.as<uint32_t>(), roots.as<uint32_t>(), cnt.as<uint32_t>() + 4, roots_cap,
+                                                 cnt.as<uint32_t>());
+    HIP_TRY(hipMemcpyAsync(h, cnt.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h[4] > roots_cap) {   // (noise at the voxel scale: more components than the list holds - the sweeps over all counters)
-        uint32_t h0[8] = {0, NOLABEL, 0, 0, 0, 0, 0, 0};
         HIP_TRY(hipMemcpyAsync(cnt.p, h0, sizeof h0, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(size.p, 0, sizeof(uint32_t) * (size_t)n, st));
         ccl_count_kernel<<<(nb < 4096u ? nb : 4096u), 256, 0, st>>>(L.as<uint32_t>(), n, size.as<uint32_t>());
-        ccl_max_kernel<<<nb, 256, 0, st>>>(size.as<uint32_t>(), n, cnt.as<uint32_t>());
-        ccl_argmax_kernel<<<nb, 256, 0, st>>>(size.as<uint32_t>(), n, cnt.as<uint32_t>());
-        HIP_TRY(hipMemcpyAsync(h, cnt.p, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (counters) {
+            ccl_max_kernel<<<nb, 256, 0, st>>>(size.as<uint32_t>(), n, cnt.as<uint32_t>());
+            ccl_argmax_kernel<<<nb, 256, 0, st>>>(size.as<uint32_t>(), n, cnt.as<uint32_t>());
+            const uint32_t nroots = h[4];
+            HIP_TRY(hipMemcpyAsync(h, cnt.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            h[4] = nroots;
+        }
     }
+    return 0;
+}
+
+static int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double threshold, double min_ratio,
+                                hipStream_t st, int64_t* n_flipped, r2s_int::ComponentTable* table = nullptr)
+{
+    const int64_t n64 = g->ngp;
+    if (n64 <= 0 || n64 >= 0xFFFFFFFFll) return fail(R2S_ERR_ARG, "grid too large for 32-bit labels");
+    const uint32_t n = (uint32_t)n64;
+    const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_ccl_mutex);   // (one call at a time uses the device's work arrays)
+    CclWork& Wk = g_ccl_work[dev];
+    uint32_t h[8];
+    int rc = ccl_label(d_sdf, n, nx, ny, nz, threshold, st, Wk, true, h);
+    if (rc) return rc;
+    // the table of the same labelling (the flip below changes neither L nor size)
+    if (table && (rc = ccl_table(Wk.L.as<uint32_t>(), Wk.size.as<uint32_t>(), n, Wk.blk, Wk.tab, Wk.cnt.as<uint32_t>() + 8, st, *table)))
+        return rc;
+    const unsigned nb = (n + 255) / 256;
     int64_t flipped = 0;
     if (h[3] != 0) {   // interior_count == 0 -> nothing to do (:150-153)
         // min_component_size = max(1, round(Int, ratio*largest)), Julia round = ties to even (:206)
         long long ms = (long long)std::nearbyint(min_ratio * (double)h[0]);
         if (ms < 1) ms = 1;
         const uint32_t min_size = ms > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)ms;
-        ccl_flip_l_kernel<<<nb, 256, 0, st>>>(d_sdf, L.as<uint32_t>(), size.as<uint32_t>(), n, h[1], min_size, cnt.as<uint32_t>());
-        HIP_TRY(hipMemcpyAsync(h, cnt.p, sizeof h, hipMemcpyDeviceToHost, st));
+        ccl_flip_l_kernel<<<nb, 256, 0, st>>>(d_sdf, Wk.L.as<uint32_t>(), Wk.size.as<uint32_t>(), n, h[1], min_size, Wk.cnt.as<uint32_t>());
+        HIP_TRY(hipMemcpyAsync(h, Wk.cnt.p, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         flipped = h[2];
     }
     if (n_flipped) *n_flipped = flipped;
     return 0;
+}
+
+// analyze_sdf_components (SdfArtifactRemoval.jl:256-311) on a device-resident field: the labelling of removal and its
+// table; d_sdf is only read
+static int analyze_components_dev(const double* d_sdf, const r2s_grid* g, double threshold, hipStream_t st,
+                                  r2s_int::ComponentTable& table)
+{
+    const int64_t n64 = g->ngp;
+    if (n64 <= 0 || n64 >= 0xFFFFFFFFll) return fail(R2S_ERR_ARG, "grid too large for 32-bit labels");
+    const uint32_t n = (uint32_t)n64;
+    const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_ccl_mutex);
+    CclWork& Wk = g_ccl_work[dev];
+    uint32_t h[8];
+    int rc = ccl_label(d_sdf, n, nx, ny, nz, threshold, st, Wk, false, h);
+    if (rc) return rc;
+    return ccl_table(Wk.L.as<uint32_t>(), Wk.size.as<uint32_t>(), n, Wk.blk, Wk.tab, Wk.cnt.as<uint32_t>() + 8, st, table);
 }
 
 // ====================================================================================
@@ -2764,14 +2917,16 @@ int exchange_halo_slabs(const std::vector<Slab>& S, const std::vector<void*>& ba
     return sync_slabs(S);
 }
 
-int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double threshold, double min_ratio, int64_t* n_flipped)
+int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double threshold, double min_ratio, int64_t* n_flipped,
+                           ComponentTable* table)
 {
     const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1;
     const int64_t plane = (int64_t)nx * ny;
     const size_t G = S.size();
     int rc = 0;
-    SlabBufs L(S), root(S), size(S), cnt(S), idx(S), val(S);
+    SlabBufs L(S), root(S), size(S), cnt(S), idx(S), val(S), tblk(S), ttab(S);
     std::vector<uint32_t> nvox(G, 0);
+    std::vector<ComponentTable> local(table ? G : 0);                 // per slab: (local root, size) in root order
     std::vector<std::vector<uint32_t>> broots(G);                    // roots of slab q that touch an interface
     std::vector<std::vector<uint32_t>> top(G), bot(G);               // root labels of the last / first owned plane
     struct Cls { uint64_t size = 0, min_gid = ~0ull; };
@@ -2824,9 +2979,13 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
         top[q].resize((size_t)plane); bot[q].resize((size_t)plane);
         SLAB_HIP(hipMemcpy(bot[q].data(), root.at<uint32_t>(q), 4 * (size_t)plane, hipMemcpyDeviceToHost));
         SLAB_HIP(hipMemcpy(top[q].data(), root.at<uint32_t>(q) + (size_t)(nvox[q] - plane), 4 * (size_t)plane, hipMemcpyDeviceToHost));
+        // the slab's component table: before the merge below rewrites size[] of the interface roots
+        if (table) SLAB_TRY(ccl_table(L.at<uint32_t>(q), size.at<uint32_t>(q), nvox[q], tblk.b[q], ttab.b[q], cnt.at<uint32_t>(q) + 8,
+                                      d.stream, local[q]));
     }
     if (interior == 0) {   // SdfArtifactRemoval.jl:150-153
         if (n_flipped) *n_flipped = 0;
+        if (table) *table = ComponentTable();
         return 0;
     }
     // ---- interface merge on the host: union-find over the roots that touch an interface ----
@@ -2874,6 +3033,37 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
                 cls[c].size += bsz[q][pos[q]++];
                 const uint64_t gid = (uint64_t)S[q].k0 * (uint64_t)plane + (uint32_t)keys[i];   // the root's index in the whole grid
                 cls[c].min_gid = std::min(cls[c].min_gid, gid);
+            }
+        }
+        if (table) {
+            // the whole grid's table: roots that touch no interface keep their slab's entry (in grid numbering, already in
+            // root order: slabs in k order), every interface class is one component keyed by its smallest member index
+            ComponentTable inner;
+            for (size_t q : order) {
+                const uint64_t off = (uint64_t)S[q].k0 * (uint64_t)plane;
+                for (size_t e = 0; e < local[q].root.size(); ++e) {
+                    if (std::binary_search(keys.begin(), keys.end(), key_of(q, (uint32_t)local[q].root[e]))) continue;
+                    inner.root.push_back((int64_t)(off + (uint64_t)local[q].root[e]));
+                    inner.size.push_back(local[q].size[e]);
+                }
+            }
+            std::vector<std::pair<uint64_t, uint64_t>> xs;
+            for (size_t i = 0; i < keys.size(); ++i)
+                if (par[i] == i) xs.emplace_back(cls[i].min_gid, cls[i].size);
+            std::sort(xs.begin(), xs.end());
+            table->root.clear();
+            table->size.clear();
+            table->root.reserve(inner.root.size() + xs.size());
+            table->size.reserve(inner.root.size() + xs.size());
+            size_t a = 0, b = 0;
+            while (a < inner.root.size() || b < xs.size()) {
+                if (b == xs.size() || (a < inner.root.size() && (uint64_t)inner.root[a] < xs[b].first)) {
+                    table->root.push_back(inner.root[a]);
+                    table->size.push_back(inner.size[a++]);
+                } else {
+                    table->root.push_back((int64_t)xs[b].first);
+                    table->size.push_back((int64_t)xs[b++].second);
+                }
             }
         }
         // every interface root now carries its class size (saturated): the keep test of a slab sees the whole component
@@ -3382,10 +3572,14 @@ done:
 }
 
 int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double threshold, double min_ratio, hipStream_t st,
-                         int64_t* n_flipped)
+                         int64_t* n_flipped, ComponentTable* table)
 {
-    return ::remove_artifacts_dev(d_sdf, g, threshold, min_ratio, st, n_flipped);
+    return ::remove_artifacts_dev(d_sdf, g, threshold, min_ratio, st, n_flipped, table);
 }
+
+// the calling thread's last component table (r2s_last_components)
+static thread_local ComponentTable g_last_components;
+void set_last_components(ComponentTable&& t) { g_last_components = std::move(t); }
 int rbf_smooth_dev(const double* d_sdf, const r2s_grid* g, int is_interp, int smooth, double kthr, double target_volume,
                    float* d_fine_out, float* th_out, int* cg_iters, const std::function<int(int64_t, int64_t)>* fine_chunk,
                    void* workspace, bool fine_early)
@@ -3428,6 +3622,64 @@ int r2s_remove_artifacts_dev(double* d_sdf, const r2s_grid* grid, double thresho
 {
     if (!d_sdf || !grid) return fail(R2S_ERR_ARG, "null argument");
     return remove_artifacts_dev(d_sdf, grid, threshold, min_ratio, (hipStream_t)stream, n_flipped);
+}
+
+// the first min(capacity, n) entries of the thread's last table, n in *n_components
+static int copy_components(int64_t* roots_out, int64_t* sizes_out, int64_t capacity, int64_t* n_components)
+{
+    const r2s_int::ComponentTable& t = r2s_int::g_last_components;
+    const int64_t m = (int64_t)t.root.size();
+    *n_components = m;
+    const int64_t k = std::min(capacity, m);
+    if (k > 0) {
+        std::memcpy(roots_out, t.root.data(), sizeof(int64_t) * (size_t)k);
+        std::memcpy(sizes_out, t.size.data(), sizeof(int64_t) * (size_t)k);
+    }
+    return 0;
+}
+
+static int components_args(int64_t* roots_out, int64_t* sizes_out, int64_t capacity, int64_t* n_components)
+{
+    if (!n_components || capacity < 0 || (capacity > 0 && (!roots_out || !sizes_out)))
+        return fail(R2S_ERR_ARG, "component table: null output with capacity > 0, negative capacity or null n_components");
+    return 0;
+}
+
+int r2s_analyze_components(const double* sdf, const r2s_grid* grid, double threshold, int32_t device, int64_t* roots_out,
+                           int64_t* sizes_out, int64_t capacity, int64_t* n_components)
+{
+    if (!sdf || !grid) return fail(R2S_ERR_ARG, "null argument");
+    int rc = components_args(roots_out, sizes_out, capacity, n_components);
+    if (rc || (rc = use_device(device))) return rc;
+    DevBuf d;
+    ENSURE(d, sizeof(double) * (size_t)grid->ngp);
+    r2s_int::ComponentTable t;
+    hipError_t e = hipMemcpy(d.p, sdf, sizeof(double) * (size_t)grid->ngp, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(R2S_ERR_HIP, "%s", hipGetErrorString(e));
+    if (!rc) rc = analyze_components_dev(d.as<double>(), grid, threshold, nullptr, t);
+    d.release();
+    if (rc) return rc;
+    r2s_int::set_last_components(std::move(t));
+    return copy_components(roots_out, sizes_out, capacity, n_components);
+}
+
+int r2s_analyze_components_dev(const double* d_sdf, const r2s_grid* grid, double threshold, void* stream, int64_t* roots_out,
+                               int64_t* sizes_out, int64_t capacity, int64_t* n_components)
+{
+    if (!d_sdf || !grid) return fail(R2S_ERR_ARG, "null argument");
+    int rc = components_args(roots_out, sizes_out, capacity, n_components);
+    if (rc || (rc = check_device(0))) return rc;
+    r2s_int::ComponentTable t;
+    if ((rc = analyze_components_dev(d_sdf, grid, threshold, (hipStream_t)stream, t))) return rc;
+    r2s_int::set_last_components(std::move(t));
+    return copy_components(roots_out, sizes_out, capacity, n_components);
+}
+
+int r2s_last_components(int64_t* roots_out, int64_t* sizes_out, int64_t capacity, int64_t* n_components)
+{
+    int rc = components_args(roots_out, sizes_out, capacity, n_components);
+    if (rc) return rc;
+    return copy_components(roots_out, sizes_out, capacity, n_components);
 }
 
 int r2s_volume_from_sdf(const float* sdf, int64_t nx, int64_t ny, int64_t nz, float edge, float iso,

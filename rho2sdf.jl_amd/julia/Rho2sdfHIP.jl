@@ -68,7 +68,8 @@ struct R2SOptions                     # mirrors r2s_options (= Rho2sdfOptions, R
     skip_rbf::Int32
     true_min::Int32
     sign_no_inner::Int32
-    reserved::NTuple{3,Int32}
+    analyze_components::Int32         # 1 (with remove_artifacts): keep the component table of the removal's labelling
+    reserved::NTuple{2,Int32}
 end
 
 struct R2SRunInfo                     # mirrors r2s_run_info
@@ -136,14 +137,14 @@ function rho2sdf_hip(taskName::String, X::Vector{Vector{Float64}}, IEN::Vector{V
     sdf_grid = options.sdf_grid_setup == :manual ? interactive_sdf_grid_setup(mesh) :
                noninteractive_sdf_grid_setup(mesh)                                 # :141-145
     smooth = options.rbf_grid == :same ? 1 : 2                                     # :222
+    want_raw = options.remove_artifacts && options.export_analysis                 # :177-189 analyses and exports the field before cleanup
     o = R2SOptions(options.threshold_density === nothing ? NaN : Float64(options.threshold_density), 1.1,
                    options.artifact_min_component_ratio, 1e-3, etype(T), Int32(options.rbf_interp), Int32(smooth),
                    Int32(options.remove_artifacts), Int32(-1), N_GPUS[], Int32(0), Int32(0), Int32(SIGN_NO_INNER[] ? 1 : 0),
-                   (0, 0, 0))
+                   Int32(want_raw), (0, 0))
     ρₙ = Vector{Float64}(undef, mesh.nnp)
     sdf_dists = pinned(Float64, sdf_grid.ngp)
     fine_sdf = pinned(Float32, ((sdf_grid.N .* smooth) .+ 1)...)
-    want_raw = options.remove_artifacts && options.export_analysis                 # :181-189 exports the field before cleanup
     sdf_raw = want_raw ? pinned(Float64, sdf_grid.ngp) : nothing
     info = Ref{R2SRunInfo}()
     check(ccall((:r2s_rho2sdf, LIB[]), Cint,
@@ -156,7 +157,10 @@ function rho2sdf_hip(taskName::String, X::Vector{Vector{Float64}}, IEN::Vector{V
     if options.export_nodal_densities                                              # :159-162
         exportToVTU(taskName * "_nodal_densities.vtu", X, IEN, T == HEX8 ? 12 : 10, ρₙ)
     end
-    if want_raw                                                                    # :181-206
+    if want_raw                                                                    # :177-206
+        # components_before (:178): the table of the labelling the removal ran on the raw field; a local in the
+        # reference too (not returned)
+        print_components(last_components())
         exportSdfToVTI(taskName * "_SDF_raw_$(element_name)_B-$(B).vti", sdf_grid, sdf_raw, "distance")
         info[].n_flipped > 0 &&
             exportSdfToVTI(taskName * "_SDF_cleaned_$(element_name)_B-$(B).vti", sdf_grid, sdf_dists, "distance")
@@ -265,6 +269,46 @@ function remove_sdf_artifacts_hip!(sdf::Vector{Float64}, grid::MeshGrid.Grid; th
     return n[]
 end
 
+# analyze_sdf_components (src/SignedDistances/SdfArtifactRemoval.jl:256-311) -> Dict{Int,Int}, printing the summary of
+# :297-308.  Keys are the Julia linear index of each component's FIRST voxel (root + 1): the reference keys a component
+# by its union-find root (union by rank, :41-60), which depends on the union order.  Partition and sizes are the same.
+# The field is only read.
+function analyze_sdf_components_hip(sdf::Vector{Float64}, grid::MeshGrid.Grid; threshold = 0.0)
+    length(sdf) == grid.ngp || error("SDF values length ($(length(sdf))) doesn't match grid points ($(grid.ngp))")
+    n = Ref{Int64}(0)
+    check(ccall((:r2s_analyze_components, LIB[]), Cint,
+                (Ptr{Float64}, Ref{R2SGrid}, Float64, Int32, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Int64}),
+                sdf, Ref(R2SGrid(grid)), Float64(threshold), Int32(-1), C_NULL, C_NULL, 0, n))
+    comps = last_components()
+    print_components(comps)
+    return comps
+end
+
+# the calling thread's last component table (count first, then copy: no second labelling) as root + 1 => size
+function last_components()
+    n = Ref{Int64}(0)
+    check(ccall((:r2s_last_components, LIB[]), Cint, (Ptr{Int64}, Ptr{Int64}, Int64, Ref{Int64}), C_NULL, C_NULL, 0, n))
+    roots = Vector{Int64}(undef, n[]); sizes = Vector{Int64}(undef, n[])
+    n[] > 0 && check(ccall((:r2s_last_components, LIB[]), Cint, (Ptr{Int64}, Ptr{Int64}, Int64, Ref{Int64}),
+                           roots, sizes, n[], n))
+    return Dict{Int,Int}(r + 1 => s for (r, s) in zip(roots, sizes))
+end
+
+function print_components(comps::Dict{Int,Int})                                   # :263-266, :297-308
+    if isempty(comps)
+        println("No interior nodes found")
+        return
+    end
+    sizes = sort!(collect(values(comps)), rev = true)
+    println("Component analysis results:")
+    println("  Total components: $(length(sizes))")
+    println("  Largest component: $(sizes[1]) nodes")
+    if length(sizes) > 1
+        println("  Second largest: $(sizes[2]) nodes")
+        println("  Smallest component: $(sizes[end]) nodes")
+    end
+end
+
 # calculate_volume_from_sdf (src/SdfSmoothing/CalcVolumeFromSDF.jl:26-125); `grid` is the reference's array of
 # per-voxel coordinate vectors - only the spacing is used (:36-39)
 function calculate_volume_from_sdf_hip(sdf::Array{Float32,3}, grid::AbstractArray{Vector{Float32},3}; iso_threshold = 0.0f0,
@@ -309,6 +353,8 @@ function enable!(libpath::AbstractString = LIB[]; n_gpus::Integer = 1)
         Sign_Detection(mesh::Mesh, grid::Grid, points::Matrix, ρₙ::Vector{Float64}, ρₜ::Float64) =
             $(Sign_Detection_hip)(mesh, grid, points, ρₙ, ρₜ)
         remove_sdf_artifacts!(sdf::Vector{Float64}, grid::Grid; kw...) = $(remove_sdf_artifacts_hip!)(sdf, grid; kw...)
+        analyze_sdf_components(sdf_values::Vector{Float64}, grid::Grid; threshold::Float64 = 0.0) =
+            $(analyze_sdf_components_hip)(sdf_values, grid; threshold = threshold)
     end
     @eval MeshGrid begin
         DenseInNodes(mesh::Mesh, rho::Vector{Float64}) = $(DenseInNodes_hip)(mesh, rho)
