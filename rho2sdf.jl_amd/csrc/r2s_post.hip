@@ -1123,8 +1123,6 @@ static int build_stencil(int s, const int frac[3], Stencil* st, double R2)
 // table-driven evaluation must stand aside
 static int build_stencils(int smooth, double kthr, std::vector<Stencil>& sts, bool* capped)
 {
-    if (!(kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0))
-        return fail(R2S_ERR_ARG, "kernel threshold must be in [%g, 1): got %g", R2S_RBF_MIN_KERNEL_THRESHOLD, kthr);
     sts.assign(1 + (size_t)smooth * smooth * smooth, Stencil{});
     const double R2 = -std::log(kthr);
     int most = 0;
@@ -1353,12 +1351,14 @@ struct RbfLutGeom {
     const uint8_t *vx, *vy, *vz;   // [2R+1][n_axis]: variant id of (index, offset), 255 = neighbour outside the lattice
     const float* T;                // [(2R+1)^3][NV][NV][NV], x variant fastest; 0 = entry absent (val <= threshold)
     const double* TA;              // [(2R+1)^3][NVA]^3: the kernel values of the EVALUATION (rbf_apply_kernel's arithmetic); 0 = beyond max_distance
-    const double* TA16;            // the same with RBF_NV slots per axis (lattice-to-lattice evaluation with <= 15 variants), or null
     // the same values in the layout of the row-walk kernels (r2s_rbf_walk.hpp), or null
     const float* WT;               // matrix entries, RBF_NV slots per axis
     const double* WA;              // evaluation, wa_nv slots per axis
     int wa_nv;
 };
+// the forms of the CG's product and of the evaluations (one choice per smoothing call: rbf_plan)
+enum class RbfMatvec { walk, lut, k, fly };   // row walk (r2s_rbf_walk.hpp), table kernels, materialised matrix, on the fly
+enum class RbfEval { walk, lut, fly };
 struct RbfLutVals {
     float v[3][7][RBF_NVA];        // the variant values per axis and offset
     int R;
@@ -1421,19 +1421,18 @@ constexpr RbfTapOrder<R> rbf_tap_order()
 // one row through per-lane clamped addresses and predicates: rows of the first / last R planes, of wavefronts that
 // straddle two planes and of a slab whose halo ends nearby
 // the table of the evaluation (rbf_apply_kernel with targets = lattice points): same differences, that kernel's arithmetic
-// (nv: variant slots per axis of this table - RBF_NVA, or RBF_NV for the compact table of the lattice-to-lattice evaluation)
-__global__ void __launch_bounds__(256) rbf_lut_build_apply_kernel(const RbfLutVals* __restrict__ Vp, double* __restrict__ TA, int nv = RBF_NVA)
+__global__ void __launch_bounds__(256) rbf_lut_build_apply_kernel(const RbfLutVals* __restrict__ Vp, double* __restrict__ TA)
 {
     const RbfLutVals& V = *Vp;
     __shared__ double etab[64];
     if (threadIdx.x < 64) etab[threadIdx.x] = c_exp2_neg_64[threadIdx.x];
     __syncthreads();
     const int W = 2 * V.R + 1;
-    const int64_t n = (int64_t)W * W * W * nv * nv * nv;
+    const int64_t n = (int64_t)W * W * W * RBF_NVA * RBF_NVA * RBF_NVA;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const int a = (int)(t % nv), b = (int)((t / nv) % nv), c = (int)((t / (nv * nv)) % nv);
-    const int tap = (int)(t / ((int64_t)nv * nv * nv));
+    const int a = (int)(t % RBF_NVA), b = (int)((t / RBF_NVA) % RBF_NVA), c = (int)((t / (RBF_NVA * RBF_NVA)) % RBF_NVA);
+    const int tap = (int)(t / (RBF_NVA * RBF_NVA * RBF_NVA));
     const int di = tap % W, dj = (tap / W) % W, dk = tap / (W * W);
     const float dx = V.v[0][di][a], dy = V.v[1][dj][b], dz = V.v[2][dk][c];
     const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
@@ -1607,106 +1606,6 @@ __global__ void __launch_bounds__(256) rbf_matvec_lut_kernel(RbfLutGeom G, const
     if (t < tend) y[t] = acc;
 }
 
-// The same product with the table rows of a workgroup staged in LDS.  A workgroup = 256 consecutive rows of one Z
-// plane: they span 1-2 (at most RBF_MV_ROWS) lattice rows j, so per neighbour offset it needs one 64-byte table row
-// (16 x variants) per j - 81 x 64 B = 5 KB per j at the default threshold.  The lanes then pick their entry with an LDS
-// read (address = per-lane x variant + immediate) instead of a 64-lane gather from L1/L2, which cost twice what the
-// loads of the vector itself do (timing-only builds without either: 2.5 / 3.9 ms of 5.25 ms at 512^3).
-#define RBF_MV_ROWS 4
-template <int R, int D2>
-__global__ void __launch_bounds__(256) rbf_matvec_lds_kernel(RbfLutGeom G, const float* __restrict__ x, float* __restrict__ y,
-                                                            int64_t t_begin, int64_t t_end, int64_t x_lo, int64_t x_hi)
-{
-    constexpr int W = 2 * R + 1;
-    constexpr RbfTapOrder<R> TO = rbf_tap_order_rowwise<R, D2>();
-    constexpr int NT = TO.n;
-    __shared__ float sT[RBF_MV_ROWS * NT * RBF_NV];
-    const int64_t n = (int64_t)G.nx * G.ny * G.nz;
-    const int64_t tend = t_end >= 0 ? t_end : n;
-    const int64_t first = x_lo, last = x_hi >= 0 ? x_hi : n - 1;
-    const int64_t tb0 = t_begin + (int64_t)blockIdx.x * 256;   // first row of the workgroup
-    if (tb0 >= tend) return;
-    const int64_t tb1 = tb0 + 255 < tend ? tb0 + 255 : tend - 1;
-    const int64_t plane = (int64_t)G.nx * G.ny;
-    const int64_t reach = (int64_t)R * plane + (int64_t)R * G.nx + R;
-    const int k = (int)(tb0 / plane);
-    const int jA = (int)((tb0 - (int64_t)k * plane) / G.nx), jB = (int)((tb1 - (int64_t)k * plane) / G.nx);
-    const bool fast = (tb1 / plane == k) && k >= R && k < G.nz - R && tb0 - reach >= first && tb1 + reach <= last &&
-                      jB - jA + 1 <= RBF_MV_ROWS;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const int64_t t = tb0 + tid;
-    if (!fast) {   // (uniform over the workgroup)
-        if (t < tend) y[t] = rbf_lut_row_clamped<R>(G, x, t, first, last);
-        return;
-    }
-    // ---- table rows of this workgroup -> LDS: sT[jr][q][x variant] ----
-    // two steps so that the loads of a step are independent of each other: (1) one thread per (j row, neighbour) chases
-    // offset -> variants of its plane / row -> position of the 64-byte table row; (2) all threads copy the rows, six
-    // 4-byte loads in flight each (one serial loop of offset look-ups + table load per element spent more time waiting
-    // than the products take)
-    const int nj = jB - jA + 1;
-    __shared__ uint32_t sBase[RBF_MV_ROWS * NT];
-    for (int e = (int)tid; e < nj * NT; e += 256) {
-        const int jr = e / NT, q = e - jr * NT;
-        const int dk = TO.dk[q], dj = TO.dj[q], di = TO.di[q];
-        const uint32_t c = G.vz[dk * G.nz + k];   // (k is interior: never 255)
-        uint32_t b = G.vy[dj * G.ny + jA + jr];
-        b = b != 255u ? b : (uint32_t)(RBF_NV - 1);
-        sBase[e] = ((((uint32_t)((dk * W + dj) * W + di)) * RBF_NV + c) * RBF_NV + b) * RBF_NV;
-    }
-    __syncthreads();
-    const int total = nj * NT * RBF_NV;
-    for (int e0 = 0; e0 < total; e0 += 6 * 256) {
-        float v[6];
-#pragma unroll
-        for (int u = 0; u < 6; ++u) {
-            const int e = e0 + u * 256 + (int)tid;
-            v[u] = e < total ? G.T[sBase[e / RBF_NV] + (uint32_t)(e % RBF_NV)] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < 6; ++u) {
-            const int e = e0 + u * 256 + (int)tid;
-            if (e < total) sT[e] = v[u];
-        }
-    }
-    __syncthreads();
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t tw0 = tb0 + (int64_t)wv * 64;
-    if (tw0 >= tend) return;
-    const int64_t tc = t < tend ? t : tend - 1;   // (idle lanes of the last wavefront repeat its last row)
-    const uint32_t r2 = (uint32_t)(tc - (int64_t)k * plane);
-    const uint32_t j = r2 / (uint32_t)G.nx, i = r2 - j * (uint32_t)G.nx;
-    uint32_t a4[W];   // byte offset of the lane's entry inside a staged table row, plus the offset of its j block
-#pragma unroll
-    for (int d = 0; d < W; ++d) {
-        const uint32_t va = G.vx[d * G.nx + i];
-        a4[d] = (va != 255u ? va : (uint32_t)(RBF_NV - 1)) * 4u + (j - (uint32_t)jA) * (uint32_t)(NT * RBF_NV * 4);
-    }
-    const uint32_t lane4 = lane * 4u;
-    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(x + (tw0 - reach)), 0, (int)((2 * reach + 64) * 4), 0x00020000);
-    float acc = 0.0f;
-#pragma unroll
-    for (int q0 = 0; q0 < NT; q0 += RBF_MATVEC_BATCH) {
-        uint32_t xb[RBF_MATVEC_BATCH];
-        float wb[RBF_MATVEC_BATCH];
-#pragma unroll
-        for (int u = 0; u < RBF_MATVEC_BATCH; ++u) {
-            const int q = q0 + u < NT ? q0 + u : NT - 1;
-            const int dk = TO.dk[q], dj = TO.dj[q], di = TO.di[q];
-            const uint32_t xoff = (uint32_t)(reach + ((int64_t)(dk - R) * G.ny + (dj - R)) * G.nx + (di - R)) * 4u;
-            xb[u] = __builtin_amdgcn_raw_buffer_load_b32(rX, (int)lane4, (int)xoff, 0);
-            wb[u] = *(const float*)((const char*)sT + a4[di] + (uint32_t)(q * RBF_NV * 4));
-        }
-#pragma unroll
-        for (int u = 0; u < RBF_MATVEC_BATCH; ++u) {
-            if (q0 + u >= NT) continue;
-            if (wb[u] != 0.0f) acc += wb[u] * __uint_as_float(xb[u]);
-        }
-    }
-    if (t < tend) y[t] = acc;
-}
-
 #include "r2s_rbf_walk.hpp"
 
 // [t0, t1) / [xlo, xhi] as whole planes, or false
@@ -1723,19 +1622,17 @@ static bool rbf_walk_planes(const RbfLutGeom& LG, int64_t t0, int64_t t1, int64_
     A->xk_lo = (int)(xlo / plane); A->xk_hi = (int)((xhi + 1) / plane) - 1;
     return true;
 }
-static void launch_rbf_matvec_lut(const RbfLutGeom& LG, unsigned nb, hipStream_t st, const float* x, float* y, int64_t t0 = 0,
-                                  int64_t t1 = -1, int64_t xlo = 0, int64_t xhi = -1, double* dot_partial = nullptr)
+// form walk (LG.WT) or lut (LG.T); dot_partial: the row walk also leaves the parts of dot(x, y) there
+static void launch_rbf_matvec_lut(RbfMatvec form, const RbfLutGeom& LG, unsigned nb, hipStream_t st, const float* x, float* y,
+                                  int64_t t0 = 0, int64_t t1 = -1, int64_t xlo = 0, int64_t xhi = -1, double* dot_partial = nullptr)
 {
-    const char* mv_env = getenv("R2S_RBF_MATVEC");
     RbfWalkArgs WAr;
-    if (!mv_env && LG.WT && rbf_walk_supported(LG.R, LG.tap_d2, LG.nx, LG.ny) && rbf_walk_planes(LG, t0, t1, xlo, xhi, &WAr)) {
+    if (form == RbfMatvec::walk && rbf_walk_planes(LG, t0, t1, xlo, xhi, &WAr)) {
         WAr.T = LG.WT; WAr.x = x; WAr.y = y; WAr.dot_partial = dot_partial;
         rbf_walk_launch(0, RBF_NV, WAr, st);
         return;
     }
-    const bool global_only = mv_env && !strcmp(mv_env, "lutg");   // table entries gathered from L1/L2 (the tests compare)
-    if (LG.R == 2 && LG.tap_d2 == 7 && !global_only) rbf_matvec_lds_kernel<2, 7><<<nb, 256, 0, st>>>(LG, x, y, t0, t1, xlo, xhi);   // threshold 1e-3 (default)
-    else if (LG.R == 2 && LG.tap_d2 == 7) rbf_matvec_lut_kernel<2, 7><<<nb, 256, 0, st>>>(LG, x, y, t0, t1, xlo, xhi);
+    if (LG.R == 2 && LG.tap_d2 == 7) rbf_matvec_lut_kernel<2, 7><<<nb, 256, 0, st>>>(LG, x, y, t0, t1, xlo, xhi);   // threshold 1e-3 (default)
     else if (LG.R == 1) rbf_matvec_lut_kernel<1, -1><<<nb, 256, 0, st>>>(LG, x, y, t0, t1, xlo, xhi);
     else if (LG.R == 2) rbf_matvec_lut_kernel<2, -1><<<nb, 256, 0, st>>>(LG, x, y, t0, t1, xlo, xhi);
     else rbf_matvec_lut_kernel<3, -1><<<nb, 256, 0, st>>>(LG, x, y, t0, t1, xlo, xhi);
@@ -1825,101 +1722,6 @@ __global__ void __launch_bounds__(256) rbf_apply_lut_kernel(RbfGeom G, RbfLutGeo
     }
     if (t < tend) out[t] = acc + add;
 }
-// The lattice-to-lattice evaluation (the LSF of the level bisection) with the table rows of a workgroup staged in LDS, as
-// in rbf_matvec_lds_kernel: with <= 15 variants per offset a row of the compact table TA16 is 128 bytes, 81 rows = 10 KB
-// per lattice row j; a workgroup of 256 consecutive targets spans at most RBF_AP_ROWS of them (else: the gathered form).
-#define RBF_AP_ROWS 2
-template <int R, int D2>
-__global__ void __launch_bounds__(256) rbf_apply_lds_kernel(RbfGeom G, RbfLutGeom L, const float* __restrict__ w,
-                                                           const Stencil* __restrict__ stencils, float add, float* __restrict__ out,
-                                                           int64_t t_begin, int64_t t_end, int64_t x_lo, int64_t x_hi)
-{
-    constexpr int W = 2 * R + 1;
-    constexpr RbfTapOrder<R> TO = rbf_tap_order<R, D2>();
-    constexpr int NT = TO.n;
-    __shared__ double sT[RBF_AP_ROWS * NT * RBF_NV];
-    __shared__ uint32_t sBase[RBF_AP_ROWS * NT];
-    __shared__ double etab[64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const int64_t n = (int64_t)G.nx * G.ny * G.nz;
-    const int64_t tend = t_end >= 0 ? t_end : n;
-    const int64_t first = x_lo, last = x_hi >= 0 ? x_hi : n - 1;
-    const int64_t tb0 = t_begin + (int64_t)blockIdx.x * 256;
-    if (tb0 >= tend) return;
-    const int64_t tb1 = tb0 + 255 < tend ? tb0 + 255 : tend - 1;
-    const int64_t plane = (int64_t)G.nx * G.ny;
-    const int64_t reach = (int64_t)R * plane + (int64_t)R * G.nx + R;
-    const int k = (int)(tb0 / plane);
-    const int jA = (int)((tb0 - (int64_t)k * plane) / G.nx), jB = (int)((tb1 - (int64_t)k * plane) / G.nx);
-    const bool fast = (tb1 / plane == k) && k >= R && k < G.nz - R && tb0 - reach >= first && tb1 + reach <= last &&
-                      jB - jA + 1 <= RBF_AP_ROWS;
-    const int64_t t = tb0 + tid;
-    if (!fast) {   // (uniform over the workgroup)
-        if (tid < 64) etab[tid] = c_exp2_neg_64[tid];
-        __syncthreads();
-        if (t < tend) out[t] = rbf_apply_point(G, w, 1, G.nx, G.ny, G.cx, G.cy, G.cz, stencils, etab, t) + add;
-        return;
-    }
-    const int nj = jB - jA + 1;
-    for (int e = (int)tid; e < nj * NT; e += 256) {
-        const int jr = e / NT, q = e - jr * NT;
-        const int dk = TO.dk[q], dj = TO.dj[q], di = TO.di[q];
-        const uint32_t c = L.vz[dk * G.nz + k];   // (k is interior: never 255)
-        uint32_t b = L.vy[dj * G.ny + jA + jr];
-        b = b != 255u ? b : (uint32_t)(RBF_NV - 1);
-        sBase[e] = ((((uint32_t)((dk * W + dj) * W + di)) * RBF_NV + c) * RBF_NV + b) * RBF_NV;
-    }
-    __syncthreads();
-    const int total = nj * NT * RBF_NV;
-    for (int e0 = 0; e0 < total; e0 += 6 * 256) {
-        double v[6];
-#pragma unroll
-        for (int u = 0; u < 6; ++u) {
-            const int e = e0 + u * 256 + (int)tid;
-            v[u] = e < total ? L.TA16[sBase[e / RBF_NV] + (uint32_t)(e % RBF_NV)] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 6; ++u) {
-            const int e = e0 + u * 256 + (int)tid;
-            if (e < total) sT[e] = v[u];
-        }
-    }
-    __syncthreads();
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t tw0 = tb0 + (int64_t)wv * 64;
-    if (tw0 >= tend) return;
-    const int64_t tc = t < tend ? t : tend - 1;
-    const uint32_t r2 = (uint32_t)(tc - (int64_t)k * plane);
-    const uint32_t j = r2 / (uint32_t)G.nx, i = r2 - j * (uint32_t)G.nx;
-    uint32_t a8[W];   // byte offset of the lane's entry inside a staged row of doubles, plus the offset of its j block
-#pragma unroll
-    for (int d = 0; d < W; ++d) {
-        const uint32_t va = L.vx[d * G.nx + i];
-        a8[d] = (va != 255u ? va : (uint32_t)(RBF_NV - 1)) * 8u + (j - (uint32_t)jA) * (uint32_t)(NT * RBF_NV * 8);
-    }
-    const uint32_t lane4 = lane * 4u;
-    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(w + (tw0 - reach)), 0, (int)((2 * reach + 64) * 4), 0x00020000);
-    float acc = 0.0f;
-#pragma unroll
-    for (int q0 = 0; q0 < NT; q0 += RBF_APPLY_BATCH) {
-        uint32_t wb[RBF_APPLY_BATCH];
-#pragma unroll
-        for (int u = 0; u < RBF_APPLY_BATCH; ++u) {
-            const int q = q0 + u < NT ? q0 + u : NT - 1;
-            const int dk = TO.dk[q], dj = TO.dj[q], di = TO.di[q];
-            const uint32_t xoff = (uint32_t)(reach + ((int64_t)(dk - R) * G.ny + (dj - R)) * G.nx + (di - R)) * 4u;
-            wb[u] = __builtin_amdgcn_raw_buffer_load_b32(rX, (int)lane4, (int)xoff, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < RBF_APPLY_BATCH; ++u) {
-            if (q0 + u >= NT) continue;
-            const double e = *(const double*)((const char*)sT + a8[TO.di[q0 + u]] + (uint32_t)((q0 + u) * RBF_NV * 8));
-            if (e != 0.0) acc = (float)((double)acc + (double)__uint_as_float(wb[u]) * e);
-        }
-    }
-    if (t < tend) out[t] = acc + add;
-}
 
 // does the run-time stencil visit the neighbours in the order the kernel above has compiled in?
 static bool rbf_stencil_is_canonical(const Stencil& S, int R, int D2)
@@ -1935,24 +1737,22 @@ static bool rbf_stencil_is_canonical(const Stencil& S, int R, int D2)
                 }
     return q == S.n;
 }
-// true if launched; false: this (R, tap_d2) has no table kernel -> the caller evaluates on the fly
-static bool launch_rbf_apply_lut(const RbfGeom& G, const RbfLutGeom& LG, const Stencil& host_stencil, unsigned nb, hipStream_t st,
-                                 const float* w, const float* tx, const float* ty, const float* tz, const Stencil* d_stencil, float add,
-                                 float* out, int64_t t0 = 0, int64_t t1 = -1, int64_t xlo = 0, int64_t xhi = -1)
+// form walk (LG.WA) or lut (LG.TA).  True if launched; false: no table for this grid, or this (R, tap_d2) has no table
+// kernel -> the caller evaluates on the fly
+static bool launch_rbf_apply_lut(RbfEval form, const RbfGeom& G, const RbfLutGeom& LG, const Stencil& host_stencil, unsigned nb,
+                                 hipStream_t st, const float* w, const float* tx, const float* ty, const float* tz,
+                                 const Stencil* d_stencil, float add, float* out, int64_t t0 = 0, int64_t t1 = -1, int64_t xlo = 0,
+                                 int64_t xhi = -1)
 {
     if (!rbf_stencil_is_canonical(host_stencil, LG.R, LG.tap_d2)) return false;
-    const char* ap_env = getenv("R2S_RBF_APPLY");
     RbfWalkArgs WAr;
-    if (!ap_env && LG.WA && rbf_walk_supported(LG.R, LG.tap_d2, LG.nx, LG.ny) && rbf_walk_planes(LG, t0, t1, xlo, xhi, &WAr)) {
+    if (form == RbfEval::walk && LG.WA && rbf_walk_planes(LG, t0, t1, xlo, xhi, &WAr)) {
         WAr.T = LG.WA; WAr.x = w; WAr.y = out; WAr.add = add;
         rbf_walk_launch(1, LG.wa_nv, WAr, st);
         return true;
     }
     if (!LG.TA) return false;
-    const bool gathered = ap_env && !strcmp(ap_env, "lutg");   // table entries gathered from L1 / L2 (the tests compare)
-    if (LG.R == 2 && LG.tap_d2 == 7 && LG.TA16 && LG.nx >= 256 && tx == G.cx && ty == G.cy && tz == G.cz && !gathered)   // (nx >= 256: a workgroup spans <= 2 rows)
-        rbf_apply_lds_kernel<2, 7><<<nb, 256, 0, st>>>(G, LG, w, d_stencil, add, out, t0, t1, xlo, xhi);
-    else if (LG.R == 2 && LG.tap_d2 == 7) rbf_apply_lut_kernel<2, 7><<<nb, 256, 0, st>>>(G, LG, w, tx, ty, tz, d_stencil, add, out, t0, t1, xlo, xhi);
+    if (LG.R == 2 && LG.tap_d2 == 7) rbf_apply_lut_kernel<2, 7><<<nb, 256, 0, st>>>(G, LG, w, tx, ty, tz, d_stencil, add, out, t0, t1, xlo, xhi);
     else if (LG.R == 1 && LG.tap_d2 <= 3) rbf_apply_lut_kernel<1, 3><<<nb, 256, 0, st>>>(G, LG, w, tx, ty, tz, d_stencil, add, out, t0, t1, xlo, xhi);
     else if (LG.R == 2 && LG.tap_d2 <= 8) rbf_apply_lut_kernel<2, 8><<<nb, 256, 0, st>>>(G, LG, w, tx, ty, tz, d_stencil, add, out, t0, t1, xlo, xhi);
     else return false;
@@ -2354,14 +2154,304 @@ static void coarse_coords(double mn, double mx, int n, std::vector<float>& c)
     c[n - 1] = (float)mx;
 }
 
+// ---- one smoothing call: the geometry, the stencils, the host halves of the tables and the forms, decided once ----
+struct RbfPlan {
+    int smooth, nx, ny, nz, fx, fy, fz;   // coarse lattice, output grid
+    int64_t n, nf;
+    std::vector<float> cx, cy, cz, tx, ty, tz;
+    std::vector<Stencil> sts;             // smooth = 1 (sts[0]) and the output grid's parity classes (build_stencils)
+    bool capped;                          // the knn cap can bind: no table-driven evaluation
+    RbfGeom G;                            // the scalars (the coordinate pointers are a device's: RbfTables)
+    bool walk_ok;                         // a row-walk kernel exists for this stencil and lattice
+    bool one_to_one;                      // smooth = 1 and the output grid has the lattice's size
+    int halo;                             // planes a stencil reaches beyond a Z-slab
+    // variant values and ids of the tables (rbf_lut_axis): LV of the lattice (matrix and LSF), LVF of the output field at
+    // smooth = 1 (its grid is rounded separately); *_ok: every axis fits
+    RbfLutVals LV, LVF;
+    std::vector<uint8_t> ix, iy, iz, fix, fiy, fiz;
+    bool lv_ok, mv_fits, lvf_ok;
+    int lutf_most;
+    RbfMatvec mv;
+    RbfEval ev;
+};
+
+// R2S_RBF_MATVEC / R2S_RBF_APPLY (read per call: the tests switch) pick another form than the default: k... the
+// materialised matrix, f... on the fly, any other value the table kernels.  A form without its tables falls back: the
+// product to the materialised matrix, the evaluation to on the fly.
+static int rbf_plan(const r2s_grid* g, int is_interp, int smooth, double kthr, RbfPlan& P)
+{
+    if (smooth < 1 || smooth > 4) return fail(R2S_ERR_ARG, "smooth must be 1..4");
+    if (!(kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0))
+        return fail(R2S_ERR_ARG, "kernel threshold must be in [%g, 1): got %g", R2S_RBF_MIN_KERNEL_THRESHOLD, kthr);
+    P.smooth = smooth;
+    P.nx = (int)g->N[0] + 1; P.ny = (int)g->N[1] + 1; P.nz = (int)g->N[2] + 1;
+    P.fx = (int)g->N[0] * smooth + 1; P.fy = (int)g->N[1] * smooth + 1; P.fz = (int)g->N[2] * smooth + 1;
+    P.n = (int64_t)P.nx * P.ny * P.nz;
+    P.nf = (int64_t)P.fx * P.fy * P.fz;
+    coarse_coords(g->aabb_min[0], g->aabb_max[0], P.nx, P.cx);
+    coarse_coords(g->aabb_min[1], g->aabb_max[1], P.ny, P.cy);
+    coarse_coords(g->aabb_min[2], g->aabb_max[2], P.nz, P.cz);
+    {
+        // create_smooth_grid (:60-74): one step dx (from the x axis) for all three axes
+        const float xmin = (float)g->aabb_min[0], xmax = (float)g->aabb_max[0], ymin = (float)g->aabb_min[1],
+                    zmin = (float)g->aabb_min[2];
+        const float dx = (xmax - xmin) / (float)(P.fx - 1);
+        P.tx.resize(P.fx); P.ty.resize(P.fy); P.tz.resize(P.fz);
+        for (int i = 0; i < P.fx; ++i) P.tx[i] = xmin + (float)i * dx;
+        for (int i = 0; i < P.fy; ++i) P.ty[i] = ymin + (float)i * dx;
+        for (int i = 0; i < P.fz; ++i) P.tz[i] = zmin + (float)i * dx;
+    }
+    const int rc = build_stencils(smooth, kthr, P.sts, &P.capped);
+    if (rc) return rc;
+    RbfGeom& G = P.G;
+    memset(&G, 0, sizeof G);
+    G.nx = P.nx; G.ny = P.ny; G.nz = P.nz;
+    G.sigma = g->cell_size;                                                    // :346
+    G.thr = kthr;
+    G.max_distance = (float)std::sqrt(-std::log(kthr) * G.sigma * G.sigma);     // :221
+    {
+        const double R2 = -std::log(kthr);                 // support radius^2 in cells (sigma = cell size)
+        G.tap_d2 = (int)std::floor(R2 * 1.05 + 0.25);      // 1e-3 -> 7 (i.e. 6: 7 is not a sum of three squares)
+        G.tap_r = (int)std::floor(std::sqrt((double)G.tap_d2));
+    }
+    P.walk_ok = rbf_walk_supported(G.tap_r, G.tap_d2, P.nx, P.ny);
+    P.one_to_one = smooth == 1 && P.fx == P.nx && P.fy == P.ny && P.fz == P.nz;
+    P.halo = G.tap_r;
+    for (const Stencil& st : P.sts)
+        for (int q = 0; q < st.n; ++q) P.halo = std::max(P.halo, std::max((int)st.off[q][2], -(int)st.off[q][2]));
+    memset(&P.LV, 0, sizeof P.LV);
+    memset(&P.LVF, 0, sizeof P.LVF);
+    P.lv_ok = P.mv_fits = P.lvf_ok = false;
+    P.lutf_most = 0;
+    if (G.tap_r >= 1 && G.tap_r <= 3) {
+        for (RbfLutVals* V : {&P.LV, &P.LVF}) {
+            V->R = G.tap_r; V->sigma = G.sigma; V->thr = G.thr; V->max_distance = G.max_distance;
+        }
+        const int m0 = rbf_lut_axis(P.cx, P.cx, G.tap_r, P.LV.v[0], P.ix), m1 = rbf_lut_axis(P.cy, P.cy, G.tap_r, P.LV.v[1], P.iy),
+                  m2 = rbf_lut_axis(P.cz, P.cz, G.tap_r, P.LV.v[2], P.iz);
+        P.lv_ok = m0 && m1 && m2;
+        P.mv_fits = std::max(m0, std::max(m1, m2)) <= RBF_NV - 1;
+        if (P.one_to_one) {
+            const int f0 = rbf_lut_axis(P.tx, P.cx, G.tap_r, P.LVF.v[0], P.fix), f1 = rbf_lut_axis(P.ty, P.cy, G.tap_r, P.LVF.v[1], P.fiy),
+                      f2 = rbf_lut_axis(P.tz, P.cz, G.tap_r, P.LVF.v[2], P.fiz);
+            P.lvf_ok = f0 && f1 && f2;
+            P.lutf_most = std::max(f0, std::max(f1, f2));
+        }
+    }
+    const char* mv_env = getenv("R2S_RBF_MATVEC");
+    const char* ap_env = getenv("R2S_RBF_APPLY");
+    const bool mv_table = is_interp && P.lv_ok && P.mv_fits;
+    if (mv_env && mv_env[0] == 'f') P.mv = RbfMatvec::fly;
+    else if ((mv_env && mv_env[0] == 'k') || !mv_table) P.mv = RbfMatvec::k;
+    else P.mv = !mv_env && P.walk_ok ? RbfMatvec::walk : RbfMatvec::lut;
+    if (P.capped || (ap_env && ap_env[0] == 'f')) P.ev = RbfEval::fly;   // (the tables cannot count the knn cap)
+    else P.ev = !ap_env && P.walk_ok ? RbfEval::walk : RbfEval::lut;
+    return 0;
+}
+
+// the device half of a plan on the current device: coordinates, stencils, variant ids and the tables of the plan's forms
+// (uploads on `st` from the plan's vectors: the plan outlives them)
+struct RbfTables {
+    DevBuf cx, cy, cz, tx, ty, tz, st;
+    DevBuf vx, vy, vz, lv, wt, t, wa, ta;   // the lattice: LG
+    DevBuf fvx, fvy, fvz, lvf, waf, taf;    // the output grid at smooth = 1: LGF
+    RbfGeom G;
+    RbfLutGeom LG, LGF;
+    int build(const RbfPlan& P, hipStream_t s);
+    void release()
+    {
+        for (DevBuf* b : {&cx, &cy, &cz, &tx, &ty, &tz, &st, &vx, &vy, &vz, &lv, &wt, &t, &wa, &ta, &fvx, &fvy, &fvz, &lvf, &waf, &taf})
+            b->release();
+    }
+};
+#define RBF_TRY(expr)                                                                 \
+    do {                                                                              \
+        const int rc_ = (expr);                                                       \
+        if (rc_) return rc_;                                                          \
+    } while (0)
+static int rbf_alloc(DevBuf& b, size_t bytes)
+{
+    if (b.ensure(bytes)) return fail(R2S_ERR_NOMEM, "hipMalloc of %zu bytes failed", bytes);
+    return 0;
+}
+static int rbf_upload(DevBuf& b, const void* src, size_t bytes, hipStream_t s)
+{
+    RBF_TRY(rbf_alloc(b, bytes));
+    HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    return 0;
+}
+int RbfTables::build(const RbfPlan& P, hipStream_t s)
+{
+    RBF_TRY(rbf_upload(cx, P.cx.data(), 4 * P.cx.size(), s));
+    RBF_TRY(rbf_upload(cy, P.cy.data(), 4 * P.cy.size(), s));
+    RBF_TRY(rbf_upload(cz, P.cz.data(), 4 * P.cz.size(), s));
+    RBF_TRY(rbf_upload(tx, P.tx.data(), 4 * P.tx.size(), s));
+    RBF_TRY(rbf_upload(ty, P.ty.data(), 4 * P.ty.size(), s));
+    RBF_TRY(rbf_upload(tz, P.tz.data(), 4 * P.tz.size(), s));
+    RBF_TRY(rbf_upload(st, P.sts.data(), sizeof(Stencil) * P.sts.size(), s));
+    G = P.G;
+    G.cx = cx.as<float>(); G.cy = cy.as<float>(); G.cz = cz.as<float>();
+    memset(&LG, 0, sizeof LG);
+    memset(&LGF, 0, sizeof LGF);
+    const int W = 2 * P.G.tap_r + 1;
+    // tables of the distinct kernel values: the CG product (WT / T) and the evaluation on the lattice (WA / TA)
+    if (P.lv_ok && (P.mv == RbfMatvec::walk || P.mv == RbfMatvec::lut || P.ev != RbfEval::fly)) {
+        RBF_TRY(rbf_upload(vx, P.ix.data(), P.ix.size(), s));
+        RBF_TRY(rbf_upload(vy, P.iy.data(), P.iy.size(), s));
+        RBF_TRY(rbf_upload(vz, P.iz.data(), P.iz.size(), s));
+        RBF_TRY(rbf_upload(lv, &P.LV, sizeof P.LV, s));
+        LG.nx = P.nx; LG.ny = P.ny; LG.nz = P.nz; LG.R = P.G.tap_r; LG.tap_d2 = P.G.tap_d2;
+        LG.vx = vx.as<uint8_t>(); LG.vy = vy.as<uint8_t>(); LG.vz = vz.as<uint8_t>();
+        const size_t nT = (size_t)W * W * W * RBF_NV * RBF_NV * RBF_NV;
+        if (P.mv == RbfMatvec::walk) {
+            RBF_TRY(rbf_alloc(wt, sizeof(float) * nT));
+            rbf_walk_table_kernel<0><<<(unsigned)((nT + 255) / 256), 256, 0, s>>>(lv.as<RbfLutVals>(), wt.p, RBF_NV);
+            LG.WT = wt.as<float>();
+        } else if (P.mv == RbfMatvec::lut) {
+            RBF_TRY(rbf_alloc(t, sizeof(float) * nT));
+            rbf_lut_build_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, s>>>(lv.as<RbfLutVals>(), t.as<float>());
+            LG.T = t.as<float>();
+        }
+        if (P.ev == RbfEval::walk) {
+            const int nv = P.mv_fits ? RBF_NV : RBF_NVA;
+            const size_t nW = (size_t)W * W * W * nv * nv * nv;
+            RBF_TRY(rbf_alloc(wa, sizeof(double) * nW));
+            rbf_walk_table_kernel<1><<<(unsigned)((nW + 255) / 256), 256, 0, s>>>(lv.as<RbfLutVals>(), wa.p, nv);
+            LG.WA = wa.as<double>(); LG.wa_nv = nv;
+        } else if (P.ev == RbfEval::lut) {
+            const size_t nTA = (size_t)W * W * W * RBF_NVA * RBF_NVA * RBF_NVA;
+            RBF_TRY(rbf_alloc(ta, sizeof(double) * nTA));
+            rbf_lut_build_apply_kernel<<<(unsigned)((nTA + 255) / 256), 256, 0, s>>>(lv.as<RbfLutVals>(), ta.as<double>());
+            LG.TA = ta.as<double>();
+        }
+    }
+    if (P.lvf_ok && P.ev != RbfEval::fly) {
+        RBF_TRY(rbf_upload(fvx, P.fix.data(), P.fix.size(), s));
+        RBF_TRY(rbf_upload(fvy, P.fiy.data(), P.fiy.size(), s));
+        RBF_TRY(rbf_upload(fvz, P.fiz.data(), P.fiz.size(), s));
+        RBF_TRY(rbf_upload(lvf, &P.LVF, sizeof P.LVF, s));
+        LGF.nx = P.nx; LGF.ny = P.ny; LGF.nz = P.nz; LGF.R = P.G.tap_r; LGF.tap_d2 = P.G.tap_d2;
+        LGF.vx = fvx.as<uint8_t>(); LGF.vy = fvy.as<uint8_t>(); LGF.vz = fvz.as<uint8_t>();
+        if (P.ev == RbfEval::walk) {
+            const int nv = P.lutf_most <= RBF_NV - 1 ? RBF_NV : RBF_NVA;
+            const size_t nW = (size_t)W * W * W * nv * nv * nv;
+            RBF_TRY(rbf_alloc(waf, sizeof(double) * nW));
+            rbf_walk_table_kernel<1><<<(unsigned)((nW + 255) / 256), 256, 0, s>>>(lvf.as<RbfLutVals>(), waf.p, nv);
+            LGF.WA = waf.as<double>(); LGF.wa_nv = nv;
+        } else {
+            const size_t nTA = (size_t)W * W * W * RBF_NVA * RBF_NVA * RBF_NVA;
+            RBF_TRY(rbf_alloc(taf, sizeof(double) * nTA));
+            rbf_lut_build_apply_kernel<<<(unsigned)((nTA + 255) / 256), 256, 0, s>>>(lvf.as<RbfLutVals>(), taf.as<double>());
+            LGF.TA = taf.as<double>();
+        }
+    }
+    return 0;
+}
+
+// the tables of the refined output grid's parity classes (smooth >= 2; one device only): F.T stays null where they do not
+// apply and the output field is evaluated on the fly
+struct RbfFineTables {
+    DevBuf ids, vals, T, taps, meta;
+    FineLut F;
+    int build(const RbfPlan& P, hipStream_t s);
+    void release()
+    {
+        for (DevBuf* b : {&ids, &vals, &T, &taps, &meta}) b->release();
+    }
+};
+int RbfFineTables::build(const RbfPlan& P, hipStream_t s)
+{
+    memset(&F, 0, sizeof F);
+    if (P.smooth < 2 || P.ev == RbfEval::fly) return 0;
+    const int smooth = P.smooth, nx = P.nx, ny = P.ny, fx = P.fx, fy = P.fy, fz = P.fz;
+    const int ncls = smooth * smooth * smooth;
+    std::vector<uint64_t> pkx, pky, pkz;
+    std::vector<float> vlx, vly, vlz;
+    int most = 1;
+    const bool fits = fine_lut_axis(P.tx, P.cx, smooth, pkx, vlx, most) && fine_lut_axis(P.ty, P.cy, smooth, pky, vly, most) &&
+                      fine_lut_axis(P.tz, P.cz, smooth, pkz, vlz, most);
+    const int nvf = most <= 15 ? 16 : (most <= 31 ? 32 : 64);
+    for (std::vector<uint64_t>* pkp : {&pkx, &pky, &pkz})   // "no such source" = the unused slot nvf - 1 (see the kernel)
+        for (uint64_t& v : *pkp)
+            for (int d8 = 0; d8 < 8; ++d8)
+                if (((v >> (8 * d8)) & 255u) == 255u) v = (v & ~(0xffull << (8 * d8))) | ((uint64_t)(nvf - 1) << (8 * d8));
+    {
+        uint64_t none = 0;
+        for (int d8 = 0; d8 < 8; ++d8) none |= (uint64_t)(nvf - 1) << (8 * d8);
+        pkx.push_back(none);   // (the pack of the lanes beyond the end of a row)
+    }
+    std::vector<FineTap> tp_all((size_t)ncls * 512);
+    std::vector<int64_t> tbase((size_t)ncls);
+    std::vector<int> ntaps((size_t)ncls);
+    int64_t total = 0;
+    bool ok = fits;
+    for (int c = 0; c < ncls && ok; ++c) {
+        const Stencil& S = P.sts[1 + (size_t)c];
+        if (S.n > 512 - 8) ok = false;   // (the kernel reads its batches past the end of a list)
+        tbase[(size_t)c] = total;
+        ntaps[(size_t)c] = S.n;
+        total += (int64_t)S.n * nvf * nvf * nvf;
+        for (int q = 0; q < S.n && ok; ++q) {
+            FineTap& tp = tp_all[(size_t)c * 512 + q];
+            tp.di = S.off[q][0]; tp.dj = S.off[q][1]; tp.dk = S.off[q][2]; tp.pad = 0;
+            if (tp.di < -3 || tp.di > 4 || tp.dj < -3 || tp.dj > 4 || tp.dk < -3 || tp.dk > 4) ok = false;
+            tp.woff = (int32_t)(((int64_t)tp.dk * ny + tp.dj) * nx + tp.di);
+        }
+    }
+    const int64_t waves = (int64_t)fz * fy * smooth * (((fx + smooth - 1) / smooth + 63) / 64);
+    if (!(ok && total * 8 <= ((int64_t)8 << 30) && P.n * 4 < ((int64_t)1 << 32) && waves < ((int64_t)1 << 32))) return 0;
+    const size_t nid = pkx.size() + pky.size() + pkz.size();
+    RBF_TRY(rbf_alloc(ids, 8 * nid));
+    RBF_TRY(rbf_alloc(vals, 4 * (vlx.size() + vly.size() + vlz.size())));
+    RBF_TRY(rbf_alloc(T, 8 * (size_t)total));
+    RBF_TRY(rbf_alloc(taps, sizeof(FineTap) * tp_all.size()));
+    RBF_TRY(rbf_alloc(meta, 8 * (size_t)ncls + 4 * (size_t)ncls));
+    // (synchronous copies: the host vectors are this function's)
+    uint64_t* dids = ids.as<uint64_t>();
+    HIP_TRY(hipMemcpy(dids, pkx.data(), 8 * pkx.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dids + pkx.size(), pky.data(), 8 * pky.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dids + pkx.size() + pky.size(), pkz.data(), 8 * pkz.size(), hipMemcpyHostToDevice));
+    float* dv = vals.as<float>();
+    HIP_TRY(hipMemcpy(dv, vlx.data(), 4 * vlx.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dv + vlx.size(), vly.data(), 4 * vly.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dv + vlx.size() + vly.size(), vlz.data(), 4 * vlz.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(taps.p, tp_all.data(), sizeof(FineTap) * tp_all.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(meta.p, tbase.data(), 8 * (size_t)ncls, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((char*)meta.p + 8 * (size_t)ncls, ntaps.data(), 4 * (size_t)ncls, hipMemcpyHostToDevice));
+    for (int c = 0; c < ncls; ++c) {
+        const int pi = c % smooth, pj = (c / smooth) % smooth, pk = c / (smooth * smooth);
+        const int64_t nt = (int64_t)ntaps[(size_t)c] * nvf * nvf * nvf;
+        if (!nt) continue;
+        fine_lut_build_kernel<<<(unsigned)((nt + 255) / 256), 256, 0, s>>>(
+            taps.as<FineTap>() + (size_t)c * 512, ntaps[(size_t)c], dv + (size_t)pi * 8 * 64, dv + vlx.size() + (size_t)pj * 8 * 64,
+            dv + vlx.size() + vly.size() + (size_t)pk * 8 * 64, P.G.sigma, P.G.max_distance, nvf, T.as<double>() + tbase[(size_t)c]);
+    }
+    F.s = smooth; F.fx = fx; F.fy = fy; F.nx = nx; F.ny = ny; F.nzc = P.nz;
+    F.nmx = (fx + smooth - 1) / smooth; F.nmy = (fy + smooth - 1) / smooth; F.nmz = (fz + smooth - 1) / smooth;
+    F.nvf = nvf;
+    F.nrec = 8;
+    for (int c = 0; c < ncls; ++c) F.nrec = std::max(F.nrec, (ntaps[(size_t)c] + 7) & ~7);
+    F.idx = dids; F.idy = dids + pkx.size(); F.idz = dids + pkx.size() + pky.size();
+    F.T = T.as<double>();
+    F.taps = taps.as<FineTap>();
+    F.tbase = (const int64_t*)meta.p;
+    F.ntaps = (const int*)((const char*)meta.p + 8 * (size_t)ncls);
+    return 0;
+}
+#undef RBF_TRY
+
 struct RbfWork {   // the device buffers of one rbf_smooth_host call
-    DevBuf b[40];
+    DevBuf sdf, f, w, lsf, fine, cnt, r, u, q, part, part2;
+    RbfTables tab;
+    RbfFineTables fine_tab;
     VolumeWork vw;
     HostMailbox mb;
     void release()
     {
         mb.release();
-        for (DevBuf& x : b) x.release();
+        for (DevBuf* b : {&sdf, &f, &w, &lsf, &fine, &cnt, &r, &u, &q, &part, &part2}) b->release();
+        tab.release();
+        fine_tab.release();
         vw.release();
     }
 };
@@ -2373,24 +2463,20 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
                            bool fine_early = false)
 {
     if (!sdf || !g || !fine_out) return fail(R2S_ERR_ARG, "null argument");
-    if (smooth < 1 || smooth > 4) return fail(R2S_ERR_ARG, "smooth must be 1..4");
-    if (!(kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0))
-        return fail(R2S_ERR_ARG, "kernel threshold must be in [%g, 1): got %g", R2S_RBF_MIN_KERNEL_THRESHOLD, kthr);
-    const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
-    const int64_t n = (int64_t)nx * ny * nz;
-    const int fx = (int)g->N[0] * smooth + 1, fy = (int)g->N[1] * smooth + 1, fz = (int)g->N[2] * smooth + 1;
-    const int64_t nf = (int64_t)fx * fy * fz;
+    RbfPlan P;
+    {
+        const int rc = rbf_plan(g, is_interp, smooth, kthr, P);
+        if (rc) return rc;
+    }
+    const int nx = P.nx, ny = P.ny, nz = P.nz, fx = P.fx, fy = P.fy, fz = P.fz;
+    const int64_t n = P.n, nf = P.nf;
     hipStream_t st = nullptr;
     // (a caller that repeats the call keeps the ~30 buffers - 4.6 GB at 512^3 - in a workspace: allocating and freeing
     //  them costs ~5 ms per call)
     RbfWork local;
     RbfWork& W = ws ? *ws : local;
-    DevBuf &d_sdf = W.b[0], &d_f = W.b[1], &d_w = W.b[2], &d_lsf = W.b[3], &d_fine = W.b[4], &d_cx = W.b[5], &d_cy = W.b[6], &d_cz = W.b[7],
-           &d_tx = W.b[8], &d_ty = W.b[9], &d_tz = W.b[10], &d_st = W.b[11], &d_cnt = W.b[12], &d_r = W.b[13], &d_u = W.b[14], &d_q = W.b[15],
-           &d_part = W.b[16], &d_sum = W.b[17], &d_lut = W.b[18], &d_luta = W.b[19], &d_vx = W.b[20], &d_vy = W.b[21], &d_vz = W.b[22],
-           &d_lutf = W.b[23], &d_fvx = W.b[24], &d_fvy = W.b[25], &d_fvz = W.b[26], &d_lv = W.b[27], &d_lvf = W.b[28], &d_luta16 = W.b[29],
-           &d_wt = W.b[30], &d_wa = W.b[31], &d_waf = W.b[32], &d_part2 = W.b[33], &d_fl_ids = W.b[34], &d_fl_vals = W.b[35],
-           &d_fl_T = W.b[36], &d_fl_taps = W.b[37], &d_fl_meta = W.b[38];
+    RbfTables& T = W.tab;
+    const FineLut& FL = W.fine_tab.F;
     VolumeWork& vw = W.vw;
     auto cleanup = [&]() {
         if (!ws) W.release();
@@ -2409,257 +2495,51 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     do {                                                                              \
         if ((buf).ensure(bytes)) { cleanup(); return fail(R2S_ERR_NOMEM, "hipMalloc of %zu bytes failed", (size_t)(bytes)); } \
     } while (0)
-    if (!sdf_dev) ENSURE_C(d_sdf, sizeof(double) * (size_t)n);
-    ENSURE_C(d_f, sizeof(float) * (size_t)n);
-    ENSURE_C(d_w, sizeof(float) * (size_t)n);
-    ENSURE_C(d_lsf, sizeof(float) * (size_t)n);
-    if (!out_dev) ENSURE_C(d_fine, sizeof(float) * (size_t)nf);
-    ENSURE_C(d_cnt, 64);
-    if (!sdf_dev) HIP_C(hipMemcpy(d_sdf.p, sdf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    const double* dsdf = sdf_dev ? sdf : d_sdf.as<double>();
-    float* dfine = out_dev ? fine_out : d_fine.as<float>();
+    if (!sdf_dev) ENSURE_C(W.sdf, sizeof(double) * (size_t)n);
+    ENSURE_C(W.f, sizeof(float) * (size_t)n);
+    ENSURE_C(W.w, sizeof(float) * (size_t)n);
+    ENSURE_C(W.lsf, sizeof(float) * (size_t)n);
+    if (!out_dev) ENSURE_C(W.fine, sizeof(float) * (size_t)nf);
+    ENSURE_C(W.cnt, 64);
+    if (!sdf_dev) HIP_C(hipMemcpy(W.sdf.p, sdf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    const double* dsdf = sdf_dev ? sdf : W.sdf.as<double>();
+    float* dfine = out_dev ? fine_out : W.fine.as<float>();
+    float* const d_f = W.f.as<float>();
+    float* const d_w = W.w.as<float>();
+    float* const d_lsf = W.lsf.as<float>();
     // ---- process_vector ----
-    HIP_C(hipMemset(d_cnt.p, 0, 64));
+    HIP_C(hipMemset(W.cnt.p, 0, 64));
     const unsigned nb = (unsigned)((n + 255) / 256);
-    pv_max_kernel<<<(nb < 2048u ? nb : 2048u), 256, 0, st>>>(dsdf, n, d_f.as<float>(), d_cnt.as<uint32_t>(), d_cnt.as<uint32_t>() + 1);
+    pv_max_kernel<<<(nb < 2048u ? nb : 2048u), 256, 0, st>>>(dsdf, n, d_f, W.cnt.as<uint32_t>(), W.cnt.as<uint32_t>() + 1);
     uint32_t hc[2];
-    TRY_C(d2h_small(hc, d_cnt.p, 8, st, W.mb));
+    TRY_C(d2h_small(hc, W.cnt.p, 8, st, W.mb));
     if (!hc[1]) { cleanup(); return fail(R2S_ERR_ARG, "every SDF value is a sentinel: nothing to smooth"); }   // A15
-    pv_replace_kernel<<<nb, 256, 0, st>>>(d_f.as<float>(), n, d_cnt.as<uint32_t>());
-    // ---- geometry ----
-    std::vector<float> cx, cy, cz, tx(fx), ty(fy), tz(fz);
-    coarse_coords(g->aabb_min[0], g->aabb_max[0], nx, cx);
-    coarse_coords(g->aabb_min[1], g->aabb_max[1], ny, cy);
-    coarse_coords(g->aabb_min[2], g->aabb_max[2], nz, cz);
-    {
-        // create_smooth_grid (:60-74): one step dx (from the x axis) for all three axes
-        const float xmin = (float)g->aabb_min[0], xmax = (float)g->aabb_max[0], ymin = (float)g->aabb_min[1],
-                    zmin = (float)g->aabb_min[2];
-        const float dx = (xmax - xmin) / (float)(fx - 1);
-        for (int i = 0; i < fx; ++i) tx[i] = xmin + (float)i * dx;
-        for (int i = 0; i < fy; ++i) ty[i] = ymin + (float)i * dx;
-        for (int i = 0; i < fz; ++i) tz[i] = zmin + (float)i * dx;
-    }
-    auto up = [&](DevBuf& b, const std::vector<float>& v) -> int {
-        if (b.ensure(sizeof(float) * v.size())) return fail(R2S_ERR_NOMEM, "hipMalloc failed");
-        if (hipMemcpy(b.p, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(R2S_ERR_HIP, "hipMemcpy failed");
-        return 0;
-    };
-    TRY_C(up(d_cx, cx)); TRY_C(up(d_cy, cy)); TRY_C(up(d_cz, cz));
-    TRY_C(up(d_tx, tx)); TRY_C(up(d_ty, ty)); TRY_C(up(d_tz, tz));
-    // stencils for smooth = 1 (one class) and for the fine grid (smooth^3 classes)
-    std::vector<Stencil> sts;
-    bool capped = false;
-    TRY_C(build_stencils(smooth, kthr, sts, &capped));
-    ENSURE_C(d_st, sizeof(Stencil) * sts.size());
-    HIP_C(hipMemcpy(d_st.p, sts.data(), sizeof(Stencil) * sts.size(), hipMemcpyHostToDevice));
-    RbfGeom G;
-    G.nx = nx; G.ny = ny; G.nz = nz;
-    G.cx = d_cx.as<float>(); G.cy = d_cy.as<float>(); G.cz = d_cz.as<float>();
-    G.sigma = g->cell_size;                                                    // :346
-    G.thr = kthr;
-    G.max_distance = (float)std::sqrt(-std::log(kthr) * G.sigma * G.sigma);     // :221
-    {
-        const double R2 = -std::log(kthr);                 // support radius^2 in cells (sigma = cell size)
-        G.tap_d2 = (int)std::floor(R2 * 1.05 + 0.25);      // 1e-3 -> 7 (i.e. 6: 7 is not a sum of three squares)
-        G.tap_r = (int)std::floor(std::sqrt((double)G.tap_d2));
-    }
-    // ---- refined output grid: the tables of its parity classes (R2S_RBF_APPLY=fly: on the fly, the tests compare) ----
-    FineLut FL;
-    memset(&FL, 0, sizeof FL);
-    if (smooth >= 2 && !capped && !(getenv("R2S_RBF_APPLY") && getenv("R2S_RBF_APPLY")[0] == 'f')) {
-        const int ncls = smooth * smooth * smooth;
-        std::vector<uint64_t> pkx, pky, pkz;
-        std::vector<float> vlx, vly, vlz;
-        int most = 1;
-        const bool fits = fine_lut_axis(tx, cx, smooth, pkx, vlx, most) && fine_lut_axis(ty, cy, smooth, pky, vly, most) &&
-                          fine_lut_axis(tz, cz, smooth, pkz, vlz, most);
-        const int nvf = most <= 15 ? 16 : (most <= 31 ? 32 : 64);
-        for (std::vector<uint64_t>* pkp : {&pkx, &pky, &pkz})   // "no such source" = the unused slot nvf - 1 (see the kernel)
-            for (uint64_t& v : *pkp)
-                for (int d8 = 0; d8 < 8; ++d8)
-                    if (((v >> (8 * d8)) & 255u) == 255u) v = (v & ~(0xffull << (8 * d8))) | ((uint64_t)(nvf - 1) << (8 * d8));
-        {
-            uint64_t none = 0;
-            for (int d8 = 0; d8 < 8; ++d8) none |= (uint64_t)(nvf - 1) << (8 * d8);
-            pkx.push_back(none);   // (the pack of the lanes beyond the end of a row)
-        }
-        std::vector<FineTap> taps((size_t)ncls * 512);
-        std::vector<int64_t> tbase((size_t)ncls);
-        std::vector<int> ntaps((size_t)ncls);
-        int64_t total = 0;
-        bool ok = fits;
-        for (int c = 0; c < ncls && ok; ++c) {
-            const Stencil& S = sts[1 + (size_t)c];
-            if (S.n > 512 - 8) ok = false;   // (the kernel reads its batches past the end of a list)
-            tbase[(size_t)c] = total;
-            ntaps[(size_t)c] = S.n;
-            total += (int64_t)S.n * nvf * nvf * nvf;
-            for (int q = 0; q < S.n && ok; ++q) {
-                FineTap& tp = taps[(size_t)c * 512 + q];
-                tp.di = S.off[q][0]; tp.dj = S.off[q][1]; tp.dk = S.off[q][2]; tp.pad = 0;
-                if (tp.di < -3 || tp.di > 4 || tp.dj < -3 || tp.dj > 4 || tp.dk < -3 || tp.dk > 4) ok = false;
-                tp.woff = (int32_t)(((int64_t)tp.dk * ny + tp.dj) * nx + tp.di);
-            }
-        }
-        const int64_t waves = (int64_t)fz * fy * smooth * (((fx + smooth - 1) / smooth + 63) / 64);
-        if (ok && total * 8 <= ((int64_t)8 << 30) && n * 4 < ((int64_t)1 << 32) && waves < ((int64_t)1 << 32)) {
-            const size_t nid = pkx.size() + pky.size() + pkz.size();
-            ENSURE_C(d_fl_ids, 8 * nid);
-            ENSURE_C(d_fl_vals, 4 * (vlx.size() + vly.size() + vlz.size()));
-            ENSURE_C(d_fl_T, 8 * (size_t)total);
-            ENSURE_C(d_fl_taps, sizeof(FineTap) * taps.size());
-            ENSURE_C(d_fl_meta, 8 * (size_t)ncls + 4 * (size_t)ncls);
-            uint64_t* dids = d_fl_ids.as<uint64_t>();
-            HIP_C(hipMemcpy(dids, pkx.data(), 8 * pkx.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(dids + pkx.size(), pky.data(), 8 * pky.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(dids + pkx.size() + pky.size(), pkz.data(), 8 * pkz.size(), hipMemcpyHostToDevice));
-            float* dv = d_fl_vals.as<float>();
-            HIP_C(hipMemcpy(dv, vlx.data(), 4 * vlx.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(dv + vlx.size(), vly.data(), 4 * vly.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(dv + vlx.size() + vly.size(), vlz.data(), 4 * vlz.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(d_fl_taps.p, taps.data(), sizeof(FineTap) * taps.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(d_fl_meta.p, tbase.data(), 8 * (size_t)ncls, hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy((char*)d_fl_meta.p + 8 * (size_t)ncls, ntaps.data(), 4 * (size_t)ncls, hipMemcpyHostToDevice));
-            const double sigma = g->cell_size;
-            const float maxd = (float)std::sqrt(-std::log(kthr) * sigma * sigma);
-            for (int c = 0; c < ncls; ++c) {
-                const int pi = c % smooth, pj = (c / smooth) % smooth, pk = c / (smooth * smooth);
-                const int64_t nt = (int64_t)ntaps[(size_t)c] * nvf * nvf * nvf;
-                if (!nt) continue;
-                fine_lut_build_kernel<<<(unsigned)((nt + 255) / 256), 256, 0, st>>>(
-                    d_fl_taps.as<FineTap>() + (size_t)c * 512, ntaps[(size_t)c], dv + (size_t)pi * 8 * 64, dv + vlx.size() + (size_t)pj * 8 * 64,
-                    dv + vlx.size() + vly.size() + (size_t)pk * 8 * 64, sigma, maxd, nvf, d_fl_T.as<double>() + tbase[(size_t)c]);
-            }
-            FL.s = smooth; FL.fx = fx; FL.fy = fy; FL.nx = nx; FL.ny = ny; FL.nzc = nz;
-            FL.nmx = (fx + smooth - 1) / smooth; FL.nmy = (fy + smooth - 1) / smooth; FL.nmz = (fz + smooth - 1) / smooth;
-            FL.nvf = nvf;
-            FL.nrec = 8;
-            for (int c = 0; c < ncls; ++c) FL.nrec = std::max(FL.nrec, (ntaps[(size_t)c] + 7) & ~7);
-            FL.idx = dids; FL.idy = dids + pkx.size(); FL.idz = dids + pkx.size() + pky.size();
-            FL.T = d_fl_T.as<double>();
-            FL.taps = d_fl_taps.as<FineTap>();
-            FL.tbase = (const int64_t*)d_fl_meta.p;
-            FL.ntaps = (const int*)((const char*)d_fl_meta.p + 8 * (size_t)ncls);
-        }
-    }
-    // ---- tables of the distinct kernel values: the CG matvec (T) and the evaluation on the same grid (TA) ----
-    // (exact, no matrix in memory; R2S_RBF_MATVEC=k|fly and R2S_RBF_APPLY=fly force the other paths - the tests compare them)
-    const char* mv_env = getenv("R2S_RBF_MATVEC");   // (read per call: the tests switch)
-    const char* ap_env = getenv("R2S_RBF_APPLY");
-    const bool want_mv_lut = is_interp && !(mv_env && (mv_env[0] == 'k' || mv_env[0] == 'f'));
-    const bool want_ap_lut = !(ap_env && ap_env[0] == 'f') && !capped;   // (the tables cannot count the knn cap)
-    RbfLutGeom LG, LGF;   // LGF: the evaluation of the output field at smooth = 1 (its grid is rounded separately)
-    memset(&LG, 0, sizeof LG);
-    memset(&LGF, 0, sizeof LGF);
-    const bool fine_one_to_one = smooth == 1 && fx == nx && fy == ny && fz == nz;
-    const bool walk_ok = rbf_walk_supported(G.tap_r, G.tap_d2, nx, ny);
-    if (G.tap_r >= 1 && G.tap_r <= 3 && want_ap_lut && fine_one_to_one) {
-        RbfLutVals LV;
-        memset(&LV, 0, sizeof LV);
-        LV.R = G.tap_r; LV.sigma = G.sigma; LV.thr = G.thr; LV.max_distance = G.max_distance;
-        std::vector<uint8_t> ix, iy, iz;
-        const int f0 = rbf_lut_axis(tx, cx, G.tap_r, LV.v[0], ix), f1 = rbf_lut_axis(ty, cy, G.tap_r, LV.v[1], iy),
-                  f2 = rbf_lut_axis(tz, cz, G.tap_r, LV.v[2], iz);
-        if (f0 && f1 && f2) {
-            const int W = 2 * G.tap_r + 1;
-            ENSURE_C(d_fvx, ix.size()); ENSURE_C(d_fvy, iy.size()); ENSURE_C(d_fvz, iz.size());
-            HIP_C(hipMemcpy(d_fvx.p, ix.data(), ix.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(d_fvy.p, iy.data(), iy.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(d_fvz.p, iz.data(), iz.size(), hipMemcpyHostToDevice));
-            LGF.nx = nx; LGF.ny = ny; LGF.nz = nz; LGF.R = G.tap_r; LGF.tap_d2 = G.tap_d2;
-            LGF.vx = d_fvx.as<uint8_t>(); LGF.vy = d_fvy.as<uint8_t>(); LGF.vz = d_fvz.as<uint8_t>();
-            ENSURE_C(d_lvf, sizeof LV);
-            HIP_C(hipMemcpy(d_lvf.p, &LV, sizeof LV, hipMemcpyHostToDevice));
-            if (walk_ok && !ap_env) {   // the table of the row-walk kernel (r2s_rbf_walk.hpp)
-                const int nv = std::max(f0, std::max(f1, f2)) <= RBF_NV - 1 ? RBF_NV : RBF_NVA;
-                const size_t nT = (size_t)W * W * W * nv * nv * nv;
-                ENSURE_C(d_waf, sizeof(double) * nT);
-                rbf_walk_table_kernel<1><<<(unsigned)((nT + 255) / 256), 256, 0, st>>>(d_lvf.as<RbfLutVals>(), d_waf.p, nv);
-                LGF.WA = d_waf.as<double>(); LGF.wa_nv = nv;
-            } else {
-                const size_t nT = (size_t)W * W * W * RBF_NVA * RBF_NVA * RBF_NVA;
-                ENSURE_C(d_lutf, sizeof(double) * nT);
-                rbf_lut_build_apply_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, st>>>(d_lvf.as<RbfLutVals>(), d_lutf.as<double>());
-                LGF.TA = d_lutf.as<double>();
-            }
-        }
-    }
-    if (G.tap_r >= 1 && G.tap_r <= 3 && (want_mv_lut || want_ap_lut)) {
-        RbfLutVals LV;
-        memset(&LV, 0, sizeof LV);
-        LV.R = G.tap_r; LV.sigma = G.sigma; LV.thr = G.thr; LV.max_distance = G.max_distance;
-        std::vector<uint8_t> ix, iy, iz;
-        const int m0 = rbf_lut_axis(cx, cx, G.tap_r, LV.v[0], ix), m1 = rbf_lut_axis(cy, cy, G.tap_r, LV.v[1], iy),
-                  m2 = rbf_lut_axis(cz, cz, G.tap_r, LV.v[2], iz);
-        const bool mv_fits = std::max(m0, std::max(m1, m2)) <= RBF_NV - 1;
-        if (m0 && m1 && m2) {
-            const int W = 2 * G.tap_r + 1;
-            const size_t nT = (size_t)W * W * W * RBF_NV * RBF_NV * RBF_NV;
-            ENSURE_C(d_vx, ix.size()); ENSURE_C(d_vy, iy.size()); ENSURE_C(d_vz, iz.size());
-            HIP_C(hipMemcpy(d_vx.p, ix.data(), ix.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(d_vy.p, iy.data(), iy.size(), hipMemcpyHostToDevice));
-            HIP_C(hipMemcpy(d_vz.p, iz.data(), iz.size(), hipMemcpyHostToDevice));
-            LG.nx = nx; LG.ny = ny; LG.nz = nz; LG.R = G.tap_r; LG.tap_d2 = G.tap_d2;
-            LG.vx = d_vx.as<uint8_t>(); LG.vy = d_vy.as<uint8_t>(); LG.vz = d_vz.as<uint8_t>();
-            ENSURE_C(d_lv, sizeof LV);
-            HIP_C(hipMemcpy(d_lv.p, &LV, sizeof LV, hipMemcpyHostToDevice));
-            if (want_mv_lut && mv_fits && walk_ok && !mv_env) {
-                ENSURE_C(d_wt, sizeof(float) * nT);
-                rbf_walk_table_kernel<0><<<(unsigned)((nT + 255) / 256), 256, 0, st>>>(d_lv.as<RbfLutVals>(), d_wt.p, RBF_NV);
-                LG.WT = d_wt.as<float>();
-            } else if (want_mv_lut && mv_fits) {
-                ENSURE_C(d_lut, sizeof(float) * nT);
-                rbf_lut_build_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, st>>>(d_lv.as<RbfLutVals>(), d_lut.as<float>());
-                LG.T = d_lut.as<float>();
-            }
-            if (want_ap_lut && walk_ok && !ap_env) {
-                const int nv = mv_fits ? RBF_NV : RBF_NVA;
-                const size_t nW = (size_t)W * W * W * nv * nv * nv;
-                ENSURE_C(d_wa, sizeof(double) * nW);
-                rbf_walk_table_kernel<1><<<(unsigned)((nW + 255) / 256), 256, 0, st>>>(d_lv.as<RbfLutVals>(), d_wa.p, nv);
-                LG.WA = d_wa.as<double>(); LG.wa_nv = nv;
-            } else if (want_ap_lut) {
-                const size_t nTA = (size_t)W * W * W * RBF_NVA * RBF_NVA * RBF_NVA;
-                ENSURE_C(d_luta, sizeof(double) * nTA);
-                rbf_lut_build_apply_kernel<<<(unsigned)((nTA + 255) / 256), 256, 0, st>>>(d_lv.as<RbfLutVals>(), d_luta.as<double>());
-                LG.TA = d_luta.as<double>();
-                if (mv_fits) {   // compact table for the kernel that stages its rows in LDS
-                    ENSURE_C(d_luta16, sizeof(double) * nT);
-                    rbf_lut_build_apply_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, st>>>(d_lv.as<RbfLutVals>(), d_luta16.as<double>(), RBF_NV);
-                    LG.TA16 = d_luta16.as<double>();
-                }
-            }
-        }
-    }
+    pv_replace_kernel<<<nb, 256, 0, st>>>(d_f, n, W.cnt.as<uint32_t>());
+    // ---- geometry and tables; the refined output grid's tables (R2S_RBF_APPLY=fly: on the fly, the tests compare) ----
+    TRY_C(T.build(P, st));
+    TRY_C(W.fine_tab.build(P, st));
+    const RbfGeom& G = T.G;
     // ---- weights ----
     int its = 0;
     if (is_interp) {   // compute_rbf_weights (:191-202): cg(K, b), IterativeSolvers 0.9.4 defaults
-        ENSURE_C(d_r, sizeof(float) * (size_t)n);
-        ENSURE_C(d_u, sizeof(float) * (size_t)n);
-        ENSURE_C(d_q, sizeof(float) * (size_t)n);
-        ENSURE_C(d_part, sizeof(double) * (size_t)std::max(nz * DOT_PARTS, 1024));
-        ENSURE_C(d_sum, 64);
-        auto dot = [&](const float* a, const float* b, float* out) -> int {
-            dot_planes_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(a, b, (int64_t)nx * ny, d_part.as<double>());
-            std::vector<double> hp((size_t)nz * DOT_PARTS);
-            { const int rc_ = d2h_small(hp.data(), d_part.p, sizeof(double) * hp.size(), st, W.mb); if (rc_) return rc_; }
-            double h = 0.0;
-            for (double v : hp) h += v;   // parts in (k, part) order (see dot_planes_kernel)
-            *out = (float)h;
-            return 0;
-        };
-        auto xr_dot = [&](float alpha, float* out) -> int {   // weights / residual update with dot(r, r)
-            cg_update_xr_dot_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_w.as<float>(), d_r.as<float>(), d_u.as<float>(), d_q.as<float>(), alpha,
-                                                                   (int64_t)nx * ny, d_part.as<double>());
-            std::vector<double> hp((size_t)nz * DOT_PARTS);
-            { const int rc_ = d2h_small(hp.data(), d_part.p, sizeof(double) * hp.size(), st, W.mb); if (rc_) return rc_; }
+        ENSURE_C(W.r, sizeof(float) * (size_t)n);
+        ENSURE_C(W.u, sizeof(float) * (size_t)n);
+        ENSURE_C(W.q, sizeof(float) * (size_t)n);
+        ENSURE_C(W.part, sizeof(double) * (size_t)std::max(nz * DOT_PARTS, 1024));
+        float* const d_r = W.r.as<float>();
+        float* const d_u = W.u.as<float>();
+        float* const d_q = W.q.as<float>();
+        // the `count` partial sums of a dot product at `parts`, added on the host in their order, rounded to Float32
+        std::vector<double> hp;
+        auto sum_parts = [&](DevBuf& parts, size_t count, float* out) -> int {
+            hp.resize(count);
+            { const int rc_ = d2h_small(hp.data(), parts.p, sizeof(double) * count, st, W.mb); if (rc_) return rc_; }
             double h = 0.0;
             for (double v : hp) h += v;
             *out = (float)h;
             return 0;
         };
+        const size_t nplane_parts = (size_t)nz * DOT_PARTS;   // in (k, part) order (see dot_planes_kernel)
         // materialise K when it fits comfortably (see rbf_kbuild_kernel)
         RbfTaps taps;
         taps.n = 0;
@@ -2672,12 +2552,11 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
                     taps.off[taps.n][0] = (signed char)di; taps.off[taps.n][1] = (signed char)dj; taps.off[taps.n][2] = (signed char)dk;
                     taps.n++;
                 }
-        // first choice: the table of distinct entries; then the materialised matrix; then on the fly
-        const bool use_lut = LG.T != nullptr || LG.WT != nullptr;
+        // the form k: the materialised matrix, else on the fly
         bool use_k = false;
         std::unique_lock<std::mutex> kv_lock(g_rbf_kv_mutex, std::defer_lock);
-        if (!use_lut && !(mv_env && mv_env[0] == 'f')) kv_lock.try_lock();   // busy: fall back to on-the-fly
-        if (!use_lut && taps_ok && kv_lock.owns_lock()) {
+        if (P.mv == RbfMatvec::k) kv_lock.try_lock();   // busy: fall back to on-the-fly
+        if (taps_ok && kv_lock.owns_lock()) {
             size_t free_b = 0, total_b = 0;
             const size_t need = sizeof(float) * (size_t)n * (size_t)taps.n;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= total_b / 4 &&
@@ -2686,78 +2565,61 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
                 use_k = true;
             }
         }
-        HIP_C(hipMemcpy(d_r.p, d_f.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));
-        HIP_C(hipMemset(d_u.p, 0, sizeof(float) * (size_t)n));
-        HIP_C(hipMemset(d_w.p, 0, sizeof(float) * (size_t)n));
+        HIP_C(hipMemcpy(d_r, d_f, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));
+        HIP_C(hipMemset(d_u, 0, sizeof(float) * (size_t)n));
+        HIP_C(hipMemset(d_w, 0, sizeof(float) * (size_t)n));
         // dot(u, q): the partial sums of the row-walk product's workgroups (formed by that kernel, or by rbf_walk_dot_kernel
-        // for the other forms of the product: every form of the CG follows the same numbers)
+        // for the other forms of the product: every form of the CG follows the same numbers), in (k, walk, row piece) order
         const size_t nparts = rbf_walk_nparts(nx, ny, nz, 0, nz);
-        ENSURE_C(d_part2, sizeof(double) * std::max(nparts, (size_t)1));
-        std::vector<double> hp2(nparts);
-        auto sum_parts2 = [&](float* out) -> int {
-            { const int rc_ = d2h_small(hp2.data(), d_part2.p, sizeof(double) * nparts, st, W.mb); if (rc_) return rc_; }
-            double h = 0.0;
-            for (double v : hp2) h += v;   // in (k, walk, row piece) order
-            *out = (float)h;
-            return 0;
-        };
+        ENSURE_C(W.part2, sizeof(double) * std::max(nparts, (size_t)1));
         float rr;
-        TRY_C(dot(d_r.as<float>(), d_r.as<float>(), &rr));
+        dot_planes_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_r, d_r, (int64_t)nx * ny, W.part.as<double>());
+        TRY_C(sum_parts(W.part, nplane_parts, &rr));
         float residual = std::sqrt(rr), prev = 1.0f;
         const float tol = 3.4526698e-4f * residual;   // reltol = sqrt(eps(Float32)), abstol = 0
         const int64_t its_cap = n;
         RbfWalkArgs WAr;
-        const bool fused = !mv_env && LG.WT && walk_ok && rbf_walk_planes(LG, 0, -1, 0, -1, &WAr) && !getenv("R2S_RBF_CG_UNFUSED");
-        if (fused) {
+        if (P.mv == RbfMatvec::walk && rbf_walk_planes(T.LG, 0, -1, 0, -1, &WAr)) {
             // three passes per iteration: [w += alpha_prev u, u = r + beta u] (the weights take the step of the PREVIOUS
             // iteration here, where u is read anyway), the product with the parts of dot(u, q), [r -= alpha q with the parts of
             // dot(r, r)].  Same operations on the same numbers as the loop below (five passes).
-            float* ucur = d_u.as<float>();
             float alpha_prev = 0.0f;
-            auto r_dot = [&](float alpha, float* out) -> int {
-                cg_update_r_dot_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_r.as<float>(), d_q.as<float>(), alpha, (int64_t)nx * ny, d_part.as<double>());
-                std::vector<double> hp((size_t)nz * DOT_PARTS);
-                { const int rc_ = d2h_small(hp.data(), d_part.p, sizeof(double) * hp.size(), st, W.mb); if (rc_) return rc_; }
-                double h = 0.0;
-                for (double v : hp) h += v;
-                *out = (float)h;
-                return 0;
-            };
             while (!(residual <= tol) && its < its_cap) {
                 const float beta = (residual * residual) / (prev * prev);
-                cg_update_wu_kernel<<<(unsigned)((n / 4 + 256) / 256), 256, 0, st>>>(d_w.as<float>(), ucur, d_r.as<float>(), alpha_prev, beta, n);
-                WAr.T = LG.WT; WAr.x = ucur; WAr.y = d_q.as<float>(); WAr.dot_partial = d_part2.as<double>();
+                cg_update_wu_kernel<<<(unsigned)((n / 4 + 256) / 256), 256, 0, st>>>(d_w, d_u, d_r, alpha_prev, beta, n);
+                WAr.T = T.LG.WT; WAr.x = d_u; WAr.y = d_q; WAr.dot_partial = W.part2.as<double>();
                 rbf_walk_launch(0, RBF_NV, WAr, st);
                 float uq;
-                TRY_C(sum_parts2(&uq));
+                TRY_C(sum_parts(W.part2, nparts, &uq));
                 const float alpha = (residual * residual) / uq;
                 prev = residual;
-                TRY_C(r_dot(alpha, &rr));
+                cg_update_r_dot_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_r, d_q, alpha, (int64_t)nx * ny, W.part.as<double>());
+                TRY_C(sum_parts(W.part, nplane_parts, &rr));
                 residual = std::sqrt(rr);
                 its++;
                 alpha_prev = alpha;
             }
-            if (its > 0) cg_axpy_kernel<<<nb, 256, 0, st>>>(d_w.as<float>(), ucur, alpha_prev, n);   // the last iteration's step
+            if (its > 0) cg_axpy_kernel<<<nb, 256, 0, st>>>(d_w, d_u, alpha_prev, n);   // the last iteration's step
         } else
         while (!(residual <= tol) && its < its_cap) {
             const float beta = (residual * residual) / (prev * prev);
-            cg_update_u_kernel<<<nb, 256, 0, st>>>(d_u.as<float>(), d_r.as<float>(), beta, n);
-            double* dp = nullptr;   // (the row-walk kernel leaves the parts of dot(u, q) itself)
-            if (use_lut && LG.WT && !mv_env) dp = d_part2.as<double>();
-            if (use_lut) launch_rbf_matvec_lut(LG, nb, st, d_u.as<float>(), d_q.as<float>(), 0, -1, 0, -1, dp);
-            else if (use_k) rbf_matvec_k_kernel<<<nb, 256, 0, st>>>(G, taps, g_rbf_kv.as<float>(), d_u.as<float>(), d_q.as<float>());
-            else rbf_matvec_kernel<<<nb, 256, 0, st>>>(G, d_u.as<float>(), d_q.as<float>());
-            if (!dp) rbf_walk_dot_launch(d_u.as<float>(), d_q.as<float>(), nx, ny, nz, 0, nz, d_part2.as<double>(), st);
+            cg_update_u_kernel<<<nb, 256, 0, st>>>(d_u, d_r, beta, n);
+            if (P.mv == RbfMatvec::lut) launch_rbf_matvec_lut(RbfMatvec::lut, T.LG, nb, st, d_u, d_q);
+            else if (use_k) rbf_matvec_k_kernel<<<nb, 256, 0, st>>>(G, taps, g_rbf_kv.as<float>(), d_u, d_q);
+            else rbf_matvec_kernel<<<nb, 256, 0, st>>>(G, d_u, d_q);
+            rbf_walk_dot_launch(d_u, d_q, nx, ny, nz, 0, nz, W.part2.as<double>(), st);
             float uq;
-            TRY_C(sum_parts2(&uq));
+            TRY_C(sum_parts(W.part2, nparts, &uq));
             const float alpha = (residual * residual) / uq;
             prev = residual;
-            TRY_C(xr_dot(alpha, &rr));
+            // weights / residual update with dot(r, r)
+            cg_update_xr_dot_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_w, d_r, d_u, d_q, alpha, (int64_t)nx * ny, W.part.as<double>());
+            TRY_C(sum_parts(W.part, nplane_parts, &rr));
             residual = std::sqrt(rr);
             its++;
         }
     } else {
-        HIP_C(hipMemcpy(d_w.p, d_f.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));   // :353
+        HIP_C(hipMemcpy(d_w, d_f, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));   // :353
     }
     if (cg_iters) *cg_iters = its;
     // the output field (:363-366) + `add`
@@ -2773,11 +2635,11 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
             const unsigned nbc = (unsigned)((t1 - t0 + 255) / 256);
             if (FL.T) {
                 const int64_t waves = (int64_t)(f1 - f0) * fy * smooth * ((FL.nmx + 63) / 64);
-                rbf_apply_fine_lut_kernel<<<(unsigned)((waves + 3) / 4), 256, (size_t)FL.nrec * 4 * 16, st>>>(FL, d_w.as<float>(), add, dfine, f0, f1);
-            } else if (!(fine_one_to_one && launch_rbf_apply_lut(G, LGF, sts[1], nbc, st, d_w.as<float>(), d_tx.as<float>(), d_ty.as<float>(),
-                                                                 d_tz.as<float>(), d_st.as<Stencil>() + 1, add, dfine, t0, t1)))
-                rbf_apply_kernel<<<nbc, 256, 0, st>>>(G, d_w.as<float>(), smooth, fx, fy, fz, d_tx.as<float>(), d_ty.as<float>(),
-                                                     d_tz.as<float>(), d_st.as<Stencil>() + 1, add, dfine, t0, t1);
+                rbf_apply_fine_lut_kernel<<<(unsigned)((waves + 3) / 4), 256, (size_t)FL.nrec * 4 * 16, st>>>(FL, d_w, add, dfine, f0, f1);
+            } else if (!(P.one_to_one && launch_rbf_apply_lut(P.ev, G, T.LGF, P.sts[1], nbc, st, d_w, T.tx.as<float>(), T.ty.as<float>(),
+                                                                T.tz.as<float>(), T.st.as<Stencil>() + 1, add, dfine, t0, t1)))
+                rbf_apply_kernel<<<nbc, 256, 0, st>>>(G, d_w, smooth, fx, fy, fz, T.tx.as<float>(), T.ty.as<float>(),
+                                                     T.tz.as<float>(), T.st.as<Stencil>() + 1, add, dfine, t0, t1);
             if (fine_chunk) {
                 const int rcc = (*fine_chunk)(t0, t1);
                 if (rcc) return rcc;
@@ -2790,30 +2652,28 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     // The device array stays WITHOUT it (the chunks may still be on their way when the level is known)
     if (fine_early) TRY_C(eval_fine(0.0f));
     // ---- LSF on the coarse grid (:357) and the volume-preserving level (:359, :265-300) ----
-    if (!launch_rbf_apply_lut(G, LG, sts[0], nb, st, d_w.as<float>(), d_cx.as<float>(), d_cy.as<float>(), d_cz.as<float>(),
-                              d_st.as<Stencil>(), 0.0f, d_lsf.as<float>()))
-        rbf_apply_kernel<<<nb, 256, 0, st>>>(G, d_w.as<float>(), 1, nx, ny, nz, d_cx.as<float>(), d_cy.as<float>(),
-                                            d_cz.as<float>(), d_st.as<Stencil>(), 0.0f, d_lsf.as<float>());
-    if (lsf_out) HIP_C(hipMemcpy(lsf_out, d_lsf.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    if (!launch_rbf_apply_lut(P.ev, G, T.LG, P.sts[0], nb, st, d_w, G.cx, G.cy, G.cz, T.st.as<Stencil>(), 0.0f, d_lsf))
+        rbf_apply_kernel<<<nb, 256, 0, st>>>(G, d_w, 1, nx, ny, nz, G.cx, G.cy, G.cz, T.st.as<Stencil>(), 0.0f, d_lsf);
+    if (lsf_out) HIP_C(hipMemcpy(lsf_out, d_lsf, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
     TRY_C(vw.init(9));
-    TRY_C(vw.prepare(d_lsf.as<float>(), nx, ny, nz, st));
+    TRY_C(vw.prepare(d_lsf, nx, ny, nz, st));
     // the range of the field = the start of the bisection: from the extrema of the 64-cell segments that `prepare` has just
     // formed (every lattice point is a corner of some cell: the same two numbers as a sweep over the field, which cost
     // 0.28 ms at 512^3); a lattice without cells: the sweep
     int mmh[4] = {0x7FFFFFFF, (int)0x80000000, 0x7FFFFFFF, (int)0x80000000};
-    HIP_C(hipMemcpyAsync(d_cnt.p, mmh, 16, hipMemcpyHostToDevice, st));
+    HIP_C(hipMemcpyAsync(W.cnt.p, mmh, 16, hipMemcpyHostToDevice, st));
     const int64_t nsegs = vw.seg_field ? (int64_t)(ny - 1) * (nz - 1) * ((nx - 1 + 63) / 64) : 0;
     if (nsegs > 0) {
         const unsigned nbs = (unsigned)std::min<int64_t>((nsegs + 255) / 256, 128);   // (two same-address atomics per wavefront at the end: few wavefronts)
-        minmax_kernel<<<nbs, 256, 0, st>>>(vw.segmn.as<float>(), nsegs, d_cnt.as<int>());
-        minmax_kernel<<<nbs, 256, 0, st>>>(vw.segmx.as<float>(), nsegs, d_cnt.as<int>() + 2);
+        minmax_kernel<<<nbs, 256, 0, st>>>(vw.segmn.as<float>(), nsegs, W.cnt.as<int>());
+        minmax_kernel<<<nbs, 256, 0, st>>>(vw.segmx.as<float>(), nsegs, W.cnt.as<int>() + 2);
     } else {
-        minmax_kernel<<<(nb < 2048u ? nb : 2048u), 256, 0, st>>>(d_lsf.as<float>(), n, d_cnt.as<int>());
+        minmax_kernel<<<(nb < 2048u ? nb : 2048u), 256, 0, st>>>(d_lsf, n, W.cnt.as<int>());
     }
-    TRY_C(d2h_small(mmh, d_cnt.p, 16, st, W.mb));
+    TRY_C(d2h_small(mmh, W.cnt.p, 16, st, W.mb));
     auto dec = [](int b) { b = b >= 0 ? b : (b ^ 0x7FFFFFFF); float f; memcpy(&f, &b, 4); return f; };
     float lo = dec(mmh[0]), hi = dec(nsegs > 0 ? mmh[3] : mmh[1]);
-    const float edge = std::sqrt((cx[1] - cx[0]) * (cx[1] - cx[0]));   // norm(fine_grid[2,1,1] - fine_grid[1,1,1])
+    const float edge = std::sqrt((P.cx[1] - P.cx[0]) * (P.cx[1] - P.cx[0]));   // norm(fine_grid[2,1,1] - fine_grid[1,1,1])
     double eps = 1.0;
     float th = 0.0f;
     int it = 0;
@@ -2821,7 +2681,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
         th = (lo + hi) / 2;
         float vol;
         if (it > 0) TRY_C(vw.narrow(nx, ny, nz, edge, lo, hi, st));   // (level 0: [lo, hi] = the range of the field, every row is live)
-        TRY_C(vw.run(d_lsf.as<float>(), nx, ny, nz, edge, th, 0.0f, st, &vol));
+        TRY_C(vw.run(d_lsf, nx, ny, nz, edge, th, 0.0f, st, &vol));
         eps = std::fabs(target_volume - (double)vol);
         if ((double)vol > target_volume) lo = th; else hi = th;
         it++;
@@ -2832,7 +2692,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     if (!fine_early) TRY_C(eval_fine(th));   // (fine_early: done above, the shift is the caller's)
     HIP_C(hipGetLastError());
     if (out_dev) HIP_C(hipDeviceSynchronize());
-    else HIP_C(hipMemcpy(fine_out, d_fine.p, sizeof(float) * (size_t)nf, hipMemcpyDeviceToHost));
+    else HIP_C(hipMemcpy(fine_out, W.fine.p, sizeof(float) * (size_t)nf, hipMemcpyDeviceToHost));
     cleanup();
     return 0;
 }
@@ -3171,88 +3031,28 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
                      float* fine_out_host, float* th_out, int* cg_iters)
 {
     if (!g || !fine_out_host) return fail(R2S_ERR_ARG, "null argument");
-    if (smooth < 1 || smooth > 4) return fail(R2S_ERR_ARG, "smooth must be 1..4");
-    if (!(kthr >= R2S_RBF_MIN_KERNEL_THRESHOLD && kthr < 1.0))
-        return fail(R2S_ERR_ARG, "kernel threshold must be in [%g, 1): got %g", R2S_RBF_MIN_KERNEL_THRESHOLD, kthr);
-    const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
+    RbfPlan P;   // (the tables of every slab are built from it: it lives for the whole call)
+    int rc = rbf_plan(g, is_interp, smooth, kthr, P);
+    if (rc) return rc;
+    const int nx = P.nx, ny = P.ny, nz = P.nz, fx = P.fx, fy = P.fy, fz = P.fz;
     const int64_t plane = (int64_t)nx * ny;
-    const int fx = (int)g->N[0] * smooth + 1, fy = (int)g->N[1] * smooth + 1, fz = (int)g->N[2] * smooth + 1;
     const int64_t fplane = (int64_t)fx * fy;
     const size_t G = S.size();
-    int rc = 0;
     std::vector<size_t> order;
     for (size_t q = 0; q < G; ++q)
         if (S[q].k1 > S[q].k0) order.push_back(q);
     std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return S[a].k0 < S[b].k0; });
     if (order.empty()) return fail(R2S_ERR_ARG, "no slab owns a plane");
-    // ---- host-side geometry (as rbf_smooth_host) ----
-    std::vector<float> cx, cy, cz, tx(fx), ty(fy), tz(fz);
-    coarse_coords(g->aabb_min[0], g->aabb_max[0], nx, cx);
-    coarse_coords(g->aabb_min[1], g->aabb_max[1], ny, cy);
-    coarse_coords(g->aabb_min[2], g->aabb_max[2], nz, cz);
-    {
-        const float xmin = (float)g->aabb_min[0], xmax = (float)g->aabb_max[0], ymin = (float)g->aabb_min[1], zmin = (float)g->aabb_min[2];
-        const float dx = (xmax - xmin) / (float)(fx - 1);
-        for (int i = 0; i < fx; ++i) tx[i] = xmin + (float)i * dx;
-        for (int i = 0; i < fy; ++i) ty[i] = ymin + (float)i * dx;
-        for (int i = 0; i < fz; ++i) tz[i] = zmin + (float)i * dx;
-    }
-    std::vector<Stencil> sts;
-    bool capped = false;
-    if ((rc = build_stencils(smooth, kthr, sts, &capped))) return rc;
-    RbfGeom G0;
-    memset(&G0, 0, sizeof G0);
-    G0.nx = nx; G0.ny = ny; G0.nz = nz;
-    G0.sigma = g->cell_size;
-    G0.thr = kthr;
-    G0.max_distance = (float)std::sqrt(-std::log(kthr) * G0.sigma * G0.sigma);
-    {
-        const double R2 = -std::log(kthr);
-        G0.tap_d2 = (int)std::floor(R2 * 1.05 + 0.25);
-        G0.tap_r = (int)std::floor(std::sqrt((double)G0.tap_d2));
-    }
-    int halo = G0.tap_r;   // planes a stencil reaches beyond the slab
-    for (const Stencil& st : sts)
-        for (int q = 0; q < st.n; ++q) halo = std::max(halo, std::max((int)st.off[q][2], -(int)st.off[q][2]));
+    const int halo = P.halo;
     for (size_t q : order)
         if (S[q].h0 > std::max(0, S[q].k0 - halo) || S[q].h1 < std::min(nz, S[q].k1 + halo))
             return fail(R2S_ERR_ARG, "slab [%d,%d) holds [%d,%d): the smoothing stencils need a halo of %d planes", S[q].k0, S[q].k1,
                         S[q].h0, S[q].h1, halo);
-    // matvec and same-grid evaluation through the tables of distinct kernel values when the lattice allows it (else on the fly)
-    RbfLutVals LV;
-    memset(&LV, 0, sizeof LV);
-    std::vector<uint8_t> ix, iy, iz;
-    bool lut_axes = false, mv_fits = false;
-    const char* ap_env = getenv("R2S_RBF_APPLY");
-    const bool want_ap_lut = !(ap_env && ap_env[0] == 'f') && !capped;   // (the tables cannot count the knn cap)
-    if ((is_interp || want_ap_lut) && G0.tap_r >= 1 && G0.tap_r <= 3) {
-        LV.R = G0.tap_r; LV.sigma = G0.sigma; LV.thr = G0.thr; LV.max_distance = G0.max_distance;
-        const int m0 = rbf_lut_axis(cx, cx, G0.tap_r, LV.v[0], ix), m1 = rbf_lut_axis(cy, cy, G0.tap_r, LV.v[1], iy),
-                  m2 = rbf_lut_axis(cz, cz, G0.tap_r, LV.v[2], iz);
-        lut_axes = m0 && m1 && m2;
-        mv_fits = std::max(m0, std::max(m1, m2)) <= RBF_NV - 1;
-    }
-    const bool use_lut = is_interp && lut_axes && mv_fits;
-    const bool fine_one_to_one = smooth == 1 && fx == nx && fy == ny && fz == nz;
-    RbfLutVals LVF;
-    memset(&LVF, 0, sizeof LVF);
-    std::vector<uint8_t> fix, fiy, fiz;
-    bool lutf_axes = false;
-    int lutf_most = 0;
-    if (want_ap_lut && fine_one_to_one && G0.tap_r >= 1 && G0.tap_r <= 3) {
-        LVF.R = G0.tap_r; LVF.sigma = G0.sigma; LVF.thr = G0.thr; LVF.max_distance = G0.max_distance;
-        const int f0 = rbf_lut_axis(tx, cx, G0.tap_r, LVF.v[0], fix), f1 = rbf_lut_axis(ty, cy, G0.tap_r, LVF.v[1], fiy),
-                  f2 = rbf_lut_axis(tz, cz, G0.tap_r, LVF.v[2], fiz);
-        lutf_axes = f0 && f1 && f2;
-        lutf_most = std::max(f0, std::max(f1, f2));
-    }
-    const bool walk_ok = rbf_walk_supported(G0.tap_r, G0.tap_d2, nx, ny);
-    const char* mv_env = getenv("R2S_RBF_MATVEC");
-    SlabBufs blutf(S), bfvx(S), bfvy(S), bfvz(S), blv(S), blvf(S), bsegmn(S), bsegmx(S), bluta16(S), bwt(S), bwa(S), bwaf(S), bpart2(S);
-    SlabBufs bf(S), bw(S), br(S), bu(S), bq(S), blsf(S), bfine(S), bcx(S), bcy(S), bcz(S), btx(S), bty(S), btz(S), bst(S), bcnt(S),
-        bpart(S), blut(S), bluta(S), bvx(S), bvy(S), bvz(S), brows(S);
-    std::vector<RbfGeom> Gq(G, G0);
-    std::vector<RbfLutGeom> LG(G), LGF(G);
+    // the product: the row walk or the table kernels as planned; the materialised matrix is one device's, so `k` runs on the fly
+    const bool mv_lut = P.mv == RbfMatvec::walk || P.mv == RbfMatvec::lut;
+    SlabBufs bsegmn(S), bsegmx(S), bpart2(S);
+    SlabBufs bf(S), bw(S), br(S), bu(S), bq(S), blsf(S), bfine(S), bcnt(S), bpart(S), brows(S);
+    std::vector<RbfTables> tab(G);
     std::vector<VolumeWork> vw(G);
     std::vector<void*> base(G, nullptr);
     auto nheld = [&](size_t q) { return (size_t)(S[q].h1 - S[q].h0) * (size_t)plane; };
@@ -3285,78 +3085,15 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
     float th = 0.0f;
     uint32_t gmax_bits = 0;
     bool any_real = false;
-    // ---- per-slab set-up: buffers, coordinates, stencils, tables, process_vector pass 1 ----
+    // ---- per-slab set-up: buffers, coordinates, stencils, tables (on the slab's device and stream), process_vector pass 1 ----
     for (size_t q : order) {
         const Slab& d = S[q];
         const size_t nh = nheld(q);
         SLAB_TRY(bf.ensure(q, 4 * nh)); SLAB_TRY(bw.ensure(q, 4 * nh)); SLAB_TRY(blsf.ensure(q, 4 * nh));
         SLAB_TRY(bcnt.ensure(q, 64)); SLAB_TRY(bpart.ensure(q, sizeof(double) * (size_t)std::max(nz * DOT_PARTS, 1024)));
         if (is_interp) { SLAB_TRY(br.ensure(q, 4 * nh)); SLAB_TRY(bu.ensure(q, 4 * nh)); SLAB_TRY(bq.ensure(q, 4 * nh)); }
-        auto up = [&](SlabBufs& B, const void* src, size_t bytes) -> int {
-            int r2 = B.ensure(q, bytes);
-            if (r2) return r2;
-            HIP_TRY(hipMemcpyAsync(B.b[q].p, src, bytes, hipMemcpyHostToDevice, d.stream));
-            return 0;
-        };
-        SLAB_TRY(up(bcx, cx.data(), 4 * cx.size())); SLAB_TRY(up(bcy, cy.data(), 4 * cy.size())); SLAB_TRY(up(bcz, cz.data(), 4 * cz.size()));
-        SLAB_TRY(up(btx, tx.data(), 4 * tx.size())); SLAB_TRY(up(bty, ty.data(), 4 * ty.size())); SLAB_TRY(up(btz, tz.data(), 4 * tz.size()));
-        SLAB_TRY(up(bst, sts.data(), sizeof(Stencil) * sts.size()));
-        Gq[q].cx = bcx.at<float>(q); Gq[q].cy = bcy.at<float>(q); Gq[q].cz = bcz.at<float>(q);
-        memset(&LG[q], 0, sizeof(RbfLutGeom));
-        if (lut_axes) {
-            const int W = 2 * G0.tap_r + 1;
-            const size_t nT = (size_t)W * W * W * RBF_NV * RBF_NV * RBF_NV;
-            SLAB_TRY(up(bvx, ix.data(), ix.size())); SLAB_TRY(up(bvy, iy.data(), iy.size())); SLAB_TRY(up(bvz, iz.data(), iz.size()));
-            SLAB_TRY(up(blv, &LV, sizeof LV));
-            LG[q].nx = nx; LG[q].ny = ny; LG[q].nz = nz; LG[q].R = G0.tap_r; LG[q].tap_d2 = G0.tap_d2;
-            LG[q].vx = bvx.at<uint8_t>(q); LG[q].vy = bvy.at<uint8_t>(q); LG[q].vz = bvz.at<uint8_t>(q);
-            if (use_lut && walk_ok && !mv_env) {
-                SLAB_TRY(bwt.ensure(q, sizeof(float) * nT));
-                rbf_walk_table_kernel<0><<<(unsigned)((nT + 255) / 256), 256, 0, d.stream>>>(blv.at<RbfLutVals>(q), bwt.b[q].p, RBF_NV);
-                LG[q].WT = bwt.at<float>(q);
-            } else if (use_lut) {
-                SLAB_TRY(blut.ensure(q, sizeof(float) * nT));
-                rbf_lut_build_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, d.stream>>>(blv.at<RbfLutVals>(q), blut.at<float>(q));
-                LG[q].T = blut.at<float>(q);
-            }
-            if (want_ap_lut && walk_ok && !ap_env) {
-                const int nv = mv_fits ? RBF_NV : RBF_NVA;
-                const size_t nW = (size_t)W * W * W * nv * nv * nv;
-                SLAB_TRY(bwa.ensure(q, sizeof(double) * nW));
-                rbf_walk_table_kernel<1><<<(unsigned)((nW + 255) / 256), 256, 0, d.stream>>>(blv.at<RbfLutVals>(q), bwa.b[q].p, nv);
-                LG[q].WA = bwa.at<double>(q); LG[q].wa_nv = nv;
-            } else if (want_ap_lut) {
-                const size_t nTA = (size_t)W * W * W * RBF_NVA * RBF_NVA * RBF_NVA;
-                SLAB_TRY(bluta.ensure(q, sizeof(double) * nTA));
-                rbf_lut_build_apply_kernel<<<(unsigned)((nTA + 255) / 256), 256, 0, d.stream>>>(blv.at<RbfLutVals>(q), bluta.at<double>(q));
-                LG[q].TA = bluta.at<double>(q);
-                if (mv_fits) {
-                    SLAB_TRY(bluta16.ensure(q, sizeof(double) * nT));
-                    rbf_lut_build_apply_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, d.stream>>>(blv.at<RbfLutVals>(q), bluta16.at<double>(q), RBF_NV);
-                    LG[q].TA16 = bluta16.at<double>(q);
-                }
-            }
-        }
-        memset(&LGF[q], 0, sizeof(RbfLutGeom));
-        if (lutf_axes) {
-            const int W = 2 * G0.tap_r + 1;
-            const size_t nT = (size_t)W * W * W * RBF_NVA * RBF_NVA * RBF_NVA;
-            SLAB_TRY(up(bfvx, fix.data(), fix.size())); SLAB_TRY(up(bfvy, fiy.data(), fiy.size())); SLAB_TRY(up(bfvz, fiz.data(), fiz.size()));
-            LGF[q].nx = nx; LGF[q].ny = ny; LGF[q].nz = nz; LGF[q].R = G0.tap_r; LGF[q].tap_d2 = G0.tap_d2;
-            LGF[q].vx = bfvx.at<uint8_t>(q); LGF[q].vy = bfvy.at<uint8_t>(q); LGF[q].vz = bfvz.at<uint8_t>(q);
-            SLAB_TRY(up(blvf, &LVF, sizeof LVF));
-            if (walk_ok && !ap_env) {
-                const int nv = lutf_most <= RBF_NV - 1 ? RBF_NV : RBF_NVA;
-                const size_t nW = (size_t)W * W * W * nv * nv * nv;
-                SLAB_TRY(bwaf.ensure(q, sizeof(double) * nW));
-                rbf_walk_table_kernel<1><<<(unsigned)((nW + 255) / 256), 256, 0, d.stream>>>(blvf.at<RbfLutVals>(q), bwaf.b[q].p, nv);
-                LGF[q].WA = bwaf.at<double>(q); LGF[q].wa_nv = nv;
-            } else {
-                SLAB_TRY(blutf.ensure(q, sizeof(double) * nT));
-                rbf_lut_build_apply_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, d.stream>>>(blvf.at<RbfLutVals>(q), blutf.at<double>(q));
-                LGF[q].TA = blutf.at<double>(q);
-            }
-        }
+        SLAB_HIP(hipSetDevice(d.device));
+        SLAB_TRY(tab[q].build(P, d.stream));
         // process_vector pass 1 on the OWNED planes (every plane counts once for the maximum)
         SLAB_HIP(hipMemsetAsync(bcnt.b[q].p, 0, 64, d.stream));
         const int64_t no = nowned(q);
@@ -3403,7 +3140,7 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
                 cg_update_u_kernel<<<(unsigned)((no + 255) / 256), 256, 0, d.stream>>>(owned(bu.at<float>(q), q), owned(br.at<float>(q), q), beta, no);
             }
             SLAB_TRY(sync_slabs(S));
-            SLAB_TRY(halo_xchg(bu, G0.tap_r));
+            SLAB_TRY(halo_xchg(bu, P.G.tap_r));
             for (size_t q : order) {
                 const Slab& d = S[q];
                 const int64_t t0 = (int64_t)d.k0 * plane, t1 = (int64_t)d.k1 * plane;
@@ -3416,9 +3153,9 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
                 const size_t np = rbf_walk_nparts(nx, ny, nz, d.k0, d.k1);
                 SLAB_TRY(bpart2.ensure(q, sizeof(double) * std::max(np, (size_t)1)));
                 hp2[q].resize(np);
-                const bool walk_mv = use_lut && LG[q].WT && !mv_env;
-                if (use_lut) launch_rbf_matvec_lut(LG[q], nb, d.stream, xv, yv, t0, t1, xlo, xhi, walk_mv ? bpart2.at<double>(q) : nullptr);
-                else rbf_matvec_kernel<<<nb, 256, 0, d.stream>>>(Gq[q], xv, yv, t0, t1);
+                const bool walk_mv = P.mv == RbfMatvec::walk;
+                if (mv_lut) launch_rbf_matvec_lut(P.mv, tab[q].LG, nb, d.stream, xv, yv, t0, t1, xlo, xhi, walk_mv ? bpart2.at<double>(q) : nullptr);
+                else rbf_matvec_kernel<<<nb, 256, 0, d.stream>>>(tab[q].G, xv, yv, t0, t1);
                 if (!walk_mv) rbf_walk_dot_launch(xv, yv, nx, ny, nz, d.k0, d.k1, bpart2.at<double>(q), d.stream);
                 SLAB_HIP(hipMemcpyAsync(hp2[q].data(), bpart2.at<double>(q), sizeof(double) * np, hipMemcpyDeviceToHost, d.stream));
             }
@@ -3465,11 +3202,12 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         const Slab& d = S[q];
         const int64_t t0 = (int64_t)d.k0 * plane, t1 = (int64_t)d.k1 * plane;
         SLAB_HIP(hipSetDevice(d.device));
-        if (!launch_rbf_apply_lut(Gq[q], LG[q], sts[0], (unsigned)((t1 - t0 + 255) / 256), d.stream, vptr(bw.at<float>(q), q), bcx.at<float>(q),
-                                  bcy.at<float>(q), bcz.at<float>(q), bst.at<Stencil>(q), 0.0f, vptr(blsf.at<float>(q), q), t0, t1,
+        const RbfGeom& Gq = tab[q].G;
+        if (!launch_rbf_apply_lut(P.ev, Gq, tab[q].LG, P.sts[0], (unsigned)((t1 - t0 + 255) / 256), d.stream, vptr(bw.at<float>(q), q), Gq.cx,
+                                  Gq.cy, Gq.cz, tab[q].st.as<Stencil>(), 0.0f, vptr(blsf.at<float>(q), q), t0, t1,
                                   (int64_t)d.h0 * plane, (int64_t)d.h1 * plane - 1))
-            rbf_apply_kernel<<<(unsigned)((t1 - t0 + 255) / 256), 256, 0, d.stream>>>(Gq[q], vptr(bw.at<float>(q), q), 1, nx, ny, nz, bcx.at<float>(q),
-                                                                                    bcy.at<float>(q), bcz.at<float>(q), bst.at<Stencil>(q), 0.0f,
+            rbf_apply_kernel<<<(unsigned)((t1 - t0 + 255) / 256), 256, 0, d.stream>>>(Gq, vptr(bw.at<float>(q), q), 1, nx, ny, nz, Gq.cx,
+                                                                                    Gq.cy, Gq.cz, tab[q].st.as<Stencil>(), 0.0f,
                                                                                     vptr(blsf.at<float>(q), q), t0, t1);
     }
     SLAB_TRY(sync_slabs(S));
@@ -3510,7 +3248,7 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
                 volume_seg_minmax_kernel<<<(kc1 - S[q].k0) * (ny - 1), 256, 0, S[q].stream>>>(vptr(blsf.at<float>(q), q), nx, ny, nz, bsegmn.at<float>(q),
                                                                                              bsegmx.at<float>(q), S[q].k0 * (ny - 1));
         }
-        const float edge = std::sqrt((cx[1] - cx[0]) * (cx[1] - cx[0]));
+        const float edge = std::sqrt((P.cx[1] - P.cx[0]) * (P.cx[1] - P.cx[0]));
         const float elvol = edge * edge * edge, jac = elvol / 8.0f;
         for (size_t q : order) {
             SLAB_HIP(hipSetDevice(S[q].device));
@@ -3554,11 +3292,12 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         const int64_t t0 = (int64_t)f0 * fplane, t1 = (int64_t)f1 * fplane;
         SLAB_HIP(hipSetDevice(d.device));
         SLAB_TRY(bfine.ensure(q, 4 * (size_t)(t1 - t0)));
-        if (!(fine_one_to_one && launch_rbf_apply_lut(Gq[q], LGF[q], sts[1], (unsigned)((t1 - t0 + 255) / 256), d.stream, vptr(bw.at<float>(q), q),
-                                                      btx.at<float>(q), bty.at<float>(q), btz.at<float>(q), bst.at<Stencil>(q) + 1, th,
-                                                      bfine.at<float>(q) - t0, t0, t1, (int64_t)d.h0 * plane, (int64_t)d.h1 * plane - 1)))
-            rbf_apply_kernel<<<(unsigned)((t1 - t0 + 255) / 256), 256, 0, d.stream>>>(Gq[q], vptr(bw.at<float>(q), q), smooth, fx, fy, fz, btx.at<float>(q),
-                                                                                    bty.at<float>(q), btz.at<float>(q), bst.at<Stencil>(q) + 1, th,
+        RbfTables& T = tab[q];
+        if (!(P.one_to_one && launch_rbf_apply_lut(P.ev, T.G, T.LGF, P.sts[1], (unsigned)((t1 - t0 + 255) / 256), d.stream, vptr(bw.at<float>(q), q),
+                                                   T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), T.st.as<Stencil>() + 1, th,
+                                                   bfine.at<float>(q) - t0, t0, t1, (int64_t)d.h0 * plane, (int64_t)d.h1 * plane - 1)))
+            rbf_apply_kernel<<<(unsigned)((t1 - t0 + 255) / 256), 256, 0, d.stream>>>(T.G, vptr(bw.at<float>(q), q), smooth, fx, fy, fz, T.tx.as<float>(),
+                                                                                    T.ty.as<float>(), T.tz.as<float>(), T.st.as<Stencil>() + 1, th,
                                                                                     bfine.at<float>(q) - t0, t0, t1);
         SLAB_HIP(hipMemcpyAsync(fine_out_host + t0, bfine.at<float>(q), 4 * (size_t)(t1 - t0), hipMemcpyDeviceToHost, d.stream));
     }
@@ -3567,6 +3306,7 @@ done:
     for (size_t q = 0; q < G; ++q) {
         (void)hipSetDevice(S[q].device);
         vw[q].release();
+        tab[q].release();
     }
     return rc;
 }

@@ -143,7 +143,7 @@ FIELD_CASES = [((4, 3, 5), 1), ((61, 7, 5), 1), ((5, 67, 3), 1), ((130, 9, 8), 1
 
 
 def _modes(smooth):
-    return ("default", "fly", "lut", "lutg") if smooth == 1 else ("default", "fly")
+    return ("default", "fly", "lut") if smooth == 1 else ("default", "fly")
 
 
 def _run_field(pkg, oracle, monkeypatch, g, sdf, target, smooth, thr, note):
@@ -166,8 +166,8 @@ def _run_field(pkg, oracle, monkeypatch, g, sdf, target, smooth, thr, note):
 
 @pytest.mark.parametrize("dims,smooth", FIELD_CASES)
 def test_rbf_fields_against_float64(pkg, oracle, monkeypatch, dims, smooth):
-    """banded synthetic spheres with sentinels on the lattices of the kernel tests (the row walk, LDS, table and
-    fine-table instantiations are the code under test), approximation mode, under every form of the evaluation"""
+    """banded synthetic spheres with sentinels on the lattices of the kernel tests (the row walk, table and fine-table
+    instantiations are the code under test), approximation mode, under every form of the evaluation"""
     g = _grid(pkg, dims)
     sdf, target = _banded_spheres(g, sum(dims) + smooth)
     worst = _run_field(pkg, oracle, monkeypatch, g, sdf, target, smooth, 1e-3, dims)

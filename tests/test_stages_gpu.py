@@ -234,11 +234,11 @@ def test_rbf_matvec_variants_are_bit_identical(pkg, oracle, monkeypatch):
     vd, vf = oracle.mesh_volume(X, IEN, rho)
     pg = pkg.noninteractive_sdf_grid_setup(pkg.Mesh(X, IEN))
     outs = {}
-    for mode in ("walk", "lut", "lutg", "k", "fly"):   # walk: default; lut: table rows staged in LDS; lutg: entries gathered from L1 / L2
+    for mode in ("walk", "lut", "k", "fly"):   # walk: default; lut: table entries gathered from L1 / L2
         _set_rbf_mode(monkeypatch, mode, ("R2S_RBF_MATVEC",))
         info = {}
         outs[mode] = (pkg.RBFs_smoothing(sdf, pg, True, 1, vd * vf, info=info), info["cg_iterations"], info["th"], info["lsf"])
-    for mode in ("walk", "lutg", "k", "fly"):
+    for mode in ("walk", "k", "fly"):
         assert outs[mode][1] == outs["lut"][1] and outs[mode][2] == outs["lut"][2]
         assert np.array_equal(outs[mode][0], outs["lut"][0]) and np.array_equal(outs[mode][3], outs["lut"][3])
     pkg._lib.lib().r2s_release_cache()
@@ -267,10 +267,10 @@ def test_rbf_tables_other_kernel_thresholds(pkg, oracle, monkeypatch, threshold)
 
 
 @pytest.mark.gpu
-def test_rbf_lds_kernels_on_a_wide_grid(pkg, monkeypatch):
-    """the kernels that stage their table rows in LDS need rows of >= 256 points (a workgroup of 256 consecutive rows then
-    spans at most two lattice rows): a 261 x 41 x 37 lattice with a banded synthetic SDF, CG + evaluation, against the
-    gathered-table kernels and neighbour-by-neighbour evaluation - bit for bit"""
+def test_rbf_forms_on_a_wide_grid(pkg, monkeypatch):
+    """rows of >= 256 points (a workgroup of 256 consecutive rows spans at most two lattice rows): a 261 x 41 x 37 lattice
+    with a banded synthetic SDF, CG + evaluation through the row walk and the table kernels, against neighbour-by-neighbour
+    evaluation - bit for bit"""
     g = pkg.Grid(np.array([0.013, -0.2, 0.07]), np.array([26.013, 3.8, 3.67]), 260, 0)
     nx, ny, nz = g.dims
     assert nx >= 256
@@ -280,11 +280,11 @@ def test_rbf_lds_kernels_on_a_wide_grid(pkg, monkeypatch):
     sdf = np.where(np.abs(sdf) < 6 * g.cell_size, sdf, np.sign(sdf) * 1e10).ravel()
     target = float((sdf > 0).sum()) * g.cell_size ** 3
     outs = {}
-    for mode in ("walk", "lut", "lutg", "fly"):
+    for mode in ("walk", "lut", "fly"):
         _set_rbf_mode(monkeypatch, mode)
         info = {}
         outs[mode] = (pkg.RBFs_smoothing(sdf, g, True, 1, target, info=info), info["cg_iterations"], info["th"], info["lsf"])
-    for mode in ("walk", "lutg", "fly"):
+    for mode in ("walk", "fly"):
         assert outs[mode][1] == outs["lut"][1] and outs[mode][2] == outs["lut"][2]
         assert np.array_equal(outs[mode][0], outs["lut"][0]) and np.array_equal(outs[mode][3], outs["lut"][3])
     assert outs["lut"][1] > 0 and np.isfinite(outs["lut"][0]).all()
@@ -328,11 +328,11 @@ def test_rbf_evaluation_table_is_bit_identical(pkg, oracle, monkeypatch, interp)
     vd, vf = oracle.mesh_volume(X, IEN, rho)
     pg = pkg.noninteractive_sdf_grid_setup(pkg.Mesh(X, IEN))
     outs = {}
-    for mode in ("walk", "lut", "lutg", "fly"):   # walk: default; lut: table rows staged in LDS where a workgroup spans <= 2 rows; lutg: gathered
+    for mode in ("walk", "lut", "fly"):   # walk: default; lut: table entries gathered from L1 / L2
         _set_rbf_mode(monkeypatch, mode, ("R2S_RBF_APPLY",))
         info = {}
         outs[mode] = (pkg.RBFs_smoothing(sdf, pg, interp, 1, vd * vf, info=info), info["th"], info["lsf"])
-    for mode in ("walk", "lutg", "fly"):
+    for mode in ("walk", "fly"):
         assert outs[mode][1] == outs["lut"][1]
         assert np.array_equal(outs[mode][0], outs["lut"][0]) and np.array_equal(outs[mode][2], outs["lut"][2])
     assert np.isfinite(outs["lut"][0]).all() and np.ptp(outs["lut"][0]) > 0
