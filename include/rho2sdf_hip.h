@@ -169,8 +169,13 @@ typedef struct {
     int32_t analyze_components;          /* 1 (with remove_artifacts): keep the component table of the labelling that artifact
                                             removal computes on the raw field at threshold 0 (analyze_sdf_components before the
                                             cleanup, RhoToSDF.jl:177-179); read it with r2s_last_components.  0 = no change */
+    /* reserved[R2S_OPT_EXTRACT_SURFACE] = extract_surface: 1 (needs the smoothing, so not with skip_rbf: R2S_ERR_ARG) keeps the
+       iso-0 surface of the returned fine field on the lattice exportSdfToVTI writes (origin aabb_min, spacing
+       cell_size / rbf_smooth) as the calling thread's last surface; read it with r2s_last_isosurface.  Bit-identical to
+       r2s_extract_isosurface of fine_sdf_out.  0 = no change.  reserved[1] must be 0. */
     int32_t reserved[2];
 } r2s_options;
+#define R2S_OPT_EXTRACT_SURFACE 0 /* index of the extract_surface flag in r2s_options.reserved */
 
 typedef struct {
     double V_domain, V_frac;             /* calculate_mesh_volume */
@@ -343,7 +348,42 @@ int r2s_rbf_smooth_dev(const double *d_sdf, const r2s_grid *grid, int32_t is_int
                        double kernel_threshold, double target_volume, float *d_fine_out, float *level_shift_out,
                        int32_t *cg_iters_out, void *stream);
 
+/* ---- iso-surface extraction ---------------------------------------------------------------
+ * The reference's only geometry output is a plot (visualize_stable_isosurface, src/Visualizations/VisualizeIsosurface.jl:
+ * Makie's contour!(sdf, levels=[0])).  This is the watertight triangle mesh of {f >= iso} on a regular lattice:
+ *   - values: dims[0] x dims[1] x dims[2] points, x fastest, Float32 (is_float32 = 1) or Float64; point (i,j,k) sits at
+ *     origin + spacing*(i,j,k).  A point is interior when f >= iso; NaN is exterior.
+ *   - one vertex on every lattice edge whose endpoints differ in interiority, at t = (iso - f0)/(f1 - f0) in double from
+ *     the lower endpoint (t = 0.5 when an endpoint is not finite), rounded to float32 once; vertices in ascending order
+ *     of the edge key 3*p + a (p = 0-based x-fastest index of the lower endpoint, a = 0/1/2 for x/y/z).
+ *   - triangles (0-based int32 vertex indices) by cube linear index, then in the order of a 256-case face-consistent
+ *     table (tools/gen_iso_table.py: ambiguous faces separate the interior corners), at most 5 per cube; normals
+ *     (v1-v0)x(v2-v0) point from the interior to the exterior.  Closed where the interior does not touch the lattice
+ *     border; there is no capping and coincident vertices (exact-iso points) are not welded.
+ *   - >= 2^31 vertices: R2S_ERR_UNSUPPORTED.  Any dim < 2, a non-positive or non-finite spacing or a NaN iso: R2S_ERR_ARG
+ *     before any device work.
+ * Host variant: *n_verts / *n_tris are always the full counts; the first min(capacity, n) entries are written (verts_out
+ * [n][3] float, tris_out [n][3] int32); pointers may be NULL only with capacity 0.  It replaces the calling thread's last
+ * surface, which r2s_last_isosurface reads (same two-step pattern as r2s_analyze_components / r2s_last_components). */
+int r2s_extract_isosurface(const void *values, int32_t is_float32, const int64_t dims[3], const double origin[3],
+                           double spacing, double iso, int32_t device, float *verts_out, int64_t vert_capacity,
+                           int32_t *tris_out, int64_t tri_capacity, int64_t *n_verts, int64_t *n_tris);
+int r2s_last_isosurface(float *verts_out, int64_t vert_capacity, int32_t *tris_out, int64_t tri_capacity,
+                        int64_t *n_verts, int64_t *n_tris);
+/* device field and device outputs on the current device, after the work on `stream`; the counts (host pointers) are
+ * always returned, the arrays are written only when both capacities hold everything (count with capacity 0, allocate,
+ * call again: the kernels run twice).  Synchronous on return.  Does not touch the thread's last surface. */
+int r2s_extract_isosurface_dev(const void *d_values, int32_t is_float32, const int64_t dims[3], const double origin[3],
+                               double spacing, double iso, float *d_verts, int64_t vert_capacity, int32_t *d_tris,
+                               int64_t tri_capacity, int64_t *n_verts, int64_t *n_tris, void *stream);
+
 /* ---- on-disk output ------------------------------------------------------------------ */
+
+/* binary STL of a triangle mesh (verts [n_verts][3], tris [n_tris][3] 0-based); host only, no device; ".stl" appended
+ * when missing.  80-byte header that does not begin with "solid", uint32 facet count, 50 bytes per facet: the float32
+ * normalised (v1-v0)x(v2-v0) ((0,0,0) for zero area), the three vertices, attribute 0.  >= 2^32 facets:
+ * R2S_ERR_UNSUPPORTED; an index outside [0, n_verts): R2S_ERR_ARG. */
+int r2s_export_stl(const char *filename, const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris);
 
 /* exportSdfToVTI(filename, grid, values, value_label, smooth)       src/DataExport/ExportToVTI.jl:22-67
  * VTK ImageData: dimensions N*smooth+1 (smooth = 0: N+1, i.e. `nothing`), Origin = AABB_min, Spacing =

@@ -8,9 +8,11 @@ from . import _lib
 from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, RBFs_smoothing, Rho2sdfOptions, Sign_Detection,
                   calculate_mesh_volume, calculate_volume_from_sdf, evalDistances, find_threshold_for_volume,
                   exportSdfToVTI, exportToVTU, export_sdf_results, getMesh_AABB, import_vtu_mesh, noninteractive_sdf_grid_setup,
-                  remove_sdf_artifacts, rho2sdf, sdf_fused, host_array, calculate_isocontour_volume, MeshInformations)
+                  remove_sdf_artifacts, rho2sdf, sdf_fused, host_array, calculate_isocontour_volume, MeshInformations,
+                  extract_isosurface, extract_isosurface_dev, export_stl)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
            "exportSdfToVTI", "exportToVTU", "export_sdf_results", "getMesh_AABB", "import_vtu_mesh", "noninteractive_sdf_grid_setup", "remove_sdf_artifacts",
-           "rho2sdf", "sdf_fused", "host_array", "calculate_isocontour_volume", "MeshInformations", "_lib"]
+           "rho2sdf", "sdf_fused", "host_array", "calculate_isocontour_volume", "MeshInformations",
+           "extract_isosurface", "extract_isosurface_dev", "export_stl", "_lib"]

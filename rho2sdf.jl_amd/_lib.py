@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("R2S_LIB_OVERRIDE") or os.path.join(_HERE, "librho2sdf
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
 c_float_p = ctypes.POINTER(ctypes.c_float)
+c_int32_p = ctypes.POINTER(ctypes.c_int32)
+OPT_EXTRACT_SURFACE = 0   # R2S_OPT_EXTRACT_SURFACE
 
 
 class R2SGrid(ctypes.Structure):
@@ -35,6 +37,9 @@ class R2SOptions(ctypes.Structure):
                 ("remove_artifacts", ctypes.c_int32), ("device", ctypes.c_int32), ("n_gpus", ctypes.c_int32),
                 ("skip_rbf", ctypes.c_int32), ("true_min", ctypes.c_int32), ("sign_no_inner", ctypes.c_int32),
                 ("analyze_components", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+    # reserved[R2S_OPT_EXTRACT_SURFACE] (include/rho2sdf_hip.h): keep the iso-0 surface of the fine field
+    extract_surface = property(lambda s: s.reserved[OPT_EXTRACT_SURFACE],
+                               lambda s, v: s.reserved.__setitem__(OPT_EXTRACT_SURFACE, int(v)))
 
 
 class R2SRunInfo(ctypes.Structure):
@@ -140,6 +145,13 @@ SYMBOLS = [
     ("r2s_import_mat", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(R2SVtuMesh)]),
     ("r2s_rbf_smooth_dev", ctypes.c_int, [_P, ctypes.POINTER(R2SGrid), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                           ctypes.c_double, _P, c_float_p, ctypes.POINTER(ctypes.c_int32), _P]),
+    ("r2s_extract_isosurface", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_int32, c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, c_int64_p,
+                                              c_int64_p]),
+    ("r2s_last_isosurface", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, c_int64_p, c_int64_p]),
+    ("r2s_extract_isosurface_dev", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                                  _P, ctypes.c_int64, _P, ctypes.c_int64, c_int64_p, c_int64_p, _P]),
+    ("r2s_export_stl", ctypes.c_int, [ctypes.c_char_p, c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64]),
 ]
 
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8

@@ -397,6 +397,77 @@ def exportSdfToVTI(filename, grid, values, value_label, smooth=None, compress=0)
     return filename if filename.endswith(".vti") else filename + ".vti"
 
 
+def _iso_lattice(grid, smooth):
+    """(dims, origin, spacing) of the lattice exportSdfToVTI writes for `grid` and `smooth` (None: N+1 points, cell_size)"""
+    s = 1 if smooth is None else int(smooth)
+    dims = (ctypes.c_int64 * 3)(*[int(n) * s + 1 for n in grid.c.N])
+    origin = (ctypes.c_double * 3)(*grid.c.aabb_min)
+    spacing = float(grid.cell_size) if smooth is None else float(grid.cell_size) / float(s)
+    return dims, origin, spacing
+
+
+def _last_isosurface():
+    """the calling thread's last surface (r2s_last_isosurface): count, then copy"""
+    nv, nt = ctypes.c_int64(), ctypes.c_int64()
+    L.check(L.lib().r2s_last_isosurface(None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt)))
+    verts, tris = np.empty((nv.value, 3), np.float32), np.empty((nt.value, 3), np.int32)
+    L.check(L.lib().r2s_last_isosurface(_f(verts), nv.value, tris.ctypes.data_as(L.c_int32_p), nt.value, ctypes.byref(nv),
+                                        ctypes.byref(nt)))
+    return verts, tris
+
+
+def extract_isosurface(values, grid, smooth=None, *, iso=0.0, device=-1):
+    """The watertight triangle mesh of {values >= iso} (include/rho2sdf_hip.h, r2s_extract_isosurface) -> (verts (nv, 3)
+    float32, tris (nt, 3) int32, 0-based).  `values` is the (nz, ny, nx) float32 fine field (smooth = the rbf_grid factor)
+    or the float64 `sdf_dists` (smooth=None); the lattice is the one exportSdfToVTI writes for the same grid and smooth, so
+    the mesh overlays the .vti.  Vertices lie on the lattice edges that cross the level, in ascending edge order; normals
+    (v1-v0)x(v2-v0) point from the interior to the exterior.  No counterpart in the reference, whose only geometry output
+    is a Makie contour plot (src/Visualizations/VisualizeIsosurface.jl)."""
+    a = np.ascontiguousarray(values)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    dims, origin, spacing = _iso_lattice(grid, smooth)
+    if a.size != dims[0] * dims[1] * dims[2]:
+        raise L.R2SError(f"values length ({a.size}) doesn't match the lattice {tuple(dims)}")
+    nv, nt = ctypes.c_int64(), ctypes.c_int64()
+    L.check(L.lib().r2s_extract_isosurface(a.ctypes.data_as(ctypes.c_void_p), int(a.dtype == np.float32), dims, origin, spacing,
+                                           float(iso), int(device), None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt)))
+    return _last_isosurface()
+
+
+def extract_isosurface_dev(t, grid, smooth=None, *, iso=0.0, stream=None):
+    """extract_isosurface on a torch tensor on the current device (float32 / float64, contiguous, x fastest) -> (verts, tris)
+    as device tensors.  Counts first, then allocates and emits: the kernels run twice."""
+    import torch
+    if t.dtype not in (torch.float32, torch.float64) or not t.is_contiguous() or not t.is_cuda:
+        raise L.R2SError("t must be a contiguous float32 / float64 device tensor")
+    dims, origin, spacing = _iso_lattice(grid, smooth)
+    if t.numel() != dims[0] * dims[1] * dims[2]:
+        raise L.R2SError(f"values length ({t.numel()}) doesn't match the lattice {tuple(dims)}")
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    nv, nt = ctypes.c_int64(), ctypes.c_int64()
+    f32 = int(t.dtype == torch.float32)
+    L.check(L.lib().r2s_extract_isosurface_dev(ctypes.c_void_p(t.data_ptr()), f32, dims, origin, spacing, float(iso), None, 0, None,
+                                               0, ctypes.byref(nv), ctypes.byref(nt), st))
+    verts = torch.empty((nv.value, 3), dtype=torch.float32, device=t.device)
+    tris = torch.empty((nt.value, 3), dtype=torch.int32, device=t.device)
+    if nv.value or nt.value:
+        L.check(L.lib().r2s_extract_isosurface_dev(ctypes.c_void_p(t.data_ptr()), f32, dims, origin, spacing, float(iso),
+                                                   ctypes.c_void_p(verts.data_ptr()), nv.value, ctypes.c_void_p(tris.data_ptr()),
+                                                   nt.value, ctypes.byref(nv), ctypes.byref(nt), st))
+    return verts, tris
+
+
+def export_stl(filename, verts, tris):
+    """binary STL of a triangle mesh (verts (nv, 3) float32, tris (nt, 3) 0-based); ".stl" is appended when missing.
+    Returns the path written."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    L.check(L.lib().r2s_export_stl(str(filename).encode(), _f(v), len(v), t.ctypes.data_as(L.c_int32_p), len(t)))
+    filename = str(filename)
+    return filename if filename.endswith(".stl") else filename + ".stl"
+
+
 def exportToVTU(fileName, X, IEN, VTK_CODE=None, rho=None):
     """exportToVTU(fileName, X, IEN, VTK_CODE, rho) - ASCII UnstructuredGrid of the mesh with optional nodal
     densities (src/DataExport/ExportToVTU.jl:2-99).  X (nnp, 3), IEN (nel, nen) 1-based; VTK_CODE defaults to
@@ -486,7 +557,7 @@ class Rho2sdfOptions:
 
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
-            info=None, pinned_results=False, fine_out=None, dists_out=None):
+            info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -499,7 +570,10 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     options.export_analysis and remove_artifacts also "components_before": analyze_sdf_components of the raw field
     (RhoToSDF.jl:177-179), taken from the labelling the artifact removal runs anyway.
     `fine_out` (Float32, one value per fine grid point) / `dists_out` (Float64, one per sdf_grid point): result arrays
-    to fill instead of new ones (e.g. from host_array); fine_sdf is then a view of fine_out."""
+    to fill instead of new ones (e.g. from host_array); fine_sdf is then a view of fine_out.
+    surface=True: the library also extracts the iso-0 surface of fine_sdf on the device (r2s_options extract_surface);
+    info["surface"] = (verts, tris) as extract_isosurface(fine_sdf, sdf_grid, smooth) returns them (bit-identical), and
+    export_results=True also writes it next to the .vti as <same name>.stl.  The return values are unchanged."""
     options = options or Rho2sdfOptions()
     mesh = Mesh(X, IEN, options.element_type)
     rho = np.ascontiguousarray(rho, dtype=np.float64)
@@ -525,6 +599,7 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
         o.rbf_kernel_threshold = float(options.rbf_kernel_threshold)
     o.device = int(device)
     o.n_gpus = int(n_gpus)
+    o.extract_surface = int(bool(surface))
     dims = tuple(int(nn) * smooth + 1 for nn in sdf_grid.c.N)
     nfine = dims[0] * dims[1] * dims[2]
     alloc = host_array if pinned_results else (lambda n, dt=np.float64: np.empty(n, dtype=dt))
@@ -539,10 +614,15 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
         info["rho_n"] = rho_n
         if analysis:
             info["components_before"] = _components_dict(lambda r, s, cap, n: L.lib().r2s_last_components(r, s, cap, n))
+    mesh_out = _last_isosurface() if surface else None
+    if info is not None and surface:
+        info["surface"] = mesh_out
     fine_sdf = fine.reshape(dims[2], dims[1], dims[0])
     xmin, xmax = np.float32(sdf_grid.AABB_min[0]), np.float32(sdf_grid.AABB_max[0])
     spacing = (xmax - xmin) / np.float32(fine_sdf.shape[2] - 1)
     fine_grid = (sdf_grid.AABB_min.astype(np.float32), float(spacing), fine_sdf.shape[::-1])
     if export_results:
-        export_sdf_results(fine_sdf, sdf_grid, taskName, smooth, options.rbf_interp, mesh.element_type)
+        vti = export_sdf_results(fine_sdf, sdf_grid, taskName, smooth, options.rbf_interp, mesh.element_type)
+        if surface:
+            export_stl(vti[:-len(".vti")] + ".stl", *mesh_out)
     return fine_sdf, fine_grid, sdf_grid, sdf_dists

@@ -191,6 +191,7 @@ struct HostSession {
     size_t pk_host_cap = 0;
     void* fine_host = nullptr;     // pinned landing zone of the smoothed field before its level shift (r2s_rho2sdf)
     size_t fine_host_cap = 0;
+    r2s_int::IsoWork iso;          // work buffers of the iso-surface of the smoothed field (r2s_rho2sdf, extract_surface)
 
     int init(int dev)
     {
@@ -222,6 +223,7 @@ struct HostSession {
         DevBuf* all[] = {&dX, &dI, &dR, &dE, &out[0], &out[1], &out[2], &out[3], &fine, &raw, &slab, &pk,
                          &pre_ws[0], &pre_ws[1], &pre_ws[2], &pre_ws[3], &pre_ws[4], &pre_ws[5], &pre_ws[6]};
         for (DevBuf* b : all) b->release();
+        iso.release();
         if (pk_host) r2s_host_free(pk_host);
         pk_host = nullptr;
         if (fine_host) r2s_host_free(fine_host);
@@ -851,7 +853,12 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     if (options) o = *options; else r2s_default_options(&o);
     if (o.elem_type != R2S_HEX8 && o.elem_type != R2S_TET4) return fail(R2S_ERR_UNSUPPORTED, "unknown element type %d", o.elem_type);
     if (!o.skip_rbf && !fine_sdf_out) return fail(R2S_ERR_ARG, "fine_sdf_out is null (set skip_rbf to stop after the raw SDF)");
+    const bool want_surface = o.reserved[R2S_OPT_EXTRACT_SURFACE] != 0;
+    if (want_surface && o.skip_rbf) return fail(R2S_ERR_ARG, "extract_surface needs the smoothed field (skip_rbf is set)");
     if (o.rbf_smooth < 1) o.rbf_smooth = 1;
+    // the lattice of the fine field as exportSdfToVTI writes it (origin aabb_min, spacing cell_size / smooth)
+    const int64_t fine_dims[3] = {grid->N[0] * o.rbf_smooth + 1, grid->N[1] * o.rbf_smooth + 1, grid->N[2] * o.rbf_smooth + 1};
+    const double fine_spacing = grid->cell_size / (double)o.rbf_smooth;
     int dev0 = 0, rc, G = o.n_gpus > 1 ? o.n_gpus : 1;
     if ((rc = resolve_device(o.device, &dev0))) return rc;
     if (G > 1) {
@@ -1049,6 +1056,12 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
                 return rc;
             ri.cg_iters = its;
         }
+        if (want_surface) {   // from the assembled host array through the standalone path on device 0 (bit-identical by construction)
+            r2s_int::Surface surf;
+            HIP_TRY(hipSetDevice(slabs[0].device));
+            if ((rc = r2s_int::extract_isosurface_host(fine_sdf_out, true, fine_dims, grid->aabb_min, fine_spacing, 0.0, surf))) return rc;
+            r2s_int::set_last_surface(std::move(surf));
+        }
         const double t6m = now_ms();
         ri.ms_rbf = t6m - t5m;
         ri.ms_download = t5m - t4m;
@@ -1190,6 +1203,18 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     }
     double t5 = now_ms();
     ri.ms_rbf = t5 - t4;
+    // ---- iso-surface of the final field, on the device where it lives, while the field travels to the host (the download
+    // thread's copy stream); on the early path the device field lacks the level shift, which the extraction adds the way
+    // the host threads do (Float32 sum), so the surface is that of the array the caller receives ----
+    if (want_surface) {
+        r2s_int::Surface surf;
+        if ((rc = r2s_int::extract_isosurface_dev(S->fine.p, true, fine_dims, grid->aabb_min, fine_spacing, 0.0, ri.level_shift, early,
+                                                  nullptr, S->iso, surf))) {
+            (void)join_dl();
+            return rc;
+        }
+        r2s_int::set_last_surface(std::move(surf));
+    }
     // ---- rest of the results to the caller ----
     if (early) {   // the level shift: fine = raw + th (Float32), by the host threads, chunk by chunk as the chunks arrive
         ensure_pool(S);

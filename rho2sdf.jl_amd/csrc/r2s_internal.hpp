@@ -82,4 +82,26 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
 // frees the cached per-device host sessions (r2s_host.hip); called by r2s_release_cache()
 void release_host_sessions();
 
+// ---- iso-surface extraction (r2s_surface.hip) -------------------------------------------------------------------------
+struct Surface {
+    std::vector<float> verts;    // [nv][3]
+    std::vector<int32_t> tris;   // [nt][3], 0-based
+};
+// replaces the calling thread's last surface (r2s_last_isosurface)
+void set_last_surface(Surface&& s);
+// device work buffers of one extraction (kept by the caller between calls on the CURRENT device)
+struct IsoWork {
+    DevBuf rows, tiles, tot, field, verts, tris;
+    void release();
+};
+// the surface of a device field (Float32 or Float64, x fastest) on the current device, after the work queued on `st`;
+// has_shift: Float32 values are read as f + shift (float32 sum), the level shift the host adds to an early fine field
+int extract_isosurface_dev(const void* d_values, bool is_float32, const int64_t dims[3], const double origin[3], double spacing,
+                           double iso, float shift, bool has_shift, hipStream_t st, IsoWork& w, Surface& out);
+// the same from a host array (uploaded to the current device)
+int extract_isosurface_host(const void* values, bool is_float32, const int64_t dims[3], const double origin[3], double spacing,
+                            double iso, Surface& out);
+// frees the work buffers r2s_extract_isosurface_dev keeps per device; called by r2s_release_cache()
+void release_iso_work();
+
 }  // namespace r2s_int

@@ -3477,6 +3477,7 @@ void r2s_release_cache(void)
         g_rbf_kv.release();
     }
     release_ccl_work();
+    r2s_int::release_iso_work();
     r2s_int::release_host_sessions();
 }
 

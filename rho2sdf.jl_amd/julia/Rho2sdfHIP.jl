@@ -309,6 +309,40 @@ function print_components(comps::Dict{Int,Int})                                 
     end
 end
 
+# The geometry of a result (no counterpart in the reference, whose only view of it is Makie's contour!(sdf, levels=[0]) in
+# src/Visualizations/VisualizeIsosurface.jl): the watertight triangle mesh of {values >= iso} on the lattice
+# exportSdfToVTI writes for (grid, smooth) - smooth = nothing: N+1 points, cell_size; so the mesh overlays the .vti.
+# values: fine_sdf (Float32) or sdf_dists / the raw field (Float64, N+1 points per axis).  Returns (3 x nv Float32,
+# 3 x nt Int32, 1-based); normals (v2-v1)x(v3-v1) point from the interior to the exterior.  Bit-identical to the surface
+# r2s_rho2sdf keeps with its extract_surface option (which this binding's rho2sdf_hip leaves off: reserved = (0, 0)).
+function extract_isosurface_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
+                                iso = 0.0f0) where {T<:Union{Float32,Float64}}
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    length(values) == prod(dims) || error("values length ($(length(values))) doesn't match the lattice $(Tuple(dims))")
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    nv = Ref{Int64}(0); nt = Ref{Int64}(0)
+    check(ccall((:r2s_extract_isosurface, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Float64, Float64, Int32, Ptr{Float32}, Int64, Ptr{Int32}, Int64,
+                 Ref{Int64}, Ref{Int64}),
+                values, Int32(T == Float32), collect(dims), collect(Float64.(grid.AABB_min)), spacing, Float64(iso), Int32(-1),
+                C_NULL, 0, C_NULL, 0, nv, nt))
+    verts = Matrix{Float32}(undef, 3, nv[]); tris = Matrix{Int32}(undef, 3, nt[])
+    check(ccall((:r2s_last_isosurface, LIB[]), Cint, (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Ref{Int64}, Ref{Int64}),
+                verts, nv[], tris, nt[], nv, nt))
+    tris .+= Int32(1)
+    return verts, tris
+end
+
+# binary STL of (3 x nv Float32, 3 x nt 1-based) as extract_isosurface_hip returns them; ".stl" appended when missing
+function export_stl_hip(filename::AbstractString, verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer})
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    t0 = Int32.(tris) .- Int32(1)
+    check(ccall((:r2s_export_stl, LIB[]), Cint, (Cstring, Ptr{Float32}, Int64, Ptr{Int32}, Int64),
+                filename, Matrix(verts), size(verts, 2), t0, size(t0, 2)))
+    return endswith(filename, ".stl") ? String(filename) : filename * ".stl"
+end
+
 # calculate_volume_from_sdf (src/SdfSmoothing/CalcVolumeFromSDF.jl:26-125); `grid` is the reference's array of
 # per-voxel coordinate vectors - only the spacing is used (:36-39)
 function calculate_volume_from_sdf_hip(sdf::Array{Float32,3}, grid::AbstractArray{Vector{Float32},3}; iso_threshold = 0.0f0,
