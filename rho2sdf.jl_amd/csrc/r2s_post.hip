@@ -602,63 +602,17 @@ static void gauss_legendre(int n, double* x, double* w)
 extern "C" void r2s_internal_gauss_legendre(int n, double* x, double* w) { gauss_legendre(n, x, w); }
 
 // ====================================================================================
-// calculate_volume_from_sdf: 1 thread / cell; full cells add a^3, cut cells run the order^3
-// tensor quadrature of the trilinear interpolant (all Float32, same expressions).  Block
-// partial sums (Float32) are reduced by a second kernel in a fixed order (the reference's
-// Float32 atomics make its own sum order-dependent).
+// calculate_volume_from_sdf: full cells add a^3, cut cells run the order^3 tensor quadrature of the
+// trilinear interpolant (all Float32, same expressions).  One wavefront per row of cells
+// (volume_rowwave_kernel) leaves one Float32 per row, summed by one workgroup (sum_f32_kernel):
+// every reduction has a fixed order (the reference's Float32 atomics make its own sum
+// order-dependent).
 // ====================================================================================
 struct QuadTab {
     float gp[32];
     float gw[32];
     int order;
 };
-
-__global__ void __launch_bounds__(256) volume_cells_kernel(const float* __restrict__ sdf, int nx, int ny, int nz,
-                                                          float shift, float iso, float elvol, float jac,
-                                                          QuadTab q, float* __restrict__ partial)
-{
-    __shared__ float red[256];
-    const int64_t ncell = (int64_t)(nx - 1) * (ny - 1) * (nz - 1);
-    float acc = 0.0f;
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < ncell; c += (int64_t)gridDim.x * blockDim.x) {
-        const int i = (int)(c % (nx - 1)), j = (int)((c / (nx - 1)) % (ny - 1)), k = (int)(c / ((int64_t)(nx - 1) * (ny - 1)));
-        const int64_t b = ((int64_t)k * ny + j) * nx + i, sy = nx, sz = (int64_t)nx * ny;
-        // `shifted_sdf .= sdf .- th` (RBFs4Smoothing.jl:286) folded into the loads
-        const float c000 = sdf[b] - shift, c100 = sdf[b + 1] - shift, c010 = sdf[b + sy] - shift,
-                    c110 = sdf[b + sy + 1] - shift, c001 = sdf[b + sz] - shift, c101 = sdf[b + sz + 1] - shift,
-                    c011 = sdf[b + sz + sy] - shift, c111 = sdf[b + sz + sy + 1] - shift;
-        const float mn = fminf(fminf(fminf(c000, c100), fminf(c010, c110)), fminf(fminf(c001, c101), fminf(c011, c111)));
-        const float mx = fmaxf(fmaxf(fmaxf(c000, c100), fmaxf(c010, c110)), fmaxf(fmaxf(c001, c101), fmaxf(c011, c111)));
-        if (mx < iso) continue;
-        if (mn >= iso) { acc += elvol; continue; }
-        float part = 0.0f;
-        for (int kq = 0; kq < q.order; ++kq) {
-            const float zeta = (q.gp[kq] + 1) / 2;
-            for (int jq = 0; jq < q.order; ++jq) {
-                const float eta = (q.gp[jq] + 1) / 2;
-                for (int iq = 0; iq < q.order; ++iq) {
-                    const float xi = (q.gp[iq] + 1) / 2;
-                    const float c00 = c000 * (1.0f - xi) + c100 * xi;
-                    const float c01 = c001 * (1.0f - xi) + c101 * xi;
-                    const float c10 = c010 * (1.0f - xi) + c110 * xi;
-                    const float c11 = c011 * (1.0f - xi) + c111 * xi;
-                    const float c0 = c00 * (1.0f - eta) + c10 * eta;
-                    const float c1 = c01 * (1.0f - eta) + c11 * eta;
-                    const float p = c0 * (1.0f - zeta) + c1 * zeta;
-                    if (p >= iso) part += q.gw[iq] * q.gw[jq] * q.gw[kq] * jac;
-                }
-            }
-        }
-        acc += part;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
 
 // (one workgroup of 1 024 threads: the row sums of a volume are summed once per bisection level, and with 256 threads the
 // 1 024 serial additions per thread took 0.24 ms of the 1.3 ms of a level.  Fixed order: thread t adds the elements
@@ -687,12 +641,8 @@ __global__ void __launch_bounds__(1024) sum_f32_kernel(const float* __restrict__
     if (threadIdx.x == 0) *out = red[0];
 }
 
-// Row version: one workgroup per (j,k) row of cells, threads along x (coalesced corner loads, no
-// integer division).  Full cells are summed per thread; cut cells are listed in LDS in x order and
-// then worked off one WAVEFRONT per cell (lanes split the order^3 Gauss points), so a few cut cells
-// do not stall 63 idle lanes for 729 iterations.  Every reduction has a fixed order (no float atomics).
 // The order^3 quadrature points of a cut cell as a table: {xi, 1-xi, eta, 1-eta, zeta, 1-zeta, weight, -} per point, in
-// the order the lanes of volume_rows_kernel visit them.  The values are those the kernel used to form per point and cell
+// the order the lanes of volume_rowwave_kernel visit them.  The values are those the kernel used to form per point and cell
 // (index decoding with three integer divisions took more instructions than the interpolation itself).
 __global__ void quad_points_kernel(QuadTab q, float jac, float* __restrict__ out)
 {
@@ -709,7 +659,7 @@ __global__ void quad_points_kernel(QuadTab q, float jac, float* __restrict__ out
 
 // smallest / largest corner value over the cells of every 64-cell segment of every cell row: the level bisection
 // evaluates the volume of the same field at up to 40 levels, and a segment whose values all lie on one side of the
-// level needs no loads (volume_rows_kernel)
+// level needs no loads (volume_rowwave_kernel)
 __global__ void __launch_bounds__(256) volume_seg_minmax_kernel(const float* __restrict__ sdf, int nx, int ny, int nz,
                                                                float* __restrict__ segmn, float* __restrict__ segmx, int row0)
 {
