@@ -348,6 +348,71 @@ int r2s_rbf_smooth_dev(const double *d_sdf, const r2s_grid *grid, int32_t is_int
                        double kernel_threshold, double target_volume, float *d_fine_out, float *level_shift_out,
                        int32_t *cg_iters_out, void *stream);
 
+/* ---- the smoothed level-set as a function: value and gradient at arbitrary points ------------------
+ * RBFs_smoothing produces f(p) = th + sum_j w_j exp(-(|p - x_j| / sigma)^2) over the coarse lattice nodes x_j
+ * (rbf_interpolation_kdtree takes any array of points, RBFs4Smoothing.jl:219-248; `+ th` at :366).  A field object keeps the
+ * weights w and the level shift th of one smoothing on its device.  Objects are independent of the library's caches
+ * (r2s_release_cache leaves them alone) and of each other; one object may be read by several threads at once.
+ *
+ * One evaluation, for a point p with Float32 coordinates (geometry as in r2s_rbf_smooth: Float32 axes of create_grid,
+ * sigma = cell_size, max_distance = Float32(sqrt(-ln(threshold) sigma^2))):
+ *   - a node takes part when it is in bounds and dist = sqrt(dx*dx + dy*dy + dz*dz) <= max_distance, every operation of
+ *     it rounded to Float32 separately (dx = p_x - x_j,x ...), as in the lattice evaluations;
+ *   - knn cap (:238): when more than 124 nodes take part by that rule, only the 124 smallest by (dist, linear node index)
+ *     do.  (Equal distances at the 124th place leave the reference's own result open; the index rule is this library's.)
+ *   - value: the sum of w_j exp(-(dist/sigma)^2) in Float64, rounded to Float32 once, then + th in Float32.  The order of
+ *     summation is a fixed function of the point and the field: results do not depend on the point's place in the array.
+ *   - gradient: sum_j w_j k_j (-2 / sigma^2) (p - x_j) with the same Float32 differences, in Float64, rounded once.
+ *   - taps: the number of nodes that took part, negative (-124) when the cap bound.  (INT32_MIN would report that the
+ *     evaluator's per-point list overflowed - an internal error, never a property of the input.)
+ *   - a non-finite coordinate: value and gradient NaN, taps 0.  No node in reach: value th, gradient 0, taps 0.
+ * Normals: with the Float32 gradient g of the evaluation, -g / |g| (|g| and the quotients in Float64, rounded once):
+ * the interior is f >= iso as in r2s_extract_isosurface, so this points outward; (0,0,0) where |g| is 0 or not finite.
+ * Projection onto {f = 0}, per point, with the Float32 value f and gradient g of the evaluation at the current p:
+ *     it = 0
+ *     loop: evaluate f, g at p
+ *           |f| <= tol            -> status 0, stop
+ *           it == max_iter        -> status 1, stop
+ *           g2 = gx*gx + gy*gy + gz*gz in Float64; not (g2 > 0) or not finite -> status 2, stop
+ *           s = f / g2;  len = |f| / sqrt(g2);  len > Float32(cell_size): s = s * (Float32(cell_size) / len)   (Float64)
+ *           p_a = Float32(p_a - s * g_a) for a = x, y, z (Float64, rounded once);  it = it + 1
+ * A non-finite input point has status 3 and stays as it is (resid NaN, iters 0).  resid_out = |f| of the last evaluation,
+ * iters_out = steps taken; status_out / resid_out / iters_out may each be NULL.
+ *
+ * Errors: NULL field / points, negative n, max_iter < 0, tol < 0 or NaN, a threshold outside
+ * [R2S_RBF_MIN_KERNEL_THRESHOLD, 1), a grid whose aabb_max is not aabb_min + N * cell_size (to 1e-3 of a cell; grids of
+ * r2s_grid_make / r2s_auto_grid are): R2S_ERR_ARG before any device work.  n = 0 succeeds and touches nothing.  Lattices of
+ * 2^31 nodes or more, or coordinates so large against cell_size that Float32 cannot separate neighbouring nodes (or, at
+ * thresholds near 1e-10, that a support outgrows the evaluator's per-point list): R2S_ERR_UNSUPPORTED.  Host variants make the field's device current; the _dev variants take device pointers on the
+ * field's device, which must be the current one, enqueue on `stream` and do not wait. */
+typedef struct r2s_rbf_field r2s_rbf_field;
+
+/* process_vector + weights (CG, or the values themselves) + level shift: the numbers r2s_rbf_smooth computes for the same
+ * input (its own code path, without the output field), kept on the device */
+int r2s_rbf_field_fit(const double *sdf, const r2s_grid *grid, int32_t is_interp, double kernel_threshold,
+                      double target_volume, int32_t device, r2s_rbf_field **out, float *level_shift_out,
+                      int32_t *cg_iters_out);
+/* the same object from given numbers: weights[ngp] Float32, x fastest */
+int r2s_rbf_field_from_weights(const float *weights, const r2s_grid *grid, double kernel_threshold, float level_shift,
+                               int32_t device, r2s_rbf_field **out);
+/* either output may be NULL */
+int r2s_rbf_field_weights(const r2s_rbf_field *f, float *weights_out, float *level_shift_out);
+void r2s_rbf_field_destroy(r2s_rbf_field *f);
+
+/* points[n][3] Float32; val_out[n], grad_out[n][3], taps_out[n] int32: NULL = not wanted */
+int r2s_rbf_field_eval(const r2s_rbf_field *f, const float *points, int64_t n, float *val_out, float *grad_out,
+                       int32_t *taps_out);
+int r2s_rbf_field_eval_dev(const r2s_rbf_field *f, const float *d_points, int64_t n, float *d_val, float *d_grad,
+                           int32_t *d_taps, void *stream);
+/* normals_out[n][3] */
+int r2s_rbf_field_normals(const r2s_rbf_field *f, const float *points, int64_t n, float *normals_out);
+int r2s_rbf_field_normals_dev(const r2s_rbf_field *f, const float *d_points, int64_t n, float *d_normals, void *stream);
+/* points_inout[n][3] are moved in place */
+int r2s_rbf_field_project(const r2s_rbf_field *f, float *points_inout, int64_t n, int32_t max_iter, float tol,
+                          int32_t *status_out, float *resid_out, int32_t *iters_out);
+int r2s_rbf_field_project_dev(const r2s_rbf_field *f, float *d_points_inout, int64_t n, int32_t max_iter, float tol,
+                              int32_t *d_status, float *d_resid, int32_t *d_iters, void *stream);
+
 /* ---- iso-surface extraction ---------------------------------------------------------------
  * The reference's only geometry output is a plot (visualize_stable_isosurface, src/Visualizations/VisualizeIsosurface.jl:
  * Makie's contour!(sdf, levels=[0])).  This is the watertight triangle mesh of {f >= iso} on a regular lattice:

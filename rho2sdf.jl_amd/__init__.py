@@ -9,10 +9,11 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   calculate_mesh_volume, calculate_volume_from_sdf, evalDistances, find_threshold_for_volume,
                   exportSdfToVTI, exportToVTU, export_sdf_results, getMesh_AABB, import_vtu_mesh, noninteractive_sdf_grid_setup,
                   remove_sdf_artifacts, rho2sdf, sdf_fused, host_array, calculate_isocontour_volume, MeshInformations,
-                  extract_isosurface, extract_isosurface_dev, export_stl)
+                  extract_isosurface, extract_isosurface_dev, export_stl, RbfField, fit_rbf_field, refine_surface)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
            "exportSdfToVTI", "exportToVTU", "export_sdf_results", "getMesh_AABB", "import_vtu_mesh", "noninteractive_sdf_grid_setup", "remove_sdf_artifacts",
            "rho2sdf", "sdf_fused", "host_array", "calculate_isocontour_volume", "MeshInformations",
-           "extract_isosurface", "extract_isosurface_dev", "export_stl", "_lib"]
+           "extract_isosurface", "extract_isosurface_dev", "export_stl", "RbfField", "fit_rbf_field", "refine_surface",
+           "_lib"]

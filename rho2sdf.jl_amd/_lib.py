@@ -152,6 +152,19 @@ SYMBOLS = [
     ("r2s_extract_isosurface_dev", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
                                                   _P, ctypes.c_int64, _P, ctypes.c_int64, c_int64_p, c_int64_p, _P]),
     ("r2s_export_stl", ctypes.c_int, [ctypes.c_char_p, c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64]),
+    ("r2s_rbf_field_fit", ctypes.c_int, [c_double_p, ctypes.POINTER(R2SGrid), ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_int32, ctypes.POINTER(_P), c_float_p, c_int32_p]),
+    ("r2s_rbf_field_from_weights", ctypes.c_int, [c_float_p, ctypes.POINTER(R2SGrid), ctypes.c_double, ctypes.c_float,
+                                                  ctypes.c_int32, ctypes.POINTER(_P)]),
+    ("r2s_rbf_field_weights", ctypes.c_int, [_P, c_float_p, c_float_p]),
+    ("r2s_rbf_field_destroy", None, [_P]),
+    ("r2s_rbf_field_eval", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, c_float_p, c_float_p, c_int32_p]),
+    ("r2s_rbf_field_eval_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, _P]),
+    ("r2s_rbf_field_normals", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, c_float_p]),
+    ("r2s_rbf_field_normals_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P]),
+    ("r2s_rbf_field_project", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, c_int32_p,
+                                             c_float_p, c_int32_p]),
+    ("r2s_rbf_field_project_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P]),
 ]
 
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8

@@ -458,6 +458,164 @@ def extract_isosurface_dev(t, grid, smooth=None, *, iso=0.0, stream=None):
     return verts, tris
 
 
+class RbfField:
+    """The smoothed level-set of one RBFs_smoothing as a function (include/rho2sdf_hip.h, r2s_rbf_field): the weights and
+    the level shift stay on the device; `eval`, `normals` and `project` take any (n, 3) array of points.  A context manager;
+    `close()` frees the device memory.  Build one with fit_rbf_field, or from given weights ((nz, ny, nx) float32)."""
+
+    def __init__(self, weights, grid, level_shift=0.0, threshold=1e-3, *, device=-1, _handle=None):
+        self.grid, self.threshold, self.cg_iterations = grid, float(threshold), None
+        if _handle is not None:
+            self._h = _handle
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.size != grid.ngp:
+            raise L.R2SError(f"weights length ({w.size}) doesn't match the grid ({grid.ngp})")
+        h = ctypes.c_void_p()
+        L.check(L.lib().r2s_rbf_field_from_weights(_f(w), ctypes.byref(grid.c), float(threshold), float(level_shift), int(device),
+                                                   ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().r2s_rbf_field_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the loader's globals may be gone already
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not self._h:
+            raise L.R2SError("the field is closed")
+        return self._h
+
+    @property
+    def weights(self):
+        w = np.empty(self.grid.ngp, dtype=np.float32)
+        L.check(L.lib().r2s_rbf_field_weights(self._handle(), _f(w), None))
+        return w.reshape(self.grid.dims[2], self.grid.dims[1], self.grid.dims[0])
+
+    @property
+    def level_shift(self):
+        th = ctypes.c_float()
+        L.check(L.lib().r2s_rbf_field_weights(self._handle(), None, ctypes.byref(th)))
+        return np.float32(th.value)
+
+    @staticmethod
+    def _points(points):
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise L.R2SError("points must be (n, 3)")
+        return p
+
+    def eval(self, points, grad=False, taps=False):
+        """f(points) incl. the level shift -> val (n,) float32; grad=True: (val, grad (n, 3)); taps=True: the number of
+        nodes that took part is appended (negative where the knn cap bound)"""
+        p = self._points(points)
+        n = len(p)
+        val = np.empty(n, np.float32)
+        g = np.empty((n, 3), np.float32) if grad else None
+        t = np.empty(n, np.int32) if taps else None
+        L.check(L.lib().r2s_rbf_field_eval(self._handle(), _f(p), n, _f(val), _f(g) if grad else None,
+                                           t.ctypes.data_as(L.c_int32_p) if taps else None))
+        out = (val,) + ((g,) if grad else ()) + ((t,) if taps else ())
+        return out[0] if len(out) == 1 else out
+
+    def normals(self, points):
+        """outward unit normals -grad f / |grad f| -> (n, 3) float32; (0,0,0) where the gradient vanishes or is not finite"""
+        p = self._points(points)
+        nv = np.empty((len(p), 3), np.float32)
+        L.check(L.lib().r2s_rbf_field_normals(self._handle(), _f(p), len(p), _f(nv)))
+        return nv
+
+    def project(self, points, max_iter=8, tol=None):
+        """points moved onto {f = 0} along the gradient (header: the step rule) -> (points (n, 3), status (n,) int32, resid
+        (n,) float32, iters (n,) int32); tol defaults to 1e-4 * cell_size.  status 0 = converged, 1 = iteration cap,
+        2 = vanishing gradient, 3 = non-finite input"""
+        p = self._points(points).copy()
+        n = len(p)
+        tol = np.float32(1e-4 * self.grid.cell_size) if tol is None else np.float32(tol)
+        status, resid, iters = np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.int32)
+        L.check(L.lib().r2s_rbf_field_project(self._handle(), _f(p), n, int(max_iter), float(tol), status.ctypes.data_as(L.c_int32_p),
+                                              _f(resid), iters.ctypes.data_as(L.c_int32_p)))
+        return p, status, resid, iters
+
+    # ---- torch tensors on the field's device (contiguous float32 (n, 3)); enqueued on the current stream ----
+    @staticmethod
+    def _dev_points(t):   # (the library checks that the current device is the field's)
+        import torch
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.dim() != 2 or t.shape[1] != 3:
+            raise L.R2SError("points must be a contiguous float32 (n, 3) device tensor")
+        if t.device.index != torch.cuda.current_device():
+            raise L.R2SError(f"points live on {t.device}, the current device is cuda:{torch.cuda.current_device()}")
+        return ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p((torch.cuda.current_stream()).cuda_stream)
+
+    def eval_dev(self, t, grad=False, taps=False):
+        import torch
+        p, st = self._dev_points(t)
+        n = t.shape[0]
+        val = torch.empty(n, dtype=torch.float32, device=t.device)
+        g = torch.empty((n, 3), dtype=torch.float32, device=t.device) if grad else None
+        k = torch.empty(n, dtype=torch.int32, device=t.device) if taps else None
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None and n else None   # noqa: E731
+        L.check(L.lib().r2s_rbf_field_eval_dev(self._handle(), p, n, ptr(val), ptr(g), ptr(k), st))
+        out = (val,) + ((g,) if grad else ()) + ((k,) if taps else ())
+        return out[0] if len(out) == 1 else out
+
+    def normals_dev(self, t):
+        import torch
+        p, st = self._dev_points(t)
+        nv = torch.empty_like(t)
+        if t.shape[0]:
+            L.check(L.lib().r2s_rbf_field_normals_dev(self._handle(), p, t.shape[0], ctypes.c_void_p(nv.data_ptr()), st))
+        return nv
+
+    def project_dev(self, t, max_iter=8, tol=None):
+        import torch
+        out = t.clone()
+        p, st = self._dev_points(out)
+        n = out.shape[0]
+        tol = np.float32(1e-4 * self.grid.cell_size) if tol is None else np.float32(tol)
+        status = torch.empty(n, dtype=torch.int32, device=t.device)
+        resid = torch.empty(n, dtype=torch.float32, device=t.device)
+        iters = torch.empty(n, dtype=torch.int32, device=t.device)
+        if n:
+            L.check(L.lib().r2s_rbf_field_project_dev(self._handle(), p, n, int(max_iter), float(tol),
+                                                      ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(resid.data_ptr()),
+                                                      ctypes.c_void_p(iters.data_ptr()), st))
+        return out, status, resid, iters
+
+
+def fit_rbf_field(sdf, grid, Is_interpolation, target_volume, threshold=1e-3, *, device=-1):
+    """The function RBFs_smoothing samples: process_vector, the weights and the volume-preserving level shift of
+    r2s_rbf_smooth for the same input, kept on the device -> RbfField (`.cg_iterations` is set)"""
+    sdf = np.ascontiguousarray(sdf, dtype=np.float64)
+    if sdf.size != grid.ngp:
+        raise L.R2SError(f"sdf length ({sdf.size}) doesn't match the grid ({grid.ngp})")
+    h, th, its = ctypes.c_void_p(), ctypes.c_float(), ctypes.c_int32()
+    L.check(L.lib().r2s_rbf_field_fit(_d(sdf), ctypes.byref(grid.c), int(bool(Is_interpolation)), float(threshold),
+                                      float(target_volume), int(device), ctypes.byref(h), ctypes.byref(th), ctypes.byref(its)))
+    f = RbfField(None, grid, threshold=threshold, _handle=h)
+    f.cg_iterations = int(its.value)
+    return f
+
+
+def refine_surface(field, verts, max_iter=8, tol=None):
+    """vertices of extract_isosurface moved onto the zero level of the function they sample, with the outward unit normals
+    there -> (verts (n, 3) float32, normals (n, 3) float32, status (n,) int32); the triangle list stays valid"""
+    p, status, _, _ = field.project(verts, max_iter=max_iter, tol=tol)
+    return p, field.normals(p), status
+
+
 def export_stl(filename, verts, tris):
     """binary STL of a triangle mesh (verts (nv, 3) float32, tris (nt, 3) 0-based); ".stl" is appended when missing.
     Returns the path written."""

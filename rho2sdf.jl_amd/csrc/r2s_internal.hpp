@@ -52,6 +52,12 @@ int rbf_smooth_dev(const double* d_sdf, const r2s_grid* g, int is_interp, int sm
                    float* d_fine_out, float* th_out, int* cg_iters,
                    const std::function<int(int64_t, int64_t)>* fine_chunk = nullptr, void* workspace = nullptr,
                    bool fine_early = false);
+// the first half of RBFs_smoothing alone (r2s_rbf_field_fit): process_vector, the weights and the level shift of the same
+// code path as rbf_smooth_dev; sdf is a host array, d_weights_out a device array of the lattice's size on the CURRENT device
+int rbf_fit_weights(const double* sdf, const r2s_grid* g, int is_interp, double kthr, double target_volume, float* d_weights_out,
+                    float* th_out, int* cg_iters);
+// one axis of create_grid (RBFs4Smoothing.jl:36-46): the Float32 coordinates of the coarse lattice
+void rbf_coarse_axis(double mn, double mx, int n, std::vector<float>& c);
 // workspace (optional): the call's device buffers, kept between calls on the CURRENT device (create / release there)
 void* rbf_workspace_create();
 void rbf_workspace_release(void* workspace);

@@ -1100,43 +1100,7 @@ struct RbfGeom {
     int tap_r, tap_d2;       // stencil radius / largest lattice distance^2 that can reach the threshold
 };
 
-// exp(-t) for 0 <= t <= 64 (kernel arguments: t = (dist/sigma)^2 <= -ln(threshold)): t = k ln2/64 + r, exp(-t) =
-// 2^(-k/64) exp(-r) with 2^(-j/64) from a 64-entry table and a degree-6 Taylor polynomial of exp(-r), |r| <= ln2/128.
-// Relative error <= 2 ulp(Float64) - the class of difference that already separates libm's exp from the device
-// library's (the smoothing stage is compared at Float32 round-off) - at a quarter of the device
-// library's instruction count; the RBF evaluations spend most of their time in it.
-__constant__ double c_exp2_neg_64[64] = {   // 2^(-j/64), j = 0..63, correctly rounded
-    1, 0.98922801319397546, 0.97857206208770009, 0.96803089674614717,
-    0.9576032806985737, 0.9472879907934828, 0.93708381705514998, 0.92698956254169274,
-    0.91700404320467122, 0.90712608775019943, 0.89735453750155358, 0.88768824626326059,
-    0.87812608018664973, 0.86866691763685311, 0.85930964906123897, 0.85005317685926174,
-    0.8408964152537145, 0.83183829016336819, 0.82287773907698247, 0.81401371092867392,
-    0.80524516597462714, 0.7965710756711335, 0.78799042255394325, 0.77950220011891846,
-    0.77110541270397037, 0.76279907537226921, 0.75458221379671142, 0.74645386414563242,
-    0.73841307296974967, 0.73045889709032352, 0.72259040348852333, 0.71480666919598501,
-    0.70710678118654757, 0.69948983626915562, 0.69195494098191601, 0.68450121148729526,
-    0.67712777346844633, 0.66983376202665146, 0.66261832157987066, 0.65548060576238221,
-    0.64841977732550482, 0.64143500803938913, 0.63452547859586661, 0.62769037851234555,
-    0.620928906036742, 0.61424026805343501, 0.60762367999023448, 0.60107836572635154,
-    0.59460355750136051, 0.58819849582514061, 0.58186242938878874, 0.57559461497649134,
-    0.56939431737834578, 0.56326080930412092, 0.55719337129794622, 0.55119129165392045,
-    0.54525386633262884, 0.53938039887855993, 0.53357020033841185, 0.52782258918027858,
-    0.52213689121370688, 0.51651243951061421, 0.51094857432705831, 0.50544464302585024,
-};
-__device__ __forceinline__ double exp_neg_fast(double t, const double* __restrict__ tab)
-{
-    const double kf = rint(t * 92.33248261689366);              // 64 / ln 2
-    double r = fma(-kf, 0.010830424696248286, t);               // ln2/64, high part (11 trailing zero bits: exact product for k < 2^11)
-    r = fma(-kf, 8.59050471673183e-16, r);                      // low part
-    const int k = (int)kf;
-    double p = fma(r, -1.0 / 720.0, 1.0 / 120.0);
-    p = fma(r, -p, 1.0 / 24.0);
-    p = fma(r, -p, 1.0 / 6.0);
-    p = fma(r, -p, 0.5);
-    p = fma(r, -p, 1.0);
-    p = fma(r, -p, 1.0);
-    return ldexp(tab[k & 63] * p, -(k >> 6));
-}
+#include "r2s_rbf_exp.hpp"   // c_exp2_neg_64, exp_neg_fast
 
 __device__ __forceinline__ float rbf_apply_point(const RbfGeom& G, const float* __restrict__ w, int s, int tnx, int tny,
                                                  const float* __restrict__ tx, const float* __restrict__ ty,
@@ -2406,13 +2370,15 @@ struct RbfWork {   // the device buffers of one rbf_smooth_host call
     }
 };
 // sdf_dev / out_dev: `sdf` / `fine_out` are device pointers (device-resident chaining of the stages)
+// d_weights_keep (optional): a device array of the lattice's size that receives the weights; with it fine_out may be null:
+// the output field is then not evaluated (r2s_rbf_field_fit keeps the function instead of samples of it)
 static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, int smooth, double kthr,
                            double target_volume, float* fine_out, float* th_out, int* cg_iters, float* lsf_out,
                            bool sdf_dev = false, bool out_dev = false,
                            const std::function<int(int64_t, int64_t)>* fine_chunk = nullptr, RbfWork* ws = nullptr,
-                           bool fine_early = false)
+                           bool fine_early = false, float* d_weights_keep = nullptr)
 {
-    if (!sdf || !g || !fine_out) return fail(R2S_ERR_ARG, "null argument");
+    if (!sdf || !g || (!fine_out && !d_weights_keep)) return fail(R2S_ERR_ARG, "null argument");
     RbfPlan P;
     {
         const int rc = rbf_plan(g, is_interp, smooth, kthr, P);
@@ -2449,7 +2415,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     ENSURE_C(W.f, sizeof(float) * (size_t)n);
     ENSURE_C(W.w, sizeof(float) * (size_t)n);
     ENSURE_C(W.lsf, sizeof(float) * (size_t)n);
-    if (!out_dev) ENSURE_C(W.fine, sizeof(float) * (size_t)nf);
+    if (!out_dev && fine_out) ENSURE_C(W.fine, sizeof(float) * (size_t)nf);
     ENSURE_C(W.cnt, 64);
     if (!sdf_dev) HIP_C(hipMemcpy(W.sdf.p, sdf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     const double* dsdf = sdf_dev ? sdf : W.sdf.as<double>();
@@ -2572,6 +2538,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
         HIP_C(hipMemcpy(d_w, d_f, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));   // :353
     }
     if (cg_iters) *cg_iters = its;
+    if (d_weights_keep) HIP_C(hipMemcpyAsync(d_weights_keep, d_w, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st));
     // the output field (:363-366) + `add`
     // (smooth = 1: one target per lattice point - through the table of ITS coordinate differences)
     // In RBF_FINE_CHUNKS Z chunks when the caller wants to forward finished chunks (fine_chunk), else in one launch.
@@ -2600,7 +2567,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     // fine_early: the field WITHOUT the level shift first (it needs the weights only), so that its chunks travel to the host
     // while the level is found; the caller adds the shift to what it received (x + 0 + th = x + th: the same Float32 sum).
     // The device array stays WITHOUT it (the chunks may still be on their way when the level is known)
-    if (fine_early) TRY_C(eval_fine(0.0f));
+    if (fine_early && fine_out) TRY_C(eval_fine(0.0f));
     // ---- LSF on the coarse grid (:357) and the volume-preserving level (:359, :265-300) ----
     if (!launch_rbf_apply_lut(P.ev, G, T.LG, P.sts[0], nb, st, d_w, G.cx, G.cy, G.cz, T.st.as<Stencil>(), 0.0f, d_lsf))
         rbf_apply_kernel<<<nb, 256, 0, st>>>(G, d_w, 1, nx, ny, nz, G.cx, G.cy, G.cz, T.st.as<Stencil>(), 0.0f, d_lsf);
@@ -2639,9 +2606,9 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     th = -th;
     if (th_out) *th_out = th;
     // ---- fine grid (:363-366) ----
-    if (!fine_early) TRY_C(eval_fine(th));   // (fine_early: done above, the shift is the caller's)
+    if (!fine_early && fine_out) TRY_C(eval_fine(th));   // (fine_early: done above, the shift is the caller's)
     HIP_C(hipGetLastError());
-    if (out_dev) HIP_C(hipDeviceSynchronize());
+    if (out_dev || !fine_out) HIP_C(hipDeviceSynchronize());
     else HIP_C(hipMemcpy(fine_out, W.fine.p, sizeof(float) * (size_t)nf, hipMemcpyDeviceToHost));
     cleanup();
     return 0;
@@ -3277,6 +3244,13 @@ int rbf_smooth_dev(const double* d_sdf, const r2s_grid* g, int is_interp, int sm
     return rbf_smooth_host(d_sdf, g, is_interp, smooth, kthr, target_volume, d_fine_out, th_out, cg_iters, nullptr, true, true,
                            fine_chunk, (RbfWork*)workspace, fine_early);
 }
+int rbf_fit_weights(const double* sdf, const r2s_grid* g, int is_interp, double kthr, double target_volume, float* d_weights_out,
+                    float* th_out, int* cg_iters)
+{
+    return rbf_smooth_host(sdf, g, is_interp, 1, kthr, target_volume, nullptr, th_out, cg_iters, nullptr, false, false, nullptr,
+                           nullptr, false, d_weights_out);
+}
+void rbf_coarse_axis(double mn, double mx, int n, std::vector<float>& c) { coarse_coords(mn, mx, n, c); }
 void* rbf_workspace_create() { return new RbfWork(); }
 void rbf_workspace_release(void* w)
 {

@@ -372,6 +372,82 @@ function RBFs_smoothing_hip(mesh::Mesh, dist::Vector{Float64}, grid::MeshGrid.Gr
     return fine, fine_grid
 end
 
+# ---- the smoothed level-set as a function (include/rho2sdf_hip.h, r2s_rbf_field) --------------------------------------
+# RBFs_smoothing samples f(p) = th + sum_j w_j exp(-(|p - x_j| / sigma)^2) on a lattice; an RbfField keeps w and th on the
+# device and evaluates f, its gradient, outward normals and the projection onto {f = 0} at any 3 x n Float32 points.
+mutable struct RbfField
+    handle::Ptr{Cvoid}
+    level_shift::Float32
+    cg_iterations::Int32
+end
+
+function destroy!(f::RbfField)
+    f.handle == C_NULL || ccall((:r2s_rbf_field_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), f.handle)
+    f.handle = C_NULL
+    return nothing
+end
+
+function fit_rbf_field_hip(mesh::Mesh, dist::Vector{Float64}, grid::MeshGrid.Grid, is_interp::Bool, threshold::Float64 = 1e-3)
+    h = Ref{Ptr{Cvoid}}(C_NULL); th = Ref{Float32}(0.0f0); its = Ref{Int32}(0)
+    check(ccall((:r2s_rbf_field_fit, LIB[]), Cint,
+                (Ptr{Float64}, Ref{R2SGrid}, Int32, Float64, Float64, Int32, Ref{Ptr{Cvoid}}, Ref{Float32}, Ref{Int32}),
+                dist, Ref(R2SGrid(grid)), Int32(is_interp), threshold, mesh.V_frac * mesh.V_domain, Int32(-1), h, th, its))
+    return finalizer(destroy!, RbfField(h[], th[], its[]))
+end
+
+function rbf_field_from_weights_hip(weights::Array{Float32}, grid::MeshGrid.Grid, level_shift::Float32 = 0.0f0,
+                                    threshold::Float64 = 1e-3)
+    length(weights) == grid.ngp || error("weights length ($(length(weights))) doesn't match grid points ($(grid.ngp))")
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:r2s_rbf_field_from_weights, LIB[]), Cint,
+                (Ptr{Float32}, Ref{R2SGrid}, Float64, Float32, Int32, Ref{Ptr{Cvoid}}),
+                weights, Ref(R2SGrid(grid)), threshold, level_shift, Int32(-1), h))
+    return finalizer(destroy!, RbfField(h[], level_shift, Int32(0)))
+end
+
+function rbf_field_weights_hip(f::RbfField, grid::MeshGrid.Grid)
+    w = Array{Float32,3}(undef, (grid.N .+ 1)...)
+    th = Ref{Float32}(0.0f0)
+    check(ccall((:r2s_rbf_field_weights, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ref{Float32}), f.handle, w, th))
+    return w, th[]
+end
+
+# -> (val::Vector{Float32}, grad::Matrix{Float32} 3 x n, taps::Vector{Int32}); taps < 0 where the knn(124) cap bound
+function rbf_field_eval_hip(f::RbfField, points::Matrix{Float32})
+    size(points, 1) == 3 || error("points must be 3 x n")
+    n = size(points, 2)
+    val = Vector{Float32}(undef, n); grad = Matrix{Float32}(undef, 3, n); taps = Vector{Int32}(undef, n)
+    check(ccall((:r2s_rbf_field_eval, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}),
+                f.handle, points, n, val, grad, taps))
+    return val, grad, taps
+end
+
+function rbf_field_normals_hip(f::RbfField, points::Matrix{Float32})
+    size(points, 1) == 3 || error("points must be 3 x n")
+    normals = similar(points)
+    check(ccall((:r2s_rbf_field_normals, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}),
+                f.handle, points, size(points, 2), normals))
+    return normals
+end
+
+# -> (projected points, status, residual |f|, steps); status 0 = converged, 1 = iteration cap, 2 = vanishing gradient,
+# 3 = non-finite input
+function rbf_field_project_hip(f::RbfField, points::Matrix{Float32}, tol::Float32; max_iter::Integer = 8)
+    size(points, 1) == 3 || error("points must be 3 x n")
+    p = copy(points); n = size(p, 2)
+    status = Vector{Int32}(undef, n); resid = Vector{Float32}(undef, n); iters = Vector{Int32}(undef, n)
+    check(ccall((:r2s_rbf_field_project, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Float32}, Int64, Int32, Float32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}),
+                f.handle, p, n, Int32(max_iter), tol, status, resid, iters))
+    return p, status, resid, iters
+end
+
+# vertices of extract_isosurface_hip moved onto the zero level of the function they sample + the unit normals there
+function refine_surface_hip(f::RbfField, verts::Matrix{Float32}, grid::MeshGrid.Grid; max_iter::Integer = 8)
+    p, status, _, _ = rbf_field_project_hip(f, verts, Float32(1e-4 * grid.cell_size); max_iter = max_iter)
+    return p, rbf_field_normals_hip(f, p), status
+end
+
 "Replace the reference methods by the HIP-backed ones (method overwrite).  `n_gpus` > 1: every call fans out over
 devices 0..n_gpus-1 inside the library (single Julia process, no MPI)."
 function enable!(libpath::AbstractString = LIB[]; n_gpus::Integer = 1)
