@@ -295,15 +295,17 @@ def DenseInNodes(mesh, rho, *, device=-1):
     return out
 
 
-def find_threshold_for_volume(mesh, rho_n, target_volume, tolerance=1e-4, max_iterations=60, *, device=-1):
+def find_threshold_for_volume(mesh, rho_n, target_volume, tolerance=1e-4, max_iterations=60, *, device=-1, info=None):
     """find_threshold_for_volume(mesh, nodal_values, tol, maxit); target_volume = V_domain*V_frac
-    src/MeshGrid/Isocontour_volume.jl:77-154"""
+    src/MeshGrid/Isocontour_volume.jl:77-154.  `info` (a dict) receives "iterations", the reference's current_iteration"""
     r = _rho(mesh, rho_n)
     rt = ctypes.c_double()
     it = ctypes.c_int32()
     L.check(L.lib().r2s_find_threshold_et(_d(mesh.X), mesh.nnp, _i(mesh.IEN), mesh.nel, mesh.element_type, _d(r),
                                           float(target_volume), float(tolerance), int(max_iterations), int(device),
                                           ctypes.byref(rt), ctypes.byref(it)))
+    if info is not None:
+        info["iterations"] = int(it.value)
     return rt.value
 
 

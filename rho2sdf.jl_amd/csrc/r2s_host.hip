@@ -889,12 +889,14 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     double t = now_ms();
     ri.ms_upload = t - t_start;
     // ---- pre-stage: mesh volume (:128), nodal densities (:148), threshold (:151-156) ----
-    if ((rc = r2s_int::mesh_volume_dev(S->dX.as<double>(), S->dI.as<int64_t>(), nel, o.elem_type, S->dE.as<double>(),
-                                       &ri.V_domain, &ri.V_frac, S->pre_ws + 5)))
-        return rc;
-    const double tp1 = now_ms();
+    // The nodal densities run first: their count pass refuses node ids outside 1..nnp, which the volume kernels would
+    // read through unchecked.  The two stages share no data, so the results do not depend on the order.
     if ((rc = r2s_int::dense_in_nodes_dev(S->dX.as<double>(), nnp, S->dI.as<int64_t>(), nel, o.elem_type, S->dE.as<double>(),
                                           S->dR.as<double>(), S->pre_ws)))
+        return rc;
+    const double tp1 = now_ms();
+    if ((rc = r2s_int::mesh_volume_dev(S->dX.as<double>(), S->dI.as<int64_t>(), nel, o.elem_type, S->dE.as<double>(),
+                                       &ri.V_domain, &ri.V_frac, S->pre_ws + 5)))
         return rc;
     const double tp2 = now_ms();
     if (std::isnan(o.threshold_density)) {
@@ -912,7 +914,7 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     {
         static const bool timing_env = getenv("R2S_HOST_TIMING") && atoi(getenv("R2S_HOST_TIMING"));
         if (timing_env)
-            fprintf(stderr, "r2s pre: mesh volume %.2f ms, nodal densities %.2f, threshold %.2f (%d iterations)\n", tp1 - t, tp2 - tp1,
+            fprintf(stderr, "r2s pre: mesh volume %.2f ms, nodal densities %.2f, threshold %.2f (%d iterations)\n", tp2 - tp1, tp1 - t,
                     t2 - tp2, ri.threshold_iters);
     }
     // ---- raw SDF = dists .* signs (:169-171) ----

@@ -10,6 +10,8 @@
 
 namespace r2s_int {
 
+// The three volume forms below read X and rho_n through dIEN unchecked: the caller has validated the connectivity
+// (dense_in_nodes_dev does; the host-pointer entry points of r2s_pre.hip run a flag pass after the upload).
 // calculate_mesh_volume (MeshVolume.jl:4-42): d_rho_e[nel] element densities
 int mesh_volume_dev(const double* dX, const int64_t* dIEN, int64_t nel, int elem_type, const double* d_rho_e,
                     double* V_domain, double* V_frac, DevBuf* ws = nullptr);

@@ -157,22 +157,32 @@ __global__ void __launch_bounds__(256) tet_iso_volume_kernel(const double* __res
         }
     const double adet = fabs(det3(J));
     double acc = 0.0;
-    if (!(mx < thr)) {
-        const bool whole = mn >= thr;
-        const int n = whole ? 3 : 15;
-        const GaussTab& g = whole ? g3 : g15;
-        for (int p = lane; p < n * n * n; p += 64) {
-            const int i = p % n, j = (p / n) % n, k = p / (n * n);
-            const double xi = (g.gp[i] + 1.0) / 2.0;
-            const double eta = (g.gp[j] + 1.0) / 2.0 * (1.0 - xi);
-            const double zeta = (g.gp[k] + 1.0) / 2.0 * (1.0 - xi - eta);
+    if (mn >= thr) {
+        // whole element: lane 0 adds the 3^3 points in tet_volume_kernel's order, so that volume(thr <= min rho) is V_domain
+        // of calculate_mesh_volume bit for bit (find_threshold compares target > vmax without slack)
+        if (lane == 0)
+            for (int k = 0; k < 3; ++k)
+                for (int j = 0; j < 3; ++j)
+                    for (int i = 0; i < 3; ++i) {
+                        const double xi = (g3.gp[i] + 1.0) / 2.0;
+                        const double eta = (g3.gp[j] + 1.0) / 2.0 * (1.0 - xi);
+                        const double zeta = (g3.gp[k] + 1.0) / 2.0 * (1.0 - xi - eta);
+                        if (xi < 0 || eta < 0 || zeta < 0 || xi + eta + zeta > 1.0) continue;
+                        const double jt = (1.0 - xi) * (1.0 - xi) * (1.0 - xi - eta) / 8.0;
+                        acc += g3.gw[i] * g3.gw[j] * g3.gw[k] * adet * jt;
+                    }
+    } else if (!(mx < thr)) {
+        for (int p = lane; p < 3375; p += 64) {
+            const int i = p % 15, j = (p / 15) % 15, k = p / 225;
+            const double xi = (g15.gp[i] + 1.0) / 2.0;
+            const double eta = (g15.gp[j] + 1.0) / 2.0 * (1.0 - xi);
+            const double zeta = (g15.gp[k] + 1.0) / 2.0 * (1.0 - xi - eta);
             if (xi < 0 || eta < 0 || zeta < 0 || xi + eta + zeta > 1.0) continue;
-            if (!whole) {   // N = [xi, eta, zeta, 1 - xi - eta - zeta] (ShapeFunctions.jl:53-72)
-                const double v = xi * re[0] + eta * re[1] + zeta * re[2] + (1.0 - xi - eta - zeta) * re[3];
-                if (v < thr) continue;
-            }
+            // N = [xi, eta, zeta, 1 - xi - eta - zeta] (ShapeFunctions.jl:53-72)
+            const double v = xi * re[0] + eta * re[1] + zeta * re[2] + (1.0 - xi - eta - zeta) * re[3];
+            if (v < thr) continue;
             const double jt = (1.0 - xi) * (1.0 - xi) * (1.0 - xi - eta) / 8.0;
-            acc += g.gw[i] * g.gw[j] * g.gw[k] * adet * jt;
+            acc += g15.gw[i] * g15.gw[j] * g15.gw[k] * adet * jt;
         }
     }
 #pragma unroll
@@ -491,6 +501,31 @@ static int build_ine_dev(const int64_t* dIEN, int64_t nel, int nen, int64_t nnp,
     return 0;
 }
 
+// The volume kernels read X and rho_n through IEN unchecked: every entry point that has not built the node -> element
+// lists (whose count pass refuses bad ids) runs this flag pass over a fresh connectivity first.
+__global__ void __launch_bounds__(256) ien_check_kernel(const int64_t* __restrict__ IEN, int64_t total, int64_t nnp,
+                                                       uint32_t* __restrict__ bad)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int64_t n = IEN[t] - 1;
+    if (n < 0 || n >= nnp) *bad = 1u;
+}
+
+static int check_ien_dev(const int64_t* dIEN, int64_t total, int64_t nnp)
+{
+    DevBuf flag;
+    auto done = [&](int r) { flag.release(); return r; };
+    if (flag.ensure(4)) return done(fail(R2S_ERR_NOMEM, "hipMalloc failed"));
+    uint32_t h_bad = 0;
+    if (hipMemsetAsync(flag.p, 0, 4, nullptr) != hipSuccess) return done(fail(R2S_ERR_HIP, "hipMemset failed"));
+    ien_check_kernel<<<(unsigned)((total + 255) / 256), 256>>>(dIEN, total, nnp, flag.as<uint32_t>());
+    if (hipMemcpy(&h_bad, flag.p, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(R2S_ERR_HIP, "connectivity check failed: %s", hipGetErrorString(hipGetLastError())));
+    if (h_bad) return done(fail(R2S_ERR_ARG, "IEN contains node ids outside 1..nnp"));
+    return done(0);
+}
+
 struct MeshDev {
     DevBuf X, IEN, a, b;
     void release() { X.release(); IEN.release(); a.release(); b.release(); }
@@ -640,6 +675,7 @@ int r2s_mesh_volume(const double* X, int64_t nnp, const int64_t* IEN, int64_t ne
     DevBuf rho;
     auto done = [&](int r) { m.release(); rho.release(); return r; };
     if ((rc = upload_mesh(m, X, nnp, IEN, nel, nen))) return done(rc);
+    if ((rc = check_ien_dev(m.IEN.as<int64_t>(), nel * nen, nnp))) return done(rc);
     if (rho.ensure(sizeof(double) * (size_t)nel)) return done(fail(R2S_ERR_NOMEM, "hipMalloc failed"));
     if (hipMemcpy(rho.p, rho_e, sizeof(double) * (size_t)nel, hipMemcpyHostToDevice) != hipSuccess)
         return done(fail(R2S_ERR_HIP, "hipMemcpy failed"));
@@ -676,6 +712,7 @@ static int upload_nodal(MeshDev& m, DevBuf& rho, const double* X, int64_t nnp, c
     const int nen = elem_type == R2S_HEX8 ? 8 : 4;
     int rc = upload_mesh(m, X, nnp, IEN, nel, nen);
     if (rc) return rc;
+    if ((rc = check_ien_dev(m.IEN.as<int64_t>(), nel * nen, nnp))) return rc;
     ENSURE(rho, sizeof(double) * (size_t)nnp);
     HIP_TRY(hipMemcpy(rho.p, rho_n, sizeof(double) * (size_t)nnp, hipMemcpyHostToDevice));
     return 0;

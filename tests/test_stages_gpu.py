@@ -210,11 +210,16 @@ def test_mesh_volume_tet4(pkg, oracle):
     assert np.abs(rn_gpu - oracle.dense_in_nodes(X, IT, rho)).max() <= 1e-12
 
 
-@pytest.mark.parametrize("badval", [0, -3, 10**9])
+@pytest.mark.parametrize("badval", [0, -3, 10**9, "nnp+1"])
 def test_connectivity_outside_node_range_is_an_error(pkg, oracle, badval):
     """IEN ids outside 1..nnp: the call fails with a message (the reference would throw a BoundsError)
-    and the device survives to run the next call."""
+    and the device survives to run the next call.  Every entry point that reads X or rho_n through IEN is covered: the
+    raw SDF, the three standalone volume calls (they validate the uploaded connectivity before their kernels read through
+    it) and the whole-call r2s_rho2sdf (its nodal-density stage, which validates, runs before the volume stage)."""
+    import ctypes
     X, IEN, rho = load_fixture("sphere")
+    if badval == "nnp+1":
+        badval = len(X) + 1
     rn = oracle.dense_in_nodes(X, IEN, rho)
     pg = pkg.Grid(X.min(0), X.max(0), 10, 3)
     bad = IEN.copy()
@@ -223,6 +228,37 @@ def test_connectivity_outside_node_range_is_an_error(pkg, oracle, badval):
         pkg.sdf_fused(pkg.Mesh(X, bad), pg, rn, 0.5)
     sdf = pkg.sdf_fused(pkg.Mesh(X, IEN), pg, rn, 0.5, band_factor=2.5)
     assert (np.abs(sdf) == 1e10).sum() == 1836
+    good, badm = pkg.Mesh(X, IEN), pkg.Mesh(X, bad)
+    vd, vf = pkg.calculate_mesh_volume(good, rho)
+    v5 = pkg.calculate_isocontour_volume(good, rn, 0.5)
+    rt = pkg.find_threshold_for_volume(good, rn, vd * vf)
+
+    def legacy_find_threshold(m):   # r2s_find_threshold: the HEX8-only form of the C ABI
+        L = pkg._lib
+        out, it = ctypes.c_double(), ctypes.c_int32()
+        dp = lambda a: a.ctypes.data_as(L.c_double_p)
+        L.check(L.lib().r2s_find_threshold(dp(m.X), m.nnp, m.IEN.ctypes.data_as(L.c_int64_p), m.nel, dp(rn), vd * vf, 1e-4, 60,
+                                           -1, ctypes.byref(out), ctypes.byref(it)))
+        return out.value
+
+    opts = pkg.Rho2sdfOptions(threshold_density=0.5, rbf_interp=False)   # (an explicit grid: the call reaches r2s_rho2sdf itself)
+    calls = {
+        "r2s_mesh_volume": lambda m: pkg.calculate_mesh_volume(m, rho),
+        "r2s_isocontour_volume": lambda m: pkg.calculate_isocontour_volume(m, rn, 0.5),
+        "r2s_find_threshold_et": lambda m: pkg.find_threshold_for_volume(m, rn, vd * vf),
+        "r2s_find_threshold": legacy_find_threshold,
+        "r2s_rho2sdf": lambda m: pkg.rho2sdf("sphere", m.X, m.IEN, rho, options=opts, sdf_grid=pg),
+    }
+    for name, call in calls.items():
+        with pytest.raises(pkg._lib.R2SError, match="IEN contains node ids outside 1..nnp"):
+            call(badm)
+    # the device runs the next calls normally, with the same answers as before
+    assert pkg.calculate_mesh_volume(good, rho) == (vd, vf)
+    assert pkg.calculate_isocontour_volume(good, rn, 0.5) == v5
+    assert pkg.find_threshold_for_volume(good, rn, vd * vf) == rt == legacy_find_threshold(good)
+    out = pkg.rho2sdf("sphere", X, IEN, rho, options=opts, sdf_grid=pg)
+    assert np.isfinite(out[0]).all()
+    assert np.array_equal(pkg.sdf_fused(good, pg, rn, 0.5, band_factor=2.5), sdf)
 
 
 def test_rbf_matvec_variants_are_bit_identical(pkg, oracle, monkeypatch):
