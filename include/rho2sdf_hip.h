@@ -442,6 +442,51 @@ int r2s_extract_isosurface_dev(const void *d_values, int32_t is_float32, const i
                                double spacing, double iso, float *d_verts, int64_t vert_capacity, int32_t *d_tris,
                                int64_t tri_capacity, int64_t *n_verts, int64_t *n_tris, void *stream);
 
+/* ---- redistancing: exact banded distance to a triangle mesh -----------------------------------
+ * Neither field rho2sdf() returns is a distance function away from the surface (the raw field holds distances within
+ * band_factor * cell_size only, the smoothed field is an RBF interpolant).  These entry points compute the Euclidean distance
+ * from every point of a regular lattice to an indexed triangle mesh, exact within `band`; no counterpart in the reference.
+ *   - lattice: dims[0] x dims[1] x dims[2] points, x fastest; point (i,j,k) sits at p = origin + spacing*(i,j,k), computed in
+ *     double (one product, one sum per axis) - the lattice of r2s_extract_isosurface.
+ *   - vertices: the given float32 values, widened to double; tris: 0-based int32 vertex indices.
+ *   - distance to one triangle (a,b,c) = the minimum of four terms: the distances to the segments a-b, a-c and b-c (the
+ *     parameter of the foot point clamped to [0,1]; a zero-length segment is a point), and the plane distance
+ *     |n.(p-a)| / |n|, counted only when n = (b-a)x(c-a) is non-zero and p projects into the triangle (the three edge
+ *     functions ((b-a)x(p-a)).n, ((c-b)x(p-b)).n, ((a-c)x(p-c)).n are all >= 0).  Zero-area triangles and coincident
+ *     vertices are ordinary input (the extraction produces them at exact-iso lattice points); the result is never NaN for
+ *     finite input.
+ *   - d(p) = the minimum over all triangles; dist_out = min(d, band), Float32 (out_is_float32 = 1) or Float64, formed in
+ *     Float64 and rounded once.
+ *   - closest_tri_out (may be NULL): the smallest triangle index that attains the computed minimum, -1 where the result is
+ *     `band`.  With n_tris == 0 every point gets band / -1.
+ *   - the result does not depend on the order of the triangles (the index follows a permutation wherever the minimum is
+ *     unique); no floating-point atomics are used.
+ * r2s_redistance: out = s * min(d, band) in the type of `values`, with s = +1 where f >= iso and -1 elsewhere (NaN included:
+ * the interiority rule of the extraction) and d measured to the mesh r2s_extract_isosurface_dev returns for the same
+ * arguments.
+ * R2S_ERR_ARG before any device work: any dim < 2; a non-finite or non-positive spacing or band; a non-finite origin; a NaN
+ * iso; a triangle index outside [0, n_verts) or a non-finite vertex (the host variant checks on the host, the _dev variant
+ * with a check kernel whose verdict is read before anything else runs; the outputs are untouched).  Meshes or lattices
+ * beyond 32-bit indices: R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.
+ * One device only (`device`, -1 = current; the _dev variants: device pointers on the current device, after the work
+ * queued on `stream`, synchronous on return); there is no n_gpus here.  The tile lists are built in batches of tile layers
+ * so that they stay under a workspace budget of 1 GiB (environment variable R2S_REDIST_WORKSPACE_MB: another budget in
+ * MiB; the result does not depend on it); the work buffers are kept per device (r2s_release_cache frees them). */
+int r2s_mesh_distance(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, const int64_t dims[3],
+                      const double origin[3], double spacing, double band, int32_t out_is_float32, int32_t device,
+                      void *dist_out, int32_t *closest_tri_out);
+int r2s_mesh_distance_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris,
+                          const int64_t dims[3], const double origin[3], double spacing, double band,
+                          int32_t out_is_float32, void *d_dist_out, int32_t *d_closest_tri_out, void *stream);
+int r2s_redistance(const void *values, int32_t is_float32, const int64_t dims[3], const double origin[3], double spacing,
+                   double iso, double band, int32_t device, void *out);
+int r2s_redistance_dev(const void *d_values, int32_t is_float32, const int64_t dims[3], const double origin[3],
+                       double spacing, double iso, double band, void *d_out, void *stream);
+/* A diagnostic of the calling thread's last call of the four above: [0] ms surface extraction, [1] ms binning (count, scan,
+ * list fills), [2] ms tile kernel (HIP events on the call's stream), [3] tile/triangle pairs tested, [4] batches,
+ * [5] triangles, [6] 8x8x8 voxel tiles, [7] tiles with a non-empty list. */
+void r2s_last_distance_stats(double out[8]);
+
 /* ---- on-disk output ------------------------------------------------------------------ */
 
 /* binary STL of a triangle mesh (verts [n_verts][3], tris [n_tris][3] 0-based); host only, no device; ".stl" appended

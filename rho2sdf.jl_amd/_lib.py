@@ -165,6 +165,15 @@ SYMBOLS = [
     ("r2s_rbf_field_project", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, c_int32_p,
                                              c_float_p, c_int32_p]),
     ("r2s_rbf_field_project_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P]),
+    ("r2s_mesh_distance", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, c_int64_p, c_double_p,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _P, c_int32_p]),
+    ("r2s_mesh_distance_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, c_int64_p, c_double_p, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_int32, _P, _P, _P]),
+    ("r2s_redistance", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_int32, _P]),
+    ("r2s_redistance_dev", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, _P, _P]),
+    ("r2s_last_distance_stats", None, [c_double_p]),
 ]
 
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8

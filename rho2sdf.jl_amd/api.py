@@ -460,6 +460,93 @@ def extract_isosurface_dev(t, grid, smooth=None, *, iso=0.0, stream=None):
     return verts, tris
 
 
+def _dist_lattice(grid_or_lattice, smooth):
+    """a Grid (with `smooth`, as _iso_lattice) or an explicit lattice (dims, origin, spacing)"""
+    if isinstance(grid_or_lattice, Grid):
+        return _iso_lattice(grid_or_lattice, smooth)
+    dims, origin, spacing = grid_or_lattice
+    return (ctypes.c_int64 * 3)(*[int(n) for n in dims]), (ctypes.c_double * 3)(*[float(x) for x in origin]), float(spacing)
+
+
+def mesh_distance(verts, tris, grid_or_lattice, band, *, smooth=None, want_index=False, device=-1):
+    """The unsigned Euclidean distance from every lattice point to the triangle mesh (verts (nv, 3) float32, tris (nt, 3)
+    int32, 0-based), exact within `band` and clamped to it (include/rho2sdf_hip.h, r2s_mesh_distance) -> float64 array
+    (nz, ny, nx); want_index=True: also the int32 index of the closest triangle (-1 where the result is `band`).  The lattice
+    is that of extract_isosurface for a Grid and `smooth`, or an explicit (dims, origin, spacing)."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+    shape = (dims[2], dims[1], dims[0])
+    dist = np.empty(shape, np.float64)
+    idx = np.empty(shape, np.int32) if want_index else None
+    L.check(L.lib().r2s_mesh_distance(_f(v), len(v), t.ctypes.data_as(L.c_int32_p), len(t), dims, origin, spacing, float(band), 0,
+                                      int(device), dist.ctypes.data_as(ctypes.c_void_p),
+                                      idx.ctypes.data_as(L.c_int32_p) if want_index else None))
+    return (dist, idx) if want_index else dist
+
+
+def mesh_distance_dev(verts, tris, grid_or_lattice, band, *, smooth=None, want_index=False, dtype=None, stream=None):
+    """mesh_distance on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous) -> a
+    device tensor (nz, ny, nx) of `dtype` (float64 by default, or float32)"""
+    import torch
+    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or not (verts.is_cuda and tris.is_cuda) \
+            or not (verts.is_contiguous() and tris.is_contiguous()):
+        raise L.R2SError("verts / tris must be contiguous float32 / int32 device tensors")
+    dtype = dtype or torch.float64
+    if dtype not in (torch.float32, torch.float64):
+        raise L.R2SError("dtype must be float32 or float64")
+    dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+    shape = (dims[2], dims[1], dims[0])
+    dist = torch.empty(shape, dtype=dtype, device=verts.device)
+    idx = torch.empty(shape, dtype=torch.int32, device=verts.device) if want_index else None
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    L.check(L.lib().r2s_mesh_distance_dev(ctypes.c_void_p(verts.data_ptr()), verts.numel() // 3, ctypes.c_void_p(tris.data_ptr()),
+                                          tris.numel() // 3, dims, origin, spacing, float(band), int(dtype == torch.float32),
+                                          ctypes.c_void_p(dist.data_ptr()), ctypes.c_void_p(idx.data_ptr()) if want_index else None,
+                                          st))
+    return (dist, idx) if want_index else dist
+
+
+def redistance(values, grid, smooth=None, *, iso=0.0, band, device=-1):
+    """The banded signed distance to the iso-surface of `values` (include/rho2sdf_hip.h, r2s_redistance): s * min(d, band)
+    with s = +1 where values >= iso and -1 elsewhere, d the exact distance to the mesh extract_isosurface returns for the
+    same arguments.  Same conventions as extract_isosurface; the result has the shape (nz, ny, nx) and the type of the
+    (float32 / float64) input."""
+    a = np.ascontiguousarray(values)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    dims, origin, spacing = _iso_lattice(grid, smooth)
+    if a.size != dims[0] * dims[1] * dims[2]:
+        raise L.R2SError(f"values length ({a.size}) doesn't match the lattice {tuple(dims)}")
+    out = np.empty((dims[2], dims[1], dims[0]), a.dtype)
+    L.check(L.lib().r2s_redistance(a.ctypes.data_as(ctypes.c_void_p), int(a.dtype == np.float32), dims, origin, spacing, float(iso),
+                                   float(band), int(device), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def redistance_dev(t, grid, smooth=None, *, iso=0.0, band, stream=None):
+    """redistance on a torch tensor on the current device (float32 / float64, contiguous, x fastest) -> a device tensor"""
+    import torch
+    if t.dtype not in (torch.float32, torch.float64) or not t.is_contiguous() or not t.is_cuda:
+        raise L.R2SError("t must be a contiguous float32 / float64 device tensor")
+    dims, origin, spacing = _iso_lattice(grid, smooth)
+    if t.numel() != dims[0] * dims[1] * dims[2]:
+        raise L.R2SError(f"values length ({t.numel()}) doesn't match the lattice {tuple(dims)}")
+    out = torch.empty((dims[2], dims[1], dims[0]), dtype=t.dtype, device=t.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    L.check(L.lib().r2s_redistance_dev(ctypes.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), dims, origin, spacing, float(iso),
+                                       float(band), ctypes.c_void_p(out.data_ptr()), st))
+    return out
+
+
+def last_distance_stats():
+    """phases and counters of the calling thread's last distance call (r2s_last_distance_stats)"""
+    s = (ctypes.c_double * 8)()
+    L.lib().r2s_last_distance_stats(s)
+    keys = ("ms_extract", "ms_binning", "ms_tile_kernel", "pairs", "batches", "n_tris", "n_tiles", "n_active_tiles")
+    return dict(zip(keys, [float(x) for x in s]))
+
+
 class RbfField:
     """The smoothed level-set of one RBFs_smoothing as a function (include/rho2sdf_hip.h, r2s_rbf_field): the weights and
     the level shift stay on the device; `eval`, `normals` and `project` take any (n, 3) array of points.  A context manager;
@@ -717,7 +804,7 @@ class Rho2sdfOptions:
 
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
-            info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False):
+            info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False, redistance_cells=None):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -733,8 +820,13 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     to fill instead of new ones (e.g. from host_array); fine_sdf is then a view of fine_out.
     surface=True: the library also extracts the iso-0 surface of fine_sdf on the device (r2s_options extract_surface);
     info["surface"] = (verts, tris) as extract_isosurface(fine_sdf, sdf_grid, smooth) returns them (bit-identical), and
-    export_results=True also writes it next to the .vti as <same name>.stl.  The return values are unchanged."""
+    export_results=True also writes it next to the .vti as <same name>.stl.  The return values are unchanged.
+    redistance_cells=k (a positive number; needs `info`): info["sdf_redistanced"] = redistance(fine_sdf, sdf_grid, smooth,
+    band=k * spacing of the fine lattice) - the banded signed distance to the iso-0 surface of fine_sdf, a second library
+    call after the first.  None: nothing is called."""
     options = options or Rho2sdfOptions()
+    if redistance_cells is not None and (info is None or not (float(redistance_cells) > 0.0)):
+        raise L.R2SError("redistance_cells must be a positive number and needs an `info` dict for the result")
     mesh = Mesh(X, IEN, options.element_type)
     rho = np.ascontiguousarray(rho, dtype=np.float64)
     if rho.shape != (mesh.nel,):
@@ -781,6 +873,9 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     xmin, xmax = np.float32(sdf_grid.AABB_min[0]), np.float32(sdf_grid.AABB_max[0])
     spacing = (xmax - xmin) / np.float32(fine_sdf.shape[2] - 1)
     fine_grid = (sdf_grid.AABB_min.astype(np.float32), float(spacing), fine_sdf.shape[::-1])
+    if redistance_cells is not None:
+        info["sdf_redistanced"] = redistance(fine_sdf, sdf_grid, smooth, band=float(redistance_cells) * _iso_lattice(sdf_grid, smooth)[2],
+                                             device=device)
     if export_results:
         vti = export_sdf_results(fine_sdf, sdf_grid, taskName, smooth, options.rbf_interp, mesh.element_type)
         if surface:

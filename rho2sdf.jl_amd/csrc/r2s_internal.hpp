@@ -112,4 +112,8 @@ int extract_isosurface_host(const void* values, bool is_float32, const int64_t d
 // frees the work buffers r2s_extract_isosurface_dev keeps per device; called by r2s_release_cache()
 void release_iso_work();
 
+// ---- redistancing (r2s_redistance.hip) --------------------------------------------------------------------------------
+// frees the work buffers the distance calls keep per device; called by r2s_release_cache()
+void release_dist_work();
+
 }  // namespace r2s_int

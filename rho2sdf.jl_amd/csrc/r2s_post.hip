@@ -3402,6 +3402,7 @@ void r2s_release_cache(void)
     }
     release_ccl_work();
     r2s_int::release_iso_work();
+    r2s_int::release_dist_work();
     r2s_int::release_host_sessions();
 }
 

@@ -343,6 +343,47 @@ function export_stl_hip(filename::AbstractString, verts::AbstractMatrix{Float32}
     return endswith(filename, ".stl") ? String(filename) : filename * ".stl"
 end
 
+# Redistancing (no counterpart in the reference): the exact Euclidean distance from every lattice point to a triangle mesh,
+# clamped to `band` (include/rho2sdf_hip.h, r2s_mesh_distance).  verts 3 x nv Float32, tris 3 x nt 1-based, as
+# extract_isosurface_hip returns them; the lattice is the one of extract_isosurface_hip for (grid, smooth).  Returns the
+# Float64 distances (x fastest) and, with want_index, the 1-based index of the closest triangle (0 where the result is band).
+function mesh_distance_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}, grid::MeshGrid.Grid, band::Real,
+                           smooth::Union{Int,Nothing} = nothing; want_index::Bool = false)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    t0 = Int32.(tris) .- Int32(1)
+    dist = Array{Float64,3}(undef, dims...)
+    idx = want_index ? Array{Int32,3}(undef, dims...) : nothing
+    check(ccall((:r2s_mesh_distance, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Float64}, Float64, Float64, Int32, Int32, Ptr{Cvoid},
+                 Ptr{Int32}),
+                Matrix(verts), size(verts, 2), t0, size(t0, 2), collect(dims), collect(Float64.(grid.AABB_min)), spacing,
+                Float64(band), Int32(0), Int32(-1), dist, want_index ? idx : C_NULL))
+    want_index || return dist
+    idx .+= Int32(1)
+    return dist, idx
+end
+
+# The banded signed distance to the iso-surface of `values` (r2s_redistance): s * min(d, band), s = +1 where values >= iso
+# and -1 elsewhere, d the exact distance to the mesh extract_isosurface_hip returns for the same arguments; same type and
+# shape conventions as extract_isosurface_hip.  redistance_hip(fine_sdf, sdf_grid, smooth; band = k * spacing) turns the
+# smoothed field of rho2sdf_hip into a distance function k cells wide.
+function redistance_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
+                        iso = 0.0, band::Real) where {T<:Union{Float32,Float64}}
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    length(values) == prod(dims) || error("values length ($(length(values))) doesn't match the lattice $(Tuple(dims))")
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    out = Array{T,3}(undef, dims...)
+    check(ccall((:r2s_redistance, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Float64, Float64, Float64, Int32, Ptr{Cvoid}),
+                values, Int32(T == Float32), collect(dims), collect(Float64.(grid.AABB_min)), spacing, Float64(iso),
+                Float64(band), Int32(-1), out))
+    return out
+end
+
 # calculate_volume_from_sdf (src/SdfSmoothing/CalcVolumeFromSDF.jl:26-125); `grid` is the reference's array of
 # per-voxel coordinate vectors - only the spacing is used (:36-39)
 function calculate_volume_from_sdf_hip(sdf::Array{Float32,3}, grid::AbstractArray{Vector{Float32},3}; iso_threshold = 0.0f0,
