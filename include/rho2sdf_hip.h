@@ -487,6 +487,54 @@ int r2s_redistance_dev(const void *d_values, int32_t is_float32, const int64_t d
  * [5] triangles, [6] 8x8x8 voxel tiles, [7] tiles with a non-empty list. */
 void r2s_last_distance_stats(double out[8]);
 
+/* ---- mesh index: exact point-to-mesh distance without a band ------------------------------------
+ * A bounding-volume hierarchy over the triangles of a mesh (one triangle per leaf, float32 boxes, built on the device from
+ * Morton codes of the triangles' box centres), and nearest-triangle queries against it: from arbitrary points, or from
+ * every point of a lattice.  An index owns device copies of verts / tris and the tree; indices are independent of the
+ * library's caches (r2s_release_cache leaves them alone) and of each other; one index may be queried by several threads.
+ *   - d(p) = the minimum over ALL triangles of the pair distance defined above for r2s_mesh_distance (vertices: float32
+ *     widened to double; points: float32 or float64 widened to double, or the lattice p = origin + spacing*(i,j,k) in
+ *     double), formed in Float64 and rounded once to the output type.  The tree only skips triangles whose box is farther
+ *     than the current minimum by more than a margin of 2^-40 of the largest coordinate, so the numbers are those of a
+ *     search over every triangle, and those of r2s_mesh_distance wherever that result is below its band.
+ *   - closest_tri_out (may be NULL): the smallest triangle index that attains the computed minimum.
+ *   - an empty mesh (n_tris == 0): +inf / -1 for every point.  A point with a non-finite coordinate: NaN / -1.
+ *   - the result depends neither on the order of the triangles (the index follows a permutation wherever the minimum is
+ *     unique) nor on the order of the points; no floating-point atomics are used.
+ * r2s_mesh_index_build: host arrays, `device` (-1 = current).  _build_dev: device arrays on the current device, read after
+ * the work queued on `stream`; both are synchronous on return and copy the mesh.  r2s_mesh_index_info: out[0] triangles,
+ * [1] nodes (leaves + internal), [2] tree depth (internal levels; the query refuses a tree deeper than its stack of 64
+ * entries, which unique 62-bit keys cannot produce), [3] device bytes held.
+ * r2s_mesh_index_query: n points [n][3] from host arrays (synchronous); _query_dev: device arrays on the index's device,
+ * which must be current; enqueues on `stream` and does not wait.  n == 0 succeeds and touches nothing.
+ * r2s_mesh_index_lattice(_dev): the same for the lattice of r2s_mesh_distance (x fastest); a wavefront takes a 4x4x4 block of
+ * lattice points.
+ * r2s_redistance_full(_dev): out = s * d in the type of `values`, with s and the mesh exactly as in r2s_redistance and no
+ * band: +-inf where the field has no surface.  Synchronous on return.
+ * R2S_ERR_ARG before any device work: NULL pointers, a negative count, a triangle index outside [0, n_verts) or a non-finite
+ * vertex (host variant: on the host; _build_dev: with the check kernel of r2s_mesh_distance_dev), any dim < 2, a non-finite
+ * origin, a non-finite or non-positive spacing, a NaN iso; a _dev call on another device than the index's.  Counts beyond
+ * 32 bits: R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  One device only; there is no n_gpus here. */
+typedef struct r2s_mesh_index r2s_mesh_index;
+int r2s_mesh_index_build(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
+                         r2s_mesh_index **out);
+int r2s_mesh_index_build_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, void *stream,
+                             r2s_mesh_index **out);
+void r2s_mesh_index_destroy(r2s_mesh_index *index);
+int r2s_mesh_index_info(const r2s_mesh_index *index, int64_t out[4]);
+int r2s_mesh_index_query(const r2s_mesh_index *index, const void *points, int32_t points_are_float32, int64_t n,
+                         int32_t out_is_float32, void *dist_out, int32_t *closest_tri_out);
+int r2s_mesh_index_query_dev(const r2s_mesh_index *index, const void *d_points, int32_t points_are_float32, int64_t n,
+                             int32_t out_is_float32, void *d_dist_out, int32_t *d_closest_tri_out, void *stream);
+int r2s_mesh_index_lattice(const r2s_mesh_index *index, const int64_t dims[3], const double origin[3], double spacing,
+                           int32_t out_is_float32, void *dist_out, int32_t *closest_tri_out);
+int r2s_mesh_index_lattice_dev(const r2s_mesh_index *index, const int64_t dims[3], const double origin[3], double spacing,
+                               int32_t out_is_float32, void *d_dist_out, int32_t *d_closest_tri_out, void *stream);
+int r2s_redistance_full(const void *values, int32_t is_float32, const int64_t dims[3], const double origin[3],
+                        double spacing, double iso, int32_t device, void *out);
+int r2s_redistance_full_dev(const void *d_values, int32_t is_float32, const int64_t dims[3], const double origin[3],
+                            double spacing, double iso, void *d_out, void *stream);
+
 /* ---- on-disk output ------------------------------------------------------------------ */
 
 /* binary STL of a triangle mesh (verts [n_verts][3], tris [n_tris][3] 0-based); host only, no device; ".stl" appended

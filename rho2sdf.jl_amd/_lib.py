@@ -174,6 +174,19 @@ SYMBOLS = [
     ("r2s_redistance_dev", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, _P, _P]),
     ("r2s_last_distance_stats", None, [c_double_p]),
+    ("r2s_mesh_index_build", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_int32,
+                                            ctypes.POINTER(_P)]),
+    ("r2s_mesh_index_build_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.POINTER(_P)]),
+    ("r2s_mesh_index_destroy", None, [_P]),
+    ("r2s_mesh_index_info", ctypes.c_int, [_P, c_int64_p]),
+    ("r2s_mesh_index_query", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _P, c_int32_p]),
+    ("r2s_mesh_index_query_dev", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _P, _P, _P]),
+    ("r2s_mesh_index_lattice", ctypes.c_int, [_P, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_int32, _P, c_int32_p]),
+    ("r2s_mesh_index_lattice_dev", ctypes.c_int, [_P, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_int32, _P, _P, _P]),
+    ("r2s_redistance_full", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_int32, _P]),
+    ("r2s_redistance_full_dev", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                               _P, _P]),
 ]
 
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8

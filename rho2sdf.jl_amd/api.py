@@ -547,6 +547,181 @@ def last_distance_stats():
     return dict(zip(keys, [float(x) for x in s]))
 
 
+class MeshIndex:
+    """A bounding-volume hierarchy over a triangle mesh on the device (include/rho2sdf_hip.h, r2s_mesh_index): the exact
+    distance to the mesh from arbitrary points (`distance`) or from every point of a lattice (`lattice`), without a band.
+    verts (nv, 3) float32, tris (nt, 3) int32, 0-based; numpy arrays, or torch tensors on the current device (then `device` is
+    ignored).  A context manager; `close()` frees the device memory."""
+
+    def __init__(self, verts, tris, device=-1):
+        h = ctypes.c_void_p()
+        if type(verts).__module__.startswith("torch"):
+            import torch
+            if verts.dtype != torch.float32 or tris.dtype != torch.int32 or not (verts.is_cuda and tris.is_cuda) \
+                    or not (verts.is_contiguous() and tris.is_contiguous()):
+                raise L.R2SError("verts / tris must be contiguous float32 / int32 device tensors")
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            L.check(L.lib().r2s_mesh_index_build_dev(ctypes.c_void_p(verts.data_ptr()), verts.numel() // 3,
+                                                     ctypes.c_void_p(tris.data_ptr()), tris.numel() // 3, st, ctypes.byref(h)))
+        else:
+            v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+            t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+            L.check(L.lib().r2s_mesh_index_build(_f(v), len(v), t.ctypes.data_as(L.c_int32_p), len(t), int(device), ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().r2s_mesh_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the loader's globals may be gone already
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not self._h:
+            raise L.R2SError("the index is closed")
+        return self._h
+
+    def info(self):
+        """{n_tris, n_nodes (leaves + internal), depth (internal levels), device_bytes}"""
+        out = (ctypes.c_int64 * 4)()
+        L.check(L.lib().r2s_mesh_index_info(self._handle(), out))
+        return dict(zip(("n_tris", "n_nodes", "depth", "device_bytes"), [int(x) for x in out]))
+
+    def distance(self, points, want_index=False, dtype=np.float64):
+        """distance of every point ((n, 3), float32 or float64; other types are converted to float64) to the mesh -> (n,)
+        array of `dtype` (float64 or float32); want_index=True: also the int32 index of the closest triangle.  An empty mesh
+        gives inf / -1, a non-finite point NaN / -1."""
+        p = np.ascontiguousarray(points)
+        if p.dtype not in (np.float32, np.float64):
+            p = p.astype(np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise L.R2SError("points must be (n, 3)")
+        dtype = np.dtype(dtype)
+        if dtype not in (np.float32, np.float64):
+            raise L.R2SError("dtype must be float32 or float64")
+        n = len(p)
+        dist = np.empty(n, dtype)
+        idx = np.empty(n, np.int32) if want_index else None
+        L.check(L.lib().r2s_mesh_index_query(self._handle(), p.ctypes.data_as(ctypes.c_void_p), int(p.dtype == np.float32), n,
+                                             int(dtype == np.float32), dist.ctypes.data_as(ctypes.c_void_p),
+                                             idx.ctypes.data_as(L.c_int32_p) if want_index else None))
+        return (dist, idx) if want_index else dist
+
+    def distance_dev(self, t, want_index=False, dtype=None, stream=None):
+        """distance on a torch tensor of points on the index's device ((n, 3) float32 / float64, contiguous) -> device
+        tensor(s); enqueued on the current stream (or `stream`)"""
+        import torch
+        if t.dtype not in (torch.float32, torch.float64) or not t.is_contiguous() or not t.is_cuda or t.dim() != 2 or t.shape[1] != 3:
+            raise L.R2SError("points must be a contiguous float32 / float64 (n, 3) device tensor")
+        dtype = dtype or torch.float64
+        if dtype not in (torch.float32, torch.float64):
+            raise L.R2SError("dtype must be float32 or float64")
+        n = t.shape[0]
+        dist = torch.empty(n, dtype=dtype, device=t.device)
+        idx = torch.empty(n, dtype=torch.int32, device=t.device) if want_index else None
+        st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        if n:
+            L.check(L.lib().r2s_mesh_index_query_dev(self._handle(), ctypes.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), n,
+                                                     int(dtype == torch.float32), ctypes.c_void_p(dist.data_ptr()),
+                                                     ctypes.c_void_p(idx.data_ptr()) if want_index else None, st))
+        return (dist, idx) if want_index else dist
+
+    def lattice(self, grid_or_lattice, smooth=None, want_index=False, dtype=np.float64):
+        """distance of every lattice point (a Grid with `smooth`, as extract_isosurface, or (dims, origin, spacing)) -> array
+        (nz, ny, nx) of `dtype`; want_index=True: also the closest triangle"""
+        dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.float32, np.float64):
+            raise L.R2SError("dtype must be float32 or float64")
+        shape = (dims[2], dims[1], dims[0])
+        dist = np.empty(shape, dtype)
+        idx = np.empty(shape, np.int32) if want_index else None
+        L.check(L.lib().r2s_mesh_index_lattice(self._handle(), dims, origin, spacing, int(dtype == np.float32),
+                                               dist.ctypes.data_as(ctypes.c_void_p),
+                                               idx.ctypes.data_as(L.c_int32_p) if want_index else None))
+        return (dist, idx) if want_index else dist
+
+    def lattice_dev(self, grid_or_lattice, smooth=None, want_index=False, dtype=None, stream=None):
+        """lattice -> torch tensor(s) on the current device (the index's); enqueued on the current stream (or `stream`)"""
+        import torch
+        dtype = dtype or torch.float64
+        if dtype not in (torch.float32, torch.float64):
+            raise L.R2SError("dtype must be float32 or float64")
+        dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+        shape = (dims[2], dims[1], dims[0])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dist = torch.empty(shape, dtype=dtype, device=dev)
+        idx = torch.empty(shape, dtype=torch.int32, device=dev) if want_index else None
+        st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        L.check(L.lib().r2s_mesh_index_lattice_dev(self._handle(), dims, origin, spacing, int(dtype == torch.float32),
+                                                   ctypes.c_void_p(dist.data_ptr()),
+                                                   ctypes.c_void_p(idx.data_ptr()) if want_index else None, st))
+        return (dist, idx) if want_index else dist
+
+
+def redistance_full(values, grid, smooth=None, *, iso=0.0, device=-1):
+    """The signed distance to the iso-surface of `values` on the whole lattice (include/rho2sdf_hip.h, r2s_redistance_full):
+    s * d with s and the mesh as in redistance and no band; +-inf where the field has no surface.  The result has the shape
+    (nz, ny, nx) and the type of the (float32 / float64) input; `grid` is a Grid (with `smooth`) or an explicit (dims, origin,
+    spacing), as in mesh_distance."""
+    a = np.ascontiguousarray(values)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    dims, origin, spacing = _dist_lattice(grid, smooth)
+    if a.size != dims[0] * dims[1] * dims[2]:
+        raise L.R2SError(f"values length ({a.size}) doesn't match the lattice {tuple(dims)}")
+    out = np.empty((dims[2], dims[1], dims[0]), a.dtype)
+    L.check(L.lib().r2s_redistance_full(a.ctypes.data_as(ctypes.c_void_p), int(a.dtype == np.float32), dims, origin, spacing,
+                                        float(iso), int(device), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def redistance_full_dev(t, grid, smooth=None, *, iso=0.0, stream=None):
+    """redistance_full on a torch tensor on the current device (float32 / float64, contiguous, x fastest) -> a device tensor"""
+    import torch
+    if t.dtype not in (torch.float32, torch.float64) or not t.is_contiguous() or not t.is_cuda:
+        raise L.R2SError("t must be a contiguous float32 / float64 device tensor")
+    dims, origin, spacing = _dist_lattice(grid, smooth)
+    if t.numel() != dims[0] * dims[1] * dims[2]:
+        raise L.R2SError(f"values length ({t.numel()}) doesn't match the lattice {tuple(dims)}")
+    out = torch.empty((dims[2], dims[1], dims[0]), dtype=t.dtype, device=t.device)
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    L.check(L.lib().r2s_redistance_full_dev(ctypes.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), dims, origin, spacing,
+                                            float(iso), ctypes.c_void_p(out.data_ptr()), st))
+    return out
+
+
+def _deviation_stats(d):
+    if d.size == 0:
+        return dict(max=0.0, mean=0.0, rms=0.0, argmax=-1)
+    return dict(max=float(d.max()), mean=float(d.mean()), rms=float(np.sqrt(np.mean(d * d))), argmax=int(d.argmax()))
+
+
+def surface_deviation(verts_a, tris_a, verts_b, tris_b, *, device=-1):
+    """How far two surfaces are apart, sampled at their vertices -> {"a_to_b": {max, mean, rms, argmax}, "b_to_a": {...},
+    "hausdorff": float}: a_to_b describes the exact distances from the vertices of A to the surface B (argmax = the vertex
+    of A that is farthest, -1 without vertices), b_to_a the reverse.  `hausdorff` is the larger of the two maxima; it is
+    vertex-sampled, hence a LOWER bound of the true Hausdorff distance of the two surfaces (the farthest point of a triangle
+    need not be a vertex).  A surface without triangles is at distance inf."""
+    va = np.ascontiguousarray(verts_a, dtype=np.float32).reshape(-1, 3)
+    vb = np.ascontiguousarray(verts_b, dtype=np.float32).reshape(-1, 3)
+    with MeshIndex(vb, tris_b, device=device) as ib:
+        a_to_b = _deviation_stats(ib.distance(va))
+    with MeshIndex(va, tris_a, device=device) as ia:
+        b_to_a = _deviation_stats(ia.distance(vb))
+    return dict(a_to_b=a_to_b, b_to_a=b_to_a, hausdorff=max(a_to_b["max"], b_to_a["max"]))
+
+
 class RbfField:
     """The smoothed level-set of one RBFs_smoothing as a function (include/rho2sdf_hip.h, r2s_rbf_field): the weights and
     the level shift stay on the device; `eval`, `normals` and `project` take any (n, 3) array of points.  A context manager;
@@ -804,7 +979,8 @@ class Rho2sdfOptions:
 
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
-            info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False, redistance_cells=None):
+            info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False, redistance_cells=None,
+            signed_distance=False, deviation=False):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -823,8 +999,15 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     export_results=True also writes it next to the .vti as <same name>.stl.  The return values are unchanged.
     redistance_cells=k (a positive number; needs `info`): info["sdf_redistanced"] = redistance(fine_sdf, sdf_grid, smooth,
     band=k * spacing of the fine lattice) - the banded signed distance to the iso-0 surface of fine_sdf, a second library
-    call after the first.  None: nothing is called."""
+    call after the first.  None: nothing is called.
+    signed_distance=True (needs `info`): info["sdf_distance"] = redistance_full(fine_sdf, sdf_grid, smooth), the signed distance
+    to the iso-0 surface of fine_sdf on the whole fine lattice.  deviation=True (needs `info`): info["smoothing_deviation"] =
+    surface_deviation of the iso-0 surface of fine_sdf (A) against the iso-0 surface of the raw sdf_dists on the coarse
+    lattice (B): how far the smoothing moved the surface.  Both are further library calls after the first; with the defaults
+    nothing new is called."""
     options = options or Rho2sdfOptions()
+    if (signed_distance or deviation) and info is None:
+        raise L.R2SError("signed_distance / deviation need an `info` dict for the result")
     if redistance_cells is not None and (info is None or not (float(redistance_cells) > 0.0)):
         raise L.R2SError("redistance_cells must be a positive number and needs an `info` dict for the result")
     mesh = Mesh(X, IEN, options.element_type)
@@ -876,6 +1059,12 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     if redistance_cells is not None:
         info["sdf_redistanced"] = redistance(fine_sdf, sdf_grid, smooth, band=float(redistance_cells) * _iso_lattice(sdf_grid, smooth)[2],
                                              device=device)
+    if signed_distance:
+        info["sdf_distance"] = redistance_full(fine_sdf, sdf_grid, smooth, device=device)
+    if deviation:
+        smoothed = mesh_out if surface else extract_isosurface(fine_sdf, sdf_grid, smooth, device=device)
+        raw = extract_isosurface(sdf_dists, sdf_grid, None, device=device)
+        info["smoothing_deviation"] = surface_deviation(*smoothed, *raw, device=device)
     if export_results:
         vti = export_sdf_results(fine_sdf, sdf_grid, taskName, smooth, options.rbf_interp, mesh.element_type)
         if surface:

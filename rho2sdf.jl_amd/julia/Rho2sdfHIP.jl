@@ -384,6 +384,78 @@ function redistance_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::U
     return out
 end
 
+# Mesh index (no counterpart in the reference): a bounding-volume hierarchy over a triangle mesh on the device and exact
+# point-to-mesh distances without a band (include/rho2sdf_hip.h, r2s_mesh_index).  verts 3 x nv Float32, tris 3 x nt 1-based.
+# The index owns device memory: close it with destroy!(index) (release!() leaves it alone).
+mutable struct MeshIndexHIP
+    handle::Ptr{Cvoid}
+end
+
+function mesh_index_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}; device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    t0 = Int32.(tris) .- Int32(1)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:r2s_mesh_index_build, LIB[]), Cint, (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Int32, Ptr{Ptr{Cvoid}}),
+                Matrix(verts), size(verts, 2), t0, size(t0, 2), Int32(device), h))
+    return finalizer(destroy!, MeshIndexHIP(h[]))
+end
+
+function destroy!(ix::MeshIndexHIP)
+    ix.handle == C_NULL || ccall((:r2s_mesh_index_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), ix.handle)
+    ix.handle = C_NULL
+    return nothing
+end
+
+# (n_tris, nodes, tree depth, device bytes)
+function mesh_index_info(ix::MeshIndexHIP)
+    out = zeros(Int64, 4)
+    check(ccall((:r2s_mesh_index_info, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}), ix.handle, out))
+    return (n_tris = out[1], nodes = out[2], depth = out[3], device_bytes = out[4])
+end
+
+# distances of the points (3 x n, Float32 or Float64) to the mesh -> Vector{Float64}; want_index: also the 1-based index of the
+# closest triangle (0 for an empty mesh or a non-finite point, whose distance is Inf / NaN)
+function mesh_index_distance(ix::MeshIndexHIP, points::AbstractMatrix{T}; want_index::Bool = false) where {T<:Union{Float32,Float64}}
+    size(points, 1) == 3 || error("points must be 3 x n")
+    n = size(points, 2)
+    dist = Vector{Float64}(undef, n)
+    idx = want_index ? Vector{Int32}(undef, n) : nothing
+    check(ccall((:r2s_mesh_index_query, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Cvoid}, Ptr{Int32}),
+                ix.handle, Matrix(points), Int32(T == Float32), n, Int32(0), dist, want_index ? idx : C_NULL))
+    want_index || return dist
+    idx .+= Int32(1)
+    return dist, idx
+end
+
+# the same on every point of the lattice of extract_isosurface_hip for (grid, smooth) -> Array{Float64,3} (x fastest)
+function mesh_index_lattice(ix::MeshIndexHIP, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing; want_index::Bool = false)
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    dist = Array{Float64,3}(undef, dims...)
+    idx = want_index ? Array{Int32,3}(undef, dims...) : nothing
+    check(ccall((:r2s_mesh_index_lattice, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Float64, Int32, Ptr{Cvoid}, Ptr{Int32}),
+                ix.handle, collect(dims), collect(Float64.(grid.AABB_min)), spacing, Int32(0), dist, want_index ? idx : C_NULL))
+    want_index || return dist
+    idx .+= Int32(1)
+    return dist, idx
+end
+
+# The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
+# +-Inf where the field has no surface.
+function redistance_full_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
+                             iso = 0.0) where {T<:Union{Float32,Float64}}
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    length(values) == prod(dims) || error("values length ($(length(values))) doesn't match the lattice $(Tuple(dims))")
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    out = Array{T,3}(undef, dims...)
+    check(ccall((:r2s_redistance_full, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Float64, Float64, Int32, Ptr{Cvoid}),
+                values, Int32(T == Float32), collect(dims), collect(Float64.(grid.AABB_min)), spacing, Float64(iso), Int32(-1), out))
+    return out
+end
+
 # calculate_volume_from_sdf (src/SdfSmoothing/CalcVolumeFromSDF.jl:26-125); `grid` is the reference's array of
 # per-voxel coordinate vectors - only the spacing is used (:36-39)
 function calculate_volume_from_sdf_hip(sdf::Array{Float32,3}, grid::AbstractArray{Vector{Float32},3}; iso_threshold = 0.0f0,
