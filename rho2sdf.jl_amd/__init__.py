@@ -11,7 +11,8 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   remove_sdf_artifacts, rho2sdf, sdf_fused, host_array, calculate_isocontour_volume, MeshInformations,
                   extract_isosurface, extract_isosurface_dev, export_stl, RbfField, fit_rbf_field, refine_surface,
                   mesh_distance, mesh_distance_dev, redistance, redistance_dev, last_distance_stats,
-                  MeshIndex, redistance_full, redistance_full_dev, surface_deviation)
+                  MeshIndex, redistance_full, redistance_full_dev, surface_deviation,
+                  vertex_normals, surface_thickness, surface_thickness_dev)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
@@ -20,4 +21,5 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "extract_isosurface", "extract_isosurface_dev", "export_stl", "RbfField", "fit_rbf_field", "refine_surface",
            "mesh_distance", "mesh_distance_dev", "redistance", "redistance_dev", "last_distance_stats",
            "MeshIndex", "redistance_full", "redistance_full_dev", "surface_deviation",
+           "vertex_normals", "surface_thickness", "surface_thickness_dev",
            "_lib"]

@@ -187,6 +187,10 @@ SYMBOLS = [
                                            ctypes.c_int32, _P]),
     ("r2s_redistance_full_dev", ctypes.c_int, [_P, ctypes.c_int32, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_double,
                                                _P, _P]),
+    ("r2s_mesh_index_raycast", ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_int32, _P, c_int32_p, _P]),
+    ("r2s_mesh_index_raycast_dev", ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                                  ctypes.c_int32, _P, _P, _P, _P]),
 ]
 
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8

@@ -668,6 +668,162 @@ class MeshIndex:
                                                    ctypes.c_void_p(idx.data_ptr()) if want_index else None, st))
         return (dist, idx) if want_index else dist
 
+    @staticmethod
+    def _window(t_min, t_max):
+        t_min, t_max = float(t_min), float(t_max)
+        if t_min != t_min or t_max != t_max or t_min > t_max:
+            raise L.R2SError("t_min <= t_max is required, neither may be NaN")
+        return t_min, t_max
+
+    def raycast(self, origins, directions, t_min=0.0, t_max=float("inf"), want_index=False, want_side=False, dtype=np.float64):
+        """first hit of every ray origins[i] + t * directions[i] with t_min <= t <= t_max (include/rho2sdf_hip.h,
+        r2s_mesh_index_raycast).  Both arrays (n, 3); both float32, or else both are taken as float64.  Directions are not
+        normalised: t is a length only for unit directions.  -> t (n,) of `dtype` (float64 or float32): inf on a miss, NaN for
+        a ray with a non-finite entry or a zero direction; want_index=True: also the int32 index of the triangle hit (-1:
+        none); want_side=True: also int8 +1 (the ray enters through the front of the winding), -1 (through the back), 0."""
+        o, d = np.ascontiguousarray(origins), np.ascontiguousarray(directions)
+        if o.dtype != np.float32 or d.dtype != np.float32:
+            o, d = np.ascontiguousarray(o, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise L.R2SError("origins and directions must both be (n, 3)")
+        dtype = np.dtype(dtype)
+        if dtype not in (np.float32, np.float64):
+            raise L.R2SError("dtype must be float32 or float64")
+        t_min, t_max = self._window(t_min, t_max)
+        n = len(o)
+        t = np.empty(n, dtype)
+        idx = np.empty(n, np.int32) if want_index else None
+        side = np.empty(n, np.int8) if want_side else None
+        vp = ctypes.c_void_p
+        L.check(L.lib().r2s_mesh_index_raycast(self._handle(), o.ctypes.data_as(vp), d.ctypes.data_as(vp), int(o.dtype == np.float32), n,
+                                               t_min, t_max, int(dtype == np.float32), t.ctypes.data_as(vp),
+                                               idx.ctypes.data_as(L.c_int32_p) if want_index else None,
+                                               side.ctypes.data_as(vp) if want_side else None))
+        res = (t,) + ((idx,) if want_index else ()) + ((side,) if want_side else ())
+        return res if len(res) > 1 else t
+
+    def raycast_dev(self, origins, directions, t_min=0.0, t_max=float("inf"), want_index=False, want_side=False, dtype=None,
+                    stream=None):
+        """raycast on torch tensors on the index's device ((n, 3), contiguous, both float32 or both float64) -> device
+        tensor(s); enqueued on the current stream (or `stream`)"""
+        import torch
+        for a in (origins, directions):
+            if a.dtype not in (torch.float32, torch.float64) or not a.is_contiguous() or not a.is_cuda or a.dim() != 2 or a.shape[1] != 3:
+                raise L.R2SError("origins / directions must be contiguous float32 / float64 (n, 3) device tensors")
+        if origins.dtype != directions.dtype or origins.shape != directions.shape or origins.device != directions.device:
+            raise L.R2SError("origins and directions must agree in type, shape and device")
+        dtype = dtype or torch.float64
+        if dtype not in (torch.float32, torch.float64):
+            raise L.R2SError("dtype must be float32 or float64")
+        t_min, t_max = self._window(t_min, t_max)
+        n = origins.shape[0]
+        t = torch.empty(n, dtype=dtype, device=origins.device)
+        idx = torch.empty(n, dtype=torch.int32, device=origins.device) if want_index else None
+        side = torch.empty(n, dtype=torch.int8, device=origins.device) if want_side else None
+        st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        if n:
+            vp = ctypes.c_void_p
+            L.check(L.lib().r2s_mesh_index_raycast_dev(self._handle(), vp(origins.data_ptr()), vp(directions.data_ptr()),
+                                                       int(origins.dtype == torch.float32), n, t_min, t_max, int(dtype == torch.float32),
+                                                       vp(t.data_ptr()), vp(idx.data_ptr()) if want_index else None,
+                                                       vp(side.data_ptr()) if want_side else None, st))
+        res = (t,) + ((idx,) if want_index else ()) + ((side,) if want_side else ())
+        return res if len(res) > 1 else t
+
+
+def vertex_normals(verts, tris):
+    """area-weighted vertex normals of the winding, float64 (nv, 3), not normalised: the sum of (b-a)x(c-a) over the
+    triangles at a vertex, from the float32 vertices widened to float64, added in the order of the triangles (corner 0 of
+    every triangle first, then corner 1, then corner 2)"""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    ab, ac = v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]]
+    fn = np.stack([ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1], ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2],
+                   ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]], axis=1)
+    n = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(n, t[:, k], fn)
+    return n
+
+
+def _unit(n):
+    """n / |n| in float64, |n| = sqrt((x*x + y*y) + z*z); a zero normal stays zero (its ray then answers NaN)"""
+    ln = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+    return n / np.where(ln > 0.0, ln, 1.0)[:, None]
+
+
+def _skip(skip):
+    skip = float(skip)
+    if not (skip >= 0.0) or skip == float("inf"):
+        raise L.R2SError("skip must be a finite length >= 0")
+    return skip
+
+
+def surface_thickness(verts, tris, normals=None, *, skip, index=None, device=-1):
+    """Wall thickness at every vertex of a surface: the first hit of the ray from the vertex along -normal with t >= skip
+    -> (thickness (nv,) float64, hit_tri (nv,) int32, side (nv,) int8) as MeshIndex.raycast returns them.  `normals`
+    (nv, 3): any vectors along which to measure, e.g. RbfField.normals(verts); default: vertex_normals(verts, tris).  They
+    are normalised in float64, so the thickness is a length.  `skip` is a length of the caller's choosing (typically a
+    fraction of the lattice spacing) that steps over the triangles at the vertex itself.  A ray that leaves the mesh gives
+    inf / -1 / 0, a vertex with a zero or non-finite normal NaN / -1 / 0.  `index`: a MeshIndex of (verts, tris) to use
+    instead of building one."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    skip = _skip(skip)
+    n = vertex_normals(v, t) if normals is None else np.ascontiguousarray(normals, dtype=np.float64)
+    if n.shape != v.shape:
+        raise L.R2SError("normals must be (n_verts, 3)")
+    d = -_unit(n)
+    if index is not None:
+        return index.raycast(v.astype(np.float64), d, t_min=skip, want_index=True, want_side=True)
+    with MeshIndex(v, t, device=device) as ix:
+        return ix.raycast(v.astype(np.float64), d, t_min=skip, want_index=True, want_side=True)
+
+
+def surface_thickness_dev(verts, tris, normals=None, *, skip, index=None, stream=None):
+    """surface_thickness on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous;
+    normals float64 or float32 (nv, 3)) -> device tensors (thickness float64, hit_tri int32, side int8).  The default
+    normals are summed per vertex in the order of vertex_normals (one conflict-free scatter per incident corner, no
+    floating-point atomics), so the result equals surface_thickness."""
+    import torch
+    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or not (verts.is_cuda and tris.is_cuda) \
+            or not (verts.is_contiguous() and tris.is_contiguous()):
+        raise L.R2SError("verts / tris must be contiguous float32 / int32 device tensors")
+    skip = _skip(skip)
+    v = verts.reshape(-1, 3).to(torch.float64)
+    nv = v.shape[0]
+    if normals is None:
+        t = tris.reshape(-1, 3).to(torch.int64)
+        ab, ac = v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]]
+        fn = torch.stack([ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1], ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2],
+                          ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]], dim=1)
+        n = torch.zeros_like(v)
+        if t.numel():
+            corner = torch.cat([t[:, 0], t[:, 1], t[:, 2]])
+            vs, order = torch.sort(corner, stable=True)
+            first = torch.searchsorted(vs, vs)                       # position of the vertex's first corner
+            rank = torch.arange(len(vs), device=vs.device) - first
+            src = order % t.shape[0]                                 # the triangle of each corner
+            for r in range(int(rank.max().item()) + 1):
+                sel = rank == r
+                n[vs[sel]] = n[vs[sel]] + fn[src[sel]]
+    else:
+        n = normals.to(torch.float64)
+        if n.shape != v.shape or n.device != v.device:
+            raise L.R2SError("normals must be (n_verts, 3) on the device of verts")
+    ln = torch.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+    d = (-(n / torch.where(ln > 0.0, ln, torch.ones_like(ln))[:, None])).contiguous()
+    own = index is None
+    ix = MeshIndex(verts, tris) if own else index
+    try:
+        out = ix.raycast_dev(v.contiguous(), d, t_min=skip, want_index=True, want_side=True, stream=stream)
+        if own:
+            (torch.cuda.current_stream() if stream is None else stream).synchronize()   # the index goes away below
+        return out
+    finally:
+        if own:
+            ix.close()
+
 
 def redistance_full(values, grid, smooth=None, *, iso=0.0, device=-1):
     """The signed distance to the iso-surface of `values` on the whole lattice (include/rho2sdf_hip.h, r2s_redistance_full):
@@ -980,7 +1136,7 @@ class Rho2sdfOptions:
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
             info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False, redistance_cells=None,
-            signed_distance=False, deviation=False):
+            signed_distance=False, deviation=False, thickness=False):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -1004,10 +1160,16 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     to the iso-0 surface of fine_sdf on the whole fine lattice.  deviation=True (needs `info`): info["smoothing_deviation"] =
     surface_deviation of the iso-0 surface of fine_sdf (A) against the iso-0 surface of the raw sdf_dists on the coarse
     lattice (B): how far the smoothing moved the surface.  Both are further library calls after the first; with the defaults
-    nothing new is called."""
+    nothing new is called.
+    thickness=True (needs `info`; implies surface=True): info["thickness"] = surface_thickness(*info["surface"], skip=half a
+    spacing of the fine lattice) - (thickness, hit_tri, side) at every vertex of the extracted surface, a further library
+    call after the first."""
     options = options or Rho2sdfOptions()
     if (signed_distance or deviation) and info is None:
         raise L.R2SError("signed_distance / deviation need an `info` dict for the result")
+    if thickness and info is None:
+        raise L.R2SError("thickness needs an `info` dict for the result")
+    surface = bool(surface) or bool(thickness)
     if redistance_cells is not None and (info is None or not (float(redistance_cells) > 0.0)):
         raise L.R2SError("redistance_cells must be a positive number and needs an `info` dict for the result")
     mesh = Mesh(X, IEN, options.element_type)
@@ -1065,6 +1227,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
         smoothed = mesh_out if surface else extract_isosurface(fine_sdf, sdf_grid, smooth, device=device)
         raw = extract_isosurface(sdf_dists, sdf_grid, None, device=device)
         info["smoothing_deviation"] = surface_deviation(*smoothed, *raw, device=device)
+    if thickness:
+        info["thickness"] = surface_thickness(*mesh_out, skip=0.5 * _iso_lattice(sdf_grid, smooth)[2], device=device)
     if export_results:
         vti = export_sdf_results(fine_sdf, sdf_grid, taskName, smooth, options.rbf_interp, mesh.element_type)
         if surface:

@@ -632,6 +632,166 @@ __global__ void __launch_bounds__(64) mi_query_kernel(MiQuery g)
     if (g.closest) g.closest[i] = idx;
 }
 
+// ---- ray queries against the same tree (include/rho2sdf_hip.h, r2s_mesh_index_raycast; DESIGN.md "Ray queries") -----------
+// mi_ray_kernel: one lane per ray, 64 rays per workgroup, the per-lane LDS stack of mi_query_kernel.  A node is read as four
+// 16-byte words; both children's parameter intervals come from the slab arithmetic of the header (mr_slab), the child with
+// the smaller lower end is entered first and the other one pushed unless its interval is empty or starts behind the best t.
+// A popped leaf is tested again against the best t of that moment through its own box, a popped node through its children.
+// The pair test is the watertight one of Woop, Benthin and Wald (2013) in double, every operation rounded on its own: the
+// edge function of a shared edge is then the exact negative in the neighbouring triangle, which a fused multiply-add would break.
+struct MiRay {
+    const MiNode* nodes;
+    const float* verts;
+    const int32_t* tris;
+    int64_t ntris;
+    int32_t root;
+    double absmax;
+    const void* org;           // [n][3]
+    const void* dir;           // [n][3]
+    int rays_f32;
+    int64_t n;
+    double tmin, tmax;
+    void* out;
+    int out_f32;
+    int32_t* tri;              // may be null
+    int8_t* side;              // may be null
+};
+
+// the per-ray constants of the node and box tests: o, inv = 1 / d (0 marks d == 0: a reciprocal is never 0), the margin
+struct MrSlab {
+    double ox, oy, oz, ix, iy, iz, m, tmin, tmax;
+};
+
+__device__ inline void mr_axis(double l, double h, double o, double inv, double& lo, double& hi)
+{
+    if (inv != 0.0) {
+        const double t1 = (l - o) * inv, t2 = (h - o) * inv;
+        lo = fmax(lo, fmin(t1, t2));     // (fmin / fmax drop a NaN of 0 * inf: that end sets no bound)
+        hi = fmin(hi, fmax(t1, t2));
+    } else if (!(l <= o && o <= h)) {
+        lo = __builtin_huge_val(), hi = -__builtin_huge_val();
+    }
+}
+
+// [lo, hi]: the ray's parameter interval through the float32 box b (lo xyz, hi xyz) inflated by m, within [tmin, tmax]
+__device__ inline void mr_slab(const MrSlab& r, const float* __restrict__ b, double& lo, double& hi)
+{
+    lo = r.tmin, hi = r.tmax;
+    mr_axis((double)b[0] - r.m, (double)b[3] + r.m, r.ox, r.ix, lo, hi);
+    mr_axis((double)b[1] - r.m, (double)b[4] + r.m, r.oy, r.iy, lo, hi);
+    mr_axis((double)b[2] - r.m, (double)b[5] + r.m, r.oz, r.iz, lo, hi);
+}
+
+__device__ inline bool mr_skip(double lo, double hi, double best) { return lo > hi || lo > best; }
+
+// component k of (x, y, z) by selects (an indexed register array would go to scratch)
+__device__ inline float mr_pick(const float* __restrict__ p, int k) { return k == 0 ? p[0] : (k == 1 ? p[1] : p[2]); }
+__device__ inline double mr_pick(double x, double y, double z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
+
+__global__ void __launch_bounds__(64) mi_ray_kernel(MiRay g)
+{
+#pragma clang fp contract(off)
+    __shared__ int32_t stk[MI_STACK * 64];
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+    if (i >= g.n) return;
+    double ox, oy, oz, dx, dy, dz;
+    if (g.rays_f32) {
+        const float *q = reinterpret_cast<const float*>(g.org) + 3 * i, *e = reinterpret_cast<const float*>(g.dir) + 3 * i;
+        ox = (double)q[0], oy = (double)q[1], oz = (double)q[2], dx = (double)e[0], dy = (double)e[1], dz = (double)e[2];
+    } else {
+        const double *q = reinterpret_cast<const double*>(g.org) + 3 * i, *e = reinterpret_cast<const double*>(g.dir) + 3 * i;
+        ox = q[0], oy = q[1], oz = q[2], dx = e[0], dy = e[1], dz = e[2];
+    }
+    const bool ok = isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(dx) && isfinite(dy) && isfinite(dz) &&
+                    (dx != 0.0 || dy != 0.0 || dz != 0.0);
+    double best = __builtin_huge_val();
+    int32_t bi = INT32_MAX;
+    int bs = 0;
+    if (ok && g.ntris > 0) {
+        MrSlab r;
+        r.ox = ox, r.oy = oy, r.oz = oz;
+        r.ix = dx != 0.0 ? 1.0 / dx : 0.0, r.iy = dy != 0.0 ? 1.0 / dy : 0.0, r.iz = dz != 0.0 ? 1.0 / dz : 0.0;
+        r.m = ldexp(fmax(fmax(fabs(ox), fabs(oy)), fmax(fabs(oz), g.absmax)), -40);
+        r.tmin = g.tmin, r.tmax = g.tmax;
+        // the shear frame: kz the axis of the largest |d| (lowest on ties), kx, ky the next two cyclically, swapped for d[kz] < 0
+        int kz = 0;
+        double big = fabs(dx);
+        if (fabs(dy) > big) kz = 1, big = fabs(dy);
+        if (fabs(dz) > big) kz = 2;
+        int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+        const double dkz = mr_pick(dx, dy, dz, kz);
+        if (dkz < 0.0) {
+            const int s = kx;
+            kx = ky, ky = s;
+        }
+        const double Sx = mr_pick(dx, dy, dz, kx) / dkz, Sy = mr_pick(dx, dy, dz, ky) / dkz, Sz = 1.0 / dkz;
+        const double okx = mr_pick(ox, oy, oz, kx), oky = mr_pick(ox, oy, oz, ky), okz = mr_pick(ox, oy, oz, kz);
+        int sp = 0;
+        int32_t cur = g.root;
+        for (;;) {
+            if (cur < 0) {
+                const int32_t t = ~cur;
+                const int32_t* tv = g.tris + 3 * (int64_t)t;
+                const float *a = g.verts + 3 * (int64_t)tv[0], *b = g.verts + 3 * (int64_t)tv[1], *c = g.verts + 3 * (int64_t)tv[2];
+                const float fa[3] = {a[0], a[1], a[2]}, fb[3] = {b[0], b[1], b[2]}, fc[3] = {c[0], c[1], c[2]};
+                float bx[6];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    bx[k] = fminf(fa[k], fminf(fb[k], fc[k]));
+                    bx[3 + k] = fmaxf(fa[k], fmaxf(fb[k], fc[k]));
+                }
+                double lo, hi;
+                mr_slab(r, bx, lo, hi);
+                if (!mr_skip(lo, hi, best)) {
+                    const double Az = (double)mr_pick(fa, kz) - okz, Bz = (double)mr_pick(fb, kz) - okz, Cz = (double)mr_pick(fc, kz) - okz;
+                    const double Ax = ((double)mr_pick(fa, kx) - okx) - Sx * Az, Ay = ((double)mr_pick(fa, ky) - oky) - Sy * Az;
+                    const double Bx = ((double)mr_pick(fb, kx) - okx) - Sx * Bz, By = ((double)mr_pick(fb, ky) - oky) - Sy * Bz;
+                    const double Cx = ((double)mr_pick(fc, kx) - okx) - Sx * Cz, Cy = ((double)mr_pick(fc, ky) - oky) - Sy * Cz;
+                    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+                    const bool mixed = (U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0);
+                    const double det = (U + V) + W;
+                    if (!mixed && det != 0.0) {
+                        const double tt = ((U * (Sz * Az) + V * (Sz * Bz)) + W * (Sz * Cz)) / det;
+                        if (tt >= lo && tt <= hi && (tt < best || (tt == best && t < bi))) best = tt, bi = t, bs = det > 0.0 ? 1 : -1;
+                    }
+                }
+            } else {
+                const uint4* w = reinterpret_cast<const uint4*>(g.nodes + cur);
+                union {
+                    uint4 q[4];
+                    MiNode n;
+                } u;
+                u.q[0] = w[0], u.q[1] = w[1], u.q[2] = w[2], u.q[3] = w[3];
+                double l0, h0, l1, h1;
+                mr_slab(r, u.n.box[0], l0, h0);
+                mr_slab(r, u.n.box[1], l1, h1);
+                const bool s0 = mr_skip(l0, h0, best), s1 = mr_skip(l1, h1, best);
+                const bool swap = s0 || (!s1 && l1 < l0);   // enter child 1 first
+                const int32_t cn = swap ? u.n.child[1] : u.n.child[0], cf = swap ? u.n.child[0] : u.n.child[1];
+                if (!s0 && !s1) {
+                    stk[sp * 64 + lane] = cf;
+                    ++sp;
+                }
+                if (!(s0 && s1)) {
+                    cur = cn;
+                    continue;
+                }
+            }
+            if (sp == 0) break;
+            --sp;
+            cur = stk[sp * 64 + lane];
+        }
+    }
+    const double tt = ok ? best + 0.0 : __builtin_nan("");   // (-0 -> +0: a zero t must not depend on which triangle gave it)
+    if (g.out_f32)
+        reinterpret_cast<float*>(g.out)[i] = (float)tt;
+    else
+        reinterpret_cast<double*>(g.out)[i] = tt;
+    if (g.tri) g.tri[i] = bi == INT32_MAX ? -1 : bi;
+    if (g.side) g.side[i] = (int8_t)bs;
+}
+
 // work buffers of the distance calls, kept per device between calls (r2s_release_cache frees them)
 struct DistWork {
     DevBuf cnt, off, list, flag;            // binning
@@ -969,6 +1129,35 @@ int query_args(const char* who, const r2s_mesh_index* ix, const void* points, in
     return 0;
 }
 
+int ray_args(const char* who, const r2s_mesh_index* ix, const void* origins, const void* dirs, int64_t n, double t_min, double t_max,
+             const void* out)
+{
+    if (!ix) return fail(R2S_ERR_ARG, "%s: null index", who);
+    if (n < 0) return fail(R2S_ERR_ARG, "%s: negative ray count", who);
+    if (std::isnan(t_min) || std::isnan(t_max)) return fail(R2S_ERR_ARG, "%s: t_min / t_max is NaN", who);
+    if (t_min > t_max) return fail(R2S_ERR_ARG, "%s: t_min > t_max", who);
+    if (n > 0 && (!origins || !dirs || !out)) return fail(R2S_ERR_ARG, "%s: null origins / directions / output", who);
+    if (n > INT32_MAX) return fail(R2S_ERR_UNSUPPORTED, "%s: %lld rays exceed one call", who, (long long)n);
+    return 0;
+}
+
+// enqueues the n > 0 rays on `st`; does not wait
+int mi_raycast(const MiTree& T, const void* d_org, const void* d_dir, bool rays_f32, int64_t n, double t_min, double t_max, void* d_out,
+               bool out_f32, int32_t* d_tri, int8_t* d_side, hipStream_t st)
+{
+    if (T.depth > MI_STACK)
+        return fail(R2S_ERR_UNSUPPORTED, "mesh_index: tree depth %d exceeds the traversal stack of %d entries", T.depth, MI_STACK);
+    MiRay g = {};
+    g.nodes = const_cast<MiTree&>(T).nodes.as<MiNode>();
+    g.verts = T.verts, g.tris = T.tris, g.ntris = T.n_tris, g.root = T.root, g.absmax = T.absmax;
+    g.org = d_org, g.dir = d_dir, g.rays_f32 = rays_f32 ? 1 : 0, g.n = n;
+    g.tmin = t_min, g.tmax = t_max;
+    g.out = d_out, g.out_f32 = out_f32 ? 1 : 0, g.tri = d_tri, g.side = d_side;
+    mi_ray_kernel<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(g);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 namespace r2s_int {
@@ -1212,6 +1401,45 @@ int r2s_mesh_index_query_dev(const r2s_mesh_index* ix, const void* d_points, int
     if ((rc = check_device(0)) || (rc = index_on_current_device("mesh_index_query", ix))) return rc;
     return mi_query(ix->tree, d_points, points_are_float32 != 0, n, nullptr, nullptr, 0.0, nullptr, false, 0.0, d_dist_out,
                     out_is_float32 != 0, d_closest_tri_out, (hipStream_t)stream);
+}
+
+int r2s_mesh_index_raycast(const r2s_mesh_index* ix, const void* origins, const void* dirs, int32_t rays_are_float32, int64_t n,
+                           double t_min, double t_max, int32_t out_is_float32, void* t_out, int32_t* tri_out, int8_t* side_out)
+{
+    int rc = ray_args("mesh_index_raycast", ix, origins, dirs, n, t_min, t_max, t_out);
+    if (rc || n == 0) return rc;
+    if ((rc = check_device(0))) return rc;
+    DeviceScope scope;
+    if ((rc = scope.enter(ix->device))) return rc;
+    const size_t psz = 3 * (rays_are_float32 ? sizeof(float) : sizeof(double)) * (size_t)n;
+    const size_t osz = (out_is_float32 ? sizeof(float) : sizeof(double)) * (size_t)n;
+    Scoped org, dir, out, idx, side;
+    ENSURE(org, psz);
+    ENSURE(dir, psz);
+    ENSURE(out, osz);
+    if (tri_out) ENSURE(idx, sizeof(int32_t) * (size_t)n);
+    if (side_out) ENSURE(side, (size_t)n);
+    HIP_TRY(hipMemcpy(org.p, origins, psz, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dir.p, dirs, psz, hipMemcpyHostToDevice));
+    if ((rc = mi_raycast(ix->tree, org.p, dir.p, rays_are_float32 != 0, n, t_min, t_max, out.p, out_is_float32 != 0,
+                         tri_out ? idx.as<int32_t>() : nullptr, side_out ? side.as<int8_t>() : nullptr, nullptr)))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(t_out, out.p, osz, hipMemcpyDeviceToHost));
+    if (tri_out) HIP_TRY(hipMemcpy(tri_out, idx.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    if (side_out) HIP_TRY(hipMemcpy(side_out, side.p, (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int r2s_mesh_index_raycast_dev(const r2s_mesh_index* ix, const void* d_origins, const void* d_dirs, int32_t rays_are_float32, int64_t n,
+                               double t_min, double t_max, int32_t out_is_float32, void* d_t_out, int32_t* d_tri_out, int8_t* d_side_out,
+                               void* stream)
+{
+    int rc = ray_args("mesh_index_raycast", ix, d_origins, d_dirs, n, t_min, t_max, d_t_out);
+    if (rc || n == 0) return rc;
+    if ((rc = check_device(0)) || (rc = index_on_current_device("mesh_index_raycast", ix))) return rc;
+    return mi_raycast(ix->tree, d_origins, d_dirs, rays_are_float32 != 0, n, t_min, t_max, d_t_out, out_is_float32 != 0, d_tri_out,
+                      d_side_out, (hipStream_t)stream);
 }
 
 int r2s_mesh_index_lattice(const r2s_mesh_index* ix, const int64_t dims[3], const double origin[3], double spacing, int32_t out_is_float32,

@@ -441,6 +441,24 @@ function mesh_index_lattice(ix::MeshIndexHIP, grid::MeshGrid.Grid, smooth::Union
     return dist, idx
 end
 
+# first hit of the rays origins + t * dirs (both 3 x n, Float32 or Float64; dirs are not normalised) with t_min <= t <= t_max
+# (include/rho2sdf_hip.h, r2s_mesh_index_raycast) -> (t, tri, side): t Vector{Float64} (Inf = miss, NaN = a bad ray), tri the
+# 1-based index of the triangle hit (0 = none), side Int8 (+1 the ray enters through the front of the winding, -1 through the
+# back, 0 = miss)
+function mesh_raycast_hip(ix::MeshIndexHIP, origins::AbstractMatrix{T}, dirs::AbstractMatrix{T}; t_min::Real = 0.0,
+                          t_max::Real = Inf) where {T<:Union{Float32,Float64}}
+    size(origins, 1) == 3 && size(origins) == size(dirs) || error("origins and dirs must both be 3 x n")
+    n = size(origins, 2)
+    t = Vector{Float64}(undef, n)
+    tri = Vector{Int32}(undef, n)
+    side = Vector{Int8}(undef, n)
+    check(ccall((:r2s_mesh_index_raycast, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Float64, Float64, Int32, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int8}),
+                ix.handle, Matrix(origins), Matrix(dirs), Int32(T == Float32), n, Float64(t_min), Float64(t_max), Int32(0), t, tri, side))
+    tri .+= Int32(1)
+    return t, tri, side
+end
+
 # The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
 # +-Inf where the field has no surface.
 function redistance_full_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
