@@ -159,6 +159,53 @@ def sdf_fused(mesh, grid, rho_n, rho_t, *, band_factor=1.1, device=-1, stats=Non
     return out
 
 
+def _stream(stream):
+    """the raw handle of a torch stream (None: the current stream), as the *_dev entry points take it"""
+    import torch
+    return ctypes.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
+
+
+def _mesh_tensors(verts, tris):
+    import torch
+    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or not (verts.is_cuda and tris.is_cuda) \
+            or not (verts.is_contiguous() and tris.is_contiguous()):
+        raise L.R2SError("verts / tris must be contiguous float32 / int32 device tensors")
+
+
+def _float_dtype(dtype, xp):
+    """`dtype` as the float32 or float64 of `xp` (numpy or torch); None: float64"""
+    dtype = xp.float64 if dtype is None else dtype
+    dtype = np.dtype(dtype) if xp is np else dtype
+    if dtype not in (xp.float32, xp.float64):
+        raise L.R2SError("dtype must be float32 or float64")
+    return dtype
+
+
+def _points_nx3(message, *arrays, same_shape=False):
+    """R2SError(message) unless every array is (n, 3); a torch tensor must also be float32 / float64, contiguous and on a device"""
+    for a in arrays:
+        ok = a.ndim == 2 and a.shape[1] == 3 and not (same_shape and a.shape != arrays[0].shape)
+        if ok and not isinstance(a, np.ndarray):
+            import torch
+            ok = a.dtype in (torch.float32, torch.float64) and a.is_contiguous() and a.is_cuda
+        if not ok:
+            raise L.R2SError(message)
+
+
+def _dist_outputs(shape, dtype, want_index, device=None):
+    """-> (result, dist pointer, index pointer or None) of a distance call: `result` is dist of `dtype`, or (dist, int32 idx)
+    with want_index; numpy arrays, or torch tensors on `device`"""
+    if device is None:
+        dist, idx = np.empty(shape, dtype), np.empty(shape, np.int32) if want_index else None
+        ptrs = dist.ctypes.data_as(ctypes.c_void_p), idx.ctypes.data_as(L.c_int32_p) if want_index else None
+    else:
+        import torch
+        dist = torch.empty(shape, dtype=dtype, device=device)
+        idx = torch.empty(shape, dtype=torch.int32, device=device) if want_index else None
+        ptrs = ctypes.c_void_p(dist.data_ptr()), ctypes.c_void_p(idx.data_ptr()) if want_index else None
+    return ((dist, idx) if want_index else dist,) + ptrs
+
+
 class DevicePlan:
     """Device-resident path (inputs/outputs are torch CUDA tensors = HBM buffers).
 
@@ -209,8 +256,7 @@ class DevicePlan:
         p.zphase = int(zphase)
         p.true_min = int(bool(true_min))
         st = L.R2SStats()
-        s = ctypes.c_void_p(stream.cuda_stream if stream is not None
-                            else torch.cuda.current_stream().cuda_stream)
+        s = _stream(stream)
         L.check(L.lib().r2s_plan_run_dev(self._h, ctypes.c_void_p(dX.data_ptr()), dX.shape[0],
                                          ctypes.c_void_p(dIEN.data_ptr()), dIEN.shape[0],
                                          ctypes.c_void_p(d_rho_n.data_ptr()), float(rho_t),
@@ -219,10 +265,7 @@ class DevicePlan:
         return st.as_dict()
 
     # ---- sparse stitching (see include/rho2sdf_hip.h) ----
-    @staticmethod
-    def _stream(stream):
-        import torch
-        return ctypes.c_void_p(stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+    _stream = staticmethod(_stream)
 
     def pack_tiles(self, local_sdf, payload, ids, stream=None):
         """pack the non-sentinel tiles of the last run's output into payload (n,64) f64 / ids (n,) i32"""
@@ -446,7 +489,7 @@ def extract_isosurface_dev(t, grid, smooth=None, *, iso=0.0, stream=None):
     dims, origin, spacing = _iso_lattice(grid, smooth)
     if t.numel() != dims[0] * dims[1] * dims[2]:
         raise L.R2SError(f"values length ({t.numel()}) doesn't match the lattice {tuple(dims)}")
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    st = _stream(stream)
     nv, nt = ctypes.c_int64(), ctypes.c_int64()
     f32 = int(t.dtype == torch.float32)
     L.check(L.lib().r2s_extract_isosurface_dev(ctypes.c_void_p(t.data_ptr()), f32, dims, origin, spacing, float(iso), None, 0, None,
@@ -476,35 +519,24 @@ def mesh_distance(verts, tris, grid_or_lattice, band, *, smooth=None, want_index
     v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
     t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
     dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
-    shape = (dims[2], dims[1], dims[0])
-    dist = np.empty(shape, np.float64)
-    idx = np.empty(shape, np.int32) if want_index else None
+    res, p_dist, p_idx = _dist_outputs((dims[2], dims[1], dims[0]), np.float64, want_index)
     L.check(L.lib().r2s_mesh_distance(_f(v), len(v), t.ctypes.data_as(L.c_int32_p), len(t), dims, origin, spacing, float(band), 0,
-                                      int(device), dist.ctypes.data_as(ctypes.c_void_p),
-                                      idx.ctypes.data_as(L.c_int32_p) if want_index else None))
-    return (dist, idx) if want_index else dist
+                                      int(device), p_dist, p_idx))
+    return res
 
 
 def mesh_distance_dev(verts, tris, grid_or_lattice, band, *, smooth=None, want_index=False, dtype=None, stream=None):
     """mesh_distance on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous) -> a
     device tensor (nz, ny, nx) of `dtype` (float64 by default, or float32)"""
     import torch
-    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or not (verts.is_cuda and tris.is_cuda) \
-            or not (verts.is_contiguous() and tris.is_contiguous()):
-        raise L.R2SError("verts / tris must be contiguous float32 / int32 device tensors")
-    dtype = dtype or torch.float64
-    if dtype not in (torch.float32, torch.float64):
-        raise L.R2SError("dtype must be float32 or float64")
+    _mesh_tensors(verts, tris)
+    dtype = _float_dtype(dtype, torch)
     dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
-    shape = (dims[2], dims[1], dims[0])
-    dist = torch.empty(shape, dtype=dtype, device=verts.device)
-    idx = torch.empty(shape, dtype=torch.int32, device=verts.device) if want_index else None
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    res, p_dist, p_idx = _dist_outputs((dims[2], dims[1], dims[0]), dtype, want_index, verts.device)
     L.check(L.lib().r2s_mesh_distance_dev(ctypes.c_void_p(verts.data_ptr()), verts.numel() // 3, ctypes.c_void_p(tris.data_ptr()),
                                           tris.numel() // 3, dims, origin, spacing, float(band), int(dtype == torch.float32),
-                                          ctypes.c_void_p(dist.data_ptr()), ctypes.c_void_p(idx.data_ptr()) if want_index else None,
-                                          st))
-    return (dist, idx) if want_index else dist
+                                          p_dist, p_idx, _stream(stream)))
+    return res
 
 
 def redistance(values, grid, smooth=None, *, iso=0.0, band, device=-1):
@@ -533,7 +565,7 @@ def redistance_dev(t, grid, smooth=None, *, iso=0.0, band, stream=None):
     if t.numel() != dims[0] * dims[1] * dims[2]:
         raise L.R2SError(f"values length ({t.numel()}) doesn't match the lattice {tuple(dims)}")
     out = torch.empty((dims[2], dims[1], dims[0]), dtype=t.dtype, device=t.device)
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    st = _stream(stream)
     L.check(L.lib().r2s_redistance_dev(ctypes.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), dims, origin, spacing, float(iso),
                                        float(band), ctypes.c_void_p(out.data_ptr()), st))
     return out
@@ -556,13 +588,9 @@ class MeshIndex:
     def __init__(self, verts, tris, device=-1):
         h = ctypes.c_void_p()
         if type(verts).__module__.startswith("torch"):
-            import torch
-            if verts.dtype != torch.float32 or tris.dtype != torch.int32 or not (verts.is_cuda and tris.is_cuda) \
-                    or not (verts.is_contiguous() and tris.is_contiguous()):
-                raise L.R2SError("verts / tris must be contiguous float32 / int32 device tensors")
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _mesh_tensors(verts, tris)
             L.check(L.lib().r2s_mesh_index_build_dev(ctypes.c_void_p(verts.data_ptr()), verts.numel() // 3,
-                                                     ctypes.c_void_p(tris.data_ptr()), tris.numel() // 3, st, ctypes.byref(h)))
+                                                     ctypes.c_void_p(tris.data_ptr()), tris.numel() // 3, _stream(None), ctypes.byref(h)))
         else:
             v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
             t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
@@ -604,69 +632,45 @@ class MeshIndex:
         p = np.ascontiguousarray(points)
         if p.dtype not in (np.float32, np.float64):
             p = p.astype(np.float64)
-        if p.ndim != 2 or p.shape[1] != 3:
-            raise L.R2SError("points must be (n, 3)")
-        dtype = np.dtype(dtype)
-        if dtype not in (np.float32, np.float64):
-            raise L.R2SError("dtype must be float32 or float64")
-        n = len(p)
-        dist = np.empty(n, dtype)
-        idx = np.empty(n, np.int32) if want_index else None
-        L.check(L.lib().r2s_mesh_index_query(self._handle(), p.ctypes.data_as(ctypes.c_void_p), int(p.dtype == np.float32), n,
-                                             int(dtype == np.float32), dist.ctypes.data_as(ctypes.c_void_p),
-                                             idx.ctypes.data_as(L.c_int32_p) if want_index else None))
-        return (dist, idx) if want_index else dist
+        _points_nx3("points must be (n, 3)", p)
+        dtype = _float_dtype(dtype, np)
+        res, p_dist, p_idx = _dist_outputs(len(p), dtype, want_index)
+        L.check(L.lib().r2s_mesh_index_query(self._handle(), p.ctypes.data_as(ctypes.c_void_p), int(p.dtype == np.float32), len(p),
+                                             int(dtype == np.float32), p_dist, p_idx))
+        return res
 
     def distance_dev(self, t, want_index=False, dtype=None, stream=None):
         """distance on a torch tensor of points on the index's device ((n, 3) float32 / float64, contiguous) -> device
         tensor(s); enqueued on the current stream (or `stream`)"""
         import torch
-        if t.dtype not in (torch.float32, torch.float64) or not t.is_contiguous() or not t.is_cuda or t.dim() != 2 or t.shape[1] != 3:
-            raise L.R2SError("points must be a contiguous float32 / float64 (n, 3) device tensor")
-        dtype = dtype or torch.float64
-        if dtype not in (torch.float32, torch.float64):
-            raise L.R2SError("dtype must be float32 or float64")
+        _points_nx3("points must be a contiguous float32 / float64 (n, 3) device tensor", t)
+        dtype = _float_dtype(dtype, torch)
         n = t.shape[0]
-        dist = torch.empty(n, dtype=dtype, device=t.device)
-        idx = torch.empty(n, dtype=torch.int32, device=t.device) if want_index else None
-        st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        res, p_dist, p_idx = _dist_outputs(n, dtype, want_index, t.device)
         if n:
             L.check(L.lib().r2s_mesh_index_query_dev(self._handle(), ctypes.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), n,
-                                                     int(dtype == torch.float32), ctypes.c_void_p(dist.data_ptr()),
-                                                     ctypes.c_void_p(idx.data_ptr()) if want_index else None, st))
-        return (dist, idx) if want_index else dist
+                                                     int(dtype == torch.float32), p_dist, p_idx, _stream(stream)))
+        return res
 
     def lattice(self, grid_or_lattice, smooth=None, want_index=False, dtype=np.float64):
         """distance of every lattice point (a Grid with `smooth`, as extract_isosurface, or (dims, origin, spacing)) -> array
         (nz, ny, nx) of `dtype`; want_index=True: also the closest triangle"""
         dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
-        dtype = np.dtype(dtype)
-        if dtype not in (np.float32, np.float64):
-            raise L.R2SError("dtype must be float32 or float64")
-        shape = (dims[2], dims[1], dims[0])
-        dist = np.empty(shape, dtype)
-        idx = np.empty(shape, np.int32) if want_index else None
-        L.check(L.lib().r2s_mesh_index_lattice(self._handle(), dims, origin, spacing, int(dtype == np.float32),
-                                               dist.ctypes.data_as(ctypes.c_void_p),
-                                               idx.ctypes.data_as(L.c_int32_p) if want_index else None))
-        return (dist, idx) if want_index else dist
+        dtype = _float_dtype(dtype, np)
+        res, p_dist, p_idx = _dist_outputs((dims[2], dims[1], dims[0]), dtype, want_index)
+        L.check(L.lib().r2s_mesh_index_lattice(self._handle(), dims, origin, spacing, int(dtype == np.float32), p_dist, p_idx))
+        return res
 
     def lattice_dev(self, grid_or_lattice, smooth=None, want_index=False, dtype=None, stream=None):
         """lattice -> torch tensor(s) on the current device (the index's); enqueued on the current stream (or `stream`)"""
         import torch
-        dtype = dtype or torch.float64
-        if dtype not in (torch.float32, torch.float64):
-            raise L.R2SError("dtype must be float32 or float64")
+        dtype = _float_dtype(dtype, torch)
         dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
-        shape = (dims[2], dims[1], dims[0])
         dev = torch.device("cuda", torch.cuda.current_device())
-        dist = torch.empty(shape, dtype=dtype, device=dev)
-        idx = torch.empty(shape, dtype=torch.int32, device=dev) if want_index else None
-        st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        L.check(L.lib().r2s_mesh_index_lattice_dev(self._handle(), dims, origin, spacing, int(dtype == torch.float32),
-                                                   ctypes.c_void_p(dist.data_ptr()),
-                                                   ctypes.c_void_p(idx.data_ptr()) if want_index else None, st))
-        return (dist, idx) if want_index else dist
+        res, p_dist, p_idx = _dist_outputs((dims[2], dims[1], dims[0]), dtype, want_index, dev)
+        L.check(L.lib().r2s_mesh_index_lattice_dev(self._handle(), dims, origin, spacing, int(dtype == torch.float32), p_dist, p_idx,
+                                                   _stream(stream)))
+        return res
 
     @staticmethod
     def _window(t_min, t_max):
@@ -684,11 +688,8 @@ class MeshIndex:
         o, d = np.ascontiguousarray(origins), np.ascontiguousarray(directions)
         if o.dtype != np.float32 or d.dtype != np.float32:
             o, d = np.ascontiguousarray(o, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
-        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
-            raise L.R2SError("origins and directions must both be (n, 3)")
-        dtype = np.dtype(dtype)
-        if dtype not in (np.float32, np.float64):
-            raise L.R2SError("dtype must be float32 or float64")
+        _points_nx3("origins and directions must both be (n, 3)", o, d, same_shape=True)
+        dtype = _float_dtype(dtype, np)
         t_min, t_max = self._window(t_min, t_max)
         n = len(o)
         t = np.empty(n, dtype)
@@ -707,26 +708,21 @@ class MeshIndex:
         """raycast on torch tensors on the index's device ((n, 3), contiguous, both float32 or both float64) -> device
         tensor(s); enqueued on the current stream (or `stream`)"""
         import torch
-        for a in (origins, directions):
-            if a.dtype not in (torch.float32, torch.float64) or not a.is_contiguous() or not a.is_cuda or a.dim() != 2 or a.shape[1] != 3:
-                raise L.R2SError("origins / directions must be contiguous float32 / float64 (n, 3) device tensors")
+        _points_nx3("origins / directions must be contiguous float32 / float64 (n, 3) device tensors", origins, directions)
         if origins.dtype != directions.dtype or origins.shape != directions.shape or origins.device != directions.device:
             raise L.R2SError("origins and directions must agree in type, shape and device")
-        dtype = dtype or torch.float64
-        if dtype not in (torch.float32, torch.float64):
-            raise L.R2SError("dtype must be float32 or float64")
+        dtype = _float_dtype(dtype, torch)
         t_min, t_max = self._window(t_min, t_max)
         n = origins.shape[0]
         t = torch.empty(n, dtype=dtype, device=origins.device)
         idx = torch.empty(n, dtype=torch.int32, device=origins.device) if want_index else None
         side = torch.empty(n, dtype=torch.int8, device=origins.device) if want_side else None
-        st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
         if n:
             vp = ctypes.c_void_p
             L.check(L.lib().r2s_mesh_index_raycast_dev(self._handle(), vp(origins.data_ptr()), vp(directions.data_ptr()),
                                                        int(origins.dtype == torch.float32), n, t_min, t_max, int(dtype == torch.float32),
                                                        vp(t.data_ptr()), vp(idx.data_ptr()) if want_index else None,
-                                                       vp(side.data_ptr()) if want_side else None, st))
+                                                       vp(side.data_ptr()) if want_side else None, _stream(stream)))
         res = (t,) + ((idx,) if want_index else ()) + ((side,) if want_side else ())
         return res if len(res) > 1 else t
 
@@ -786,9 +782,7 @@ def surface_thickness_dev(verts, tris, normals=None, *, skip, index=None, stream
     normals are summed per vertex in the order of vertex_normals (one conflict-free scatter per incident corner, no
     floating-point atomics), so the result equals surface_thickness."""
     import torch
-    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or not (verts.is_cuda and tris.is_cuda) \
-            or not (verts.is_contiguous() and tris.is_contiguous()):
-        raise L.R2SError("verts / tris must be contiguous float32 / int32 device tensors")
+    _mesh_tensors(verts, tris)
     skip = _skip(skip)
     v = verts.reshape(-1, 3).to(torch.float64)
     nv = v.shape[0]
@@ -851,7 +845,7 @@ def redistance_full_dev(t, grid, smooth=None, *, iso=0.0, stream=None):
     if t.numel() != dims[0] * dims[1] * dims[2]:
         raise L.R2SError(f"values length ({t.numel()}) doesn't match the lattice {tuple(dims)}")
     out = torch.empty((dims[2], dims[1], dims[0]), dtype=t.dtype, device=t.device)
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    st = _stream(stream)
     L.check(L.lib().r2s_redistance_full_dev(ctypes.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), dims, origin, spacing,
                                             float(iso), ctypes.c_void_p(out.data_ptr()), st))
     return out
@@ -977,7 +971,7 @@ class RbfField:
             raise L.R2SError("points must be a contiguous float32 (n, 3) device tensor")
         if t.device.index != torch.cuda.current_device():
             raise L.R2SError(f"points live on {t.device}, the current device is cuda:{torch.cuda.current_device()}")
-        return ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p((torch.cuda.current_stream()).cuda_stream)
+        return ctypes.c_void_p(t.data_ptr()), _stream(None)
 
     def eval_dev(self, t, grad=False, taps=False):
         import torch

@@ -66,8 +66,16 @@ struct DevBuf {
     }
     template <class T>
     T* as() { return reinterpret_cast<T*>(p); }
+    template <class T>
+    const T* as() const { return reinterpret_cast<const T*>(p); }
 };
-
+// a DevBuf that frees itself (on whichever device is current when it dies)
+struct Scoped : DevBuf {
+    Scoped() = default;
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+    ~Scoped() { release(); }
+};
 
 inline int check_device(int device)
 {

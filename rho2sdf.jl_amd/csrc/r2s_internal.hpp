@@ -1,6 +1,6 @@
 // Cross-file internals of the library (C++ linkage, not part of the C ABI): device-pointer forms of the
 // pre-stage and post-processing stages, used by the host-pointer entry points of their own files and by the
-// chained r2s_rho2sdf() in r2s_host.hip.  All of them run on the CURRENT device and are synchronous on return.
+// chained r2s_rho2sdf() in r2s_host.hip, and the seam between r2s_redistance.hip and r2s_mesh_index.hip.  All of them run on the CURRENT device and are synchronous on return.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -115,5 +115,38 @@ void release_iso_work();
 // ---- redistancing (r2s_redistance.hip) --------------------------------------------------------------------------------
 // frees the work buffers the distance calls keep per device; called by r2s_release_cache()
 void release_dist_work();
+
+// ---- mesh index (r2s_mesh_index.hip) and what its entry points share with r2s_redistance.hip -------------------------------
+// the tree of a mesh index and the mesh it refers to (r2s_mesh_index owns all three; redistance_full borrows the mesh)
+struct MiTree {
+    const float* verts = nullptr;
+    const int32_t* tris = nullptr;
+    int64_t n_verts = 0, n_tris = 0;
+    Scoped nodes;
+    int32_t root = 0;
+    int32_t depth = 0;
+    double absmax = 0.0;
+};
+// the tree over the device mesh (verts, tris) on the current device, after the work queued on `st`; synchronous
+int mi_build_tree(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n_tris, hipStream_t st, MiTree& T);
+// enqueues the query of n points (pts != null) or of the lattice (dims != null) on `st`; does not wait
+int mi_query(const MiTree& T, const void* d_pts, bool pts_f32, int64_t n, const int64_t* dims, const double* origin, double spacing,
+             const void* d_field, bool field_f32, double iso, void* d_out, bool out_f32, int32_t* d_closest, hipStream_t st);
+
+// argument checks and mesh handling of both files, defined in r2s_redistance.hip; `who` heads the error text
+int lattice_args(const char* who, const int64_t dims[3], const double origin[3], double spacing, double band);
+int mesh_args(const char* who, const void* verts, int64_t n_verts, const void* tris, int64_t n_tris);
+// every triangle index in [0, n_verts) and every vertex finite: a host mesh, and a device mesh (flag: one int32 the call may
+// grow; synchronises `st`)
+int check_mesh_host(const char* who, const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris);
+int check_mesh_dev(const char* who, const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n_tris, DevBuf& flag,
+                   hipStream_t st);
+inline size_t real_bytes(int32_t is_float32) { return is_float32 ? sizeof(float) : sizeof(double); }
+inline size_t vert_bytes(int64_t n_verts) { return 3 * sizeof(float) * (size_t)n_verts; }
+inline size_t tri_bytes(int64_t n_tris) { return 3 * sizeof(int32_t) * (size_t)n_tris; }
+// sizes dv / dt for the mesh (at least one element each) and copies it in: from the host with hipMemcpy, or
+// (from_device) from the current device on `st`
+int upload_mesh(DevBuf& dv, DevBuf& dt, const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, bool from_device,
+                hipStream_t st);
 
 }  // namespace r2s_int

@@ -1,0 +1,108 @@
+// Device-side triangle arithmetic shared by the tile kernel of r2s_redistance.hip and the traversals of r2s_mesh_index.hip:
+// the triangle record and the point-to-triangle distance built on it (the same arithmetic, hence the same numbers wherever
+// both answer), and the typed access to float32 / float64 fields and results.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+constexpr int REC = 40;        // doubles per record
+// record layout (doubles): a 0-2, b 3-5, ab 6-8, ac 9-11, bc 12-14, n 15-17, n x ab 18-20, n x ac 21-23, n x bc 24-26,
+// 1/ab.ab 27, 1/ac.ac 28, 1/bc.bc 29, 1/n.n 30 (0 = the feature is degenerate), AABB lo 31-33, hi 34-36, index 37 (as int64)
+
+struct Vec3 {
+    double x, y, z;
+};
+__device__ __host__ inline Vec3 sub(Vec3 a, Vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __host__ inline double dot(Vec3 a, Vec3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __host__ inline Vec3 cross(Vec3 a, Vec3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+
+// a*b - c*d with at most 1.5 ulp of error (Kahan's difference of products; the explicit fma is kept under -ffp-contract=off)
+__device__ inline double diff_of_products(double a, double b, double c, double d)
+{
+    const double w = c * d;
+    const double e = fma(-c, d, w);
+    const double f = fma(a, b, -w);
+    return f + e;
+}
+// the normal of a triangle must keep its direction when the edges are nearly parallel (slivers): with plain products the
+// cancellation tilts the plane by 2^-53 / aspect, which shows as an error of that times the triangle's length
+__device__ inline Vec3 cross_exact(Vec3 a, Vec3 b)
+{
+    return {diff_of_products(a.y, b.z, a.z, b.y), diff_of_products(a.z, b.x, a.x, b.z), diff_of_products(a.x, b.y, a.y, b.x)};
+}
+
+__device__ inline Vec3 load_vert(const float* __restrict__ v, int32_t i)
+{
+    const float* p = v + 3 * (int64_t)i;
+    return {(double)p[0], (double)p[1], (double)p[2]};
+}
+
+// squared distance from p to the segment u + t e, t in [0, 1]; w = p - u, inv = 1 / e.e (0 for a zero-length segment)
+__device__ inline double seg_d2(Vec3 w, Vec3 e, double inv)
+{
+    double t = dot(w, e) * inv;
+    t = t < 0.0 ? 0.0 : t > 1.0 ? 1.0 : t;
+    const Vec3 q = {w.x - t * e.x, w.y - t * e.y, w.z - t * e.z};
+    return dot(q, q);
+}
+
+// squared distance from p to the triangle of record r (the definition of the header)
+__device__ inline double pair_d2(const double* __restrict__ r, Vec3 p)
+{
+    const Vec3 a = {r[0], r[1], r[2]}, b = {r[3], r[4], r[5]};
+    const Vec3 ab = {r[6], r[7], r[8]}, ac = {r[9], r[10], r[11]}, bc = {r[12], r[13], r[14]};
+    const Vec3 ap = sub(p, a), bp = sub(p, b);
+    double d2 = seg_d2(ap, ab, r[27]);
+    const double d_ac = seg_d2(ap, ac, r[28]);
+    d2 = d_ac < d2 ? d_ac : d2;
+    const double d_bc = seg_d2(bp, bc, r[29]);
+    d2 = d_bc < d2 ? d_bc : d2;
+    const double inv_nn = r[30];
+    if (inv_nn > 0.0) {
+        const Vec3 mab = {r[18], r[19], r[20]}, mac = {r[21], r[22], r[23]}, mbc = {r[24], r[25], r[26]};
+        // edge functions (ab x ap).n, (bc x bp).n, (ca x cp).n as dot products with the in-plane edge normals
+        if (dot(ap, mab) >= 0.0 && dot(bp, mbc) >= 0.0 && -dot(ap, mac) >= 0.0) {
+            const Vec3 n = {r[15], r[16], r[17]};
+            const double s = dot(n, ap);
+            const double dp = s * s * inv_nn;
+            d2 = dp < d2 ? dp : d2;
+        }
+    }
+    return d2;
+}
+
+__device__ inline void build_record(double* __restrict__ r, const float* __restrict__ verts, const int32_t* __restrict__ tris, int32_t t)
+{
+    const Vec3 a = load_vert(verts, tris[3 * (int64_t)t]), b = load_vert(verts, tris[3 * (int64_t)t + 1]),
+               c = load_vert(verts, tris[3 * (int64_t)t + 2]);
+    const Vec3 ab = sub(b, a), ac = sub(c, a), bc = sub(c, b);
+    const Vec3 n = cross_exact(ab, ac);
+    const Vec3 mab = cross(n, ab), mac = cross(n, ac), mbc = cross(n, bc);
+    const double eab = dot(ab, ab), eac = dot(ac, ac), ebc = dot(bc, bc), nn = dot(n, n);
+    r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = b.x, r[4] = b.y, r[5] = b.z;
+    r[6] = ab.x, r[7] = ab.y, r[8] = ab.z, r[9] = ac.x, r[10] = ac.y, r[11] = ac.z, r[12] = bc.x, r[13] = bc.y, r[14] = bc.z;
+    r[15] = n.x, r[16] = n.y, r[17] = n.z;
+    r[18] = mab.x, r[19] = mab.y, r[20] = mab.z, r[21] = mac.x, r[22] = mac.y, r[23] = mac.z, r[24] = mbc.x, r[25] = mbc.y, r[26] = mbc.z;
+    r[27] = eab > 0.0 ? 1.0 / eab : 0.0;
+    r[28] = eac > 0.0 ? 1.0 / eac : 0.0;
+    r[29] = ebc > 0.0 ? 1.0 / ebc : 0.0;
+    const double inn = nn > 0.0 ? 1.0 / nn : 0.0;
+    r[30] = isfinite(inn) ? inn : 0.0;   // (n.n underflowed: the plane term is not counted, the segments cover the triangle)
+    r[31] = fmin(a.x, fmin(b.x, c.x)), r[32] = fmin(a.y, fmin(b.y, c.y)), r[33] = fmin(a.z, fmin(b.z, c.z));
+    r[34] = fmax(a.x, fmax(b.x, c.x)), r[35] = fmax(a.y, fmax(b.y, c.y)), r[36] = fmax(a.z, fmax(b.z, c.z));
+    reinterpret_cast<int64_t*>(r)[37] = (int64_t)t;
+}
+
+// element i of a float32 (f32 != 0) or float64 array, read as / stored from a double
+__device__ inline double load_real(const void* p, int f32, int64_t i)
+{
+    return f32 ? (double)reinterpret_cast<const float*>(p)[i] : reinterpret_cast<const double*>(p)[i];
+}
+__device__ inline void store_real(void* p, int f32, int64_t i, double v)
+{
+    if (f32)
+        reinterpret_cast<float*>(p)[i] = (float)v;
+    else
+        reinterpret_cast<double*>(p)[i] = v;
+}

@@ -7,5 +7,5 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $ROOT/diag
 C=$ROOT/rho2sdf.jl_amd/csrc
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -std=c++17 "$@" -o $ROOT/diag/$NAME.so \
-    $C/rho2sdf_hip.hip $C/r2s_pre.hip $C/r2s_post.hip $C/r2s_io.hip $C/r2s_host.hip -lz
+    $C/*.hip -lz
 echo built diag/$NAME.so
