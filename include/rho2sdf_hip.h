@@ -378,6 +378,23 @@ int r2s_rbf_smooth_dev(const double *d_sdf, const r2s_grid *grid, int32_t is_int
  *           p_a = Float32(p_a - s * g_a) for a = x, y, z (Float64, rounded once);  it = it + 1
  * A non-finite input point has status 3 and stays as it is (resid NaN, iters 0).  resid_out = |f| of the last evaluation,
  * iters_out = steps taken; status_out / resid_out / iters_out may each be NULL.
+ * Hessian (r2s_rbf_field_hessian): candidates, Float32 distance, support test, knn cap, exp and weights are those of the
+ * evaluation with gradient, and value, gradient and taps are its numbers bit for bit.  With the same Float32 differences
+ * d = p - x_j and k_j = exp(-(dist/sigma)^2):
+ *     H_ab = sum_j w_j k_j (4 d_a d_b / sigma^4 - 2 delta_ab / sigma^2)
+ * as H_aa = 4/sigma^4 s_aa - 2/sigma^2 s and H_ab = 4/sigma^4 s_ab, where s_ab = sum_j w_j k_j d_a d_b and s (the value's
+ * own sum) are Float64 sums in the evaluation's fixed order; Float64 throughout, each component rounded to Float32 once.
+ * hess_out[n][6] = xx, yy, zz, xy, xz, yz.  A non-finite coordinate: value, gradient and Hessian NaN, taps 0.  No node in
+ * reach: value th, gradient 0, Hessian 0.
+ * Curvature (r2s_rbf_field_curvature) of the level set through p, oriented by the normal n = -g / |g| (a convex solid has
+ * positive mean curvature), in Float64 from the Float32 gradient g and Hessian H of the call above:
+ *     g2    = gx*gx + gy*gy + gz*gz
+ *     mean  = -(g2 (Hxx + Hyy + Hzz) - g^T H g) / (2 g2 sqrt(g2))
+ *     gauss = (g^T adj(H) g) / (g2 g2)                    adj(H): the symmetric matrix of cofactors
+ *     disc  = max(mean*mean - gauss, 0);  k1 = mean + sqrt(disc);  k2 = mean - sqrt(disc)
+ * curv_out[n][4] = mean, gauss, k1, k2, each rounded to Float32 once (k1, k2 are formed from the Float64 mean and gauss).
+ * All four are NaN where g2 is 0 or not finite: non-finite points, points with no node in reach, critical points of f.
+ * grad_out / hess_out of the curvature call are the g and H it used.
  *
  * Errors: NULL field / points, negative n, max_iter < 0, tol < 0 or NaN, a threshold outside
  * [R2S_RBF_MIN_KERNEL_THRESHOLD, 1), a grid whose aabb_max is not aabb_min + N * cell_size (to 1e-3 of a cell; grids of
@@ -407,6 +424,16 @@ int r2s_rbf_field_eval_dev(const r2s_rbf_field *f, const float *d_points, int64_
 /* normals_out[n][3] */
 int r2s_rbf_field_normals(const r2s_rbf_field *f, const float *points, int64_t n, float *normals_out);
 int r2s_rbf_field_normals_dev(const r2s_rbf_field *f, const float *d_points, int64_t n, float *d_normals, void *stream);
+/* hess_out[n][6] Float32; any output may be NULL (without hess_out this is r2s_rbf_field_eval) */
+int r2s_rbf_field_hessian(const r2s_rbf_field *f, const float *points, int64_t n, float *val_out, float *grad_out,
+                          float *hess_out, int32_t *taps_out);
+int r2s_rbf_field_hessian_dev(const r2s_rbf_field *f, const float *d_points, int64_t n, float *d_val, float *d_grad,
+                              float *d_hess, int32_t *d_taps, void *stream);
+/* curv_out[n][4] Float32 is required (NULL: R2S_ERR_ARG); grad_out / hess_out may be NULL */
+int r2s_rbf_field_curvature(const r2s_rbf_field *f, const float *points, int64_t n, float *curv_out, float *grad_out,
+                            float *hess_out);
+int r2s_rbf_field_curvature_dev(const r2s_rbf_field *f, const float *d_points, int64_t n, float *d_curv, float *d_grad,
+                                float *d_hess, void *stream);
 /* points_inout[n][3] are moved in place */
 int r2s_rbf_field_project(const r2s_rbf_field *f, float *points_inout, int64_t n, int32_t max_iter, float tol,
                           int32_t *status_out, float *resid_out, int32_t *iters_out);

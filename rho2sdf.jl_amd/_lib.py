@@ -160,6 +160,10 @@ SYMBOLS = [
     ("r2s_rbf_field_destroy", None, [_P]),
     ("r2s_rbf_field_eval", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, c_float_p, c_float_p, c_int32_p]),
     ("r2s_rbf_field_eval_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, _P]),
+    ("r2s_rbf_field_hessian", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, c_float_p, c_float_p, c_float_p, c_int32_p]),
+    ("r2s_rbf_field_hessian_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    ("r2s_rbf_field_curvature", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, c_float_p, c_float_p, c_float_p]),
+    ("r2s_rbf_field_curvature_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, _P]),
     ("r2s_rbf_field_normals", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, c_float_p]),
     ("r2s_rbf_field_normals_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P]),
     ("r2s_rbf_field_project", ctypes.c_int, [_P, c_float_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, c_int32_p,

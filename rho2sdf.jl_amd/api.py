@@ -874,7 +874,7 @@ def surface_deviation(verts_a, tris_a, verts_b, tris_b, *, device=-1):
 
 class RbfField:
     """The smoothed level-set of one RBFs_smoothing as a function (include/rho2sdf_hip.h, r2s_rbf_field): the weights and
-    the level shift stay on the device; `eval`, `normals` and `project` take any (n, 3) array of points.  A context manager;
+    the level shift stay on the device; `eval`, `normals`, `curvature` and `project` take any (n, 3) array of points.  A context manager;
     `close()` frees the device memory.  Build one with fit_rbf_field, or from given weights ((nz, ny, nx) float32)."""
 
     def __init__(self, weights, grid, level_shift=0.0, threshold=1e-3, *, device=-1, _handle=None):
@@ -931,18 +931,33 @@ class RbfField:
             raise L.R2SError("points must be (n, 3)")
         return p
 
-    def eval(self, points, grad=False, taps=False):
-        """f(points) incl. the level shift -> val (n,) float32; grad=True: (val, grad (n, 3)); taps=True: the number of
-        nodes that took part is appended (negative where the knn cap bound)"""
+    def eval(self, points, grad=False, hess=False, taps=False):
+        """f(points) incl. the level shift -> val (n,) float32; grad=True: (val, grad (n, 3)); hess=True: (val, grad, hess
+        (n, 6) = xx, yy, zz, xy, xz, yz), the gradient included; taps=True: the number of nodes that took part is appended
+        (negative where the knn cap bound)"""
         p = self._points(points)
         n = len(p)
+        grad = grad or hess
         val = np.empty(n, np.float32)
         g = np.empty((n, 3), np.float32) if grad else None
+        h = np.empty((n, 6), np.float32) if hess else None
         t = np.empty(n, np.int32) if taps else None
-        L.check(L.lib().r2s_rbf_field_eval(self._handle(), _f(p), n, _f(val), _f(g) if grad else None,
-                                           t.ctypes.data_as(L.c_int32_p) if taps else None))
-        out = (val,) + ((g,) if grad else ()) + ((t,) if taps else ())
+        tp = t.ctypes.data_as(L.c_int32_p) if taps else None
+        if hess:
+            L.check(L.lib().r2s_rbf_field_hessian(self._handle(), _f(p), n, _f(val), _f(g), _f(h), tp))
+        else:
+            L.check(L.lib().r2s_rbf_field_eval(self._handle(), _f(p), n, _f(val), _f(g) if grad else None, tp))
+        out = (val,) + ((g,) if grad else ()) + ((h,) if hess else ()) + ((t,) if taps else ())
         return out[0] if len(out) == 1 else out
+
+    def curvature(self, points):
+        """curvatures of the level set of f through each point, oriented by the outward normal -grad f / |grad f| (a convex
+        solid has positive mean curvature) -> (mean, gauss, k1, k2), (n,) float32 each, k1 >= k2; NaN where the gradient
+        vanishes or is not finite"""
+        p = self._points(points)
+        c = np.empty((len(p), 4), np.float32)
+        L.check(L.lib().r2s_rbf_field_curvature(self._handle(), _f(p), len(p), _f(c), None, None))
+        return tuple(np.ascontiguousarray(c[:, k]) for k in range(4))
 
     def normals(self, points):
         """outward unit normals -grad f / |grad f| -> (n, 3) float32; (0,0,0) where the gradient vanishes or is not finite"""
@@ -984,6 +999,29 @@ class RbfField:
         L.check(L.lib().r2s_rbf_field_eval_dev(self._handle(), p, n, ptr(val), ptr(g), ptr(k), st))
         out = (val,) + ((g,) if grad else ()) + ((k,) if taps else ())
         return out[0] if len(out) == 1 else out
+
+    def hessian_dev(self, t, taps=False):
+        """-> (val (n,), grad (n, 3), hess (n, 6)) float32 tensors; taps=True appends the int32 tap counts"""
+        import torch
+        p, st = self._dev_points(t)
+        n = t.shape[0]
+        val = torch.empty(n, dtype=torch.float32, device=t.device)
+        g = torch.empty((n, 3), dtype=torch.float32, device=t.device)
+        h = torch.empty((n, 6), dtype=torch.float32, device=t.device)
+        k = torch.empty(n, dtype=torch.int32, device=t.device) if taps else None
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None and n else None   # noqa: E731
+        L.check(L.lib().r2s_rbf_field_hessian_dev(self._handle(), p, n, ptr(val), ptr(g), ptr(h), ptr(k), st))
+        return (val, g, h) + ((k,) if taps else ())
+
+    def curvature_dev(self, t):
+        """-> (n, 4) float32 tensor: mean, gauss, k1, k2"""
+        import torch
+        p, st = self._dev_points(t)
+        n = t.shape[0]
+        c = torch.empty((n, 4), dtype=torch.float32, device=t.device)
+        if n:
+            L.check(L.lib().r2s_rbf_field_curvature_dev(self._handle(), p, n, ctypes.c_void_p(c.data_ptr()), None, None, st))
+        return c
 
     def normals_dev(self, t):
         import torch
@@ -1028,6 +1066,21 @@ def refine_surface(field, verts, max_iter=8, tol=None):
     there -> (verts (n, 3) float32, normals (n, 3) float32, status (n,) int32); the triangle list stays valid"""
     p, status, _, _ = field.project(verts, max_iter=max_iter, tol=tol)
     return p, field.normals(p), status
+
+
+def surface_curvature(field, verts):
+    """Curvature of the smoothed surface at given vertices, typically those of refine_surface(field, verts) -> {"mean",
+    "gauss", "k1", "k2": (n,) float32 (RbfField.curvature); "min_radius": (n,) float64, 1 / max(|k1|, |k2|), the smallest
+    radius of curvature (inf where both are 0, NaN where the curvature is NaN); "n_undefined": vertices with NaN curvature;
+    "min_radius_p01", "min_radius_p50": the 1 % and 50 % quantiles of min_radius over its finite entries (NaN without any)}"""
+    mean, gauss, k1, k2 = field.curvature(verts)
+    kmax = np.maximum(np.abs(k1), np.abs(k2)).astype(np.float64)
+    with np.errstate(divide="ignore"):
+        radius = 1.0 / kmax
+    fin = radius[np.isfinite(radius)]
+    p01, p50 = (float(q) for q in np.quantile(fin, [0.01, 0.5])) if fin.size else (float("nan"), float("nan"))
+    return dict(mean=mean, gauss=gauss, k1=k1, k2=k2, min_radius=radius, n_undefined=int(np.isnan(mean).sum()),
+                min_radius_p01=p01, min_radius_p50=p50)
 
 
 def export_stl(filename, verts, tris):

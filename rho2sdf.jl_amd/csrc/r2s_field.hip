@@ -13,7 +13,7 @@
 //   - knn cap: the list's length is the number of in-bounds nodes inside the support.  Only when it exceeds 124 (never at
 //     1e-3) each entry is ranked against the others by (distance, node index) and the 124 smallest take part.
 //   - pass 2: the lanes stride over the list: weight gather, exp, Float64 partial sums of the value and of the three gradient
-//     components; a fixed xor butterfly over the 16 lanes adds them.  The order of summation is a function of the point and
+//     components (second-derivative modes: also of the six products d_a d_b); a fixed xor butterfly over the 16 lanes adds them.  The order of summation is a function of the point and
 //     the lattice alone: no atomics, nothing depends on the point's place in the array or on the launch.
 // No host work per point, no synchronisation besides one workgroup barrier (the exp table), no LDS traffic between points.
 #include <hip/hip_runtime.h>
@@ -51,7 +51,7 @@ struct FieldGeom {
     int cap;                     // list entries per point (>= any support's node count)
 };
 
-enum { FIELD_VALUE = 0, FIELD_GRAD = 1, FIELD_NORMALS = 2, FIELD_PROJECT = 3 };
+enum { FIELD_VALUE = 0, FIELD_GRAD = 1, FIELD_NORMALS = 2, FIELD_PROJECT = 3, FIELD_HESS = 4, FIELD_CURV = 5 };
 
 struct FieldOut {
     float* val;       // [n]
@@ -63,13 +63,17 @@ struct FieldOut {
     int32_t* iters;
     int max_iter;
     float tol;
+    float* hess;      // FIELD_HESS / FIELD_CURV: [n][6] = xx, yy, zz, xy, xz, yz
+    float* curv;      // FIELD_CURV: [n][4] = mean, gauss, k1, k2
 };
 
-// value (with the level shift), gradient and tap count at one finite point, by the 16 lanes of its sub-group; every lane
-// returns the same numbers
-template <bool GRAD>
+// value (with the level shift), derivatives up to order ORD (1: gradient, 2: gradient and Hessian xx, yy, zz, xy, xz, yz)
+// and tap count at one finite point, by the 16 lanes of its sub-group; every lane returns the same numbers.  `h` is
+// touched for ORD == 2 only.
+template <int ORD>
 __device__ __forceinline__ void field_point(const FieldGeom& G, uint2* __restrict__ list, const double* __restrict__ etab, int l,
-                                            int sg_shift, float px, float py, float pz, float& val, float g[3], int& taps)
+                                            int sg_shift, float px, float py, float pz, float& val, float g[3], int& taps,
+                                            float* h = nullptr)
 {
     __threadfence_block();   // (projection: the previous step's reads of the list come first)
     const double q[3] = {((double)px - G.amin[0]) * G.inv_h, ((double)py - G.amin[1]) * G.inv_h, ((double)pz - G.amin[2]) * G.inv_h};
@@ -107,6 +111,7 @@ __device__ __forceinline__ void field_point(const FieldGeom& G, uint2* __restric
     __threadfence_block();
     const bool capped = cnt > FIELD_KNN;
     double sv = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    double sxx = 0.0, syy = 0.0, szz = 0.0, sxy = 0.0, sxz = 0.0, syz = 0.0;   // ORD == 2: sums of wk d_a d_b
     for (int e = l; e < cnt; e += FIELD_SG) {
         const uint2 en = list[e];
         const float dist = __uint_as_float(en.x);
@@ -125,27 +130,53 @@ __device__ __forceinline__ void field_point(const FieldGeom& G, uint2* __restric
             const double u = (double)dist * G.inv_sigma;
             const double wk = (double)G.w[((int64_t)ck * G.ny + cj) * G.nx + ci] * exp_neg_fast(u * u, etab);
             sv += wk;
-            if (GRAD) {
+            if (ORD >= 1) {
                 const float dx = px - G.cx[ci], dy = py - G.cy[cj], dz = pz - G.cz[ck];
-                sx += wk * (double)dx;
-                sy += wk * (double)dy;
-                sz += wk * (double)dz;
+                const double tx = wk * (double)dx, ty = wk * (double)dy, tz = wk * (double)dz;
+                sx += tx;
+                sy += ty;
+                sz += tz;
+                if (ORD >= 2) {
+                    sxx += tx * (double)dx;
+                    syy += ty * (double)dy;
+                    szz += tz * (double)dz;
+                    sxy += tx * (double)dy;
+                    sxz += tx * (double)dz;
+                    syz += ty * (double)dz;
+                }
             }
         }
     }
 #pragma unroll
     for (int m = FIELD_SG / 2; m >= 1; m >>= 1) {
         sv += __shfl_xor(sv, m, FIELD_SG);
-        if (GRAD) {
+        if (ORD >= 1) {
             sx += __shfl_xor(sx, m, FIELD_SG);
             sy += __shfl_xor(sy, m, FIELD_SG);
             sz += __shfl_xor(sz, m, FIELD_SG);
+        }
+        if (ORD >= 2) {
+            sxx += __shfl_xor(sxx, m, FIELD_SG);
+            syy += __shfl_xor(syy, m, FIELD_SG);
+            szz += __shfl_xor(szz, m, FIELD_SG);
+            sxy += __shfl_xor(sxy, m, FIELD_SG);
+            sxz += __shfl_xor(sxz, m, FIELD_SG);
+            syz += __shfl_xor(syz, m, FIELD_SG);
         }
     }
     val = (float)sv + G.th;
     g[0] = (float)(sx * G.gscale);
     g[1] = (float)(sy * G.gscale);
     g[2] = (float)(sz * G.gscale);
+    if (ORD >= 2) {   // H_ab = 4 / sigma^4 s_ab - 2 / sigma^2 delta_ab sv: the delta term is the value's own sum
+        const double hs = G.gscale * G.gscale, dg = G.gscale * sv;
+        h[0] = (float)(hs * sxx + dg);
+        h[1] = (float)(hs * syy + dg);
+        h[2] = (float)(hs * szz + dg);
+        h[3] = (float)(hs * sxy);
+        h[4] = (float)(hs * sxz);
+        h[5] = (float)(hs * syz);
+    }
     taps = overflow ? INT32_MIN : capped ? -FIELD_KNN : cnt;
 }
 
@@ -168,7 +199,7 @@ __global__ void __launch_bounds__(256) rbf_field_kernel(FieldGeom G, const float
     float val = fnan, g[3] = {fnan, fnan, fnan};
     int taps = 0;
     if (MODE == FIELD_VALUE || MODE == FIELD_GRAD) {
-        if (finite) field_point<MODE == FIELD_GRAD>(G, list, etab, l, sg_shift, px, py, pz, val, g, taps);
+        if (finite) field_point<MODE == FIELD_GRAD ? 1 : 0>(G, list, etab, l, sg_shift, px, py, pz, val, g, taps);
         if (l == 0) {
             if (O.val) O.val[t] = val;
             if (MODE == FIELD_GRAD && O.grad) { O.grad[3 * t] = g[0]; O.grad[3 * t + 1] = g[1]; O.grad[3 * t + 2] = g[2]; }
@@ -177,7 +208,7 @@ __global__ void __launch_bounds__(256) rbf_field_kernel(FieldGeom G, const float
     } else if (MODE == FIELD_NORMALS) {
         float nv[3] = {0.0f, 0.0f, 0.0f};
         if (finite) {
-            field_point<true>(G, list, etab, l, sg_shift, px, py, pz, val, g, taps);
+            field_point<1>(G, list, etab, l, sg_shift, px, py, pz, val, g, taps);
             const double g2 = (double)g[0] * g[0] + (double)g[1] * g[1] + (double)g[2] * g[2];
             if (g2 > 0.0 && isfinite(g2)) {
                 const double len = sqrt(g2);
@@ -185,11 +216,46 @@ __global__ void __launch_bounds__(256) rbf_field_kernel(FieldGeom G, const float
             }
         }
         if (l == 0) { O.grad[3 * t] = nv[0]; O.grad[3 * t + 1] = nv[1]; O.grad[3 * t + 2] = nv[2]; }
+    } else if (MODE == FIELD_HESS || MODE == FIELD_CURV) {
+        float h[6] = {fnan, fnan, fnan, fnan, fnan, fnan};
+        if (finite) field_point<2>(G, list, etab, l, sg_shift, px, py, pz, val, g, taps, h);
+        float cv[4] = {fnan, fnan, fnan, fnan};
+        if (MODE == FIELD_CURV && finite) {
+            // curvatures of the level set through p with the normal -g / |g|, in Float64 from the Float32 g and H above
+            const double gx = g[0], gy = g[1], gz = g[2];
+            const double hxx = h[0], hyy = h[1], hzz = h[2], hxy = h[3], hxz = h[4], hyz = h[5];
+            const double g2 = gx * gx + gy * gy + gz * gz;
+            if (g2 > 0.0 && isfinite(g2)) {
+                const double ghg = gx * (hxx * gx + hxy * gy + hxz * gz) + gy * (hxy * gx + hyy * gy + hyz * gz) +
+                                   gz * (hxz * gx + hyz * gy + hzz * gz);
+                const double axx = hyy * hzz - hyz * hyz, ayy = hxx * hzz - hxz * hxz, azz = hxx * hyy - hxy * hxy;
+                const double axy = hxz * hyz - hxy * hzz, axz = hxy * hyz - hxz * hyy, ayz = hxy * hxz - hxx * hyz;
+                const double gag = gx * (axx * gx + axy * gy + axz * gz) + gy * (axy * gx + ayy * gy + ayz * gz) +
+                                   gz * (axz * gx + ayz * gy + azz * gz);
+                const double mean = -(g2 * (hxx + hyy + hzz) - ghg) / (2.0 * g2 * sqrt(g2));
+                const double gauss = gag / (g2 * g2);
+                const double root = sqrt(fmax(mean * mean - gauss, 0.0));
+                cv[0] = (float)mean; cv[1] = (float)gauss; cv[2] = (float)(mean + root); cv[3] = (float)(mean - root);
+            }
+        }
+        if (l == 0) {
+            if (O.val) O.val[t] = val;
+            if (O.grad) { O.grad[3 * t] = g[0]; O.grad[3 * t + 1] = g[1]; O.grad[3 * t + 2] = g[2]; }
+            if (O.hess) {
+#pragma unroll
+                for (int a = 0; a < 6; ++a) O.hess[6 * t + a] = h[a];
+            }
+            if (O.taps) O.taps[t] = taps;
+            if (MODE == FIELD_CURV) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a) O.curv[4 * t + a] = cv[a];
+            }
+        }
     } else {
         int status = 3, it = 0;
         if (finite) {
             for (;;) {
-                field_point<true>(G, list, etab, l, sg_shift, px, py, pz, val, g, taps);
+                field_point<1>(G, list, etab, l, sg_shift, px, py, pz, val, g, taps);
                 if (fabsf(val) <= O.tol) { status = 0; break; }
                 if (it >= O.max_iter) { status = 1; break; }
                 const double g2 = (double)g[0] * g[0] + (double)g[1] * g[1] + (double)g[2] * g[2];
@@ -342,6 +408,24 @@ int eval_dev(const r2s_rbf_field* f, const float* d_points, int64_t n, float* d_
     return d_grad ? field_launch<FIELD_GRAD>(f, d_points, n, O, st) : field_launch<FIELD_VALUE>(f, d_points, n, O, st);
 }
 
+int hessian_dev(const r2s_rbf_field* f, const float* d_points, int64_t n, float* d_val, float* d_grad, float* d_hess, int32_t* d_taps,
+                hipStream_t st)
+{
+    if (!d_hess) return eval_dev(f, d_points, n, d_val, d_grad, d_taps, st);   // (the same numbers from the cheaper kernel)
+    FieldOut O;
+    memset(&O, 0, sizeof O);
+    O.val = d_val; O.grad = d_grad; O.hess = d_hess; O.taps = d_taps;
+    return field_launch<FIELD_HESS>(f, d_points, n, O, st);
+}
+
+int curvature_dev(const r2s_rbf_field* f, const float* d_points, int64_t n, float* d_curv, float* d_grad, float* d_hess, hipStream_t st)
+{
+    FieldOut O;
+    memset(&O, 0, sizeof O);
+    O.curv = d_curv; O.grad = d_grad; O.hess = d_hess;
+    return field_launch<FIELD_CURV>(f, d_points, n, O, st);
+}
+
 int normals_dev(const r2s_rbf_field* f, const float* d_points, int64_t n, float* d_normals, hipStream_t st)
 {
     FieldOut O;
@@ -473,6 +557,68 @@ int r2s_rbf_field_eval(const r2s_rbf_field* f, const float* points, int64_t n, f
     if (!rc) rc = io.down(1, val_out, 4 * N);
     if (!rc) rc = io.down(2, grad_out, 12 * N);
     if (!rc) rc = io.down(3, taps_out, 4 * N);
+    io.release();
+    return rc;
+}
+
+int r2s_rbf_field_hessian_dev(const r2s_rbf_field* f, const float* d_points, int64_t n, float* d_val, float* d_grad, float* d_hess,
+                              int32_t* d_taps, void* stream)
+{
+    int rc = points_args(f, d_points, n);
+    if (rc || n == 0 || (rc = field_on_current(f))) return rc;
+    return hessian_dev(f, d_points, n, d_val, d_grad, d_hess, d_taps, (hipStream_t)stream);
+}
+
+int r2s_rbf_field_hessian(const r2s_rbf_field* f, const float* points, int64_t n, float* val_out, float* grad_out, float* hess_out,
+                          int32_t* taps_out)
+{
+    int rc = points_args(f, points, n);
+    if (rc || n == 0 || (!val_out && !grad_out && !hess_out && !taps_out)) return rc;
+    HIP_TRY(hipSetDevice(f->device));
+    HostIo io;
+    const size_t N = (size_t)n;
+    rc = io.up(0, points, 12 * N);
+    if (!rc && val_out) rc = io.up(1, nullptr, 4 * N);
+    if (!rc && grad_out) rc = io.up(2, nullptr, 12 * N);
+    if (!rc && taps_out) rc = io.up(3, nullptr, 4 * N);
+    if (!rc && hess_out) rc = io.up(4, nullptr, 24 * N);
+    if (!rc) rc = hessian_dev(f, io.b[0].as<float>(), n, val_out ? io.b[1].as<float>() : nullptr, grad_out ? io.b[2].as<float>() : nullptr,
+                              hess_out ? io.b[4].as<float>() : nullptr, taps_out ? io.b[3].as<int32_t>() : nullptr, nullptr);
+    if (!rc) rc = io.down(1, val_out, 4 * N);
+    if (!rc) rc = io.down(2, grad_out, 12 * N);
+    if (!rc) rc = io.down(3, taps_out, 4 * N);
+    if (!rc) rc = io.down(4, hess_out, 24 * N);
+    io.release();
+    return rc;
+}
+
+int r2s_rbf_field_curvature_dev(const r2s_rbf_field* f, const float* d_points, int64_t n, float* d_curv, float* d_grad, float* d_hess,
+                                void* stream)
+{
+    int rc = points_args(f, d_points, n);
+    if (rc || n == 0) return rc;
+    if (!d_curv) return fail(R2S_ERR_ARG, "null curvature output");
+    if ((rc = field_on_current(f))) return rc;
+    return curvature_dev(f, d_points, n, d_curv, d_grad, d_hess, (hipStream_t)stream);
+}
+
+int r2s_rbf_field_curvature(const r2s_rbf_field* f, const float* points, int64_t n, float* curv_out, float* grad_out, float* hess_out)
+{
+    int rc = points_args(f, points, n);
+    if (rc || n == 0) return rc;
+    if (!curv_out) return fail(R2S_ERR_ARG, "null curvature output");
+    HIP_TRY(hipSetDevice(f->device));
+    HostIo io;
+    const size_t N = (size_t)n;
+    rc = io.up(0, points, 12 * N);
+    if (!rc) rc = io.up(1, nullptr, 16 * N);
+    if (!rc && grad_out) rc = io.up(2, nullptr, 12 * N);
+    if (!rc && hess_out) rc = io.up(3, nullptr, 24 * N);
+    if (!rc) rc = curvature_dev(f, io.b[0].as<float>(), n, io.b[1].as<float>(), grad_out ? io.b[2].as<float>() : nullptr,
+                                hess_out ? io.b[3].as<float>() : nullptr, nullptr);
+    if (!rc) rc = io.down(1, curv_out, 16 * N);
+    if (!rc) rc = io.down(2, grad_out, 12 * N);
+    if (!rc) rc = io.down(3, hess_out, 24 * N);
     io.release();
     return rc;
 }

@@ -553,6 +553,46 @@ function rbf_field_eval_hip(f::RbfField, points::Matrix{Float32})
     return val, grad, taps
 end
 
+# -> (val, grad 3 x n, hess 6 x n = xx, yy, zz, xy, xz, yz per point, taps): the evaluation with its second derivatives
+function rbf_field_hessian_hip(f::RbfField, points::Matrix{Float32})
+    size(points, 1) == 3 || error("points must be 3 x n")
+    n = size(points, 2)
+    val = Vector{Float32}(undef, n); grad = Matrix{Float32}(undef, 3, n); hess = Matrix{Float32}(undef, 6, n)
+    taps = Vector{Int32}(undef, n)
+    check(ccall((:r2s_rbf_field_hessian, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}),
+                f.handle, points, n, val, grad, hess, taps))
+    return val, grad, hess, taps
+end
+
+# -> curv 4 x n = mean, gauss, k1, k2 per point (normal -grad / |grad|: a convex solid has positive mean curvature; NaN where
+# the gradient vanishes), with the gradient and Hessian they were formed from
+function rbf_field_curvature_hip(f::RbfField, points::Matrix{Float32})
+    size(points, 1) == 3 || error("points must be 3 x n")
+    n = size(points, 2)
+    curv = Matrix{Float32}(undef, 4, n); grad = Matrix{Float32}(undef, 3, n); hess = Matrix{Float32}(undef, 6, n)
+    check(ccall((:r2s_rbf_field_curvature, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                f.handle, points, n, curv, grad, hess))
+    return curv, grad, hess
+end
+
+# device-pointer variants: pointers on the field's device (the current one), enqueued on `stream`, no wait; C_NULL = not wanted
+function rbf_field_hessian_dev_hip(f::RbfField, d_points::Ptr{Float32}, n::Integer, d_val::Ptr{Float32}, d_grad::Ptr{Float32},
+                                   d_hess::Ptr{Float32}, d_taps::Ptr{Int32}; stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:r2s_rbf_field_hessian_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{Cvoid}),
+                f.handle, d_points, Int64(n), d_val, d_grad, d_hess, d_taps, stream))
+end
+
+function rbf_field_curvature_dev_hip(f::RbfField, d_points::Ptr{Float32}, n::Integer, d_curv::Ptr{Float32},
+                                     d_grad::Ptr{Float32} = Ptr{Float32}(C_NULL), d_hess::Ptr{Float32} = Ptr{Float32}(C_NULL);
+                                     stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:r2s_rbf_field_curvature_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+                f.handle, d_points, Int64(n), d_curv, d_grad, d_hess, stream))
+end
+
 function rbf_field_normals_hip(f::RbfField, points::Matrix{Float32})
     size(points, 1) == 3 || error("points must be 3 x n")
     normals = similar(points)

@@ -7,15 +7,17 @@ r2s_rbf_field_from_weights - the evaluator's cost does not depend on their value
   a   the 513^3 lattice points (the field's own Float32 axes) in lattice order, value only; its yardstick is the library's
       neighbour-by-neighbour lattice evaluation rbf_apply_kernel (R2S_RBF_APPLY=fly) on the same lattice: `--cases fly`
       runs it (approximation mode, smooth = 1: its two evaluations are 513^3 targets over the 513^3 lattice each)
-  c   10^7 uniformly random points, value; cg: the same with the gradient
+  c   10^7 uniformly random points, value; cg: the same with the gradient; ch: with gradient and Hessian, timed beside the
+      gradient mode in the same run (ratio recorded)
 On a fitted field (sphere fixture, N_max 160, fit + smooth = 2 + extract_isosurface):
   b   value + gradient at the surface's vertices;  d: their projection (8 steps at most, tol 1e-4 cell)
+  bk  curvature at the surface's vertices, timed beside the gradient mode in the same run (ratio recorded)
 
 Kernel times: run one case under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python
 tools/field_bench.py --cases X --no-json` (a run of its own per case: tracing slows the host, and a and c share a kernel
 name), then `--merge X=DIR ...` adds the per-launch kernel times of those traces to the JSON.
 
-    python tools/field_bench.py [--cases a,c,cg,b,d] [--reps 7] [--merge a=DIR fly=DIR ...]
+    python tools/field_bench.py [--cases a,c,cg,ch,b,d,bk] [--update] [--reps 7] [--merge a=DIR fly=DIR ...]
 """
 import argparse
 import json
@@ -70,9 +72,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--cases", default="a,c,cg,b,d")
+    ap.add_argument("--cases", default="a,c,cg,ch,b,d,bk")
     ap.add_argument("--no-json", action="store_true", help="do not write the result file (runs under the profiler)")
     ap.add_argument("--merge", nargs="*", default=None, metavar="CASE=DIR", help="add the kernel times of rocprofv3 output directories")
+    ap.add_argument("--update", action="store_true", help="add this run's cases and ratios to the existing result file instead of replacing it")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "field_bench.json"))
     a = ap.parse_args()
     if a.merge is not None:
@@ -104,7 +107,7 @@ def main():
                                   taps_per_s=npts * taps_per_point / (med * 1e-3), **extra)
         print(name, json.dumps(res["cases"][name]), flush=True)
 
-    if cases & {"a", "c", "cg", "fly"}:
+    if cases & {"a", "c", "cg", "ch", "fly"}:
         w = (np.sin(ax[0])[None, None, :] * np.cos(ax[1])[None, :, None] + np.sin(ax[1])[None, :, None] * np.cos(ax[2])[:, None, None]
              + np.sin(ax[2])[:, None, None] * np.cos(ax[0])[None, None, :]).astype(np.float32) * np.float32(0.18)
     if "fly" in cases:
@@ -112,7 +115,7 @@ def main():
         for _ in range(3):
             pkg.RBFs_smoothing(w.astype(np.float64).ravel(), grid, False, 1, 0.5, 1e-3, device=0)
         del os.environ["R2S_RBF_APPLY"]
-    if cases & {"a", "c", "cg"}:
+    if cases & {"a", "c", "cg", "ch"}:
         with pkg.RbfField(w, grid, 0.0, 1e-3, device=0) as f:
             amin, amax = grid.AABB_min, grid.AABB_max
             cx, cy, cz = [torch.tensor(_coarse_axis(amin[k], amax[k], d), device=dev) for k, d in enumerate((nx, ny, nz))]
@@ -124,7 +127,7 @@ def main():
                 taps = f.eval_dev(lat[:: max(1, lat.shape[0] // 100000)].contiguous(), taps=True)[1].abs().float().mean().item()
                 record("a_lattice_value", lat.shape[0], taps, _median_ms(lambda: f.eval_dev(lat), a.reps, torch))
                 del lat
-            if cases & {"c", "cg"}:
+            if cases & {"c", "cg", "ch"}:
                 torch.manual_seed(1)
                 rnd = torch.rand((10_000_000, 3), device=dev, dtype=torch.float32)
                 taps = f.eval_dev(rnd[:100000].contiguous(), taps=True)[1].abs().float().mean().item()
@@ -132,8 +135,13 @@ def main():
                     record("c_random_value", rnd.shape[0], taps, _median_ms(lambda: f.eval_dev(rnd), a.reps, torch))
                 if "cg" in cases:
                     record("c_random_value_grad", rnd.shape[0], taps, _median_ms(lambda: f.eval_dev(rnd, grad=True), a.reps, torch))
+                if "ch" in cases:
+                    grad_ms = _median_ms(lambda: f.eval_dev(rnd, grad=True), a.reps, torch)
+                    record("c_random_hessian", rnd.shape[0], taps, _median_ms(lambda: f.hessian_dev(rnd), a.reps, torch),
+                           grad_ms_same_run=grad_ms[0])
+                    res["ratio_hessian_to_grad_random"] = res["cases"]["c_random_hessian"]["ms_median"] / grad_ms[0]
                 del rnd
-    if cases & {"b", "d"}:
+    if cases & {"b", "d", "bk"}:
         d = np.load(os.path.join(ROOT, "tests", "golden", "sphere.npz"))
         X, IEN, rho = d["X"], d["IEN"].astype(np.int64), d["rho"]
         mesh = pkg.Mesh(X, IEN)
@@ -153,10 +161,21 @@ def main():
                 extra.update(status0_share=float((status == 0).float().mean().item()), mean_steps=float(iters.float().mean().item()))
                 record("d_surface_project", verts.shape[0], taps * (1.0 + extra["mean_steps"]),
                        _median_ms(lambda: f.project_dev(verts, 8), a.reps, torch), **extra)
+            if "bk" in cases:
+                grad_ms = _median_ms(lambda: f.eval_dev(verts, grad=True), a.reps, torch)
+                record("b_surface_curvature", verts.shape[0], taps, _median_ms(lambda: f.curvature_dev(verts), a.reps, torch),
+                       grad_ms_same_run=grad_ms[0], **{"lattice": list(sg.dims)})
+                res["ratio_curvature_to_grad_surface"] = res["cases"]["b_surface_curvature"]["ms_median"] / grad_ms[0]
     c = res["cases"]
     if "a_lattice_value" in c and "c_random_value" in c:
         res["ratio_random_to_lattice_per_point"] = (c["c_random_value"]["ms_median"] / c["c_random_value"]["points"]) / (
             c["a_lattice_value"]["ms_median"] / c["a_lattice_value"]["points"])
+    if a.update and os.path.exists(a.out):
+        with open(a.out) as fh:
+            old = json.load(fh)
+        old["cases"].update(res["cases"])
+        old.update({k: v for k, v in res.items() if k.startswith("ratio_")})
+        res = old
     if not a.no_json:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as fh:
