@@ -610,6 +610,64 @@ int r2s_mesh_index_raycast_dev(const r2s_mesh_index *index, const void *d_origin
                                int32_t rays_are_float32, int64_t n, double t_min, double t_max, int32_t out_is_float32,
                                void *d_t_out, int32_t *d_tri_out, int8_t *d_side_out, void *stream);
 
+/* ---- mesh shells: per-shell topology and mass properties ----------------------------------------
+ * What a triangle mesh is: its separate bodies (shells), whether each is closed and consistently oriented, and the area,
+ * volume and moments of each.  verts float32 [n_verts][3], tris int32 [n_tris][3], 0-based, as everywhere else.
+ *   - collapsed triangle: two of its three vertex INDICES are equal.  It takes no part in edges, shells or sums; its
+ *     shell_of_tri is -1; it is counted in the totals.  Coincident coordinates under distinct indices are ordinary input.
+ *   - half-edge: corner c of triangle t runs from i_c to i_((c+1)%3); its undirected key is (min << 32) | max.
+ *   - edge classes: the half-edges of all non-collapsed triangles, grouped by key.  A group of 1: boundary edge; of exactly
+ *     2 in opposite directions: regular; of exactly 2 in the same direction: flipped; of 3 or more: non-manifold.
+ *   - shell: a connected component of the graph on the non-collapsed triangles in which two triangles are adjacent when
+ *     they share an undirected edge of any class (sharing only a vertex does not join them).  Shells are numbered by
+ *     ascending smallest triangle index; shell_of_tri[t] is that number.
+ *   - integer record of a shell, int64[8]: [0] first_tri (its smallest triangle index), [1] n_tris, [2] n_verts (distinct
+ *     vertex indices its triangles reference; a vertex used by two shells counts in both), [3] n_edges (distinct undirected
+ *     edges), [4] n_boundary, [5] n_flipped, [6] n_nonmanifold (edges of that class), [7] 0 (reserved).
+ *   - totals, int64[8]: [0] shells, [1] triangles (n_tris), [2] collapsed triangles, [3] distinct edges, [4] boundary,
+ *     [5] flipped, [6] non-manifold edges, [7] distinct vertex indices referenced by non-collapsed triangles.
+ *   - reference point r: per axis 0.5 * (lo + hi) of the float32 coordinates of ALL n_verts given vertices, lo and hi widened
+ *     to double, the sum and the product each rounded in double; (0, 0, 0) when n_verts == 0.  Returned in ref_point.
+ *   - Float64 record of a shell, double[11]: [0] area, [1] volume, [2..4] first moments x y z about r, [5..10] second moments
+ *     xx yy zz xy xz yz about r: the sums over the shell's triangles (a, b, c) of the terms below.  Every product, sum,
+ *     quotient and square root is rounded on its own (no fma); parentheses give the order:
+ *       A_i = (double)a_i - r_i, likewise B, C (one subtraction each);      S_i = (A_i + B_i) + C_i;
+ *       E = B - A, F = C - A;   N_x = E_y*F_z - E_z*F_y, N_y = E_z*F_x - E_x*F_z, N_z = E_x*F_y - E_y*F_x;
+ *       area  = 0.5 * sqrt((N_x*N_x + N_y*N_y) + N_z*N_z);
+ *       det   = (A_x*(B_y*C_z - B_z*C_y) + A_y*(B_z*C_x - B_x*C_z)) + A_z*(B_x*C_y - B_y*C_x);
+ *       volume = det / 6;       first moment i = (det * S_i) / 24;
+ *       second moment ij = (det * (((A_i*A_j + B_i*B_j) + C_i*C_j) + S_i*S_j)) / 120.
+ *     A closed, outward-oriented shell has a positive volume; a closed shell of negative volume is an enclosed void.
+ *   - summation: no floating-point atomics and no library scan or reduction touch the Float64 sums.  The triangles are sorted
+ *     by shell number with a stable sort (ascending triangle index within a shell); blocks of 256 consecutive sorted
+ *     triangles are summed per shell in a fixed binary tree (round d = 1, 2, .., 128: position p takes position p + d of its
+ *     block when both belong to one shell), then the up to 64 equal runs of a shell's consecutive block partials are summed
+ *     in ascending block order and those run sums in a fixed binary tree.  The order is a fixed function of the triangle
+ *     order of the input: the same input gives the same bits on every call and from both variants.  The sums are NOT
+ *     independent of the triangle order: under a permutation of the triangles the partition, every integer and first_tri
+ *     follow the permutation exactly, the sums only to within (n_tris + K) * 2^-53 * T, T the sum of the absolute values
+ *     of the term's monomials in A, B, C and K the roundings on its longest chain, a product counting the chains of both
+ *     factors (area 8, volume 9, first moments 13, second moments 18; counted in tests/mesh_shells_ref64.py).
+ * r2s_mesh_shells: host arrays, `device` (-1 = current); shell_of_tri_out [n_tris] may be NULL.  *n_shells, ref_point and
+ * totals are always written on success; the two tables become the calling thread's last result, read with
+ * r2s_last_mesh_shells: counts_out [capacity][8], sums_out [capacity][11]; *n_shells is always the full count, the first
+ * min(capacity, n) records are written; the pointers may be NULL only with capacity == 0.
+ * r2s_mesh_shells_dev: device arrays on the current device, read after the work queued on `stream`; d_shell_of_tri [n_tris]
+ * (may be NULL), d_counts [shell_capacity][8] and d_sums [shell_capacity][11] are device pointers, n_shells / ref_point /
+ * totals host pointers.  The counts are always returned; the tables are written only when shell_capacity >= *n_shells
+ * (else they are left untouched: ask with shell_capacity 0, then call again).  Synchronous on return; it does not touch the
+ * thread's last result.  Work buffers are kept per device and freed by r2s_release_cache.
+ * R2S_ERR_ARG before anything else runs, outputs untouched: NULL arrays with a count, a negative count, NULL n_shells /
+ * ref_point / totals, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the host; _dev: the
+ * check kernel of r2s_mesh_distance_dev).  n_tris > 2^30 or n_verts beyond 32 bits: R2S_ERR_UNSUPPORTED.  No GPU:
+ * R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 shells.  Not here: which shell encloses which, welding, repair. */
+int r2s_mesh_shells(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
+                    int32_t *shell_of_tri_out, int64_t *n_shells, double ref_point[3], int64_t totals[8]);
+int r2s_last_mesh_shells(int64_t *counts_out, double *sums_out, int64_t capacity, int64_t *n_shells);
+int r2s_mesh_shells_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris,
+                        int32_t *d_shell_of_tri, int64_t *d_counts, double *d_sums, int64_t shell_capacity,
+                        int64_t *n_shells, double ref_point[3], int64_t totals[8], void *stream);
+
 /* ---- on-disk output ------------------------------------------------------------------ */
 
 /* binary STL of a triangle mesh (verts [n_verts][3], tris [n_tris][3] 0-based); host only, no device; ".stl" appended

@@ -13,7 +13,8 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   surface_curvature,
                   mesh_distance, mesh_distance_dev, redistance, redistance_dev, last_distance_stats,
                   MeshIndex, redistance_full, redistance_full_dev, surface_deviation,
-                  vertex_normals, surface_thickness, surface_thickness_dev)
+                  vertex_normals, surface_thickness, surface_thickness_dev,
+                  MeshShells, mesh_shells, mesh_shells_dev, select_shells)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
@@ -24,4 +25,5 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "mesh_distance", "mesh_distance_dev", "redistance", "redistance_dev", "last_distance_stats",
            "MeshIndex", "redistance_full", "redistance_full_dev", "surface_deviation",
            "vertex_normals", "surface_thickness", "surface_thickness_dev",
+           "MeshShells", "mesh_shells", "mesh_shells_dev", "select_shells",
            "_lib"]

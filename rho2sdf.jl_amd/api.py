@@ -727,6 +727,126 @@ class MeshIndex:
         return res if len(res) > 1 else t
 
 
+class MeshShells:
+    """The shells of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_shells): the raw tables and what follows from them.
+    Raw: `counts` (n, 8) int64 (first_tri, n_tris, n_verts, n_edges, n_boundary, n_flipped, n_nonmanifold, 0), `sums` (n, 11)
+    float64 (area, volume, first moments x y z and second moments xx yy zz xy xz yz about `ref_point`), `ref_point` (3,),
+    `totals` (8,) int64 (shells, triangles, collapsed, edges, boundary, flipped, non-manifold, referenced vertices) and
+    `shell_of_tri` (-1 for a collapsed triangle; a device tensor from mesh_shells_dev).  Derived, in float64 numpy:
+        closed        = (n_boundary == 0) & (n_flipped == 0) & (n_nonmanifold == 0)
+        euler         = n_verts - n_edges + n_tris
+        genus         = (2 - euler) // 2 for closed shells, else -1
+        is_void       = closed & (volume < 0)
+        centroid      = ref_point + M1 / volume                         M1 = sums[:, 2:5]
+        second_moment = P - volume * d d^T  (n, 3, 3)                   P the symmetric matrix of sums[:, 5:11], d = M1 / volume
+        inertia       = trace(second_moment) * identity - second_moment (unit density, about the centroid)
+    centroid, second_moment and inertia are NaN unless the shell is closed with a non-zero volume."""
+
+    def __init__(self, counts, sums, ref_point, totals, shell_of_tri):
+        self.counts, self.sums, self.ref_point, self.totals, self.shell_of_tri = counts, sums, ref_point, totals, shell_of_tri
+
+    n_shells = property(lambda s: len(s.counts))
+    first_tri = property(lambda s: s.counts[:, 0])
+    n_tris = property(lambda s: s.counts[:, 1])
+    n_verts = property(lambda s: s.counts[:, 2])
+    n_edges = property(lambda s: s.counts[:, 3])
+    n_boundary = property(lambda s: s.counts[:, 4])
+    n_flipped = property(lambda s: s.counts[:, 5])
+    n_nonmanifold = property(lambda s: s.counts[:, 6])
+    area = property(lambda s: s.sums[:, 0])
+    volume = property(lambda s: s.sums[:, 1])
+    closed = property(lambda s: (s.n_boundary == 0) & (s.n_flipped == 0) & (s.n_nonmanifold == 0))
+    euler = property(lambda s: s.n_verts - s.n_edges + s.n_tris)
+    genus = property(lambda s: np.where(s.closed, (2 - s.euler) // 2, -1))
+    is_void = property(lambda s: s.closed & (s.volume < 0))
+
+    def __len__(self):
+        return len(self.counts)
+
+    def _offset(self):
+        """d = M1 / volume, NaN unless closed with a non-zero volume"""
+        ok = self.closed & (self.volume != 0)
+        v = np.where(ok, self.volume, np.nan)
+        return self.sums[:, 2:5] / v[:, None], v
+
+    @property
+    def centroid(self):
+        return self.ref_point[None, :] + self._offset()[0]
+
+    @property
+    def second_moment(self):
+        d, v = self._offset()
+        q = self.sums[:, 5:11]
+        P = np.stack([q[:, [0, 3, 4]], q[:, [3, 1, 5]], q[:, [4, 5, 2]]], axis=1)
+        return P - v[:, None, None] * d[:, :, None] * d[:, None, :]
+
+    @property
+    def inertia(self):
+        c = self.second_moment
+        return np.trace(c, axis1=1, axis2=2)[:, None, None] * np.eye(3)[None] - c
+
+
+def mesh_shells(verts, tris, *, device=-1):
+    """The shells of a triangle mesh (verts (nv, 3) float32, tris (nt, 3) int32, 0-based): connected components over shared
+    edges, edge classes, and per shell the counts, area, volume and moments -> MeshShells (its docstring has the fields and the
+    formulas of the derived ones).  One library call and a copy of the thread's last tables."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    sot = np.empty(len(t), np.int32)
+    n = ctypes.c_int64()
+    ref, tot = np.zeros(3), np.zeros(8, np.int64)
+    L.check(L.lib().r2s_mesh_shells(_f(v) if len(v) else None, len(v), t.ctypes.data_as(L.c_int32_p) if len(t) else None, len(t),
+                                    int(device), sot.ctypes.data_as(L.c_int32_p), ctypes.byref(n), _d(ref), _i(tot)))
+    counts, sums = np.empty((n.value, 8), np.int64), np.empty((n.value, 11))
+    if n.value:
+        L.check(L.lib().r2s_last_mesh_shells(_i(counts), _d(sums), n.value, ctypes.byref(n)))
+    return MeshShells(counts, sums, ref, tot, sot)
+
+
+def mesh_shells_dev(verts, tris, stream=None, *, capacity=0):
+    """mesh_shells on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous).  The tables
+    come back as numpy arrays, shell_of_tri stays a device tensor.  The library writes the tables only into room for all shells:
+    with more shells than `capacity` the call is made a second time."""
+    import torch
+    _mesh_tensors(verts, tris)
+    st = _stream(stream)
+    nt = tris.numel() // 3
+    sot = torch.empty(nt, dtype=torch.int32, device=verts.device)
+    n = ctypes.c_int64()
+    ref, tot = np.zeros(3), np.zeros(8, np.int64)
+    cap = int(capacity)
+    while True:
+        counts = torch.empty((cap, 8), dtype=torch.int64, device=verts.device)
+        sums = torch.empty((cap, 11), dtype=torch.float64, device=verts.device)
+        vp = ctypes.c_void_p
+        L.check(L.lib().r2s_mesh_shells_dev(vp(verts.data_ptr()), verts.numel() // 3, vp(tris.data_ptr()), nt, vp(sot.data_ptr()),
+                                            vp(counts.data_ptr()) if cap else None, vp(sums.data_ptr()) if cap else None, cap,
+                                            ctypes.byref(n), _d(ref), _i(tot), st))
+        if n.value <= cap:
+            break
+        cap = n.value
+    return MeshShells(counts[:n.value].cpu().numpy(), sums[:n.value].cpu().numpy(), ref, tot, sot)
+
+
+def select_shells(verts, tris, shells, keep):
+    """The triangles of the shells where `keep` is true -> (verts, tris) with the vertices compacted (ascending old index) and the
+    indices remapped; the mesh-level counterpart of remove_sdf_artifacts.  `shells` is the MeshShells of (verts, tris); `keep` a
+    boolean array with one entry per shell, or a callable on `shells` that returns one, e.g.
+    lambda s: s.volume > 0.01 * s.volume.max().  Collapsed triangles (shell -1) are dropped.  Plain array code, no device."""
+    v = np.asarray(verts).reshape(-1, 3)
+    t = np.asarray(tris).reshape(-1, 3)
+    k = np.asarray(keep(shells) if callable(keep) else keep, dtype=bool).reshape(-1)
+    sot = shells.shell_of_tri
+    sot = np.asarray(sot.cpu() if hasattr(sot, "cpu") else sot)
+    if len(k) != shells.n_shells or len(sot) != len(t):
+        raise L.R2SError("keep needs one entry per shell, and shells must belong to this mesh")
+    sel = t[(sot >= 0) & np.concatenate([k, [False]])[sot]]
+    used = np.zeros(len(v), bool)
+    used[sel.ravel()] = True
+    remap = np.cumsum(used) - 1
+    return v[used], remap[sel].astype(t.dtype).reshape(-1, 3)
+
+
 def vertex_normals(verts, tris):
     """area-weighted vertex normals of the winding, float64 (nv, 3), not normalised: the sum of (b-a)x(c-a) over the
     triangles at a vertex, from the float32 vertices widened to float64, added in the order of the triangles (corner 0 of
@@ -1183,7 +1303,7 @@ class Rho2sdfOptions:
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
             info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False, redistance_cells=None,
-            signed_distance=False, deviation=False, thickness=False):
+            signed_distance=False, deviation=False, thickness=False, shells=False):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -1210,13 +1330,17 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     nothing new is called.
     thickness=True (needs `info`; implies surface=True): info["thickness"] = surface_thickness(*info["surface"], skip=half a
     spacing of the fine lattice) - (thickness, hit_tri, side) at every vertex of the extracted surface, a further library
-    call after the first."""
+    call after the first.
+    shells=True (needs `info`; implies surface=True): info["shells"] = mesh_shells(*info["surface"]) - the bodies of the exported
+    mesh, their topology, volumes and enclosed voids - a further library call after the first."""
     options = options or Rho2sdfOptions()
     if (signed_distance or deviation) and info is None:
         raise L.R2SError("signed_distance / deviation need an `info` dict for the result")
     if thickness and info is None:
         raise L.R2SError("thickness needs an `info` dict for the result")
-    surface = bool(surface) or bool(thickness)
+    if shells and info is None:
+        raise L.R2SError("shells needs an `info` dict for the result")
+    surface = bool(surface) or bool(thickness) or bool(shells)
     if redistance_cells is not None and (info is None or not (float(redistance_cells) > 0.0)):
         raise L.R2SError("redistance_cells must be a positive number and needs an `info` dict for the result")
     mesh = Mesh(X, IEN, options.element_type)
@@ -1276,6 +1400,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
         info["smoothing_deviation"] = surface_deviation(*smoothed, *raw, device=device)
     if thickness:
         info["thickness"] = surface_thickness(*mesh_out, skip=0.5 * _iso_lattice(sdf_grid, smooth)[2], device=device)
+    if shells:
+        info["shells"] = mesh_shells(*mesh_out, device=device)
     if export_results:
         vti = export_sdf_results(fine_sdf, sdf_grid, taskName, smooth, options.rbf_interp, mesh.element_type)
         if surface:

@@ -149,4 +149,8 @@ inline size_t tri_bytes(int64_t n_tris) { return 3 * sizeof(int32_t) * (size_t)n
 int upload_mesh(DevBuf& dv, DevBuf& dt, const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, bool from_device,
                 hipStream_t st);
 
+// ---- mesh shells (r2s_mesh_shells.hip) --------------------------------------------------------------------------------
+// frees the work buffers the shell calls keep per device; called by r2s_release_cache()
+void release_shell_work();
+
 }  // namespace r2s_int

@@ -1,0 +1,652 @@
+// Mesh shells: the connected components of a triangle mesh over shared edges, the edge classes, and per shell the integer
+// record and the Float64 area / volume / moments (include/rho2sdf_hip.h, r2s_mesh_shells; DESIGN.md "Mesh shells").
+//   ms_bounds_kernel   the box of all vertices (integer atomics on order-preserving bit patterns) -> the reference point
+//   ms_key_kernel      one half-edge key per corner, (min << 33) | (max << 1) | direction, payload 3t + c; collapsed
+//                      triangles get a key above every real one -> rocPRIM radix sort of pairs
+//   ms_union_kernel    one union per run member with the member before it (integer union-find: the larger root is hooked
+//                      under the smaller with a compare-and-swap, paths are halved with atomicMin, so the final root of a
+//                      component is its smallest triangle whatever the race)
+//   ms_flatten_kernel  label = root, root flags -> rocPRIM exclusive scan (integers) -> ms_number_kernel: shell numbers
+//   -> stable radix sort of the triangle ids by shell number -> ms_segment_kernel: where each shell starts
+//   ms_sum_kernel      blocks of 256 consecutive sorted triangles, the 11 terms per triangle, a segmented fixed tree in LDS,
+//                      one partial per (block, shell) at slot block + shell
+//   ms_combine_kernel  one wavefront per shell: up to 64 equal runs of its block partials in ascending order, then a fixed tree
+//   ms_edge_kernel     the sorted edge runs again: class of each run, counted into the shell of its first half-edge
+//   ms_vkey_kernel     (shell << 32) | vertex per corner -> radix sort of keys -> ms_vcount_kernel: distinct vertices per shell
+//   ms_totals_kernel   the column sums of the integer table and the number of referenced vertices
+// Integer counts use integer atomics (a workgroup whose entries all fall into one shell adds once per column); no
+// floating-point atomic and no library reduction touches the Float64 sums.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "r2s_common.hpp"
+#include "r2s_internal.hpp"
+
+using namespace r2s_int;
+
+namespace {
+
+constexpr int MS_BLOCK = 256;   // triangles per block of the Float64 sums (the header's definition)
+constexpr int MS_NSUM = 11, MS_NCNT = 8;
+constexpr int64_t MS_MAX_TRIS = (int64_t)1 << 30;
+// slots of the small device array: [0..5] the bounds, then
+constexpr int MS_COLLAPSED = 6, MS_NSHELLS = 7, MS_TOT = 8;   // [MS_TOT .. MS_TOT + 4]: edges, boundary, flipped, non-manifold, vertices
+constexpr int MS_SMALL = 16;
+
+__device__ inline uint32_t ms_ordered(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+inline float ms_unordered(uint32_t u)
+{
+    const uint32_t b = (u >> 31) ? (u & 0x7fffffffu) : ~u;
+    float f;
+    std::memcpy(&f, &b, sizeof f);
+    return f;
+}
+
+__device__ inline bool ms_collapsed(const int32_t* __restrict__ tris, int64_t t, int32_t& i0, int32_t& i1, int32_t& i2)
+{
+    i0 = tris[3 * t], i1 = tris[3 * t + 1], i2 = tris[3 * t + 2];
+    return i0 == i1 || i1 == i2 || i0 == i2;
+}
+
+// bb[0..2] = min, bb[3..5] = max over all vertices, as ordered bit patterns (bb starts as ~0, ~0, ~0, 0, 0, 0)
+__global__ void __launch_bounds__(256) ms_bounds_kernel(const float* __restrict__ verts, int64_t nverts, uint64_t* __restrict__ small)
+{
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    if (v < nverts) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) lo[k] = hi[k] = ms_ordered(verts[3 * v + k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const uint32_t a = __shfl_xor(lo[k], d, 64), b = __shfl_xor(hi[k], d, 64);
+            lo[k] = a < lo[k] ? a : lo[k];
+            hi[k] = b > hi[k] ? b : hi[k];
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            atomicMin((unsigned long long*)&small[k], (unsigned long long)lo[k]);
+            atomicMax((unsigned long long*)&small[3 + k], (unsigned long long)hi[k]);
+        }
+    }
+}
+
+// one thread per triangle: its three half-edge keys, parent[t] = t, the referenced-vertex flags, the collapsed count
+__global__ void __launch_bounds__(256) ms_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ vals, uint32_t* __restrict__ parent, int32_t* __restrict__ vflag,
+                                                      uint64_t* __restrict__ small)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool col = false;
+    if (t < n) {
+        int32_t i[3];
+        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
+        parent[t] = (uint32_t)t;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
+            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
+            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
+            vals[3 * t + c] = (uint32_t)(3 * t + c);
+            if (!col) vflag[i[c]] = 1;
+        }
+    }
+    const unsigned long long m = __ballot(col);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MS_COLLAPSED], (unsigned long long)__popcll(m));
+}
+
+// parents are rewritten by other CUs during the kernel: bypass the per-CU L1
+__device__ inline uint32_t ms_load(const uint32_t* L, uint32_t i) { return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x; every visited node is pointed at its grandparent (atomicMin: a parent only ever moves to a smaller ancestor)
+__device__ inline uint32_t ms_find(uint32_t* L, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = ms_load(L, x);
+        if (p == x) return x;
+        const uint32_t g = ms_load(L, p);
+        if (g != p) atomicMin(&L[x], g);
+        x = g;
+    }
+}
+
+__device__ inline void ms_union(uint32_t* L, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = ms_find(L, a);
+        b = ms_find(L, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }   // link the larger root under the smaller
+        if (atomicCAS(&L[a], a, b) == a) return;             // a was still a root
+    }
+}
+
+// one thread per sorted half-edge: joins its triangle to that of the member before it in the same run
+__global__ void __launch_bounds__(256) ms_union_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
+                                                        uint64_t ckey, uint32_t* parent)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < 1 || i >= nh) return;
+    const uint64_t k = keys[i];
+    if (k >= ckey || (keys[i - 1] >> 1) != (k >> 1)) return;
+    ms_union(parent, vals[i - 1] / 3u, vals[i] / 3u);
+}
+
+__global__ void __launch_bounds__(256) ms_flatten_kernel(const int32_t* __restrict__ tris, int64_t n, uint32_t* parent, int32_t* __restrict__ flag)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    int32_t i0, i1, i2;
+    if (ms_collapsed(tris, t, i0, i1, i2)) {
+        flag[t] = 0;
+        return;
+    }
+    const uint32_t r = ms_find(parent, (uint32_t)t);
+    if (r != (uint32_t)t) atomicMin(&parent[t], r);
+    flag[t] = r == (uint32_t)t ? 1 : 0;
+}
+
+// num = the exclusive scan of flag: shell_of[t], the sort key of t (collapsed: n_shells, behind every shell), n_shells
+__global__ void __launch_bounds__(256) ms_number_kernel(const int32_t* __restrict__ tris, int64_t n, const uint32_t* __restrict__ parent,
+                                                         const int32_t* __restrict__ num, const int32_t* __restrict__ flag,
+                                                         int32_t* __restrict__ shell_of, uint32_t* __restrict__ skey, uint32_t* __restrict__ sval,
+                                                         uint64_t* __restrict__ small)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int32_t nsh = num[n - 1] + flag[n - 1];
+    int32_t i0, i1, i2;
+    const int32_t s = ms_collapsed(tris, t, i0, i1, i2) ? -1 : num[parent[t]];   // (ms_flatten_kernel left parent = root)
+    shell_of[t] = s;
+    skey[t] = s < 0 ? (uint32_t)nsh : (uint32_t)s;
+    sval[t] = (uint32_t)t;
+    if (t == n - 1) small[MS_NSHELLS] = (uint64_t)nsh;
+}
+
+// seg[s] = the first sorted position of shell s, seg[n_shells] = nvalid; the shell's first triangle
+__global__ void __launch_bounds__(256) ms_segment_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ stri, int64_t nvalid,
+                                                          int64_t nsh, int64_t* __restrict__ seg, int64_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvalid) return;
+    const uint32_t s = skey[i];
+    if (i == 0 || skey[i - 1] != s) {
+        seg[s] = i;
+        counts[(int64_t)s * MS_NCNT] = (int64_t)stri[i];
+    }
+    if (i == 0) seg[nsh] = nvalid;
+}
+
+// the 11 terms of one triangle in the header's operation order
+__device__ inline void ms_terms(const float* __restrict__ verts, int32_t i0, int32_t i1, int32_t i2, double rx, double ry, double rz, double v[MS_NSUM])
+{
+#pragma clang fp contract(off)
+    const float *pa = verts + 3 * (int64_t)i0, *pb = verts + 3 * (int64_t)i1, *pc = verts + 3 * (int64_t)i2;
+    const double Ax = (double)pa[0] - rx, Ay = (double)pa[1] - ry, Az = (double)pa[2] - rz;
+    const double Bx = (double)pb[0] - rx, By = (double)pb[1] - ry, Bz = (double)pb[2] - rz;
+    const double Cx = (double)pc[0] - rx, Cy = (double)pc[1] - ry, Cz = (double)pc[2] - rz;
+    const double Sx = (Ax + Bx) + Cx, Sy = (Ay + By) + Cy, Sz = (Az + Bz) + Cz;
+    const double Ex = Bx - Ax, Ey = By - Ay, Ez = Bz - Az, Fx = Cx - Ax, Fy = Cy - Ay, Fz = Cz - Az;
+    const double Nx = Ey * Fz - Ez * Fy, Ny = Ez * Fx - Ex * Fz, Nz = Ex * Fy - Ey * Fx;
+    v[0] = 0.5 * sqrt((Nx * Nx + Ny * Ny) + Nz * Nz);
+    const double det = (Ax * (By * Cz - Bz * Cy) + Ay * (Bz * Cx - Bx * Cz)) + Az * (Bx * Cy - By * Cx);
+    v[1] = det / 6.0;
+    v[2] = (det * Sx) / 24.0;
+    v[3] = (det * Sy) / 24.0;
+    v[4] = (det * Sz) / 24.0;
+    v[5] = (det * (((Ax * Ax + Bx * Bx) + Cx * Cx) + Sx * Sx)) / 120.0;
+    v[6] = (det * (((Ay * Ay + By * By) + Cy * Cy) + Sy * Sy)) / 120.0;
+    v[7] = (det * (((Az * Az + Bz * Bz) + Cz * Cz) + Sz * Sz)) / 120.0;
+    v[8] = (det * (((Ax * Ay + Bx * By) + Cx * Cy) + Sx * Sy)) / 120.0;
+    v[9] = (det * (((Ax * Az + Bx * Bz) + Cx * Cz) + Sx * Sz)) / 120.0;
+    v[10] = (det * (((Ay * Az + By * Bz) + Cy * Cz) + Sy * Sz)) / 120.0;
+}
+
+// block b: the sorted positions [256 b, 256 b + 256); the partial of (block b, shell s) goes to slot b + s (both only grow
+// along the sorted order, so the slots are distinct; there are fewer than blocks + shells of them)
+__global__ void __launch_bounds__(MS_BLOCK) ms_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
+                                                           const uint32_t* __restrict__ skey, const uint32_t* __restrict__ stri, int64_t nvalid,
+                                                           double rx, double ry, double rz, double* __restrict__ partial)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_v[MS_NSUM][MS_BLOCK];
+    __shared__ uint32_t s_key[MS_BLOCK];
+    const int j = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MS_BLOCK + j;
+    const bool active = i < nvalid;
+    uint32_t key = 0xffffffffu;
+    double v[MS_NSUM];
+#pragma unroll
+    for (int q = 0; q < MS_NSUM; ++q) v[q] = 0.0;
+    if (active) {
+        key = skey[i];
+        const int64_t t = (int64_t)stri[i];
+        ms_terms(verts, tris[3 * t], tris[3 * t + 1], tris[3 * t + 2], rx, ry, rz, v);
+    }
+    s_key[j] = key;
+#pragma unroll
+    for (int q = 0; q < MS_NSUM; ++q) s_v[q][j] = v[q];
+    __syncthreads();
+    const bool head = active && (j == 0 || s_key[j - 1] != key);
+#pragma unroll
+    for (int d = 1; d < MS_BLOCK; d <<= 1) {
+        const bool take = active && j + d < MS_BLOCK && s_key[j + d] == key;
+        double o[MS_NSUM];
+#pragma unroll
+        for (int q = 0; q < MS_NSUM; ++q) o[q] = take ? s_v[q][j + d] : 0.0;
+        __syncthreads();
+        if (take) {
+#pragma unroll
+            for (int q = 0; q < MS_NSUM; ++q) {
+                v[q] = v[q] + o[q];
+                s_v[q][j] = v[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (head) {
+        double* out = partial + ((int64_t)blockIdx.x + (int64_t)key) * MS_NSUM;
+#pragma unroll
+        for (int q = 0; q < MS_NSUM; ++q) out[q] = v[q];
+    }
+}
+
+// one wavefront per shell: lane l sums the l-th run of `chunk` consecutive block partials in ascending block order, then the
+// run sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while that lane has a run)
+__global__ void __launch_bounds__(256) ms_combine_kernel(const int64_t* __restrict__ seg, int64_t nsh, const double* __restrict__ partial,
+                                                          double* __restrict__ sums, int64_t* __restrict__ counts)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= nsh) return;   // (the whole wavefront)
+    const int64_t start = seg[s], end = seg[s + 1];
+    const int64_t b0 = start / MS_BLOCK, nb = (end - 1) / MS_BLOCK - b0 + 1;
+    const int64_t chunk = (nb + 63) / 64;
+    const int m = (int)((nb + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
+    double v[MS_NSUM];
+#pragma unroll
+    for (int q = 0; q < MS_NSUM; ++q) v[q] = 0.0;
+    if (lane < m) {
+        const int64_t lo = lane * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
+        const double* p = partial + (b0 + lo + s) * MS_NSUM;
+#pragma unroll
+        for (int q = 0; q < MS_NSUM; ++q) v[q] = p[q];
+        for (int64_t b = lo + 1; b < hi; ++b) {
+            p += MS_NSUM;
+#pragma unroll
+            for (int q = 0; q < MS_NSUM; ++q) v[q] = v[q] + p[q];
+        }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (int q = 0; q < MS_NSUM; ++q) {
+            const double o = __shfl_down(v[q], d, 64);
+            if (lane + d < m) v[q] = v[q] + o;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < MS_NSUM; ++q) sums[s * MS_NSUM + q] = v[q];
+        counts[s * MS_NCNT + 1] = end - start;
+    }
+}
+
+// adds 1 to counts[shell][col0 + k] for every k < NC with add[k] set, over the workgroup's active threads: once per column
+// when all of them name one shell, else one atomic per entry.  Called by all 256 threads.
+template <int NC>
+__device__ inline void ms_count(bool active, int32_t shell, const bool add[NC], int col0, int64_t* __restrict__ counts)
+{
+    __shared__ int32_t s_shell, s_mixed;
+    __shared__ uint32_t s_cnt[NC];
+    if (threadIdx.x == 0) s_shell = -1, s_mixed = 0;
+    if (threadIdx.x < NC) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    if (active) atomicCAS(&s_shell, -1, shell);
+    __syncthreads();
+    if (active && shell != s_shell) s_mixed = 1;
+    __syncthreads();
+    if (s_mixed) {
+        if (active) {
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+                if (add[k]) atomicAdd((unsigned long long*)&counts[(int64_t)shell * MS_NCNT + col0 + k], 1ull);
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const unsigned long long m = __ballot(active && add[k]);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_cnt[k], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < NC && s_shell >= 0 && s_cnt[threadIdx.x])
+        atomicAdd((unsigned long long*)&counts[(int64_t)s_shell * MS_NCNT + col0 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// one thread per sorted half-edge; the first member of a run classifies it and counts it into the shell of its triangle
+__global__ void __launch_bounds__(256) ms_edge_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
+                                                       uint64_t ckey, const int32_t* __restrict__ shell_of, int64_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool head = false;
+    bool add[4] = {false, false, false, false};   // edge, boundary, flipped, non-manifold
+    int32_t shell = -1;
+    if (i < nh) {
+        const uint64_t k = keys[i];
+        head = k < ckey && (i == 0 || (keys[i - 1] >> 1) != (k >> 1));
+        if (head) {
+            const uint64_t k1 = i + 1 < nh ? keys[i + 1] : ~0ull, k2 = i + 2 < nh ? keys[i + 2] : ~0ull;
+            const bool two = (k1 >> 1) == (k >> 1), three = two && (k2 >> 1) == (k >> 1);
+            add[0] = true;
+            add[1] = !two;
+            add[2] = two && !three && ((k1 ^ k) & 1ull) == 0ull;
+            add[3] = three;
+            shell = shell_of[vals[i] / 3u];
+        }
+    }
+    ms_count<4>(head, shell, add, 3, counts);
+}
+
+__global__ void __launch_bounds__(256) ms_vkey_kernel(const int32_t* __restrict__ tris, int64_t n, const int32_t* __restrict__ shell_of,
+                                                       uint64_t nsh, uint64_t* __restrict__ vkeys)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int32_t s = shell_of[t];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vkeys[3 * t + c] = s < 0 ? (nsh << 32) : (((uint64_t)(uint32_t)s << 32) | (uint64_t)(uint32_t)tris[3 * t + c]);
+}
+
+__global__ void __launch_bounds__(256) ms_vcount_kernel(const uint64_t* __restrict__ vkeys, int64_t nh, uint64_t nsh, int64_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool head = false;
+    int32_t shell = -1;
+    if (i < nh) {
+        const uint64_t k = vkeys[i];
+        head = (k >> 32) < nsh && (i == 0 || vkeys[i - 1] != k);
+        shell = (int32_t)(k >> 32);
+    }
+    const bool add[1] = {true};
+    ms_count<1>(head, shell, add, 2, counts);
+}
+
+// small[MS_TOT + 0..3] = the sums of columns 3..6 over the shells, small[MS_TOT + 4] = the number of set vertex flags
+__global__ void __launch_bounds__(256) ms_totals_kernel(const int64_t* __restrict__ counts, int64_t nsh, const int32_t* __restrict__ vflag,
+                                                         int64_t nverts, uint64_t* __restrict__ small)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    long long c[5] = {0, 0, 0, 0, 0};
+    if (i < nsh) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = counts[i * MS_NCNT + 3 + k];
+    }
+    if (i < nverts) c[4] = vflag[i] ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) c[k] += __shfl_xor(c[k], d, 64);
+        if ((threadIdx.x & 63) == 0 && c[k]) atomicAdd((unsigned long long*)&small[MS_TOT + k], (unsigned long long)c[k]);
+    }
+}
+
+// work buffers of the shell calls, kept per device between calls (r2s_release_cache frees them)
+struct ShellWork {
+    DevBuf verts, tris, flag, small, keys, keys2, vals, vals2, temp, parent, rflag, num, shell, skey, skey2, sval, sval2, seg, partial,
+        counts, sums, vflag;
+    void release()
+    {
+        DevBuf* all[] = {&verts, &tris, &flag, &small, &keys, &keys2, &vals, &vals2, &temp, &parent, &rflag, &num, &shell, &skey, &skey2,
+                         &sval, &sval2, &seg, &partial, &counts, &sums, &vflag};
+        for (DevBuf* b : all) b->release();
+    }
+};
+std::mutex g_shell_mu;
+std::map<int, ShellWork> g_shell_work;
+
+struct ShellTables {
+    std::vector<int64_t> counts;   // [n][8]
+    std::vector<double> sums;      // [n][11]
+};
+thread_local ShellTables g_last_shells;
+
+inline unsigned ms_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+inline unsigned ms_bits(uint64_t max_value)
+{
+    unsigned b = 1;
+    while (b < 64 && (max_value >> b)) ++b;
+    return b;
+}
+
+// The shells of the device mesh on the current device, after the work queued on `st`; synchronous.  Leaves shell_of_tri in
+// w.shell [n_tris] and the tables in w.counts / w.sums [n_shells]; the scalars go to the host pointers.
+int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, hipStream_t st, ShellWork& w, int64_t* n_shells,
+                double ref_point[3], int64_t totals[8])
+{
+    uint64_t h_small[MS_SMALL] = {};
+    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
+    ENSURE(w.small, sizeof h_small);
+    uint64_t* small = w.small.as<uint64_t>();
+    HIP_TRY(hipMemcpyAsync(small, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
+    if (n_verts > 0) {
+        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, small);
+        HIP_TRY(hipGetLastError());
+    }
+    const int64_t nh = 3 * n;
+    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    if (n > 0) {
+        ENSURE(w.keys, sizeof(uint64_t) * (size_t)nh);
+        ENSURE(w.keys2, sizeof(uint64_t) * (size_t)nh);
+        ENSURE(w.vals, sizeof(uint32_t) * (size_t)nh);
+        ENSURE(w.vals2, sizeof(uint32_t) * (size_t)nh);
+        ENSURE(w.parent, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
+        ENSURE(w.num, sizeof(int32_t) * (size_t)n);
+        ENSURE(w.shell, sizeof(int32_t) * (size_t)n);
+        ENSURE(w.skey, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.skey2, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.sval, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.sval2, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.vflag, sizeof(int32_t) * (size_t)std::max<int64_t>(n_verts, 1));
+        HIP_TRY(hipMemsetAsync(w.vflag.p, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(n_verts, 1), st));
+        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
+        uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>(), *parent = w.parent.as<uint32_t>();
+        ms_key_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ckey, keys, vals, parent, w.vflag.as<int32_t>(), small);
+        HIP_TRY(hipGetLastError());
+        const unsigned ebits = 33u + ms_bits((uint64_t)n_verts);   // (the collapsed key included)
+        size_t tb = 0, tb2 = 0;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
+        HIP_TRY(rocprim::exclusive_scan(nullptr, tb2, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
+        ENSURE(w.temp, std::max<size_t>(std::max(tb, tb2), 16));
+        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
+        ms_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, parent);
+        HIP_TRY(hipGetLastError());
+        ms_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.rflag.as<int32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::exclusive_scan(w.temp.p, tb2, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
+        ms_number_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.num.as<int32_t>(), w.rflag.as<int32_t>(), w.shell.as<int32_t>(),
+                                                     w.skey.as<uint32_t>(), w.sval.as<uint32_t>(), small);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    double r[3] = {0.0, 0.0, 0.0};
+    if (n_verts > 0)
+        for (int k = 0; k < 3; ++k) r[k] = 0.5 * ((double)ms_unordered((uint32_t)h_small[k]) + (double)ms_unordered((uint32_t)h_small[3 + k]));
+    const int64_t nsh = (int64_t)h_small[MS_NSHELLS], ncol = (int64_t)h_small[MS_COLLAPSED], nvalid = n - ncol;
+    if (nsh > 0) {
+        const int64_t nblk = (nvalid + MS_BLOCK - 1) / MS_BLOCK;
+        ENSURE(w.seg, sizeof(int64_t) * (size_t)(nsh + 1));
+        ENSURE(w.partial, sizeof(double) * MS_NSUM * (size_t)(nblk + nsh));
+        ENSURE(w.counts, sizeof(int64_t) * MS_NCNT * (size_t)nsh);
+        ENSURE(w.sums, sizeof(double) * MS_NSUM * (size_t)nsh);
+        int64_t* counts = w.counts.as<int64_t>();
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * MS_NCNT * (size_t)nsh, st));
+        uint32_t *skey = w.skey.as<uint32_t>(), *skey2 = w.skey2.as<uint32_t>(), *sval = w.sval.as<uint32_t>(), *sval2 = w.sval2.as<uint32_t>();
+        size_t tb = 0, tb2 = 0;
+        const unsigned sbits = ms_bits((uint64_t)nsh), vbits = 32u + ms_bits((uint64_t)nsh);
+        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
+        HIP_TRY(rocprim::radix_sort_keys(nullptr, tb2, keys, keys2, (size_t)nh, 0u, vbits, st));
+        ENSURE(w.temp, std::max<size_t>(std::max(tb, tb2), 16));
+        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
+        ms_segment_kernel<<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, nsh, w.seg.as<int64_t>(), counts);
+        HIP_TRY(hipGetLastError());
+        ms_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, skey2, sval2, nvalid, r[0], r[1], r[2], w.partial.as<double>());
+        HIP_TRY(hipGetLastError());
+        ms_combine_kernel<<<(unsigned)((nsh + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), nsh, w.partial.as<double>(), w.sums.as<double>(), counts);
+        HIP_TRY(hipGetLastError());
+        // (keys2 / vals2 still hold the sorted half-edges)
+        ms_edge_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, w.vals2.as<uint32_t>(), nh, ckey, w.shell.as<int32_t>(), counts);
+        HIP_TRY(hipGetLastError());
+        ms_vkey_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, w.shell.as<int32_t>(), (uint64_t)nsh, keys);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::radix_sort_keys(w.temp.p, tb2, keys, keys2, (size_t)nh, 0u, vbits, st));
+        ms_vcount_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, nh, (uint64_t)nsh, counts);
+        HIP_TRY(hipGetLastError());
+        ms_totals_kernel<<<ms_blocks(std::max(nsh, n_verts)), 256, 0, st>>>(counts, nsh, w.vflag.as<int32_t>(), n_verts, small);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_shells = nsh;
+    for (int k = 0; k < 3; ++k) ref_point[k] = r[k];
+    totals[0] = nsh, totals[1] = n, totals[2] = ncol;
+    for (int k = 0; k < 5; ++k) totals[3 + k] = nsh > 0 ? (int64_t)h_small[MS_TOT + k] : 0;
+    return 0;
+}
+
+int shells_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tris, const int64_t* n_shells, const double* ref_point,
+                const int64_t* totals)
+{
+    const int rc = mesh_args("mesh_shells", verts, n_verts, tris, n_tris);
+    if (rc) return rc;
+    if (n_tris > MS_MAX_TRIS) return fail(R2S_ERR_UNSUPPORTED, "mesh_shells: %lld triangles exceed 2^30", (long long)n_tris);
+    if (!n_shells || !ref_point || !totals) return fail(R2S_ERR_ARG, "mesh_shells: null n_shells / ref_point / totals");
+    return 0;
+}
+
+ShellWork* work_of_current_device(int& rc)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
+        return nullptr;
+    }
+    rc = 0;
+    return &g_shell_work[dev];
+}
+
+}  // namespace
+
+namespace r2s_int {
+
+void release_shell_work()
+{
+    std::lock_guard<std::mutex> lock(g_shell_mu);
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+    for (auto& kv : g_shell_work) {
+        (void)hipSetDevice(kv.first);
+        kv.second.release();
+    }
+    g_shell_work.clear();
+    if (cur >= 0) (void)hipSetDevice(cur);
+    (void)hipGetLastError();
+}
+
+}  // namespace r2s_int
+
+extern "C" {
+
+int r2s_mesh_shells(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, int32_t device, int32_t* shell_of_tri_out,
+                    int64_t* n_shells, double ref_point[3], int64_t totals[8])
+{
+    int rc = shells_args(verts, n_verts, tris, n_tris, n_shells, ref_point, totals);
+    if (rc) return rc;
+    if ((rc = check_mesh_host("mesh_shells", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
+    std::lock_guard<std::mutex> lock(g_shell_mu);
+    ShellWork* w = work_of_current_device(rc);
+    if (rc) return rc;
+    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
+    int64_t nsh = 0, tot[8];
+    double r[3];
+    if ((rc = shells_core(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, nullptr, *w, &nsh, r, tot))) return rc;
+    ShellTables tab;
+    tab.counts.resize((size_t)nsh * MS_NCNT);
+    tab.sums.resize((size_t)nsh * MS_NSUM);
+    if (nsh > 0) {
+        HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tab.sums.data(), w->sums.p, sizeof(double) * tab.sums.size(), hipMemcpyDeviceToHost));
+    }
+    if (shell_of_tri_out && n_tris > 0) HIP_TRY(hipMemcpy(shell_of_tri_out, w->shell.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToHost));
+    g_last_shells = std::move(tab);
+    *n_shells = nsh;
+    std::memcpy(ref_point, r, sizeof r);
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
+int r2s_last_mesh_shells(int64_t* counts_out, double* sums_out, int64_t capacity, int64_t* n_shells)
+{
+    if (!n_shells || capacity < 0 || (capacity > 0 && (!counts_out || !sums_out)))
+        return fail(R2S_ERR_ARG, "last_mesh_shells: null output or negative capacity");
+    const int64_t n = (int64_t)(g_last_shells.counts.size() / MS_NCNT), m = std::min(capacity, n);
+    *n_shells = n;
+    if (m > 0) {
+        std::memcpy(counts_out, g_last_shells.counts.data(), sizeof(int64_t) * MS_NCNT * (size_t)m);
+        std::memcpy(sums_out, g_last_shells.sums.data(), sizeof(double) * MS_NSUM * (size_t)m);
+    }
+    return 0;
+}
+
+int r2s_mesh_shells_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n_tris, int32_t* d_shell_of_tri,
+                        int64_t* d_counts, double* d_sums, int64_t shell_capacity, int64_t* n_shells, double ref_point[3],
+                        int64_t totals[8], void* stream)
+{
+    int rc = shells_args(d_verts, n_verts, d_tris, n_tris, n_shells, ref_point, totals);
+    if (rc) return rc;
+    if (shell_capacity < 0 || (shell_capacity > 0 && (!d_counts || !d_sums)))
+        return fail(R2S_ERR_ARG, "mesh_shells: null tables or negative shell_capacity");
+    if ((rc = check_device(0))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g_shell_mu);
+    ShellWork* w = work_of_current_device(rc);
+    if (rc) return rc;
+    if ((rc = check_mesh_dev("mesh_shells", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
+    int64_t nsh = 0, tot[8];
+    double r[3];
+    if ((rc = shells_core(d_verts, n_verts, d_tris, n_tris, st, *w, &nsh, r, tot))) return rc;
+    if (d_shell_of_tri && n_tris > 0)
+        HIP_TRY(hipMemcpyAsync(d_shell_of_tri, w->shell.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToDevice, st));
+    if (nsh > 0 && shell_capacity >= nsh) {
+        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MS_NCNT * (size_t)nsh, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_sums, w->sums.p, sizeof(double) * MS_NSUM * (size_t)nsh, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_shells = nsh;
+    std::memcpy(ref_point, r, sizeof r);
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
+}  // extern "C"

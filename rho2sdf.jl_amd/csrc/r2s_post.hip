@@ -3403,6 +3403,7 @@ void r2s_release_cache(void)
     release_ccl_work();
     r2s_int::release_iso_work();
     r2s_int::release_dist_work();
+    r2s_int::release_shell_work();
     r2s_int::release_host_sessions();
 }
 

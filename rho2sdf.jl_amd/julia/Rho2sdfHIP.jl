@@ -459,6 +459,50 @@ function mesh_raycast_hip(ix::MeshIndexHIP, origins::AbstractMatrix{T}, dirs::Ab
     return t, tri, side
 end
 
+# The shells of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_shells): verts 3 x nv Float32, tris 3 x nt 1-based ->
+# (shell_of_tri (1-based shell number, 0 = collapsed triangle), counts 8 x n Int64 with first_tri 1-based, sums 11 x n Float64,
+# ref_point, totals)
+function mesh_shells_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}; device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    t0 = Int32.(tris) .- Int32(1)
+    shell = Vector{Int32}(undef, size(t0, 2))
+    n = Ref{Int64}(0)
+    ref = zeros(Float64, 3)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_shells, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                Matrix(verts), size(verts, 2), t0, size(t0, 2), Int32(device), shell, n, ref, totals))
+    counts, sums = last_mesh_shells_hip(n[])
+    shell .+= Int32(1)
+    return (shell_of_tri = shell, counts = counts, sums = sums, ref_point = ref, totals = totals)
+end
+
+# the calling thread's last shell tables (r2s_last_mesh_shells): counts 8 x n (first_tri made 1-based), sums 11 x n
+function last_mesh_shells_hip(capacity::Integer)
+    counts = Matrix{Int64}(undef, 8, capacity)
+    sums = Matrix{Float64}(undef, 11, capacity)
+    n = Ref{Int64}(0)
+    check(ccall((:r2s_last_mesh_shells, LIB[]), Cint, (Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}),
+                capacity == 0 ? C_NULL : counts, capacity == 0 ? C_NULL : sums, Int64(capacity), n))
+    counts[1, :] .+= 1
+    return counts, sums
+end
+
+# the same on device arrays of the current device (raw pointers, e.g. of AMDGPU.jl ROCArrays); the tables are written only when
+# shell_capacity holds all shells -> (n_shells, ref_point, totals); indices stay 0-based on the device
+function mesh_shells_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer, d_shell_of_tri::Ptr{Cvoid},
+                             d_counts::Ptr{Cvoid}, d_sums::Ptr{Cvoid}, shell_capacity::Integer; stream::Ptr{Cvoid} = C_NULL)
+    n = Ref{Int64}(0)
+    ref = zeros(Float64, 3)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_shells_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64},
+                 Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), d_shell_of_tri, d_counts, d_sums, Int64(shell_capacity), n, ref, totals,
+                stream))
+    return n[], ref, totals
+end
+
 # The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
 # +-Inf where the field has no surface.
 function redistance_full_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
