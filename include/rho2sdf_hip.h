@@ -20,6 +20,35 @@
  *     never keep caller pointers after returning.
  *   - the library fails with R2S_ERR_NO_DEVICE when no gfx950 device is usable;
  *     there is no CPU fallback.
+ *
+ * Streams (every `*_dev` entry point; tests/test_stream_order_gpu.py is the executable form of this paragraph)
+ *   - `stream` is a hipStream_t (NULL = the null stream); it may be a non-blocking stream.  Device inputs need only be
+ *     ready IN STREAM ORDER: work queued on `stream` before the call (a copy that fills an input, the kernel that
+ *     produces it) need not have finished, and nothing need be synchronised with the host.  Outputs are complete in stream
+ *     order: work queued on `stream` after the call sees them.
+ *   - no work is put on a stream the caller cannot order against.  Where an entry point uses streams of its own, they are
+ *     forked from `stream` and joined back into it by events before the call returns (r2s_plan_run_dev: two streams the plan
+ *     owns); the one entry point that works on the null stream, r2s_rbf_smooth_dev, waits for `stream` first and for the
+ *     whole device before it returns.
+ *   - which calls wait.  Enqueue only, return with the work still queued: r2s_fill_dev, r2s_plan_pack_tiles_dev,
+ *     r2s_plan_pack_tiles2_dev, r2s_unpack_tiles_dev, r2s_unpack_masks_dev, r2s_unpack_segments_dev, r2s_rbf_field_eval_dev /
+ *     _normals_dev / _hessian_dev / _curvature_dev / _project_dev, r2s_mesh_index_query_dev / _lattice_dev / _raycast_dev.
+ *     Return only after `stream` has drained (they hand counts to the host, or size their work from counts read back):
+ *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
+ *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
+ *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev.
+ *     A caller should still order its consumers on `stream`, not on that wait.
+ *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
+ *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
+ *     on that run's stream before the plan's next run; different plans are independent and may be driven on different
+ *     streams.  A field (r2s_rbf_field) and a mesh index are only read by their _dev entry points: one object may be used
+ *     from several streams and threads at once.  The entry points that keep work buffers per device (removal and component
+ *     analysis, smoothing, extraction, redistancing, shells) take a lock for the length of the call: concurrent calls are
+ *     safe and run one after the other.
+ *   - devices.  Device pointers and `stream` belong to one device.  r2s_plan_run_dev and r2s_plan_pack_tiles*_dev make the
+ *     plan's device current (and leave it current); the _dev entry points of a field or an index refuse a call while
+ *     another device than the object's is current (R2S_ERR_ARG, outputs untouched); for every other _dev entry point the
+ *     device of the pointers must be the current one - a call with another device current is outside the contract.
  */
 #ifndef RHO2SDF_HIP_H
 #define RHO2SDF_HIP_H
@@ -230,7 +259,7 @@ void r2s_plan_destroy(r2s_plan *plan);
  * (hipStream_t as void*, NULL = default stream).  The FIRST call for a set of shapes waits for the stream twice in the
  * middle (item and list sizes are read back); later calls with the same shapes enqueue everything in one go from the
  * sizes of the previous call (a device-side check falls back to the waiting way when they do not hold) and wait once,
- * at the end, when `stats` is requested or an earlier speculated size has to be confirmed. */
+ * at the end, with or without `stats`: the speculated sizes are confirmed on the host there.  See "Streams" above. */
 int r2s_plan_run_dev(r2s_plan *plan, const double *dX, int64_t nnp, const int64_t *dIEN, int64_t nel,
                      const double *d_rho_n, double rho_t, const r2s_grid *grid,
                      const r2s_params *params, int64_t k_begin, int64_t k_end, int32_t mode,
