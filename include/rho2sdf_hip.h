@@ -36,14 +36,15 @@
  *     Return only after `stream` has drained (they hand counts to the host, or size their work from counts read back):
  *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
  *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
- *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev.
+ *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev,
+ *     r2s_mesh_sections_dev.
  *     A caller should still order its consumers on `stream`, not on that wait.
  *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
  *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
  *     on that run's stream before the plan's next run; different plans are independent and may be driven on different
  *     streams.  A field (r2s_rbf_field) and a mesh index are only read by their _dev entry points: one object may be used
  *     from several streams and threads at once.  The entry points that keep work buffers per device (removal and component
- *     analysis, smoothing, extraction, redistancing, shells) take a lock for the length of the call: concurrent calls are
+ *     analysis, smoothing, extraction, redistancing, shells, sections) take a lock for the length of the call: concurrent calls are
  *     safe and run one after the other.
  *   - devices.  Device pointers and `stream` belong to one device.  r2s_plan_run_dev and r2s_plan_pack_tiles*_dev make the
  *     plan's device current (and leave it current); the _dev entry points of a field or an index refuse a call while
@@ -696,6 +697,78 @@ int r2s_last_mesh_shells(int64_t *counts_out, double *sums_out, int64_t capacity
 int r2s_mesh_shells_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris,
                         int32_t *d_shell_of_tri, int64_t *d_counts, double *d_sums, int64_t shell_capacity,
                         int64_t *n_shells, double ref_point[3], int64_t totals[8], void *stream);
+
+/* ---- mesh sections: plane contours of a triangle mesh -------------------------------------------
+ * Cuts the mesh with the planes h = c_k: per level the contours, whether each is closed, and the length, area vector and first
+ * moments of each - cross-section properties along an axis, and the closed loops of every layer.  verts float32 [n_verts][3],
+ * tris int32 [n_tris][3], 0-based; normal double[3] (host), finite, not all zero, every |component| <= 2^500 (no height can
+ * overflow), NOT normalised by the library; levels double [n_levels] (host), finite and strictly ascending.
+ *   - height: h(v) = (n_x*x + n_y*y) + n_z*z with x, y, z widened to double; every product and sum is rounded on its own (no
+ *     fma).  With normal = (0, 0, 1) this is z exactly.
+ *   - side: vertex v is ABOVE level k iff h(v) >= c_k, else BELOW.  No vertex is ever "on" a plane: this is the whole
+ *     degeneracy rule.
+ *   - collapsed triangle: two equal vertex INDICES; it takes no part and is counted in the totals.
+ *   - crossing: a non-collapsed triangle crosses level k iff its vertices are not all on one side, hmin < c_k <= hmax.  The
+ *     crossed levels are a contiguous range of k; in each of them exactly two of the triangle's half-edges change side.
+ *   - node: a pair (level k, undirected edge {i, j}, i < j) whose ends are on different sides.  Its point is taken from the
+ *     smaller index, whichever triangle asks: t = (c_k - h_i) / (h_j - h_i), p_a = X_i,a + t * (X_j,a - X_i,a) per axis in
+ *     double, no fma.  The triangles that share the edge get the same bits, and 0 <= t <= 1.
+ *   - segment: one per (triangle, crossed level), directed FROM the node on the half-edge that goes above -> below TO the node
+ *     on the half-edge that goes below -> above, walking the corners 0 -> 1 -> 2 -> 0.  On a closed, outward-oriented shell
+ *     the material is on the left when seen from the tip of `normal`: outer loops run counter-clockwise, holes clockwise.
+ *   - segment id: the position in ascending (triangle index, level).  More than 2^31 - 1 segments: R2S_ERR_UNSUPPORTED.
+ *   - node classes, over the segment ends at a node (like the shells' edge classes): one outgoing (FROM) and one incoming (TO)
+ *     end: regular; one end: open; two ends of the same kind: flipped; three or more: branch.
+ *   - contour: a connected component of the segments of one level, two segments being adjacent when they share a node of any
+ *     class.  It is CLOSED iff all its nodes are regular; it is then one simple cycle.  Contours are numbered by ascending
+ *     (level, smallest segment id).
+ *   - output order of the segments: by contour number; inside a closed contour from its smallest segment id along the
+ *     successors (the segment whose FROM node is this one's TO node); inside any other contour in ascending segment id (no
+ *     walk is promised there).
+ *   - tables: contour_start int64 [n_contours + 1] (output positions); per output position seg_tri int32 and seg_points
+ *     double [2][3] (from, to); per contour the integer record int64[8]: [0] level k, [1] first segment id, [2] n_segs,
+ *     [3] n_nodes, [4] open, [5] flipped, [6] branch nodes, [7] 0 (reserved); and the Float64 record double[7] about the
+ *     shells' reference point r (same definition, returned in ref_point): the sums over the contour's segments of the terms
+ *       A = from - r, B = to - r (one subtraction each), D = B - A,
+ *       C_x = A_y*B_z - A_z*B_y, C_y = A_z*B_x - A_x*B_z, C_z = A_x*B_y - A_y*B_x,   w = (n_x*C_x + n_y*C_y) + n_z*C_z:
+ *       [0] length sqrt((D_x*D_x + D_y*D_y) + D_z*D_z), [1..3] C, [4..6] w * (A_a + B_a),
+ *     every operation rounded on its own.  Of a closed contour 0.5 * (n . sum C) / |n| is the signed area (negative: a hole)
+ *     and r + sum [4..6] / (3 * n . sum C) the centroid up to its offset along the normal.
+ *   - totals, int64[8]: [0] contours, [1] segments, [2] collapsed triangles, [3] nodes, [4] open, [5] flipped, [6] branch
+ *     nodes, [7] closed contours.
+ *   - summation: the shells' scheme on the output order - blocks of 256 consecutive output positions are summed per contour
+ *     in a fixed binary tree (round d = 1, 2, .., 128: position p takes position p + d of its block when both belong to one
+ *     contour), then the up to 64 equal runs of a contour's consecutive block partials are summed in ascending block order
+ *     and those run sums in a fixed binary tree.  No floating-point atomics and no library reduction; the same input gives the
+ *     same bits on every call and from both variants.  Under a permutation of the triangles the points and every integer
+ *     follow exactly (a closed loop as a cyclic sequence: its head segment may change), the sums to within
+ *     (n_segs + K) * 2^-53 * T, T the sum of the absolute values of the term's monomials in A, B and K the roundings on its
+ *     longest chain (length 5, C 4, moments 10; counted in tests/mesh_sections_ref64.py).
+ * r2s_mesh_sections: host arrays, `device` (-1 = current).  *n_contours, *n_segments, ref_point and totals are always written
+ * on success; the tables become the calling thread's last result, read with r2s_last_mesh_sections: contour_start_out
+ * [contour_capacity + 1], counts_out [contour_capacity][8], sums_out [contour_capacity][7], seg_tri_out [segment_capacity],
+ * seg_points_out [segment_capacity][2][3]; the counts are always the full ones, the first min(capacity, n) records of each
+ * group are written (contour_start: one more); pointers of a group may be NULL only with its capacity == 0.
+ * r2s_mesh_sections_dev: d_verts / d_tris and the five tables are device pointers on the current device, read after the work
+ * queued on `stream`; normal, levels and the scalar outputs are host pointers.  The counts are always returned; the tables
+ * are written only when contour_capacity >= *n_contours and segment_capacity >= *n_segments (else all are left untouched:
+ * ask with capacities 0, then call again).  Synchronous on return; it does not touch the thread's last result.  Work buffers
+ * are kept per device and freed by r2s_release_cache.
+ * R2S_ERR_ARG before anything else runs, outputs untouched: as for r2s_mesh_shells (NULL arrays with a count, a negative
+ * count, NULL scalar outputs, a triangle index outside [0, n_verts), a non-finite vertex), and a NULL, non-finite, zero or
+ * too large normal, NULL levels with a count, non-finite or not strictly ascending levels, NULL tables with a capacity.
+ * n_tris or n_levels > 2^30, n_verts beyond 32 bits: R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  n_levels == 0 or
+ * n_tris == 0 succeeds with nothing.  Not here: which loop lies inside which, infill, offsetting. */
+int r2s_mesh_sections(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, const double normal[3],
+                      const double *levels, int64_t n_levels, int32_t device, int64_t *n_contours, int64_t *n_segments,
+                      double ref_point[3], int64_t totals[8]);
+int r2s_last_mesh_sections(int64_t *contour_start_out, int64_t *counts_out, double *sums_out, int64_t contour_capacity,
+                           int32_t *seg_tri_out, double *seg_points_out, int64_t segment_capacity, int64_t *n_contours,
+                           int64_t *n_segments);
+int r2s_mesh_sections_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, const double normal[3],
+                          const double *levels, int64_t n_levels, int64_t *d_contour_start, int64_t *d_counts, double *d_sums,
+                          int64_t contour_capacity, int32_t *d_seg_tri, double *d_seg_points, int64_t segment_capacity,
+                          int64_t *n_contours, int64_t *n_segments, double ref_point[3], int64_t totals[8], void *stream);
 
 /* ---- on-disk output ------------------------------------------------------------------ */
 

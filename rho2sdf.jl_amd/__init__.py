@@ -14,7 +14,8 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   mesh_distance, mesh_distance_dev, redistance, redistance_dev, last_distance_stats,
                   MeshIndex, redistance_full, redistance_full_dev, surface_deviation,
                   vertex_normals, surface_thickness, surface_thickness_dev,
-                  MeshShells, mesh_shells, mesh_shells_dev, select_shells)
+                  MeshShells, mesh_shells, mesh_shells_dev, select_shells,
+                  MeshSections, mesh_sections, mesh_sections_dev)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
@@ -26,4 +27,5 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "MeshIndex", "redistance_full", "redistance_full_dev", "surface_deviation",
            "vertex_normals", "surface_thickness", "surface_thickness_dev",
            "MeshShells", "mesh_shells", "mesh_shells_dev", "select_shells",
+           "MeshSections", "mesh_sections", "mesh_sections_dev",
            "_lib"]

@@ -200,6 +200,12 @@ SYMBOLS = [
     ("r2s_last_mesh_shells", ctypes.c_int, [c_int64_p, c_double_p, ctypes.c_int64, c_int64_p]),
     ("r2s_mesh_shells_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, c_int64_p, c_double_p,
                                            c_int64_p, _P]),
+    ("r2s_mesh_sections", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64,
+                                         ctypes.c_int32, c_int64_p, c_int64_p, c_double_p, c_int64_p]),
+    ("r2s_last_mesh_sections", ctypes.c_int, [c_int64_p, c_int64_p, c_double_p, ctypes.c_int64, c_int32_p, c_double_p, ctypes.c_int64,
+                                              c_int64_p, c_int64_p]),
+    ("r2s_mesh_sections_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, _P, _P, _P,
+                                             ctypes.c_int64, _P, _P, ctypes.c_int64, c_int64_p, c_int64_p, c_double_p, c_int64_p, _P]),
 ]
 
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8

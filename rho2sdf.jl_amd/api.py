@@ -847,6 +847,140 @@ def select_shells(verts, tris, shells, keep):
     return v[used], remap[sel].astype(t.dtype).reshape(-1, 3)
 
 
+class MeshSections:
+    """The plane sections of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_sections): the raw tables and what follows from
+    them.  Raw: `normal` (3,), `levels` (n_levels,), `contour_start` (n + 1,) int64, `counts` (n, 8) int64 (level, first segment id,
+    n_segs, n_nodes, open, flipped, branch, 0), `sums` (n, 7) float64 (length, the area vector C, the first moments about
+    `ref_point`), `ref_point` (3,), `totals` (8,) int64 (contours, segments, collapsed triangles, nodes, open, flipped, branch,
+    closed contours), and per output position `seg_tri` (m,) int32 and `seg_points` (m, 2, 3) float64 (from, to); device tensors
+    from mesh_sections_dev keep the two segment tables on the device.  Derived per contour, in float64 numpy:
+        closed   = (open == 0) & (flipped == 0) & (branch == 0)
+        area     = 0.5 * (normal . C) / |normal|, signed: negative for a hole; is_hole = closed & (area < 0)
+        length   = sums[:, 0]
+        centroid = ref_point + M / (3 * normal . C), moved along the normal onto the plane of its level; NaN unless closed with
+                   a non-zero area                                      M = sums[:, 4:7]
+    and per level (n_levels,): level_n_contours, level_area (the closed contours, holes subtracting), level_perimeter (all
+    contours) and level_centroid (the closed contours together; NaN without area)."""
+
+    def __init__(self, normal, levels, contour_start, counts, sums, ref_point, totals, seg_tri, seg_points):
+        self.normal, self.levels = np.asarray(normal, np.float64).reshape(3), np.asarray(levels, np.float64).reshape(-1)
+        self.contour_start, self.counts, self.sums, self.ref_point, self.totals = contour_start, counts, sums, ref_point, totals
+        self.seg_tri, self.seg_points = seg_tri, seg_points
+
+    n_contours = property(lambda s: len(s.counts))
+    n_segments = property(lambda s: int(s.totals[1]))
+    level = property(lambda s: s.counts[:, 0])
+    first_seg = property(lambda s: s.counts[:, 1])
+    n_segs = property(lambda s: s.counts[:, 2])
+    n_nodes = property(lambda s: s.counts[:, 3])
+    n_open = property(lambda s: s.counts[:, 4])
+    n_flipped = property(lambda s: s.counts[:, 5])
+    n_branch = property(lambda s: s.counts[:, 6])
+    closed = property(lambda s: (s.n_open == 0) & (s.n_flipped == 0) & (s.n_branch == 0))
+    length = property(lambda s: s.sums[:, 0])
+    area = property(lambda s: 0.5 * (s.sums[:, 1:4] @ s.normal) / np.sqrt(s.normal @ s.normal))
+    is_hole = property(lambda s: s.closed & (s.area < 0))
+
+    def __len__(self):
+        return len(self.counts)
+
+    def _on_plane(self, W, M, c):
+        """ref_point + M / (3 W) moved along the normal to height c (W = normal . sum C; NaN where W is 0)"""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            g = self.ref_point[None, :] + M / (3.0 * np.where(W != 0, W, np.nan))[:, None]
+        return g + ((c - g @ self.normal) / (self.normal @ self.normal))[:, None] * self.normal[None, :]
+
+    @property
+    def centroid(self):
+        W = np.where(self.closed, self.sums[:, 1:4] @ self.normal, 0.0)
+        return self._on_plane(W, self.sums[:, 4:7], self.levels[self.level])
+
+    def _per_level(self, values, mask=None):
+        out = np.zeros((len(self.levels),) + values.shape[1:])
+        k = self.level if mask is None else self.level[mask]
+        np.add.at(out, k, values if mask is None else values[mask])
+        return out
+
+    level_n_contours = property(lambda s: np.bincount(s.level, minlength=len(s.levels)))
+    level_area = property(lambda s: s._per_level(s.area, s.closed))
+    level_perimeter = property(lambda s: s._per_level(s.length))
+
+    @property
+    def level_centroid(self):
+        W = self._per_level(self.sums[:, 1:4] @ self.normal, self.closed)
+        return self._on_plane(W, self._per_level(self.sums[:, 4:7], self.closed), self.levels)
+
+    def loops(self, level):
+        """the closed contours of level index `level`, in contour order: a list of (m, 3) float64 arrays, the FROM points of
+        the m segments in walking order (the loop closes from the last point back to the first); material is on the left
+        seen from the tip of the normal, so outer loops run counter-clockwise and holes clockwise"""
+        pts = self.seg_points
+        pts = np.asarray(pts.cpu() if hasattr(pts, "cpu") else pts)
+        return [pts[self.contour_start[c]:self.contour_start[c + 1], 0].copy()
+                for c in np.nonzero((self.level == int(level)) & self.closed)[0]]
+
+
+def _section_inputs(normal, levels):
+    nrm = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1)
+    lev = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    if nrm.shape != (3,):
+        raise L.R2SError("normal must have three components")
+    return nrm, lev
+
+
+def mesh_sections(verts, tris, normal, levels, *, device=-1):
+    """The sections of a triangle mesh (verts (nv, 3) float32, tris (nt, 3) int32, 0-based) with the planes normal . x = levels[k]
+    (normal (3,), not normalised; levels ascending): per level the contours, their node classes, lengths, areas and first moments,
+    and every segment in output order -> MeshSections (its docstring has the fields and the formulas of the derived ones).  One
+    library call and a copy of the thread's last tables."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    nrm, lev = _section_inputs(normal, levels)
+    nc, ns = ctypes.c_int64(), ctypes.c_int64()
+    ref, tot = np.zeros(3), np.zeros(8, np.int64)
+    L.check(L.lib().r2s_mesh_sections(_f(v) if len(v) else None, len(v), t.ctypes.data_as(L.c_int32_p) if len(t) else None, len(t),
+                                      _d(nrm), _d(lev) if len(lev) else None, len(lev), int(device), ctypes.byref(nc), ctypes.byref(ns),
+                                      _d(ref), _i(tot)))
+    start, counts, sums = np.zeros(nc.value + 1, np.int64), np.empty((nc.value, 8), np.int64), np.empty((nc.value, 7))
+    seg_tri, pts = np.empty(ns.value, np.int32), np.empty((ns.value, 2, 3))
+    if nc.value:
+        L.check(L.lib().r2s_last_mesh_sections(_i(start), _i(counts), _d(sums), nc.value, seg_tri.ctypes.data_as(L.c_int32_p), _d(pts),
+                                               ns.value, ctypes.byref(nc), ctypes.byref(ns)))
+    return MeshSections(nrm, lev, start, counts, sums, ref, tot, seg_tri, pts)
+
+
+def mesh_sections_dev(verts, tris, normal, levels, stream=None, *, contour_capacity=0, segment_capacity=0):
+    """mesh_sections on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous; normal and
+    levels are host values).  The contour tables come back as numpy arrays, seg_tri and seg_points stay device tensors.  The
+    library writes the tables only into room for all contours and segments: with more of either than the capacities the call
+    is made a second time."""
+    import torch
+    _mesh_tensors(verts, tris)
+    nrm, lev = _section_inputs(normal, levels)
+    st = _stream(stream)
+    nc, ns = ctypes.c_int64(), ctypes.c_int64()
+    ref, tot = np.zeros(3), np.zeros(8, np.int64)
+    ccap, scap = int(contour_capacity), int(segment_capacity)
+    vp = ctypes.c_void_p
+    dev = verts.device
+    while True:
+        start = torch.zeros(ccap + 1, dtype=torch.int64, device=dev)
+        counts = torch.empty((ccap, 8), dtype=torch.int64, device=dev)
+        sums = torch.empty((ccap, 7), dtype=torch.float64, device=dev)
+        seg_tri = torch.empty(scap, dtype=torch.int32, device=dev)
+        pts = torch.empty((scap, 2, 3), dtype=torch.float64, device=dev)
+        L.check(L.lib().r2s_mesh_sections_dev(
+            vp(verts.data_ptr()), verts.numel() // 3, vp(tris.data_ptr()), tris.numel() // 3, _d(nrm), _d(lev) if len(lev) else None,
+            len(lev), vp(start.data_ptr()) if ccap else None, vp(counts.data_ptr()) if ccap else None,
+            vp(sums.data_ptr()) if ccap else None, ccap, vp(seg_tri.data_ptr()) if scap else None, vp(pts.data_ptr()) if scap else None,
+            scap, ctypes.byref(nc), ctypes.byref(ns), _d(ref), _i(tot), st))
+        if nc.value <= ccap and ns.value <= scap:
+            break
+        ccap, scap = max(ccap, nc.value), max(scap, ns.value)
+    return MeshSections(nrm, lev, start[:nc.value + 1].cpu().numpy(), counts[:nc.value].cpu().numpy(), sums[:nc.value].cpu().numpy(),
+                        ref, tot, seg_tri[:ns.value], pts[:ns.value])
+
+
 def vertex_normals(verts, tris):
     """area-weighted vertex normals of the winding, float64 (nv, 3), not normalised: the sum of (b-a)x(c-a) over the
     triangles at a vertex, from the float32 vertices widened to float64, added in the order of the triangles (corner 0 of
@@ -1303,7 +1437,7 @@ class Rho2sdfOptions:
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
             info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False, redistance_cells=None,
-            signed_distance=False, deviation=False, thickness=False, shells=False):
+            signed_distance=False, deviation=False, thickness=False, shells=False, sections=None):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -1332,7 +1466,9 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     spacing of the fine lattice) - (thickness, hit_tri, side) at every vertex of the extracted surface, a further library
     call after the first.
     shells=True (needs `info`; implies surface=True): info["shells"] = mesh_shells(*info["surface"]) - the bodies of the exported
-    mesh, their topology, volumes and enclosed voids - a further library call after the first."""
+    mesh, their topology, volumes and enclosed voids - a further library call after the first.
+    sections=(normal, levels) (needs `info`; implies surface=True): info["sections"] = mesh_sections(*info["surface"], normal,
+    levels) - the cross-sections of the exported mesh along an axis, a further library call after the first."""
     options = options or Rho2sdfOptions()
     if (signed_distance or deviation) and info is None:
         raise L.R2SError("signed_distance / deviation need an `info` dict for the result")
@@ -1340,7 +1476,9 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
         raise L.R2SError("thickness needs an `info` dict for the result")
     if shells and info is None:
         raise L.R2SError("shells needs an `info` dict for the result")
-    surface = bool(surface) or bool(thickness) or bool(shells)
+    if sections is not None and info is None:
+        raise L.R2SError("sections needs an `info` dict for the result")
+    surface = bool(surface) or bool(thickness) or bool(shells) or sections is not None
     if redistance_cells is not None and (info is None or not (float(redistance_cells) > 0.0)):
         raise L.R2SError("redistance_cells must be a positive number and needs an `info` dict for the result")
     mesh = Mesh(X, IEN, options.element_type)
@@ -1402,6 +1540,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
         info["thickness"] = surface_thickness(*mesh_out, skip=0.5 * _iso_lattice(sdf_grid, smooth)[2], device=device)
     if shells:
         info["shells"] = mesh_shells(*mesh_out, device=device)
+    if sections is not None:
+        info["sections"] = mesh_sections(*mesh_out, sections[0], sections[1], device=device)
     if export_results:
         vti = export_sdf_results(fine_sdf, sdf_grid, taskName, smooth, options.rbf_interp, mesh.element_type)
         if surface:

@@ -153,4 +153,8 @@ int upload_mesh(DevBuf& dv, DevBuf& dt, const float* verts, int64_t n_verts, con
 // frees the work buffers the shell calls keep per device; called by r2s_release_cache()
 void release_shell_work();
 
+// ---- mesh sections (r2s_mesh_sections.hip) ----------------------------------------------------------------------------
+// frees the work buffers the section calls keep per device; called by r2s_release_cache()
+void release_section_work();
+
 }  // namespace r2s_int

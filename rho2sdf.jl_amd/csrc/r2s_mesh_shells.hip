@@ -30,6 +30,7 @@
 
 #include "r2s_common.hpp"
 #include "r2s_internal.hpp"
+#include "r2s_mesh_graph.hpp"
 
 using namespace r2s_int;
 
@@ -41,52 +42,6 @@ constexpr int64_t MS_MAX_TRIS = (int64_t)1 << 30;
 // slots of the small device array: [0..5] the bounds, then
 constexpr int MS_COLLAPSED = 6, MS_NSHELLS = 7, MS_TOT = 8;   // [MS_TOT .. MS_TOT + 4]: edges, boundary, flipped, non-manifold, vertices
 constexpr int MS_SMALL = 16;
-
-__device__ inline uint32_t ms_ordered(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-inline float ms_unordered(uint32_t u)
-{
-    const uint32_t b = (u >> 31) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    std::memcpy(&f, &b, sizeof f);
-    return f;
-}
-
-__device__ inline bool ms_collapsed(const int32_t* __restrict__ tris, int64_t t, int32_t& i0, int32_t& i1, int32_t& i2)
-{
-    i0 = tris[3 * t], i1 = tris[3 * t + 1], i2 = tris[3 * t + 2];
-    return i0 == i1 || i1 == i2 || i0 == i2;
-}
-
-// bb[0..2] = min, bb[3..5] = max over all vertices, as ordered bit patterns (bb starts as ~0, ~0, ~0, 0, 0, 0)
-__global__ void __launch_bounds__(256) ms_bounds_kernel(const float* __restrict__ verts, int64_t nverts, uint64_t* __restrict__ small)
-{
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-    if (v < nverts) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) lo[k] = hi[k] = ms_ordered(verts[3 * v + k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t a = __shfl_xor(lo[k], d, 64), b = __shfl_xor(hi[k], d, 64);
-            lo[k] = a < lo[k] ? a : lo[k];
-            hi[k] = b > hi[k] ? b : hi[k];
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            atomicMin((unsigned long long*)&small[k], (unsigned long long)lo[k]);
-            atomicMax((unsigned long long*)&small[3 + k], (unsigned long long)hi[k]);
-        }
-    }
-}
 
 // one thread per triangle: its three half-edge keys, parent[t] = t, the referenced-vertex flags, the collapsed count
 __global__ void __launch_bounds__(256) ms_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
@@ -110,32 +65,6 @@ __global__ void __launch_bounds__(256) ms_key_kernel(const int32_t* __restrict__
     }
     const unsigned long long m = __ballot(col);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MS_COLLAPSED], (unsigned long long)__popcll(m));
-}
-
-// parents are rewritten by other CUs during the kernel: bypass the per-CU L1
-__device__ inline uint32_t ms_load(const uint32_t* L, uint32_t i) { return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x; every visited node is pointed at its grandparent (atomicMin: a parent only ever moves to a smaller ancestor)
-__device__ inline uint32_t ms_find(uint32_t* L, uint32_t x)
-{
-    for (;;) {
-        const uint32_t p = ms_load(L, x);
-        if (p == x) return x;
-        const uint32_t g = ms_load(L, p);
-        if (g != p) atomicMin(&L[x], g);
-        x = g;
-    }
-}
-
-__device__ inline void ms_union(uint32_t* L, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = ms_find(L, a);
-        b = ms_find(L, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }   // link the larger root under the smaller
-        if (atomicCAS(&L[a], a, b) == a) return;             // a was still a root
-    }
 }
 
 // one thread per sorted half-edge: joins its triangle to that of the member before it in the same run
@@ -429,14 +358,6 @@ struct ShellTables {
 };
 thread_local ShellTables g_last_shells;
 
-inline unsigned ms_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline unsigned ms_bits(uint64_t max_value)
-{
-    unsigned b = 1;
-    while (b < 64 && (max_value >> b)) ++b;
-    return b;
-}
-
 // The shells of the device mesh on the current device, after the work queued on `st`; synchronous.  Leaves shell_of_tri in
 // w.shell [n_tris] and the tables in w.counts / w.sums [n_shells]; the scalars go to the host pointers.
 int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, hipStream_t st, ShellWork& w, int64_t* n_shells,
@@ -489,9 +410,8 @@ int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
     }
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    double r[3] = {0.0, 0.0, 0.0};
-    if (n_verts > 0)
-        for (int k = 0; k < 3; ++k) r[k] = 0.5 * ((double)ms_unordered((uint32_t)h_small[k]) + (double)ms_unordered((uint32_t)h_small[3 + k]));
+    double r[3];
+    ms_ref_point(h_small, n_verts, r);
     const int64_t nsh = (int64_t)h_small[MS_NSHELLS], ncol = (int64_t)h_small[MS_COLLAPSED], nvalid = n - ncol;
     if (nsh > 0) {
         const int64_t nblk = (nvalid + MS_BLOCK - 1) / MS_BLOCK;

@@ -3404,6 +3404,7 @@ void r2s_release_cache(void)
     r2s_int::release_iso_work();
     r2s_int::release_dist_work();
     r2s_int::release_shell_work();
+    r2s_int::release_section_work();
     r2s_int::release_host_sessions();
 }
 

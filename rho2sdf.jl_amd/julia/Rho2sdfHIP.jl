@@ -503,6 +503,65 @@ function mesh_shells_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{
     return n[], ref, totals
 end
 
+# The sections of a triangle mesh with the planes normal . x = levels[k] (include/rho2sdf_hip.h, r2s_mesh_sections): verts
+# 3 x nv Float32, tris 3 x nt 1-based, levels ascending -> (contour_start (1-based output positions, n + 1 entries), counts 8 x n
+# Int64 with level, first segment and nothing else made 1-based, sums 7 x n Float64, seg_tri (1-based), seg_points 3 x 2 x m
+# (from, to), ref_point, totals)
+function mesh_sections_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}, normal::AbstractVector{<:Real},
+                           levels::AbstractVector{<:Real}; device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 && length(normal) == 3 || error("verts and tris must be 3 x n, normal of length 3")
+    t0 = Int32.(tris) .- Int32(1)
+    nrm, lev = Vector{Float64}(normal), Vector{Float64}(levels)
+    nc, ns = Ref{Int64}(0), Ref{Int64}(0)
+    ref = zeros(Float64, 3)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_sections, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+                 Ptr{Int64}),
+                Matrix(verts), size(verts, 2), t0, size(t0, 2), nrm, isempty(lev) ? C_NULL : lev, length(lev), Int32(device), nc, ns, ref,
+                totals))
+    tables = last_mesh_sections_hip(nc[], ns[])
+    return (; tables..., ref_point = ref, totals = totals)
+end
+
+# the calling thread's last section tables (r2s_last_mesh_sections), indices made 1-based
+function last_mesh_sections_hip(contour_capacity::Integer, segment_capacity::Integer)
+    start = zeros(Int64, contour_capacity + 1)
+    counts = Matrix{Int64}(undef, 8, contour_capacity)
+    sums = Matrix{Float64}(undef, 7, contour_capacity)
+    seg_tri = Vector{Int32}(undef, segment_capacity)
+    pts = Array{Float64,3}(undef, 3, 2, segment_capacity)
+    nc, ns = Ref{Int64}(0), Ref{Int64}(0)
+    none = contour_capacity == 0
+    check(ccall((:r2s_last_mesh_sections, LIB[]), Cint,
+                (Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}),
+                none ? C_NULL : start, none ? C_NULL : counts, none ? C_NULL : sums, Int64(contour_capacity),
+                segment_capacity == 0 ? C_NULL : seg_tri, segment_capacity == 0 ? C_NULL : pts, Int64(segment_capacity), nc, ns))
+    start .+= 1
+    counts[1:2, :] .+= 1
+    seg_tri .+= Int32(1)
+    return (contour_start = start, counts = counts, sums = sums, seg_tri = seg_tri, seg_points = pts)
+end
+
+# the same on device arrays of the current device (raw pointers, e.g. of AMDGPU.jl ROCArrays; normal and levels are host
+# vectors); the tables are written only when both capacities hold everything -> (n_contours, n_segments, ref_point, totals);
+# indices stay 0-based on the device
+function mesh_sections_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer,
+                               normal::AbstractVector{<:Real}, levels::AbstractVector{<:Real}, d_contour_start::Ptr{Cvoid},
+                               d_counts::Ptr{Cvoid}, d_sums::Ptr{Cvoid}, contour_capacity::Integer, d_seg_tri::Ptr{Cvoid},
+                               d_seg_points::Ptr{Cvoid}, segment_capacity::Integer; stream::Ptr{Cvoid} = C_NULL)
+    nrm, lev = Vector{Float64}(normal), Vector{Float64}(levels)
+    nc, ns = Ref{Int64}(0), Ref{Int64}(0)
+    ref = zeros(Float64, 3)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_sections_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+                 Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), nrm, isempty(lev) ? C_NULL : lev, length(lev), d_contour_start, d_counts,
+                d_sums, Int64(contour_capacity), d_seg_tri, d_seg_points, Int64(segment_capacity), nc, ns, ref, totals, stream))
+    return nc[], ns[], ref, totals
+end
+
 # The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
 # +-Inf where the field has no surface.
 function redistance_full_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
