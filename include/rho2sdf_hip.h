@@ -37,14 +37,14 @@
  *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
  *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
  *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev,
- *     r2s_mesh_sections_dev.
+ *     r2s_mesh_sections_dev, r2s_mesh_weld_dev.
  *     A caller should still order its consumers on `stream`, not on that wait.
  *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
  *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
  *     on that run's stream before the plan's next run; different plans are independent and may be driven on different
  *     streams.  A field (r2s_rbf_field) and a mesh index are only read by their _dev entry points: one object may be used
  *     from several streams and threads at once.  The entry points that keep work buffers per device (removal and component
- *     analysis, smoothing, extraction, redistancing, shells, sections) take a lock for the length of the call: concurrent calls are
+ *     analysis, smoothing, extraction, redistancing, shells, sections, weld) take a lock for the length of the call: concurrent calls are
  *     safe and run one after the other.
  *   - devices.  Device pointers and `stream` belong to one device.  r2s_plan_run_dev and r2s_plan_pack_tiles*_dev make the
  *     plan's device current (and leave it current); the _dev entry points of a field or an index refuse a call while
@@ -481,7 +481,9 @@ int r2s_rbf_field_project_dev(const r2s_rbf_field *f, float *d_points_inout, int
  *   - triangles (0-based int32 vertex indices) by cube linear index, then in the order of a 256-case face-consistent
  *     table (tools/gen_iso_table.py: ambiguous faces separate the interior corners), at most 5 per cube; normals
  *     (v1-v0)x(v2-v0) point from the interior to the exterior.  Closed where the interior does not touch the lattice
- *     border; there is no capping and coincident vertices (exact-iso points) are not welded.
+ *     border; there is no capping and coincident vertices (exact-iso points) are not welded here.  The mesh is topologically
+ *     closed as it stands; r2s_mesh_weld merges the coincident vertices on request, which collapses the zero-area triangles
+ *     between them and can leave non-manifold vertices or edges that r2s_mesh_shells reports - so it is offered, not applied.
  *   - >= 2^31 vertices: R2S_ERR_UNSUPPORTED.  Any dim < 2, a non-positive or non-finite spacing or a NaN iso: R2S_ERR_ARG
  *     before any device work.
  * Host variant: *n_verts / *n_tris are always the full counts; the first min(capacity, n) entries are written (verts_out
@@ -690,7 +692,8 @@ int r2s_mesh_index_raycast_dev(const r2s_mesh_index *index, const void *d_origin
  * R2S_ERR_ARG before anything else runs, outputs untouched: NULL arrays with a count, a negative count, NULL n_shells /
  * ref_point / totals, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the host; _dev: the
  * check kernel of r2s_mesh_distance_dev).  n_tris > 2^30 or n_verts beyond 32 bits: R2S_ERR_UNSUPPORTED.  No GPU:
- * R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 shells.  Not here: which shell encloses which, welding, repair. */
+ * R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 shells.  Not here: which shell encloses which, repair; for welding
+ * see r2s_mesh_weld below. */
 int r2s_mesh_shells(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
                     int32_t *shell_of_tri_out, int64_t *n_shells, double ref_point[3], int64_t totals[8]);
 int r2s_last_mesh_shells(int64_t *counts_out, double *sums_out, int64_t capacity, int64_t *n_shells);
@@ -770,6 +773,61 @@ int r2s_mesh_sections_dev(const float *d_verts, int64_t n_verts, const int32_t *
                           int64_t contour_capacity, int32_t *d_seg_tri, double *d_seg_points, int64_t segment_capacity,
                           int64_t *n_contours, int64_t *n_segments, double ref_point[3], int64_t totals[8], void *stream);
 
+/* ---- mesh weld: shared vertices for a triangle soup or a mesh with coincident vertices ---------------
+ * Every mesh tool above wants an INDEXED mesh: without shared vertices r2s_mesh_shells reports n_tris shells with three boundary
+ * edges each and r2s_mesh_sections finds no closed loop.  The weld turns unindexed triangles (what an STL file holds, see
+ * r2s_import_stl) or a mesh with coincident vertices into a mesh whose equal points are one vertex.  Integer and copy work only.
+ *   - input: verts float32 [n_verts][3]; tris int32 [n_tris][3], 0-based.  tris == NULL means SOUP: triangle t uses the vertices
+ *     3t, 3t + 1, 3t + 2 and there are n_verts / 3 triangles; n_verts % 3 != 0 is R2S_ERR_ARG, and the n_tris argument must then be
+ *     0 or n_verts / 3.  (A mesh with vertices and no triangle passes a non-NULL tris with n_tris == 0.)
+ *   - which vertices are the same, snap == 0: two vertices are the same iff their x, y and z compare equal as float32.  So
+ *     -0.0f == +0.0f, and denormals are ordinary values (nothing is flushed).
+ *   - which vertices are the same, snap > 0: iff they fall into the same cell q_a = floor((double)v_a / snap) on every axis a: one
+ *     division rounded in double, then floor.  This is GRID SNAPPING, NOT A DISTANCE TOLERANCE: two points closer than snap that
+ *     lie on either side of a cell face stay apart, and two points of one cell merge although they may be almost snap * sqrt(3)
+ *     apart.  Every q_a must lie in [-2^31, 2^31); otherwise R2S_ERR_ARG ("snap is too fine for the extent"), outputs untouched.
+ *     A negative or non-finite snap is R2S_ERR_ARG.
+ *   - class, representative, output order: a class is a set of vertices that are the same; its representative is the member with
+ *     the smallest input index.  The output vertices are the representatives in ascending input index (first-occurrence order).
+ *     Their coordinates are COPIED bit for bit - no averaging, no snapping to a cell centre: every output vertex is an input
+ *     vertex (of signed zeros the first one's bits are kept).
+ *   - vert_map[i]: the output index of vertex i's class, or -1 if the class was dropped as unreferenced (see the flags).
+ *   - triangles are remapped through vert_map; the survivors keep their input order and their corner order.  tri_map[t]: the
+ *     output index of triangle t, or -1 if it was dropped.
+ *   - collapsed triangle: two of its three remapped indices are equal.  Duplicates: non-collapsed triangles that are equal up to
+ *     a rotation of their corners (the same orientation); (a,b,c), (b,c,a), (c,a,b) are duplicates of each other, (a,c,b) is not.
+ *   - flags, a bit mask: R2S_WELD_DROP_COLLAPSED (1) drops the collapsed triangles; R2S_WELD_DROP_DUPLICATES (2) keeps, of every
+ *     set of duplicates, the one with the smallest input index; R2S_WELD_DROP_UNUSED (4) drops the output vertices that no
+ *     surviving triangle references, the rest keep their relative order.  Any other bit: R2S_ERR_ARG.
+ *   - totals, int64[8]: [0] output vertices, [1] output triangles, [2] n_verts minus the number of classes (vertices merged
+ *     away), [3] collapsed triangles after the weld, counted whether or not they are dropped, [4] same-orientation duplicates
+ *     (every member of a duplicate set but its first), counted likewise, [5] opposite pairs: classes of non-collapsed triangles on
+ *     the same three vertices that contain both orientations, counted once per class and never dropped, [6] classes that no
+ *     surviving triangle references, counted whether or not they are dropped, [7] 0.
+ * r2s_mesh_weld: host arrays, `device` (-1 = current).  The outputs are sized by the caller to the INPUT counts (verts_out
+ * [n_verts][3], tris_out [n_tris][3], vert_map_out [n_verts], tri_map_out [n_tris]; soup: n_tris = n_verts / 3); only the first
+ * totals[0] rows of verts_out and totals[1] rows of tris_out are written.  The two maps may be NULL.
+ * r2s_mesh_weld_dev: the same with device pointers on the current device, read after the work queued on `stream`; totals is a
+ * host pointer.  Synchronous on return.  The outputs must not overlap the inputs.  Work buffers are kept per device and freed
+ * by r2s_release_cache.
+ * Refused before any output is touched, as by r2s_mesh_shells: R2S_ERR_ARG for NULL arrays with a count (NULL tris excepted: the
+ * soup), NULL outputs with a count or NULL totals, a negative count, a triangle index outside [0, n_verts) or a non-finite vertex
+ * (host variant: on the host; _dev: the check kernel of r2s_mesh_distance_dev); n_tris > 2^30 or n_verts >= 2^31:
+ * R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  n_verts == 0 or n_tris == 0 succeed.
+ * The same input gives the same output on every call and from both variants (no result depends on an atomic's arrival order).
+ * Caveat for meshes of r2s_extract_isosurface: they are topologically closed WITHOUT welding; welding their exact-iso vertices
+ * collapses the zero-area triangles between them and can leave non-manifold vertices or edges, which r2s_mesh_shells reports.
+ * Not here: distance-tolerance welding, re-orientation of flipped triangles, hole filling, decimation. */
+#define R2S_WELD_DROP_COLLAPSED 1
+#define R2S_WELD_DROP_DUPLICATES 2
+#define R2S_WELD_DROP_UNUSED 4
+int r2s_mesh_weld(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, double snap, int32_t flags,
+                  int32_t device, float *verts_out, int32_t *tris_out, int32_t *vert_map_out, int32_t *tri_map_out,
+                  int64_t totals[8]);
+int r2s_mesh_weld_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, double snap, int32_t flags,
+                      float *d_verts_out, int32_t *d_tris_out, int32_t *d_vert_map_out, int32_t *d_tri_map_out,
+                      int64_t totals[8], void *stream);
+
 /* ---- on-disk output ------------------------------------------------------------------ */
 
 /* binary STL of a triangle mesh (verts [n_verts][3], tris [n_tris][3] 0-based); host only, no device; ".stl" appended
@@ -777,6 +835,25 @@ int r2s_mesh_sections_dev(const float *d_verts, int64_t n_verts, const int32_t *
  * normalised (v1-v0)x(v2-v0) ((0,0,0) for zero area), the three vertices, attribute 0.  >= 2^32 facets:
  * R2S_ERR_UNSUPPORTED; an index outside [0, n_verts): R2S_ERR_ARG. */
 int r2s_export_stl(const char *filename, const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris);
+
+/* The triangles of an STL file as a soup: verts float32 [3 n_tris][3], triangle t = vertices 3t, 3t + 1, 3t + 2 (the input of
+ * r2s_mesh_weld with tris == NULL).  Facet normals and attribute bytes are ignored.  Host only, no device.
+ *   - the file is BINARY when its size equals 84 + 50 * count, count the little-endian uint32 at byte 80 (whatever the header
+ *     says, "solid" included); the coordinates are taken bit for bit.
+ *   - otherwise it is parsed as ASCII: solid [name] / facet normal nx ny nz / outer loop / vertex x y z (three times) / endloop /
+ *     endfacet / endsolid [name].  Any whitespace between the words, any case of the keywords, several solid blocks in one file;
+ *     a name runs to the next facet / endsolid (after solid) or solid (after endsolid) keyword.  Each coordinate is read with
+ *     strtod and that double is rounded to float32 once.
+ *   - R2S_ERR_ARG (the code of r2s_import_vtu for malformed files) with a text in r2s_last_error: a file that cannot be opened, a
+ *     truncated file (binary: the size does not fit; ASCII: the text ends inside a solid), a facet without exactly three
+ *     vertices, an unknown word, a coordinate that is not a number or not finite as float32.  *out is zeroed then.
+ * verts is malloc'ed by the library: release it with r2s_free_stl_mesh (NULL-safe, zeroes the struct). */
+typedef struct {
+    int64_t n_tris;
+    float *verts; /* [3 * n_tris][3] */
+} r2s_stl_mesh;
+int r2s_import_stl(const char *filename, r2s_stl_mesh *out);
+void r2s_free_stl_mesh(r2s_stl_mesh *m);
 
 /* exportSdfToVTI(filename, grid, values, value_label, smooth)       src/DataExport/ExportToVTI.jl:22-67
  * VTK ImageData: dimensions N*smooth+1 (smooth = 0: N+1, i.e. `nothing`), Origin = AABB_min, Spacing =

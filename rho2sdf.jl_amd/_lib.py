@@ -76,6 +76,10 @@ class R2SVtuMesh(ctypes.Structure):
                 ("IEN", c_int64_p), ("rho", c_double_p), ("density_field", ctypes.c_char * 64)]
 
 
+class R2SStlMesh(ctypes.Structure):
+    _fields_ = [("n_tris", ctypes.c_int64), ("verts", c_float_p)]
+
+
 # every symbol include/rho2sdf_hip.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _MESH = [c_double_p, ctypes.c_int64, c_int64_p, ctypes.c_int64]
@@ -206,10 +210,17 @@ SYMBOLS = [
                                               c_int64_p, c_int64_p]),
     ("r2s_mesh_sections_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, _P, _P, _P,
                                              ctypes.c_int64, _P, _P, ctypes.c_int64, c_int64_p, c_int64_p, c_double_p, c_int64_p, _P]),
+    ("r2s_mesh_weld", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int32,
+                                     ctypes.c_int32, c_float_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p]),
+    ("r2s_mesh_weld_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P,
+                                         c_int64_p, _P]),
+    ("r2s_import_stl", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(R2SStlMesh)]),
+    ("r2s_free_stl_mesh", None, [ctypes.POINTER(R2SStlMesh)]),
 ]
 
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8
 HEX8, TET4 = 0, 1
+WELD_DROP_COLLAPSED, WELD_DROP_DUPLICATES, WELD_DROP_UNUSED = 1, 2, 4
 
 _lib = None
 

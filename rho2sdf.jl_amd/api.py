@@ -828,6 +828,78 @@ def mesh_shells_dev(verts, tris, stream=None, *, capacity=0):
     return MeshShells(counts[:n.value].cpu().numpy(), sums[:n.value].cpu().numpy(), ref, tot, sot)
 
 
+class MeshWeld:
+    """The result of mesh_weld (include/rho2sdf_hip.h, r2s_mesh_weld): `verts` (nv_out, 3) float32, every row an input vertex bit
+    for bit, in first-occurrence order; `tris` (nt_out, 3) int32 into them; `vert_map` (nv_in,) and `tri_map` (nt_in,) int32,
+    input index -> output index or -1 for what was dropped; `totals` (8,) int64 (output vertices, output triangles, vertices
+    merged away, collapsed triangles, same-orientation duplicates, opposite pairs, unreferenced classes, 0).  numpy arrays from
+    mesh_weld, device tensors (totals stays numpy) from mesh_weld_dev."""
+
+    def __init__(self, verts, tris, vert_map, tri_map, totals):
+        self.verts, self.tris, self.vert_map, self.tri_map, self.totals = verts, tris, vert_map, tri_map, totals
+
+    n_verts = property(lambda s: int(s.totals[0]))
+    n_tris = property(lambda s: int(s.totals[1]))
+    n_merged = property(lambda s: int(s.totals[2]))
+    n_collapsed = property(lambda s: int(s.totals[3]))
+    n_duplicates = property(lambda s: int(s.totals[4]))
+    n_opposite = property(lambda s: int(s.totals[5]))
+    n_unused = property(lambda s: int(s.totals[6]))
+
+
+def _weld_flags(drop_collapsed, drop_duplicates, drop_unused):
+    return (L.WELD_DROP_COLLAPSED if drop_collapsed else 0) | (L.WELD_DROP_DUPLICATES if drop_duplicates else 0) \
+        | (L.WELD_DROP_UNUSED if drop_unused else 0)
+
+
+def mesh_weld(verts, tris=None, *, snap=0.0, drop_collapsed=True, drop_duplicates=False, drop_unused=True, device=-1):
+    """Welds the vertices of a triangle mesh that are the same point (verts (nv, 3) float32; tris (nt, 3) int32 0-based, or None
+    for a triangle soup: triangle t = vertices 3t, 3t + 1, 3t + 2) -> MeshWeld.  snap = 0: the same iff x, y and z compare equal
+    as float32; snap > 0: iff they fall into the same cell floor(v / snap) per axis - grid snapping, NOT a distance tolerance:
+    two points closer than snap on either side of a cell face stay apart.  Output vertices are copies of the first input vertex
+    of each class, in first-occurrence order; surviving triangles keep their order and corner order.  drop_collapsed drops the
+    triangles with two equal indices after the weld, drop_duplicates all but the first of the triangles equal up to a rotation
+    of their corners, drop_unused the vertices no surviving triangle references.
+    The mesh of extract_isosurface is already topologically closed; welding its exact-iso vertices collapses zero-area triangles
+    and can leave non-manifold vertices that mesh_shells reports, so the weld is offered, not applied by default."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = None if tris is None else np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    if t is None and len(v) % 3:
+        raise L.R2SError("a soup (tris=None) needs a multiple of 3 vertices")
+    nt = len(v) // 3 if t is None else len(t)
+    vo, to = np.empty((len(v), 3), np.float32), np.empty((nt, 3), np.int32)
+    vm, tm = np.empty(len(v), np.int32), np.empty(nt, np.int32)
+    tot = np.zeros(8, np.int64)
+    ip = lambda a: a.ctypes.data_as(L.c_int32_p)
+    pad = np.zeros(3, np.int32)   # (a non-NULL pointer for a mesh without triangles: NULL means soup)
+    L.check(L.lib().r2s_mesh_weld(_f(v) if len(v) else None, len(v), None if t is None else ip(t if len(t) else pad), nt, float(snap),
+                                  _weld_flags(drop_collapsed, drop_duplicates, drop_unused), int(device), _f(vo), ip(to), ip(vm),
+                                  ip(tm), _i(tot)))
+    return MeshWeld(vo[:tot[0]].copy(), to[:tot[1]].copy(), vm, tm, tot)
+
+
+def mesh_weld_dev(verts, tris=None, stream=None, *, snap=0.0, drop_collapsed=True, drop_duplicates=False, drop_unused=True):
+    """mesh_weld on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3) or None, contiguous).  All four
+    arrays of the MeshWeld stay device tensors, verts and tris trimmed to the counts; totals is numpy."""
+    import torch
+    dev = verts.device
+    pad = torch.zeros(3, dtype=torch.int32, device=dev)   # (torch's empty tensors have a NULL pointer; NULL tris means soup)
+    _mesh_tensors(verts, pad if tris is None else tris)
+    nv = verts.numel() // 3
+    if tris is None and nv % 3:
+        raise L.R2SError("a soup (tris=None) needs a multiple of 3 vertices")
+    nt = nv // 3 if tris is None else tris.numel() // 3
+    st = _stream(stream)
+    vo, to = torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    vm, tm = torch.empty(nv, dtype=torch.int32, device=dev), torch.empty(nt, dtype=torch.int32, device=dev)
+    tot = np.zeros(8, np.int64)
+    vp = lambda x: ctypes.c_void_p(x.data_ptr())
+    L.check(L.lib().r2s_mesh_weld_dev(vp(verts), nv, None if tris is None else vp(tris if nt else pad), nt, float(snap),
+                                      _weld_flags(drop_collapsed, drop_duplicates, drop_unused), vp(vo), vp(to), vp(vm), vp(tm),
+                                      _i(tot), st))
+    return MeshWeld(vo[:tot[0]], to[:tot[1]], vm, tm, tot)
+
+
 def select_shells(verts, tris, shells, keep):
     """The triangles of the shells where `keep` is true -> (verts, tris) with the vertices compacted (ascending old index) and the
     indices remapped; the mesh-level counterpart of remove_sdf_artifacts.  `shells` is the MeshShells of (verts, tris); `keep` a
@@ -1345,6 +1417,24 @@ def export_stl(filename, verts, tris):
     L.check(L.lib().r2s_export_stl(str(filename).encode(), _f(v), len(v), t.ctypes.data_as(L.c_int32_p), len(t)))
     filename = str(filename)
     return filename if filename.endswith(".stl") else filename + ".stl"
+
+
+def import_stl(filename, *, weld=True, snap=0.0, device=-1):
+    """The triangles of a binary or ASCII STL file -> (verts (nv, 3) float32, tris (nt, 3) int32).  weld=True (needs the GPU): the
+    vertices that are the same point are merged by mesh_weld(soup, snap=snap) with its defaults (collapsed triangles and unused
+    vertices dropped), so the mesh tools see shared vertices; weld=False: the soup as the file holds it, 3 nt vertices and
+    tris = arange.  Facet normals and attribute bytes are ignored."""
+    m = L.R2SStlMesh()
+    L.check(L.lib().r2s_import_stl(str(filename).encode(), ctypes.byref(m)))
+    try:
+        n = int(m.n_tris)
+        soup = np.ctypeslib.as_array(m.verts, shape=(3 * n, 3)).copy() if n else np.empty((0, 3), np.float32)
+    finally:
+        L.lib().r2s_free_stl_mesh(ctypes.byref(m))
+    if not weld:
+        return soup, np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
+    w = mesh_weld(soup, None, snap=snap, device=device)
+    return w.verts, w.tris
 
 
 def exportToVTU(fileName, X, IEN, VTK_CODE=None, rho=None):

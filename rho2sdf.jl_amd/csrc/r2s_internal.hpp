@@ -157,4 +157,8 @@ void release_shell_work();
 // frees the work buffers the section calls keep per device; called by r2s_release_cache()
 void release_section_work();
 
+// ---- mesh weld (r2s_mesh_weld.hip) ------------------------------------------------------------------------------------
+// frees the work buffers the weld calls keep per device; called by r2s_release_cache()
+void release_weld_work();
+
 }  // namespace r2s_int

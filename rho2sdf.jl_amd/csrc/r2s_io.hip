@@ -1,6 +1,8 @@
 // On-disk output of the hot path's result: VTK ImageData (.vti), the format rho2sdf() hands to ParaView
 // (reference: src/DataExport/ExportToVTI.jl:22-67, WriteVTK's vtk_grid(filename, x, y, z) for three ranges).
 // Host code only (no device work); part of the library so that non-Julia hosts get the same artefact.
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cctype>
@@ -696,3 +698,125 @@ extern "C" int r2s_import_mat(const char* filename, r2s_vtu_mesh* out)
     snprintf(out->density_field, sizeof out->density_field, "rho");
     return 0;
 }
+
+// ---- STL import (include/rho2sdf_hip.h, r2s_import_stl): the triangles of a binary or an ASCII file as a soup ----------------
+namespace {
+
+// the next whitespace-separated word of s from pos on ("" at the end of the text)
+std::string stl_word(const std::string& s, size_t& pos)
+{
+    while (pos < s.size() && isspace((unsigned char)s[pos])) ++pos;
+    const size_t a = pos;
+    while (pos < s.size() && !isspace((unsigned char)s[pos])) ++pos;
+    return s.substr(a, pos - a);
+}
+
+bool stl_is(const std::string& w, const char* key) { return strcasecmp(w.c_str(), key) == 0; }
+
+// one coordinate: strtod over the whole word, the double rounded to float32 once; false unless finite as float32
+bool stl_number(const std::string& w, float& out)
+{
+    if (w.empty()) return false;
+    char* end = nullptr;
+    const double v = strtod(w.c_str(), &end);
+    if (end != w.c_str() + w.size()) return false;
+    out = (float)v;
+    return std::isfinite(out);
+}
+
+int stl_ascii(const char* filename, const std::string& s, std::vector<float>& verts)
+{
+    size_t pos = 0;
+    long long facet = 0;
+    bool any_solid = false;
+    std::string w = stl_word(s, pos);
+    while (!w.empty()) {
+        if (!stl_is(w, "solid")) return fail(R2S_ERR_ARG, "%s: not an STL file (\"solid\" expected, found \"%.32s\")", filename, w.c_str());
+        any_solid = true;
+        // the name: up to the first facet / endsolid keyword
+        for (w = stl_word(s, pos); !w.empty() && !stl_is(w, "facet") && !stl_is(w, "endsolid"); w = stl_word(s, pos)) {}
+        while (stl_is(w, "facet")) {
+            float x[3];
+            if (!stl_is(stl_word(s, pos), "normal")) return fail(R2S_ERR_ARG, "%s: facet %lld: \"normal\" expected", filename, facet);
+            for (int k = 0; k < 3; ++k) {   // read and ignored; any number text is accepted here, nan included
+                const std::string nw = stl_word(s, pos);
+                char* end = nullptr;
+                (void)strtod(nw.c_str(), &end);
+                if (nw.empty() || end != nw.c_str() + nw.size()) return fail(R2S_ERR_ARG, "%s: facet %lld: malformed normal", filename, facet);
+            }
+            if (!stl_is(stl_word(s, pos), "outer") || !stl_is(stl_word(s, pos), "loop"))
+                return fail(R2S_ERR_ARG, "%s: facet %lld: \"outer loop\" expected", filename, facet);
+            for (int c = 0; c < 3; ++c) {
+                w = stl_word(s, pos);
+                if (!stl_is(w, "vertex"))
+                    return fail(R2S_ERR_ARG, "%s: facet %lld has %d vertices (three expected, found \"%.32s\")", filename, facet, c, w.c_str());
+                for (int k = 0; k < 3; ++k) {
+                    w = stl_word(s, pos);
+                    if (!stl_number(w, x[k]))
+                        return fail(R2S_ERR_ARG, "%s: facet %lld: coordinate \"%.32s\" is not a finite float32 number", filename, facet, w.c_str());
+                }
+                verts.insert(verts.end(), x, x + 3);
+            }
+            w = stl_word(s, pos);
+            if (!stl_is(w, "endloop"))
+                return fail(R2S_ERR_ARG, "%s: facet %lld: \"endloop\" expected after three vertices, found \"%.32s\"", filename, facet, w.c_str());
+            if (!stl_is(stl_word(s, pos), "endfacet")) return fail(R2S_ERR_ARG, "%s: facet %lld: \"endfacet\" expected", filename, facet);
+            ++facet;
+            w = stl_word(s, pos);
+        }
+        if (!stl_is(w, "endsolid"))
+            return fail(R2S_ERR_ARG, "%s: truncated or malformed after facet %lld (\"facet\" or \"endsolid\" expected, found \"%.32s\")", filename,
+                        facet, w.c_str());
+        // the name: up to the next solid keyword
+        for (w = stl_word(s, pos); !w.empty() && !stl_is(w, "solid"); w = stl_word(s, pos)) {}
+    }
+    if (!any_solid) return fail(R2S_ERR_ARG, "%s: not an STL file (empty)", filename);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void r2s_free_stl_mesh(r2s_stl_mesh* m)
+{
+    if (!m) return;
+    free(m->verts);
+    m->verts = nullptr;
+    m->n_tris = 0;
+}
+
+int r2s_import_stl(const char* filename, r2s_stl_mesh* out)
+{
+    if (!filename || !out) return fail(R2S_ERR_ARG, "bad argument");
+    memset(out, 0, sizeof *out);
+    FILE* f = fopen(filename, "rb");
+    if (!f) return fail(R2S_ERR_ARG, "STL file not found: %s", filename);
+    std::string s;
+    {
+        char buf[1 << 16];
+        size_t n;
+        while ((n = fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, n);
+    }
+    fclose(f);
+    std::vector<float> verts;
+    uint32_t count = 0;
+    if (s.size() >= 84) memcpy(&count, s.data() + 80, 4);   // (little endian, like every other reader of this file)
+    if (s.size() >= 84 && (uint64_t)s.size() == 84ull + 50ull * count) {
+        verts.resize(9 * (size_t)count);
+        for (size_t t = 0; t < count; ++t) memcpy(verts.data() + 9 * t, s.data() + 84 + 50 * t + 12, 36);
+        for (size_t i = 0; i < verts.size(); ++i)
+            if (!std::isfinite(verts[i])) return fail(R2S_ERR_ARG, "%s: facet %zu has a non-finite coordinate", filename, i / 9);
+    } else {
+        const int rc = stl_ascii(filename, s, verts);
+        if (rc) return rc;
+    }
+    const size_t nt = verts.size() / 9;
+    out->verts = (float*)malloc(sizeof(float) * std::max<size_t>(verts.size(), 1));
+    if (!out->verts) return fail(R2S_ERR_ARG, "out of memory");
+    if (!verts.empty()) memcpy(out->verts, verts.data(), sizeof(float) * verts.size());
+    out->n_tris = (int64_t)nt;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // What r2s_mesh_shells.hip and r2s_mesh_sections.hip share: the box of the vertices behind the reference point, the
-// collapsed-triangle test and the integer union-find with min-root.  Everything has internal linkage: each file gets its own
-// copy of the kernel.
+// collapsed-triangle test and the integer union-find with min-root.  r2s_mesh_weld.hip takes the order-preserving bit pattern
+// of a float32 and the launch / bit-count helpers from here.  Everything has internal linkage: each file gets its own copy of
+// the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 

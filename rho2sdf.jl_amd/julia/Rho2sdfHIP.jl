@@ -562,6 +562,65 @@ function mesh_sections_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Pt
     return nc[], ns[], ref, totals
 end
 
+# Welds the vertices of a triangle mesh that are the same point (include/rho2sdf_hip.h, r2s_mesh_weld): verts 3 x nv Float32, tris
+# 3 x nt 1-based or `nothing` for a triangle soup (triangle t = columns 3t-2, 3t-1, 3t).  snap = 0: the same iff x, y, z compare
+# equal as Float32; snap > 0: iff they fall into the same cell floor(v / snap) per axis - grid snapping, not a distance tolerance.
+# -> (verts 3 x nv_out, every column an input vertex bit for bit in first-occurrence order, tris 3 x nt_out 1-based, vert_map and
+# tri_map 1-based with 0 for what was dropped, totals).  The mesh of extract_isosurface_hip is closed without welding; welding its
+# exact-iso vertices collapses zero-area triangles and can leave non-manifold vertices that mesh_shells_hip reports: offered, not
+# applied by default.
+function mesh_weld_hip(verts::AbstractMatrix{Float32}, tris::Union{Nothing,AbstractMatrix{<:Integer}} = nothing; snap::Real = 0.0,
+                       drop_collapsed::Bool = true, drop_duplicates::Bool = false, drop_unused::Bool = true, device::Integer = -1)
+    size(verts, 1) == 3 && (tris === nothing ? size(verts, 2) % 3 == 0 : size(tris, 1) == 3) ||
+        error("verts and tris must be 3 x n (a soup: a multiple of 3 vertices)")
+    nv = size(verts, 2)
+    t0 = tris === nothing ? nothing : Int32.(tris) .- Int32(1)
+    nt = tris === nothing ? div(nv, 3) : size(t0, 2)
+    flags = Int32((drop_collapsed ? 1 : 0) | (drop_duplicates ? 2 : 0) | (drop_unused ? 4 : 0))
+    vout = Matrix{Float32}(undef, 3, nv); tout = Matrix{Int32}(undef, 3, nt)
+    vmap = Vector{Int32}(undef, nv); tmap = Vector{Int32}(undef, nt)
+    totals = zeros(Int64, 8)
+    pad = zeros(Int32, 3)                 # a mesh without triangles passes a non-NULL tris: NULL means soup
+    check(ccall((:r2s_mesh_weld, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Float64, Int32, Int32, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+                 Ptr{Int64}),
+                Matrix(verts), nv, t0 === nothing ? C_NULL : (nt == 0 ? pad : t0), nt, Float64(snap), flags, Int32(device), vout, tout,
+                vmap, tmap, totals))
+    return (verts = vout[:, 1:totals[1]], tris = tout[:, 1:totals[2]] .+ Int32(1), vert_map = vmap .+ Int32(1),
+            tri_map = tmap .+ Int32(1), totals = totals)
+end
+
+# the same on device arrays of the current device (raw pointers; d_tris == C_NULL: the soup, n_tris = n_verts / 3); the outputs are
+# sized to the input counts, the maps may be C_NULL -> totals; indices stay 0-based on the device
+function mesh_weld_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer, d_verts_out::Ptr{Cvoid},
+                           d_tris_out::Ptr{Cvoid}, d_vert_map::Ptr{Cvoid}, d_tri_map::Ptr{Cvoid}; snap::Real = 0.0,
+                           flags::Integer = 5, stream::Ptr{Cvoid} = C_NULL)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_weld_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Float64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64},
+                 Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), Float64(snap), Int32(flags), d_verts_out, d_tris_out, d_vert_map,
+                d_tri_map, totals, stream))
+    return totals
+end
+
+mutable struct R2SStlMesh              # mirrors r2s_stl_mesh
+    n_tris::Int64
+    verts::Ptr{Float32}
+end
+
+# The triangles of a binary or ASCII STL file (r2s_import_stl) -> (verts 3 x nv Float32, tris 3 x nt 1-based).  weld = true: the
+# equal vertices are merged by mesh_weld_hip(soup; snap); weld = false: the soup as the file holds it, tris = 1:3nt.
+function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real = 0.0, device::Integer = -1)
+    m = R2SStlMesh(0, C_NULL)
+    check(ccall((:r2s_import_stl, LIB[]), Cint, (Cstring, Ref{R2SStlMesh}), filename, m))
+    soup = copy(unsafe_wrap(Array, m.verts, (3, 3 * Int(m.n_tris))))
+    ccall((:r2s_free_stl_mesh, LIB[]), Cvoid, (Ref{R2SStlMesh},), m)
+    weld || return soup, reshape(Int32.(1:size(soup, 2)), 3, :)
+    w = mesh_weld_hip(soup; snap = snap, device = device)
+    return w.verts, w.tris
+end
+
 # The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
 # +-Inf where the field has no surface.
 function redistance_full_hip(values::AbstractArray{T}, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
