@@ -37,7 +37,7 @@
  *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
  *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
  *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev,
- *     r2s_mesh_sections_dev, r2s_mesh_weld_dev.
+ *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev.
  *     A caller should still order its consumers on `stream`, not on that wait.
  *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
  *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
@@ -692,8 +692,8 @@ int r2s_mesh_index_raycast_dev(const r2s_mesh_index *index, const void *d_origin
  * R2S_ERR_ARG before anything else runs, outputs untouched: NULL arrays with a count, a negative count, NULL n_shells /
  * ref_point / totals, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the host; _dev: the
  * check kernel of r2s_mesh_distance_dev).  n_tris > 2^30 or n_verts beyond 32 bits: R2S_ERR_UNSUPPORTED.  No GPU:
- * R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 shells.  Not here: which shell encloses which, repair; for welding
- * see r2s_mesh_weld below. */
+ * R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 shells.  Not here: which shell encloses which, hole filling; for welding
+ * see r2s_mesh_weld below, for the repair of flipped triangles r2s_mesh_orient. */
 int r2s_mesh_shells(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
                     int32_t *shell_of_tri_out, int64_t *n_shells, double ref_point[3], int64_t totals[8]);
 int r2s_last_mesh_shells(int64_t *counts_out, double *sums_out, int64_t capacity, int64_t *n_shells);
@@ -817,7 +817,7 @@ int r2s_mesh_sections_dev(const float *d_verts, int64_t n_verts, const int32_t *
  * The same input gives the same output on every call and from both variants (no result depends on an atomic's arrival order).
  * Caveat for meshes of r2s_extract_isosurface: they are topologically closed WITHOUT welding; welding their exact-iso vertices
  * collapses the zero-area triangles between them and can leave non-manifold vertices or edges, which r2s_mesh_shells reports.
- * Not here: distance-tolerance welding, re-orientation of flipped triangles, hole filling, decimation. */
+ * Not here: distance-tolerance welding, hole filling, decimation; flipped triangles are re-oriented by r2s_mesh_orient below. */
 #define R2S_WELD_DROP_COLLAPSED 1
 #define R2S_WELD_DROP_DUPLICATES 2
 #define R2S_WELD_DROP_UNUSED 4
@@ -827,6 +827,75 @@ int r2s_mesh_weld(const float *verts, int64_t n_verts, const int32_t *tris, int6
 int r2s_mesh_weld_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, double snap, int32_t flags,
                       float *d_verts_out, int32_t *d_tris_out, int32_t *d_vert_map_out, int32_t *d_tri_map_out,
                       int64_t totals[8], void *stream);
+
+/* ---- mesh orient: consistent, outward triangle winding ------------------------------------------
+ * STL files from the wild have facets, or whole bodies, wound the wrong way; r2s_mesh_shells reads a shell's volume sign as
+ * "body or void", r2s_mesh_sections promises "material on the left" and the ray `side` reads the winding.  The orient finds the
+ * orientable patches of a mesh, gives each a consistent winding and chooses that winding by a stated rule.  verts float32
+ * [n_verts][3], tris int32 [n_tris][3], 0-based; collapsed triangles, half-edges and edge groups are those of r2s_mesh_shells.
+ *   - patch: a connected component of the non-collapsed triangles in which two triangles are adjacent iff they share an
+ *     undirected edge whose group has EXACTLY TWO half-edges, regular or flipped.  Boundary edges and non-manifold edges (three
+ *     or more half-edges) join nothing: no partner is defined across them, so patches are finer than shells.  Patches are
+ *     numbered by ascending smallest triangle index; patch_of_tri[t] is that number, -1 for a collapsed triangle.
+ *   - relative parity: f = the patch's smallest triangle.  Along a regular edge two triangles agree, along a flipped edge they
+ *     disagree; the patch is ORIENTABLE iff every cycle agrees, and then rel[t] in {0, 1} is unique with rel[f] = 0.
+ *   - a NON-ORIENTABLE patch (a Moebius strip, a Klein bottle): its triangles are copied unchanged, its flip flags are 0, it is
+ *     counted.
+ *   - a patch is CLOSED iff every half-edge of its triangles lies in a group of exactly two; only then is its volume independent
+ *     of the reference point.
+ *   - tentative volume V: the sum over the patch's triangles of the shells' `volume` term (same reference point r, same
+ *     operation order, no fma), negated where rel[t] = 1.  Swapping corners 1 and 2 negates det exactly in that formula, so this
+ *     is the volume of the re-wound patch.
+ *   - whole-patch flip g of an orientable patch with n1 triangles of rel = 1 and n0 of rel = 0:
+ *         flag R2S_ORIENT_OUTWARD set, the patch closed and V != 0:   g = (V < 0); the patch is "decided by volume"
+ *         otherwise (and always without the flag), the MAJORITY:      g = (n1 > n0); a tie gives g = 0: the first triangle
+ *                                                                     keeps its winding
+ *     Any other flag bit: R2S_ERR_ARG.
+ *   - output: flip[t] = rel[t] ^ g.  A flipped triangle (i0, i1, i2) is written as (i0, i2, i1): the first corner is kept, the
+ *     triangle order is unchanged.  Collapsed triangles are copied.
+ *   - integer record of a patch, int64[8]: [0] first_tri, [1] n_tris, [2] triangles flipped in the output, [3] status bits:
+ *     1 closed, 2 non-orientable, 4 decided by volume, [4] its half-edges in boundary groups, [5] its half-edges in non-manifold
+ *     groups, [6] flipped edges (groups of two in the same direction) inside it IN THE INPUT, [7] 0.
+ *   - Float64 of a patch: its signed volume AS WRITTEN about r: g ? -V : V; of a non-orientable patch the plain sum.
+ *   - totals, int64[8]: [0] patches, [1] triangles (n_tris), [2] collapsed, [3] flipped triangles, [4] non-orientable patches,
+ *     [5] closed patches, [6] patches decided by volume, [7] flipped edges remaining IN THE OUTPUT: 0 unless a patch is
+ *     non-orientable; equal to totals[5] of r2s_mesh_shells on the output mesh.
+ *   - NOT HERE.  Nesting is ignored: R2S_ORIENT_OUTWARD makes EVERY closed patch a positive body, so an enclosed void becomes a
+ *     body (reverse it again with the patch labels if you know it is a void); the majority rule leaves a void as most of its
+ *     triangles say.  That is why OUTWARD is opt-in.  No orientation is carried across non-manifold edges.  No hole filling.
+ *   - determinism: no result depends on an atomic's arrival order (the union-find hooks the larger root under the smaller, the
+ *     counts are integer sums); no floating-point atomic and no library reduction touches V.  V is summed by the shells' scheme:
+ *     the triangles sorted by patch with a stable sort, blocks of 256 consecutive sorted triangles per patch in a fixed binary
+ *     tree, then the up to 64 equal runs of a patch's block partials in ascending block order and those run sums in a fixed
+ *     binary tree - a fixed function of the triangle order, the same bits on every call and from both variants.  Under a
+ *     permutation of the triangles everything follows the permutation, with two exceptions: (1) a majority TIE is broken by the
+ *     patch's first triangle, which the permutation may change; (2) V changes within the shells' bound (n_tris + 9) * 2^-53 * T
+ *     (T the sum of the absolute values of the volume term's monomials), so where |V| is within that bound of zero the sign
+ *     OUTWARD reads, or the fall-through of V == 0 to the majority, may change.
+ * r2s_mesh_orient: host arrays, `device` (-1 = current).  tris_out [n_tris][3] is required when n_tris > 0 and must not overlap
+ * tris; flip_out [n_tris] (0 / 1) and patch_of_tri_out [n_tris] may be NULL.  *n_patches, ref_point and totals are always
+ * written on success; the two tables become the calling thread's last result, read with r2s_last_mesh_orient: counts_out
+ * [capacity][8], volume_out [capacity]; *n_patches is always the full count, the first min(capacity, n) records are written; the
+ * pointers may be NULL only with capacity == 0.
+ * r2s_mesh_orient_dev: device arrays on the current device, read after the work queued on `stream`, which is the only stream the
+ * call queues on; d_tris_out, d_flip_out (may be NULL), d_patch_of_tri (may be NULL), d_counts [patch_capacity][8] and d_volume
+ * [patch_capacity] are device pointers, n_patches / ref_point / totals host pointers.  d_tris_out, the flips and the patch labels
+ * are always written; the tables only when patch_capacity >= *n_patches (else they are left untouched: ask with patch_capacity
+ * 0, then call again).  Synchronous on return; it does not touch the thread's last result.  Work buffers are kept per device and
+ * freed by r2s_release_cache.
+ * R2S_ERR_ARG before any output is touched, as by r2s_mesh_shells: NULL arrays with a count, a negative count, NULL tris_out
+ * with a count, NULL n_patches / ref_point / totals, NULL tables with a capacity, a bad flag, a triangle index outside
+ * [0, n_verts) or a non-finite vertex (host variant: on the host; _dev: the check kernel of r2s_mesh_distance_dev).  n_tris >
+ * 2^30 or n_verts beyond 32 bits: R2S_ERR_UNSUPPORTED, before anything is read.  No GPU: R2S_ERR_NO_DEVICE.  n_tris == 0
+ * succeeds with 0 patches. */
+#define R2S_ORIENT_OUTWARD 1
+int r2s_mesh_orient(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t flags, int32_t device,
+                    int32_t *tris_out, int32_t *flip_out, int32_t *patch_of_tri_out, int64_t *n_patches, double ref_point[3],
+                    int64_t totals[8]);
+int r2s_last_mesh_orient(int64_t *counts_out, double *volume_out, int64_t capacity, int64_t *n_patches);
+int r2s_mesh_orient_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, int32_t flags,
+                        int32_t *d_tris_out, int32_t *d_flip_out, int32_t *d_patch_of_tri, int64_t *d_counts, double *d_volume,
+                        int64_t patch_capacity, int64_t *n_patches, double ref_point[3], int64_t totals[8], void *stream);
 
 /* ---- on-disk output ------------------------------------------------------------------ */
 

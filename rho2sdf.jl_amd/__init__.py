@@ -16,7 +16,8 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   vertex_normals, surface_thickness, surface_thickness_dev,
                   MeshShells, mesh_shells, mesh_shells_dev, select_shells,
                   MeshSections, mesh_sections, mesh_sections_dev,
-                  MeshWeld, mesh_weld, mesh_weld_dev, import_stl)
+                  MeshWeld, mesh_weld, mesh_weld_dev, import_stl,
+                  MeshOrient, mesh_orient, mesh_orient_dev, flip_patches)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
@@ -30,4 +31,5 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "MeshShells", "mesh_shells", "mesh_shells_dev", "select_shells",
            "MeshSections", "mesh_sections", "mesh_sections_dev",
            "MeshWeld", "mesh_weld", "mesh_weld_dev", "import_stl",
+           "MeshOrient", "mesh_orient", "mesh_orient_dev", "flip_patches",
            "_lib"]

@@ -919,6 +919,109 @@ def select_shells(verts, tris, shells, keep):
     return v[used], remap[sel].astype(t.dtype).reshape(-1, 3)
 
 
+class MeshOrient:
+    """The result of mesh_orient (include/rho2sdf_hip.h, r2s_mesh_orient): `tris` (nt, 3) int32, the input triangles in their
+    order with the flipped ones written (i0, i2, i1); `flipped` (nt,) bool; `patch_of_tri` (nt,) int32 (-1 for a collapsed
+    triangle); `counts` (n, 8) int64 (first_tri, n_tris, triangles flipped, status bits 1 closed / 2 non-orientable / 4 decided
+    by volume, boundary half-edges, non-manifold half-edges, flipped edges of the input, 0); `volume` (n,) float64, the signed
+    volume of each patch as written, about `ref_point` (3,); `totals` (8,) int64 (patches, triangles, collapsed, flipped
+    triangles, non-orientable, closed, decided by volume, flipped edges left in the output).  numpy arrays from mesh_orient;
+    mesh_orient_dev keeps tris, flipped and patch_of_tri on the device."""
+
+    def __init__(self, tris, flipped, patch_of_tri, counts, volume, ref_point, totals):
+        self.tris, self.flipped, self.patch_of_tri, self.counts, self.volume = tris, flipped, patch_of_tri, counts, volume
+        self.ref_point, self.totals = ref_point, totals
+
+    n_patches = property(lambda s: len(s.counts))
+    first_tri = property(lambda s: s.counts[:, 0])
+    n_tris = property(lambda s: s.counts[:, 1])
+    n_flipped = property(lambda s: s.counts[:, 2])
+    closed = property(lambda s: (s.counts[:, 3] & 1) != 0)
+    orientable = property(lambda s: (s.counts[:, 3] & 2) == 0)
+    by_volume = property(lambda s: (s.counts[:, 3] & 4) != 0)
+
+    def __len__(self):
+        return len(self.counts)
+
+
+def mesh_orient(verts, tris, *, outward=False, device=-1):
+    """A consistent winding for a triangle mesh (verts (nv, 3) float32, tris (nt, 3) int32, 0-based) -> MeshOrient.  The mesh falls
+    into patches over the edges that exactly two triangles share; inside an orientable patch every triangle gets the winding of
+    its neighbours, and the patch as a whole keeps the winding of the MAJORITY of its triangles (a tie: of its first triangle).
+    outward=True: a closed patch with a non-zero volume is wound so that its volume is positive instead.  Nesting is ignored:
+    outward=True turns an enclosed void into a body (reverse it again with flip_patches if you know it is one), the majority
+    rule leaves a void as most of its triangles say.  Non-orientable patches are copied unchanged and counted; no orientation is
+    carried across non-manifold edges; no holes are filled.  One library call and a copy of the thread's last tables."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    out, flip, pot = np.empty((len(t), 3), np.int32), np.empty(len(t), np.int32), np.empty(len(t), np.int32)
+    n = ctypes.c_int64()
+    ref, tot = np.zeros(3), np.zeros(8, np.int64)
+    ip = lambda a: a.ctypes.data_as(L.c_int32_p)
+    L.check(L.lib().r2s_mesh_orient(_f(v) if len(v) else None, len(v), ip(t) if len(t) else None, len(t),
+                                    L.ORIENT_OUTWARD if outward else 0, int(device), ip(out), ip(flip), ip(pot), ctypes.byref(n),
+                                    _d(ref), _i(tot)))
+    counts, volume = np.empty((n.value, 8), np.int64), np.empty(n.value)
+    if n.value:
+        L.check(L.lib().r2s_last_mesh_orient(_i(counts), _d(volume), n.value, ctypes.byref(n)))
+    return MeshOrient(out, flip != 0, pot, counts, volume, ref, tot)
+
+
+def mesh_orient_dev(verts, tris, stream=None, *, outward=False, capacity=0):
+    """mesh_orient on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous).  The tables
+    come back as numpy arrays; tris, flipped and patch_of_tri stay device tensors.  The library writes the tables only into room
+    for all patches: with more patches than `capacity` the call is made a second time."""
+    import torch
+    _mesh_tensors(verts, tris)
+    st = _stream(stream)
+    dev = verts.device
+    nt = tris.numel() // 3
+    out = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    flip, pot = torch.empty(nt, dtype=torch.int32, device=dev), torch.empty(nt, dtype=torch.int32, device=dev)
+    n = ctypes.c_int64()
+    ref, tot = np.zeros(3), np.zeros(8, np.int64)
+    cap = int(capacity)
+    vp = ctypes.c_void_p
+    while True:
+        counts = torch.empty((cap, 8), dtype=torch.int64, device=dev)
+        volume = torch.empty(cap, dtype=torch.float64, device=dev)
+        L.check(L.lib().r2s_mesh_orient_dev(vp(verts.data_ptr()), verts.numel() // 3, vp(tris.data_ptr()), nt,
+                                            L.ORIENT_OUTWARD if outward else 0, vp(out.data_ptr()), vp(flip.data_ptr()),
+                                            vp(pot.data_ptr()), vp(counts.data_ptr()) if cap else None,
+                                            vp(volume.data_ptr()) if cap else None, cap, ctypes.byref(n), _d(ref), _i(tot), st))
+        if n.value <= cap:
+            break
+        cap = n.value
+    return MeshOrient(out, flip != 0, pot, counts[:n.value].cpu().numpy(), volume[:n.value].cpu().numpy(), ref, tot)
+
+
+def flip_patches(tris, patch_of_tri, which):
+    """`tris` with the triangles of the chosen patches reversed, (i0, i1, i2) -> (i0, i2, i1), e.g. the voids a user knows about
+    after mesh_orient(outward=True).  `patch_of_tri` is MeshOrient.patch_of_tri (shell_of_tri of a MeshShells works the same
+    way); `which` a boolean array with one entry per patch, or a list of patch numbers.  Triangles of patch -1 are left alone.
+    Plain array code, no device."""
+    t = np.array(tris, dtype=np.int32).reshape(-1, 3)
+    pot = patch_of_tri
+    pot = np.asarray(pot.cpu() if hasattr(pot, "cpu") else pot).reshape(-1)
+    if len(pot) != len(t):
+        raise L.R2SError("patch_of_tri needs one entry per triangle")
+    n = int(pot.max()) + 1 if len(pot) else 0
+    w = np.asarray(which)
+    if w.dtype == bool:
+        if w.shape != (n,):
+            raise L.R2SError("a boolean `which` needs one entry per patch")
+        sel = w
+    else:
+        w = w.astype(np.int64).reshape(-1)
+        if len(w) and (w.min() < 0 or w.max() >= n):
+            raise L.R2SError("`which` names a patch that does not exist")
+        sel = np.zeros(n, bool)
+        sel[w] = True
+    rev = (pot >= 0) & np.concatenate([sel, [False]])[pot]
+    t[rev] = t[rev][:, [0, 2, 1]]
+    return t
+
+
 class MeshSections:
     """The plane sections of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_sections): the raw tables and what follows from
     them.  Raw: `normal` (3,), `levels` (n_levels,), `contour_start` (n + 1,) int64, `counts` (n, 8) int64 (level, first segment id,
@@ -1419,11 +1522,17 @@ def export_stl(filename, verts, tris):
     return filename if filename.endswith(".stl") else filename + ".stl"
 
 
-def import_stl(filename, *, weld=True, snap=0.0, device=-1):
+def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None):
     """The triangles of a binary or ASCII STL file -> (verts (nv, 3) float32, tris (nt, 3) int32).  weld=True (needs the GPU): the
     vertices that are the same point are merged by mesh_weld(soup, snap=snap) with its defaults (collapsed triangles and unused
     vertices dropped), so the mesh tools see shared vertices; weld=False: the soup as the file holds it, 3 nt vertices and
-    tris = arange.  Facet normals and attribute bytes are ignored."""
+    tris = arange.  Facet normals and attribute bytes are ignored.  orient=None: the windings as the file holds them;
+    "majority" or "outward" (needs weld=True): the welded triangles go through mesh_orient(outward=(orient == "outward")), whose
+    docstring has the rules and the caveat about enclosed voids."""
+    if orient not in (None, "majority", "outward"):
+        raise L.R2SError('orient must be None, "majority" or "outward"')
+    if orient is not None and not weld:
+        raise L.R2SError("orient needs weld=True: a soup has no shared edges to orient across")
     m = L.R2SStlMesh()
     L.check(L.lib().r2s_import_stl(str(filename).encode(), ctypes.byref(m)))
     try:
@@ -1434,7 +1543,9 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1):
     if not weld:
         return soup, np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
     w = mesh_weld(soup, None, snap=snap, device=device)
-    return w.verts, w.tris
+    if orient is None:
+        return w.verts, w.tris
+    return w.verts, mesh_orient(w.verts, w.tris, outward=orient == "outward", device=device).tris
 
 
 def exportToVTU(fileName, X, IEN, VTK_CODE=None, rho=None):

@@ -161,4 +161,8 @@ void release_section_work();
 // frees the work buffers the weld calls keep per device; called by r2s_release_cache()
 void release_weld_work();
 
+// ---- mesh orient (r2s_mesh_orient.hip) --------------------------------------------------------------------------------
+// frees the work buffers the orient calls keep per device; called by r2s_release_cache()
+void release_orient_work();
+
 }  // namespace r2s_int

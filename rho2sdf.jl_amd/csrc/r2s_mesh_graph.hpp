@@ -1,5 +1,6 @@
-// What r2s_mesh_shells.hip and r2s_mesh_sections.hip share: the box of the vertices behind the reference point, the
-// collapsed-triangle test and the integer union-find with min-root.  r2s_mesh_weld.hip takes the order-preserving bit pattern
+// What r2s_mesh_shells.hip, r2s_mesh_sections.hip and r2s_mesh_orient.hip share: the box of the vertices behind the reference
+// point, the collapsed-triangle test, the integer union-find with min-root and (shells, orient) the per-group integer
+// counting.  r2s_mesh_weld.hip takes the order-preserving bit pattern
 // of a float32 and the launch / bit-count helpers from here.  Everything has internal linkage: each file gets its own copy of
 // the kernel.
 #pragma once
@@ -87,6 +88,38 @@ __device__ inline void ms_union(uint32_t* L, uint32_t a, uint32_t b)
         if (a < b) { const uint32_t t = a; a = b; b = t; }   // link the larger root under the smaller
         if (atomicCAS(&L[a], a, b) == a) return;             // a was still a root
     }
+}
+
+// adds 1 to counts[group][col0 + k] (rows of STRIDE) for every k < NC with add[k] set, over the workgroup's active threads: once
+// per column when all of them name one group (a shell, a patch), else one atomic per entry.  Called by all 256 threads.
+template <int NC, int STRIDE = 8>
+__device__ inline void ms_count(bool active, int32_t group, const bool add[NC], int col0, int64_t* __restrict__ counts)
+{
+    __shared__ int32_t s_group, s_mixed;
+    __shared__ uint32_t s_cnt[NC];
+    if (threadIdx.x == 0) s_group = -1, s_mixed = 0;
+    if (threadIdx.x < NC) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    if (active) atomicCAS(&s_group, -1, group);
+    __syncthreads();
+    if (active && group != s_group) s_mixed = 1;
+    __syncthreads();
+    if (s_mixed) {
+        if (active) {
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+                if (add[k]) atomicAdd((unsigned long long*)&counts[(int64_t)group * STRIDE + col0 + k], 1ull);
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const unsigned long long m = __ballot(active && add[k]);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_cnt[k], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < NC && s_group >= 0 && s_cnt[threadIdx.x])
+        atomicAdd((unsigned long long*)&counts[(int64_t)s_group * STRIDE + col0 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
 inline unsigned ms_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }

@@ -1,0 +1,589 @@
+// Mesh orient: the orientable patches of a triangle mesh, a consistent winding for each, and the choice of that winding by the
+// signed volume or by the majority (include/rho2sdf_hip.h, r2s_mesh_orient; DESIGN.md "Mesh orient").
+//   ms_bounds_kernel   the box of all vertices -> the reference point (the shells' kernel)
+//   mo_key_kernel      one half-edge key per corner, the shells' keys, payload 3t + c; parent[x] = x on the DOUBLED graph of
+//                      2 n_tris nodes, node 2t + s = "triangle t with parity s" -> rocPRIM radix sort of pairs
+//   mo_union_kernel    the second member of every run of EXACTLY two: opposite directions join (2a, 2b) and (2a+1, 2b+1), equal
+//                      directions join (2a, 2b+1) and (2a+1, 2b) (the shells' union-find: larger root under the smaller)
+//   mo_flatten_kernel  root(2t) = 2f + rel[t] in an orientable patch with first triangle f, root(2t) = root(2t+1) = 2f in a
+//                      non-orientable one: first triangle, parity and orientability of every triangle; root flags
+//   -> rocPRIM exclusive scan (integers) -> mo_number_kernel: patch numbers, sort keys
+//   -> stable radix sort of the triangle ids by patch -> mo_segment_kernel: where each patch starts, its first triangle
+//   mo_sum_kernel      blocks of 256 consecutive sorted triangles, the volume term negated where rel = 1, a segmented fixed
+//                      tree in LDS, one partial per (block, patch) at slot block + patch
+//   mo_combine_kernel  one wavefront per patch: up to 64 equal runs of its block partials in ascending order, then a fixed tree
+//   mo_parity_kernel   n1 per patch; mo_edge_kernel: the sorted edge runs again, boundary / non-manifold half-edges and the
+//                      flipped edges of the input per patch
+//   mo_decide_kernel   one thread per patch: closed, the whole-patch flip g, the record, the totals
+//   mo_apply_kernel    one thread per triangle: flip = rel ^ g, (i0, i1, i2) -> (i0, i2, i1)
+//   mo_remain_kernel   the sorted edge runs a third time: the flipped edges that remain in the output
+// Integer counts use integer atomics; no floating-point atomic and no library reduction touches V.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "r2s_common.hpp"
+#include "r2s_internal.hpp"
+#include "r2s_mesh_graph.hpp"
+
+using namespace r2s_int;
+
+namespace {
+
+constexpr int MO_BLOCK = 256;   // triangles per block of the volume sums (the shells' definition)
+constexpr int MO_NCNT = 8;
+constexpr int64_t MO_MAX_TRIS = (int64_t)1 << 30;
+constexpr int32_t MO_FLAGS = 1;   // R2S_ORIENT_OUTWARD
+constexpr uint32_t MO_NONORIENTABLE = 0x80000000u;   // bit 31 of info[t]; bits 0..30: root(2t) = 2 first_tri + rel
+// slots of the small device array: [0..5] the bounds, then
+constexpr int MO_COLLAPSED = 6, MO_NPATCHES = 7, MO_TOT = 8;   // [MO_TOT .. MO_TOT + 4]: flipped triangles, non-orientable, closed, by volume, remaining flipped edges
+constexpr int MO_SMALL = 16;
+// columns of the per-patch record
+constexpr int MO_FIRST = 0, MO_NTRIS = 1, MO_NFLIP = 2, MO_STATUS = 3, MO_BOUNDARY = 4, MO_NONMANIFOLD = 5, MO_FLIPPED_IN = 6;
+
+// one thread per triangle: its three half-edge keys, parent[x] = x for both of its nodes, the collapsed count
+__global__ void __launch_bounds__(256) mo_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ vals, uint32_t* __restrict__ parent, uint64_t* __restrict__ small)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool col = false;
+    if (t < n) {
+        int32_t i[3];
+        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
+        parent[2 * t] = (uint32_t)(2 * t);
+        parent[2 * t + 1] = (uint32_t)(2 * t + 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
+            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
+            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
+            vals[3 * t + c] = (uint32_t)(3 * t + c);
+        }
+    }
+    const unsigned long long m = __ballot(col);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MO_COLLAPSED], (unsigned long long)__popcll(m));
+}
+
+// the number of members of the run of sorted half-edge i, capped at 3 (i is a real half-edge: keys[i] < ckey)
+__device__ inline int mo_run_size(const uint64_t* __restrict__ keys, int64_t i, int64_t nh, bool& head)
+{
+    const uint64_t e = keys[i] >> 1;
+    const bool p1 = i >= 1 && (keys[i - 1] >> 1) == e, p2 = p1 && i >= 2 && (keys[i - 2] >> 1) == e;
+    const bool n1 = i + 1 < nh && (keys[i + 1] >> 1) == e, n2 = n1 && i + 2 < nh && (keys[i + 2] >> 1) == e;
+    head = !p1;
+    if (!p1 && !n1) return 1;
+    return (p2 || (p1 && n1) || n2) ? 3 : 2;
+}
+
+// one thread per sorted half-edge: the second member of a run of exactly two joins the two triangles on the doubled graph
+__global__ void __launch_bounds__(256) mo_union_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
+                                                        uint64_t ckey, uint32_t* parent)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < 1 || i >= nh) return;
+    const uint64_t k = keys[i];
+    if (k >= ckey) return;
+    bool head;
+    if (mo_run_size(keys, i, nh, head) != 2 || head) return;
+    const uint32_t a = vals[i - 1] / 3u, b = vals[i] / 3u;
+    const uint32_t same = (uint32_t)(((keys[i - 1] ^ k) & 1ull) == 0ull);   // equal directions: a flipped edge, the parities differ
+    ms_union(parent, 2u * a, 2u * b + same);
+    ms_union(parent, 2u * a + 1u, 2u * b + (same ^ 1u));
+}
+
+// info[t] = root(2t) | (root(2t) == root(2t + 1) ? MO_NONORIENTABLE : 0); flag[t] = 1 for the first triangle of a patch
+__global__ void __launch_bounds__(256) mo_flatten_kernel(const int32_t* __restrict__ tris, int64_t n, uint32_t* parent, uint32_t* __restrict__ info,
+                                                          int32_t* __restrict__ flag)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    int32_t i0, i1, i2;
+    if (ms_collapsed(tris, t, i0, i1, i2)) {
+        flag[t] = 0;
+        info[t] = 0u;
+        return;
+    }
+    const uint32_t r0 = ms_find(parent, (uint32_t)(2 * t)), r1 = ms_find(parent, (uint32_t)(2 * t + 1));
+    info[t] = r0 | (r0 == r1 ? MO_NONORIENTABLE : 0u);
+    flag[t] = r0 == (uint32_t)(2 * t) ? 1 : 0;
+}
+
+// num = the exclusive scan of flag: patch_of[t], the sort key of t (collapsed: n_patches, behind every patch), n_patches
+__global__ void __launch_bounds__(256) mo_number_kernel(const int32_t* __restrict__ tris, int64_t n, const uint32_t* __restrict__ info,
+                                                         const int32_t* __restrict__ num, const int32_t* __restrict__ flag,
+                                                         int32_t* __restrict__ patch_of, uint32_t* __restrict__ skey, uint32_t* __restrict__ sval,
+                                                         uint64_t* __restrict__ small)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int32_t np = num[n - 1] + flag[n - 1];
+    int32_t i0, i1, i2;
+    const int32_t s = ms_collapsed(tris, t, i0, i1, i2) ? -1 : num[(info[t] & ~MO_NONORIENTABLE) >> 1];
+    patch_of[t] = s;
+    skey[t] = s < 0 ? (uint32_t)np : (uint32_t)s;
+    sval[t] = (uint32_t)t;
+    if (t == n - 1) small[MO_NPATCHES] = (uint64_t)np;
+}
+
+// seg[s] = the first sorted position of patch s, seg[n_patches] = nvalid; the patch's first triangle
+__global__ void __launch_bounds__(256) mo_segment_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ stri, int64_t nvalid,
+                                                          int64_t np, int64_t* __restrict__ seg, int64_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvalid) return;
+    const uint32_t s = skey[i];
+    if (i == 0 || skey[i - 1] != s) {
+        seg[s] = i;
+        counts[(int64_t)s * MO_NCNT + MO_FIRST] = (int64_t)stri[i];
+    }
+    if (i == 0) seg[np] = nvalid;
+}
+
+// the shells' volume term of one triangle, in the header's operation order
+__device__ inline double mo_volume_term(const float* __restrict__ verts, int32_t i0, int32_t i1, int32_t i2, double rx, double ry, double rz)
+{
+#pragma clang fp contract(off)
+    const float *pa = verts + 3 * (int64_t)i0, *pb = verts + 3 * (int64_t)i1, *pc = verts + 3 * (int64_t)i2;
+    const double Ax = (double)pa[0] - rx, Ay = (double)pa[1] - ry, Az = (double)pa[2] - rz;
+    const double Bx = (double)pb[0] - rx, By = (double)pb[1] - ry, Bz = (double)pb[2] - rz;
+    const double Cx = (double)pc[0] - rx, Cy = (double)pc[1] - ry, Cz = (double)pc[2] - rz;
+    const double det = (Ax * (By * Cz - Bz * Cy) + Ay * (Bz * Cx - Bx * Cz)) + Az * (Bx * Cy - By * Cx);
+    return det / 6.0;
+}
+
+// block b: the sorted positions [256 b, 256 b + 256); the partial of (block b, patch s) goes to slot b + s (the shells' scheme)
+__global__ void __launch_bounds__(MO_BLOCK) mo_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
+                                                           const uint32_t* __restrict__ info, const uint32_t* __restrict__ skey,
+                                                           const uint32_t* __restrict__ stri, int64_t nvalid, double rx, double ry, double rz,
+                                                           double* __restrict__ partial)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_v[MO_BLOCK];
+    __shared__ uint32_t s_key[MO_BLOCK];
+    const int j = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MO_BLOCK + j;
+    const bool active = i < nvalid;
+    uint32_t key = 0xffffffffu;
+    double v = 0.0;
+    if (active) {
+        key = skey[i];
+        const int64_t t = (int64_t)stri[i];
+        v = mo_volume_term(verts, tris[3 * t], tris[3 * t + 1], tris[3 * t + 2], rx, ry, rz);
+        if (info[t] & 1u) v = -v;   // (a non-orientable patch has rel = 0 everywhere: the plain sum)
+    }
+    s_key[j] = key;
+    s_v[j] = v;
+    __syncthreads();
+    const bool head = active && (j == 0 || s_key[j - 1] != key);
+#pragma unroll
+    for (int d = 1; d < MO_BLOCK; d <<= 1) {
+        const bool take = active && j + d < MO_BLOCK && s_key[j + d] == key;
+        const double o = take ? s_v[j + d] : 0.0;
+        __syncthreads();
+        if (take) {
+            v = v + o;
+            s_v[j] = v;
+        }
+        __syncthreads();
+    }
+    if (head) partial[(int64_t)blockIdx.x + (int64_t)key] = v;
+}
+
+// one wavefront per patch: lane l sums the l-th run of `chunk` consecutive block partials in ascending block order, then the
+// run sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while that lane has a run)
+__global__ void __launch_bounds__(256) mo_combine_kernel(const int64_t* __restrict__ seg, int64_t np, const double* __restrict__ partial,
+                                                          double* __restrict__ vol, int64_t* __restrict__ counts)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= np) return;   // (the whole wavefront)
+    const int64_t start = seg[s], end = seg[s + 1];
+    const int64_t b0 = start / MO_BLOCK, nb = (end - 1) / MO_BLOCK - b0 + 1;
+    const int64_t chunk = (nb + 63) / 64;
+    const int m = (int)((nb + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
+    double v = 0.0;
+    if (lane < m) {
+        const int64_t lo = lane * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
+        const double* p = partial + (b0 + lo + s);
+        v = p[0];
+        for (int64_t b = lo + 1; b < hi; ++b) v = v + p[b - lo];
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = __shfl_down(v, d, 64);
+        if (lane + d < m) v = v + o;
+    }
+    if (lane == 0) {
+        vol[s] = v;
+        counts[s * MO_NCNT + MO_NTRIS] = end - start;
+    }
+}
+
+// one thread per triangle: n1 of its patch, kept in column MO_NFLIP until mo_decide_kernel turns it into the flipped count
+__global__ void __launch_bounds__(256) mo_parity_kernel(int64_t n, const uint32_t* __restrict__ info, const int32_t* __restrict__ patch_of,
+                                                         int64_t* __restrict__ counts)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int32_t patch = -1;
+    bool odd = false;
+    if (t < n) {
+        patch = patch_of[t];
+        odd = patch >= 0 && (info[t] & 1u);
+    }
+    const bool add[1] = {true};
+    ms_count<1, MO_NCNT>(odd, patch, add, MO_NFLIP, counts);
+}
+
+// one thread per sorted half-edge: boundary and non-manifold half-edges count into the patch of their own triangle, a flipped
+// edge (a run of two in the same direction: both triangles are in one patch) once, from its first member
+__global__ void __launch_bounds__(256) mo_edge_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
+                                                       uint64_t ckey, const int32_t* __restrict__ patch_of, int64_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool add[3] = {false, false, false};   // boundary, non-manifold, flipped
+    int32_t patch = -1;
+    bool any = false;
+    if (i < nh && keys[i] < ckey) {
+        bool head;
+        const int size = mo_run_size(keys, i, nh, head);
+        add[0] = size == 1;
+        add[1] = size == 3;
+        add[2] = size == 2 && head && ((keys[i + 1] ^ keys[i]) & 1ull) == 0ull;
+        any = add[0] || add[1] || add[2];
+        if (any) patch = patch_of[vals[i] / 3u];
+    }
+    ms_count<3, MO_NCNT>(any, patch, add, MO_BOUNDARY, counts);
+}
+
+// one thread per patch: closed, the whole-patch flip, the record and the volume as written; the totals
+__global__ void __launch_bounds__(256) mo_decide_kernel(int64_t np, int32_t flags, const uint32_t* __restrict__ info, int64_t* __restrict__ counts,
+                                                         double* __restrict__ vol, int32_t* __restrict__ gflag, uint64_t* __restrict__ small)
+{
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    long long c[4] = {0, 0, 0, 0};   // flipped triangles, non-orientable, closed, by volume
+    if (s < np) {
+        int64_t* rec = counts + s * MO_NCNT;
+        const bool nonor = (info[rec[MO_FIRST]] & MO_NONORIENTABLE) != 0u;
+        const bool closed = rec[MO_BOUNDARY] == 0 && rec[MO_NONMANIFOLD] == 0;
+        const int64_t n1 = rec[MO_NFLIP], n0 = rec[MO_NTRIS] - n1;
+        const double V = vol[s];
+        bool g = false, by_volume = false;
+        if (!nonor) {
+            by_volume = (flags & MO_FLAGS) && closed && V != 0.0;
+            g = by_volume ? V < 0.0 : n1 > n0;
+        }
+        const int64_t nflip = nonor ? 0 : (g ? n0 : n1);
+        rec[MO_NFLIP] = nflip;
+        rec[MO_STATUS] = (closed ? 1 : 0) | (nonor ? 2 : 0) | (by_volume ? 4 : 0);
+        rec[7] = 0;
+        if (g) vol[s] = -V;
+        gflag[s] = g ? 1 : 0;
+        c[0] = nflip, c[1] = nonor, c[2] = closed, c[3] = by_volume;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) c[k] += __shfl_xor(c[k], d, 64);
+        if ((threadIdx.x & 63) == 0 && c[k]) atomicAdd((unsigned long long*)&small[MO_TOT + k], (unsigned long long)c[k]);
+    }
+}
+
+// one thread per triangle: flip = rel ^ g of its patch (0 in a non-orientable patch and for a collapsed triangle)
+__global__ void __launch_bounds__(256) mo_apply_kernel(const int32_t* __restrict__ tris, int64_t n, const uint32_t* __restrict__ info,
+                                                        const int32_t* __restrict__ patch_of, const int32_t* __restrict__ gflag,
+                                                        int32_t* __restrict__ tris_out, int32_t* __restrict__ flip)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int32_t i0 = tris[3 * t], i1 = tris[3 * t + 1], i2 = tris[3 * t + 2];
+    const int32_t s = patch_of[t];
+    const uint32_t f = info[t];
+    const bool fl = s >= 0 && !(f & MO_NONORIENTABLE) && (((f & 1u) != 0u) != (gflag[s] != 0));
+    tris_out[3 * t] = i0;
+    tris_out[3 * t + 1] = fl ? i2 : i1;
+    tris_out[3 * t + 2] = fl ? i1 : i2;
+    flip[t] = fl ? 1 : 0;
+}
+
+// one thread per sorted half-edge of the INPUT; the first member of a run of two tells whether the two half-edges still run in
+// the same direction after the flips (a flipped triangle reverses all three of its half-edges)
+__global__ void __launch_bounds__(256) mo_remain_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
+                                                         uint64_t ckey, const int32_t* __restrict__ flip, uint64_t* __restrict__ small)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool left = false;
+    if (i < nh && keys[i] < ckey) {
+        bool head;
+        if (mo_run_size(keys, i, nh, head) == 2 && head) {
+            const uint32_t da = (uint32_t)(keys[i] & 1ull) ^ (uint32_t)flip[vals[i] / 3u];
+            const uint32_t db = (uint32_t)(keys[i + 1] & 1ull) ^ (uint32_t)flip[vals[i + 1] / 3u];
+            left = da == db;
+        }
+    }
+    const unsigned long long m = __ballot(left);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MO_TOT + 4], (unsigned long long)__popcll(m));
+}
+
+// work buffers of the orient calls, kept per device between calls (r2s_release_cache frees them)
+struct OrientWork {
+    DevBuf verts, tris, tris_out, flag, small, keys, keys2, vals, vals2, temp, parent, info, rflag, num, patch, flip, skey, skey2, sval, sval2,
+        seg, partial, counts, vol, gflag;
+    void release()
+    {
+        DevBuf* all[] = {&verts, &tris, &tris_out, &flag, &small, &keys, &keys2, &vals, &vals2, &temp, &parent, &info, &rflag, &num, &patch,
+                         &flip, &skey, &skey2, &sval, &sval2, &seg, &partial, &counts, &vol, &gflag};
+        for (DevBuf* b : all) b->release();
+    }
+};
+std::mutex g_orient_mu;
+std::map<int, OrientWork> g_orient_work;
+
+struct OrientTables {
+    std::vector<int64_t> counts;   // [n][8]
+    std::vector<double> volume;    // [n]
+};
+thread_local OrientTables g_last_orient;
+
+// The oriented copy of the device mesh on the current device, after the work queued on `st`; synchronous.  Writes d_tris_out
+// [n], leaves flip in w.flip and patch_of_tri in w.patch [n] and the tables in w.counts / w.vol [n_patches]; the scalars go to
+// the host pointers.
+int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, int32_t flags, hipStream_t st, OrientWork& w,
+                int32_t* d_tris_out, int64_t* n_patches, double ref_point[3], int64_t totals[8])
+{
+    uint64_t h_small[MO_SMALL] = {};
+    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
+    ENSURE(w.small, sizeof h_small);
+    uint64_t* small = w.small.as<uint64_t>();
+    HIP_TRY(hipMemcpyAsync(small, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
+    if (n_verts > 0) {
+        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, small);
+        HIP_TRY(hipGetLastError());
+    }
+    const int64_t nh = 3 * n;
+    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    size_t scan_bytes = 0;
+    if (n > 0) {
+        ENSURE(w.keys, sizeof(uint64_t) * (size_t)nh);
+        ENSURE(w.keys2, sizeof(uint64_t) * (size_t)nh);
+        ENSURE(w.vals, sizeof(uint32_t) * (size_t)nh);
+        ENSURE(w.vals2, sizeof(uint32_t) * (size_t)nh);
+        ENSURE(w.parent, sizeof(uint32_t) * 2 * (size_t)n);
+        ENSURE(w.info, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
+        ENSURE(w.num, sizeof(int32_t) * (size_t)n);
+        ENSURE(w.patch, sizeof(int32_t) * (size_t)n);
+        ENSURE(w.flip, sizeof(int32_t) * (size_t)n);
+        ENSURE(w.skey, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.skey2, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.sval, sizeof(uint32_t) * (size_t)n);
+        ENSURE(w.sval2, sizeof(uint32_t) * (size_t)n);
+        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
+        uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>(), *parent = w.parent.as<uint32_t>();
+        mo_key_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ckey, keys, vals, parent, small);
+        HIP_TRY(hipGetLastError());
+        const unsigned ebits = 33u + ms_bits((uint64_t)n_verts);   // (the collapsed key included)
+        size_t tb = 0;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
+        HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n,
+                                        rocprim::plus<int32_t>(), st));
+        ENSURE(w.temp, std::max<size_t>(std::max(tb, scan_bytes), 16));
+        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
+        mo_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, parent);
+        HIP_TRY(hipGetLastError());
+        mo_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.info.as<uint32_t>(), w.rflag.as<int32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::exclusive_scan(w.temp.p, scan_bytes, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n,
+                                        rocprim::plus<int32_t>(), st));
+        mo_number_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, w.info.as<uint32_t>(), w.num.as<int32_t>(), w.rflag.as<int32_t>(),
+                                                     w.patch.as<int32_t>(), w.skey.as<uint32_t>(), w.sval.as<uint32_t>(), small);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    double r[3];
+    ms_ref_point(h_small, n_verts, r);
+    const int64_t np = (int64_t)h_small[MO_NPATCHES], ncol = (int64_t)h_small[MO_COLLAPSED], nvalid = n - ncol;
+    if (n > 0) {
+        const int64_t nblk = (nvalid + MO_BLOCK - 1) / MO_BLOCK;
+        ENSURE(w.seg, sizeof(int64_t) * (size_t)(np + 1));
+        ENSURE(w.partial, sizeof(double) * (size_t)(nblk + np + 1));
+        ENSURE(w.counts, sizeof(int64_t) * MO_NCNT * (size_t)std::max<int64_t>(np, 1));
+        ENSURE(w.vol, sizeof(double) * (size_t)std::max<int64_t>(np, 1));
+        ENSURE(w.gflag, sizeof(int32_t) * (size_t)std::max<int64_t>(np, 1));
+        int64_t* counts = w.counts.as<int64_t>();
+        const uint32_t* info = w.info.as<uint32_t>();
+        const int32_t* patch = w.patch.as<int32_t>();
+        if (np > 0) {
+            HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * MO_NCNT * (size_t)np, st));
+            uint32_t *skey = w.skey.as<uint32_t>(), *skey2 = w.skey2.as<uint32_t>(), *sval = w.sval.as<uint32_t>(), *sval2 = w.sval2.as<uint32_t>();
+            size_t tb = 0;
+            const unsigned sbits = ms_bits((uint64_t)np);
+            HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
+            ENSURE(w.temp, std::max<size_t>(tb, 16));
+            HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
+            mo_segment_kernel<<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, np, w.seg.as<int64_t>(), counts);
+            HIP_TRY(hipGetLastError());
+            mo_sum_kernel<<<(unsigned)nblk, MO_BLOCK, 0, st>>>(d_verts, d_tris, info, skey2, sval2, nvalid, r[0], r[1], r[2],
+                                                              w.partial.as<double>());
+            HIP_TRY(hipGetLastError());
+            mo_combine_kernel<<<(unsigned)((np + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), np, w.partial.as<double>(), w.vol.as<double>(), counts);
+            HIP_TRY(hipGetLastError());
+            mo_parity_kernel<<<ms_blocks(n), 256, 0, st>>>(n, info, patch, counts);
+            HIP_TRY(hipGetLastError());
+            // (keys2 / vals2 still hold the sorted half-edges)
+            mo_edge_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, patch, counts);
+            HIP_TRY(hipGetLastError());
+            mo_decide_kernel<<<ms_blocks(np), 256, 0, st>>>(np, flags, info, counts, w.vol.as<double>(), w.gflag.as<int32_t>(), small);
+            HIP_TRY(hipGetLastError());
+        }
+        mo_apply_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, info, patch, w.gflag.as<int32_t>(), d_tris_out, w.flip.as<int32_t>());
+        HIP_TRY(hipGetLastError());
+        if (np > 0) {
+            mo_remain_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, w.flip.as<int32_t>(), small);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_patches = np;
+    for (int k = 0; k < 3; ++k) ref_point[k] = r[k];
+    totals[0] = np, totals[1] = n, totals[2] = ncol;
+    for (int k = 0; k < 5; ++k) totals[3 + k] = np > 0 ? (int64_t)h_small[MO_TOT + k] : 0;
+    return 0;
+}
+
+int orient_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tris, int32_t flags, const void* tris_out,
+                const int64_t* n_patches, const double* ref_point, const int64_t* totals)
+{
+    const int rc = mesh_args("mesh_orient", verts, n_verts, tris, n_tris);
+    if (rc) return rc;
+    if (n_tris > MO_MAX_TRIS) return fail(R2S_ERR_UNSUPPORTED, "mesh_orient: %lld triangles exceed 2^30", (long long)n_tris);
+    if (flags & ~MO_FLAGS) return fail(R2S_ERR_ARG, "mesh_orient: unknown flag bits in %d", (int)flags);
+    if (n_tris > 0 && !tris_out) return fail(R2S_ERR_ARG, "mesh_orient: null tris_out");
+    if (!n_patches || !ref_point || !totals) return fail(R2S_ERR_ARG, "mesh_orient: null n_patches / ref_point / totals");
+    return 0;
+}
+
+OrientWork* orient_work_of_current_device(int& rc)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
+        return nullptr;
+    }
+    rc = 0;
+    return &g_orient_work[dev];
+}
+
+}  // namespace
+
+namespace r2s_int {
+
+void release_orient_work()
+{
+    std::lock_guard<std::mutex> lock(g_orient_mu);
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+    for (auto& kv : g_orient_work) {
+        (void)hipSetDevice(kv.first);
+        kv.second.release();
+    }
+    g_orient_work.clear();
+    if (cur >= 0) (void)hipSetDevice(cur);
+    (void)hipGetLastError();
+}
+
+}  // namespace r2s_int
+
+extern "C" {
+
+int r2s_mesh_orient(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, int32_t flags, int32_t device,
+                    int32_t* tris_out, int32_t* flip_out, int32_t* patch_of_tri_out, int64_t* n_patches, double ref_point[3],
+                    int64_t totals[8])
+{
+    int rc = orient_args(verts, n_verts, tris, n_tris, flags, tris_out, n_patches, ref_point, totals);
+    if (rc) return rc;
+    if ((rc = check_mesh_host("mesh_orient", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
+    std::lock_guard<std::mutex> lock(g_orient_mu);
+    OrientWork* w = orient_work_of_current_device(rc);
+    if (rc) return rc;
+    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
+    ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)));
+    int64_t np = 0, tot[8];
+    double r[3];
+    if ((rc = orient_core(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, flags, nullptr, *w, w->tris_out.as<int32_t>(), &np, r,
+                          tot)))
+        return rc;
+    OrientTables tab;
+    tab.counts.resize((size_t)np * MO_NCNT);
+    tab.volume.resize((size_t)np);
+    if (np > 0) {
+        HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tab.volume.data(), w->vol.p, sizeof(double) * tab.volume.size(), hipMemcpyDeviceToHost));
+    }
+    if (n_tris > 0) {
+        HIP_TRY(hipMemcpy(tris_out, w->tris_out.p, tri_bytes(n_tris), hipMemcpyDeviceToHost));
+        if (flip_out) HIP_TRY(hipMemcpy(flip_out, w->flip.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToHost));
+        if (patch_of_tri_out) HIP_TRY(hipMemcpy(patch_of_tri_out, w->patch.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToHost));
+    }
+    g_last_orient = std::move(tab);
+    *n_patches = np;
+    std::memcpy(ref_point, r, sizeof r);
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
+int r2s_last_mesh_orient(int64_t* counts_out, double* volume_out, int64_t capacity, int64_t* n_patches)
+{
+    if (!n_patches || capacity < 0 || (capacity > 0 && (!counts_out || !volume_out)))
+        return fail(R2S_ERR_ARG, "last_mesh_orient: null output or negative capacity");
+    const int64_t n = (int64_t)g_last_orient.volume.size(), m = std::min(capacity, n);
+    *n_patches = n;
+    if (m > 0) {
+        std::memcpy(counts_out, g_last_orient.counts.data(), sizeof(int64_t) * MO_NCNT * (size_t)m);
+        std::memcpy(volume_out, g_last_orient.volume.data(), sizeof(double) * (size_t)m);
+    }
+    return 0;
+}
+
+int r2s_mesh_orient_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n_tris, int32_t flags, int32_t* d_tris_out,
+                        int32_t* d_flip_out, int32_t* d_patch_of_tri, int64_t* d_counts, double* d_volume, int64_t patch_capacity,
+                        int64_t* n_patches, double ref_point[3], int64_t totals[8], void* stream)
+{
+    int rc = orient_args(d_verts, n_verts, d_tris, n_tris, flags, d_tris_out, n_patches, ref_point, totals);
+    if (rc) return rc;
+    if (patch_capacity < 0 || (patch_capacity > 0 && (!d_counts || !d_volume)))
+        return fail(R2S_ERR_ARG, "mesh_orient: null tables or negative patch_capacity");
+    if ((rc = check_device(0))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g_orient_mu);
+    OrientWork* w = orient_work_of_current_device(rc);
+    if (rc) return rc;
+    if ((rc = check_mesh_dev("mesh_orient", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
+    int64_t np = 0, tot[8];
+    double r[3];
+    if ((rc = orient_core(d_verts, n_verts, d_tris, n_tris, flags, st, *w, d_tris_out, &np, r, tot))) return rc;
+    if (n_tris > 0) {
+        if (d_flip_out) HIP_TRY(hipMemcpyAsync(d_flip_out, w->flip.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToDevice, st));
+        if (d_patch_of_tri) HIP_TRY(hipMemcpyAsync(d_patch_of_tri, w->patch.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToDevice, st));
+    }
+    if (np > 0 && patch_capacity >= np) {
+        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MO_NCNT * (size_t)np, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_volume, w->vol.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_patches = np;
+    std::memcpy(ref_point, r, sizeof r);
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
+}  // extern "C"

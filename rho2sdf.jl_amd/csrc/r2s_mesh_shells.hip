@@ -239,38 +239,6 @@ __global__ void __launch_bounds__(256) ms_combine_kernel(const int64_t* __restri
     }
 }
 
-// adds 1 to counts[shell][col0 + k] for every k < NC with add[k] set, over the workgroup's active threads: once per column
-// when all of them name one shell, else one atomic per entry.  Called by all 256 threads.
-template <int NC>
-__device__ inline void ms_count(bool active, int32_t shell, const bool add[NC], int col0, int64_t* __restrict__ counts)
-{
-    __shared__ int32_t s_shell, s_mixed;
-    __shared__ uint32_t s_cnt[NC];
-    if (threadIdx.x == 0) s_shell = -1, s_mixed = 0;
-    if (threadIdx.x < NC) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    if (active) atomicCAS(&s_shell, -1, shell);
-    __syncthreads();
-    if (active && shell != s_shell) s_mixed = 1;
-    __syncthreads();
-    if (s_mixed) {
-        if (active) {
-#pragma unroll
-            for (int k = 0; k < NC; ++k)
-                if (add[k]) atomicAdd((unsigned long long*)&counts[(int64_t)shell * MS_NCNT + col0 + k], 1ull);
-        }
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-        const unsigned long long m = __ballot(active && add[k]);
-        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_cnt[k], (uint32_t)__popcll(m));
-    }
-    __syncthreads();
-    if (threadIdx.x < NC && s_shell >= 0 && s_cnt[threadIdx.x])
-        atomicAdd((unsigned long long*)&counts[(int64_t)s_shell * MS_NCNT + col0 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-}
-
 // one thread per sorted half-edge; the first member of a run classifies it and counts it into the shell of its triangle
 __global__ void __launch_bounds__(256) ms_edge_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
                                                        uint64_t ckey, const int32_t* __restrict__ shell_of, int64_t* __restrict__ counts)
@@ -292,7 +260,7 @@ __global__ void __launch_bounds__(256) ms_edge_kernel(const uint64_t* __restrict
             shell = shell_of[vals[i] / 3u];
         }
     }
-    ms_count<4>(head, shell, add, 3, counts);
+    ms_count<4, MS_NCNT>(head, shell, add, 3, counts);
 }
 
 __global__ void __launch_bounds__(256) ms_vkey_kernel(const int32_t* __restrict__ tris, int64_t n, const int32_t* __restrict__ shell_of,
@@ -316,7 +284,7 @@ __global__ void __launch_bounds__(256) ms_vcount_kernel(const uint64_t* __restri
         shell = (int32_t)(k >> 32);
     }
     const bool add[1] = {true};
-    ms_count<1>(head, shell, add, 2, counts);
+    ms_count<1, MS_NCNT>(head, shell, add, 2, counts);
 }
 
 // small[MS_TOT + 0..3] = the sums of columns 3..6 over the shells, small[MS_TOT + 4] = the number of set vertex flags

@@ -609,16 +609,82 @@ mutable struct R2SStlMesh              # mirrors r2s_stl_mesh
     verts::Ptr{Float32}
 end
 
+# A consistent winding for a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_orient): verts 3 x nv Float32, tris 3 x nt 1-based.
+# The mesh falls into patches over the edges that exactly two triangles share; inside an orientable patch every triangle gets
+# the winding of its neighbours, and the patch as a whole
+#     outward = true, the patch closed with a volume V != 0:   is wound so that V > 0 ("decided by volume")
+#     otherwise (and always with outward = false):              keeps the winding of the MAJORITY of its triangles, on a tie
+#                                                               that of its first triangle
+# A flipped triangle (i0, i1, i2) comes back as (i0, i2, i1).  Nesting is ignored: outward = true turns an enclosed void into a
+# body, the majority rule leaves a void as most of its triangles say.  Non-orientable patches are copied unchanged and counted;
+# no orientation is carried across non-manifold edges; no holes are filled.
+# -> (tris 3 x nt 1-based, flipped (Bool), patch_of_tri (1-based patch number, 0 = collapsed triangle), counts 8 x n Int64
+# (first_tri 1-based, n_tris, flipped triangles, status bits 1 closed / 2 non-orientable / 4 decided by volume, boundary and
+# non-manifold half-edges, flipped edges of the input, 0), volume (n, as written, about ref_point), ref_point, totals)
+const ORIENT_OUTWARD = Int32(1)
+function mesh_orient_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}; outward::Bool = false, device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    t0 = Int32.(tris) .- Int32(1)
+    nt = size(t0, 2)
+    tout = Matrix{Int32}(undef, 3, nt)
+    flip = Vector{Int32}(undef, nt); patch = Vector{Int32}(undef, nt)
+    n = Ref{Int64}(0)
+    ref = zeros(Float64, 3)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_orient, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Float64},
+                 Ptr{Int64}),
+                Matrix(verts), size(verts, 2), t0, nt, outward ? ORIENT_OUTWARD : Int32(0), Int32(device), tout, flip, patch, n, ref,
+                totals))
+    counts, volume = last_mesh_orient_hip(n[])
+    return (tris = tout .+ Int32(1), flipped = flip .!= 0, patch_of_tri = patch .+ Int32(1), counts = counts, volume = volume,
+            ref_point = ref, totals = totals)
+end
+
+# the calling thread's last orient tables (r2s_last_mesh_orient): counts 8 x n (first_tri made 1-based), volume n
+function last_mesh_orient_hip(capacity::Integer)
+    counts = Matrix{Int64}(undef, 8, capacity)
+    volume = Vector{Float64}(undef, capacity)
+    n = Ref{Int64}(0)
+    check(ccall((:r2s_last_mesh_orient, LIB[]), Cint, (Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}),
+                capacity == 0 ? C_NULL : counts, capacity == 0 ? C_NULL : volume, Int64(capacity), n))
+    counts[1, :] .+= 1
+    return counts, volume
+end
+
+# the same on device arrays of the current device (raw pointers, e.g. of AMDGPU.jl ROCArrays); d_tris_out must not overlap d_tris,
+# d_flip and d_patch_of_tri may be C_NULL; the triangles, flips and labels are always written, the tables only when
+# patch_capacity holds all patches -> (n_patches, ref_point, totals); indices stay 0-based on the device
+function mesh_orient_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer, d_tris_out::Ptr{Cvoid},
+                             d_flip::Ptr{Cvoid}, d_patch_of_tri::Ptr{Cvoid}, d_counts::Ptr{Cvoid}, d_volume::Ptr{Cvoid},
+                             patch_capacity::Integer; outward::Bool = false, stream::Ptr{Cvoid} = C_NULL)
+    n = Ref{Int64}(0)
+    ref = zeros(Float64, 3)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_orient_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+                 Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), outward ? ORIENT_OUTWARD : Int32(0), d_tris_out, d_flip, d_patch_of_tri,
+                d_counts, d_volume, Int64(patch_capacity), n, ref, totals, stream))
+    return n[], ref, totals
+end
+
 # The triangles of a binary or ASCII STL file (r2s_import_stl) -> (verts 3 x nv Float32, tris 3 x nt 1-based).  weld = true: the
 # equal vertices are merged by mesh_weld_hip(soup; snap); weld = false: the soup as the file holds it, tris = 1:3nt.
-function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real = 0.0, device::Integer = -1)
+# orient = nothing: the windings as the file holds them; :majority or :outward (needs weld = true): the welded triangles go
+# through mesh_orient_hip (see there for the rules and the caveat about enclosed voids).
+function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real = 0.0, device::Integer = -1,
+                        orient::Union{Nothing,Symbol} = nothing)
+    orient === nothing || orient in (:majority, :outward) || error("orient must be nothing, :majority or :outward")
+    orient === nothing || weld || error("orient needs weld = true")
     m = R2SStlMesh(0, C_NULL)
     check(ccall((:r2s_import_stl, LIB[]), Cint, (Cstring, Ref{R2SStlMesh}), filename, m))
     soup = copy(unsafe_wrap(Array, m.verts, (3, 3 * Int(m.n_tris))))
     ccall((:r2s_free_stl_mesh, LIB[]), Cvoid, (Ref{R2SStlMesh},), m)
     weld || return soup, reshape(Int32.(1:size(soup, 2)), 3, :)
     w = mesh_weld_hip(soup; snap = snap, device = device)
-    return w.verts, w.tris
+    orient === nothing && return w.verts, w.tris
+    return w.verts, mesh_orient_hip(w.verts, w.tris; outward = orient === :outward, device = device).tris
 end
 
 # The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
