@@ -897,6 +897,69 @@ int r2s_mesh_orient_dev(const float *d_verts, int64_t n_verts, const int32_t *d_
                         int32_t *d_tris_out, int32_t *d_flip_out, int32_t *d_patch_of_tri, int64_t *d_counts, double *d_volume,
                         int64_t patch_capacity, int64_t *n_patches, double ref_point[3], int64_t totals[8], void *stream);
 
+/* ---- mesh index: self-intersection pairs --------------------------------------------------------
+ * Does the surface pass through itself?  The shells' volume and "void" verdict, OUTWARD orientation, "material on the left" of a
+ * section and the wall thickness all read the mesh as an embedded surface; this is the check that says whether they may.  For
+ * every unordered pair of triangles of ONE mesh that intersect or touch: the pair, the number of such pairs per triangle, and
+ * totals.  Against the same index (tree, device copies) as the distance and ray queries; the index is not changed.
+ * Vertices: the float32 values widened to double.  Every product, sum, difference and quotient is rounded on its own (no fma).
+ *   - collapsed triangle: two of its three vertex INDICES are equal.  It takes part in no pair and is counted (totals[5]).
+ *   - box of a triangle: per axis the float32 min and max of its three vertices.
+ *   - candidate pair (s, t): s < t, both non-collapsed, and the closed boxes overlap on all three axes:
+ *     lo_s[k] <= hi_t[k] && lo_t[k] <= hi_s[k] for k = x, y, z, compared in float32.
+ *   - shared indices of a candidate pair = the number of corners of s whose vertex index is also a corner of t:
+ *       2 or 3: the pair is skipped and counted as adjacent (totals[3]).  Edge neighbours and duplicates always touch; a fold of a
+ *               triangle onto its edge neighbour is coplanar and out of scope.
+ *       1 (the index v): two segment tests: the edge of s opposite v against t, and the edge of t opposite v against s.  (The
+ *               edges through v meet the other triangle at v by construction.)  Counted in totals[4].
+ *       0: six segment tests: the three edges of s against t and the three edges of t against s.
+ *     Edge c of a triangle (c = 0, 1, 2) runs from its corner c to its corner (c + 1) % 3, in that direction; the edge opposite
+ *     corner c is edge (c + 1) % 3.
+ *   - segment test (edge p -> q, triangle a b c): the ray pair test of r2s_mesh_index_raycast above, steps 1 to 7, with o = p
+ *     and d = q - p (one subtraction per component, in double).  No box condition, no t_min / t_max.  A hit requires all of: not
+ *     rejected by step 5, det != 0, and 0 <= t <= 1 (both ends inclusive).  d == 0 in all three components: no hit.
+ *   - the pair is INTERSECTING iff any of its segment tests hits.  The predicate uses only the two triangles' own data and does
+ *     not depend on which of them is s: under a permutation of the triangles the result follows the permutation exactly.  (No
+ *     claim is made under a rotation of a triangle's corners: the edges' directions change.)
+ *   - consequences.  A segment parallel to the triangle's plane has det == 0 and never hits: COPLANAR OVERLAP IS NOT REPORTED.
+ *     CONTACT COUNTS: a vertex on a face, an edge through an edge, coincident coordinates under different indices all hit.  An
+ *     unwelded triangle soup therefore reports every neighbour of every triangle: WELD FIRST (r2s_mesh_weld), so that
+ *     neighbours share indices.  A zero-area triangle with distinct indices is ordinary input (its plane tests have det == 0;
+ *     its edges are still tested against others).
+ *   - hits_of_tri[t], int32: the number of intersecting pairs that contain t.
+ *   - pairs [n][2], int32: s < t, sorted ascending by (s, t).
+ *   - totals, int64[8]: [0] intersecting pairs, [1] triangles in at least one intersecting pair, [2] candidate pairs, [3]
+ *     candidate pairs skipped as adjacent, [4] candidate pairs sharing exactly one index, [5] collapsed triangles, [6], [7] 0.
+ *   - why the tree is exact: two triangles with a common point have overlapping closed boxes, and a node's box is the exact
+ *     float32 min / max of its leaves' boxes, so every ancestor of t overlaps the box of s too: entering every node whose box
+ *     overlaps the box of s reaches every candidate pair.  The results are those of a loop over all pairs s < t, bit for bit.
+ *     All outputs are integers, no floating-point value leaves the call, nothing depends on the traversal order or on the
+ *     arrival order of an atomic (integer atomics only; the pair list is sorted).
+ * r2s_mesh_index_intersections: host arrays; hits_of_tri_out [n_tris] may be NULL.  totals is always written on success.  The
+ * pair list is written only when pair_capacity >= totals[0]; otherwise pairs_out is left untouched: ask with pair_capacity 0,
+ * then call again.  pairs_out may be NULL only with pair_capacity == 0.
+ * r2s_mesh_index_intersections_dev: d_hits_of_tri (may be NULL) and d_pairs are device pointers on the index's device, which must
+ * be current; totals is a host pointer.  Reads after the work queued on `stream`, runs its own work on `stream`, and is
+ * synchronous on return (the count comes back on the host).
+ * r2s_mesh_intersections / _dev: the same for a mesh without an index (host arrays and `device`, -1 = current; or device arrays
+ * on the current device): a tree is built, used and dropped.
+ * Work buffers are kept per device and freed by r2s_release_cache.  An empty mesh succeeds with zeros.
+ * R2S_ERR_ARG before any device work, outputs untouched: a NULL index, NULL totals, NULL arrays with a count, NULL pairs with a
+ * capacity, a negative count or capacity, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the
+ * host; _dev: the check kernel of r2s_mesh_distance_dev), an index on another device than the current one (_dev).
+ * R2S_ERR_UNSUPPORTED: a tree deeper than the traversal stack (64 levels), more than 2^31 - 1 intersecting pairs.  No GPU:
+ * R2S_ERR_NO_DEVICE.  Not here: coplanar overlap and fold-overs between edge neighbours, intersections between two different
+ * meshes, the intersection curve, repair, any inside / outside sign. */
+int r2s_mesh_index_intersections(const r2s_mesh_index *index, int32_t *hits_of_tri_out, int32_t *pairs_out,
+                                 int64_t pair_capacity, int64_t totals[8]);
+int r2s_mesh_index_intersections_dev(const r2s_mesh_index *index, int32_t *d_hits_of_tri, int32_t *d_pairs,
+                                     int64_t pair_capacity, int64_t totals[8], void *stream);
+int r2s_mesh_intersections(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
+                           int32_t *hits_of_tri_out, int32_t *pairs_out, int64_t pair_capacity, int64_t totals[8]);
+int r2s_mesh_intersections_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris,
+                               int32_t *d_hits_of_tri, int32_t *d_pairs, int64_t pair_capacity, int64_t totals[8],
+                               void *stream);
+
 /* ---- on-disk output ------------------------------------------------------------------ */
 
 /* binary STL of a triangle mesh (verts [n_verts][3], tris [n_tris][3] 0-based); host only, no device; ".stl" appended

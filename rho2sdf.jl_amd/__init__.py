@@ -17,7 +17,8 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   MeshShells, mesh_shells, mesh_shells_dev, select_shells,
                   MeshSections, mesh_sections, mesh_sections_dev,
                   MeshWeld, mesh_weld, mesh_weld_dev, import_stl,
-                  MeshOrient, mesh_orient, mesh_orient_dev, flip_patches)
+                  MeshOrient, mesh_orient, mesh_orient_dev, flip_patches,
+                  MeshIntersections, mesh_intersections, mesh_intersections_dev)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
@@ -32,4 +33,5 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "MeshSections", "mesh_sections", "mesh_sections_dev",
            "MeshWeld", "mesh_weld", "mesh_weld_dev", "import_stl",
            "MeshOrient", "mesh_orient", "mesh_orient_dev", "flip_patches",
+           "MeshIntersections", "mesh_intersections", "mesh_intersections_dev",
            "_lib"]

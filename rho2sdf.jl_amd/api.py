@@ -726,6 +726,92 @@ class MeshIndex:
         res = (t,) + ((idx,) if want_index else ()) + ((side,) if want_side else ())
         return res if len(res) > 1 else t
 
+    def self_intersections(self, want_pairs=True):
+        """The pairs of triangles of the indexed mesh that intersect or touch (include/rho2sdf_hip.h,
+        r2s_mesh_index_intersections) -> MeshIntersections; want_pairs=False: counts only (`pairs` is None).  The index is not
+        changed."""
+        h = self._handle()
+        nt = self.info()["n_tris"]
+        return _intersections_host(nt, want_pairs, lambda hits, pairs, cap, tot: L.lib().r2s_mesh_index_intersections(h, hits, pairs, cap, tot))
+
+    def self_intersections_dev(self, want_pairs=True, stream=None, *, capacity=0):
+        """self_intersections with the results on the index's device, which must be current: `hits_of_tri` and `pairs` are torch
+        tensors, `totals` a numpy array.  Reads after the work queued on the current stream (or `stream`); synchronous."""
+        h = self._handle()
+        nt = self.info()["n_tris"]
+        return _intersections_dev(nt, want_pairs, capacity, stream,
+                                  lambda hits, pairs, cap, tot, st: L.lib().r2s_mesh_index_intersections_dev(h, hits, pairs, cap, tot, st))
+
+
+class MeshIntersections:
+    """The self-intersections of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_index_intersections): `pairs` (n, 2) int32, the
+    intersecting or touching pairs (s, t) with s < t, ascending by (s, t) (None when they were not asked for); `hits_of_tri` (nt,)
+    int32, the number of pairs each triangle is in; `totals` (8,) int64 (intersecting pairs, triangles involved, candidate pairs,
+    candidates skipped as adjacent, candidates sharing exactly one vertex index, collapsed triangles, 0, 0).  len() is the number
+    of pairs; `tris` the ascending indices of the triangles involved.  Coplanar overlap is not reported; contact counts, so weld a
+    soup first.  numpy arrays, or (from the *_dev calls) torch tensors for pairs and hits_of_tri."""
+
+    def __init__(self, pairs, hits_of_tri, totals):
+        self.pairs, self.hits_of_tri, self.totals = pairs, hits_of_tri, totals
+
+    def __len__(self):
+        return int(self.totals[0])
+
+    @property
+    def tris(self):
+        h = self.hits_of_tri
+        return np.nonzero(h)[0] if isinstance(h, np.ndarray) else h.nonzero().reshape(-1)
+
+
+def _intersections_host(nt, want_pairs, call):
+    """the two-call capacity protocol of the host entry points: counts first, then the pairs into room for all of them"""
+    hits, tot = np.zeros(nt, np.int32), np.zeros(8, np.int64)
+    ip = lambda a: a.ctypes.data_as(L.c_int32_p)   # noqa: E731
+    L.check(call(ip(hits), None, 0, _i(tot)))
+    if not want_pairs:
+        return MeshIntersections(None, hits, tot)
+    pairs = np.empty((int(tot[0]), 2), np.int32)
+    if len(pairs):
+        L.check(call(ip(hits), ip(pairs), len(pairs), _i(tot)))
+    return MeshIntersections(pairs, hits, tot)
+
+
+def _intersections_dev(nt, want_pairs, capacity, stream, call):
+    import torch
+    st = _stream(stream)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    hits, tot = torch.zeros(nt, dtype=torch.int32, device=dev), np.zeros(8, np.int64)
+    vp = ctypes.c_void_p
+    cap = int(capacity) if want_pairs else 0
+    while True:
+        pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+        L.check(call(vp(hits.data_ptr()) if nt else None, vp(pairs.data_ptr()) if cap else None, cap, _i(tot), st))
+        if not want_pairs or tot[0] <= cap:
+            break
+        cap = int(tot[0])
+    return MeshIntersections(pairs[:int(tot[0])] if want_pairs else None, hits, tot)
+
+
+def mesh_intersections(verts, tris, *, device=-1):
+    """The self-intersections of a triangle mesh without an index (verts (nv, 3) float32, tris (nt, 3) int32, 0-based) ->
+    MeshIntersections: the library builds a tree, uses it and drops it.  With a MeshIndex at hand use its self_intersections()."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    pv, pt = _f(v) if len(v) else None, t.ctypes.data_as(L.c_int32_p) if len(t) else None
+    return _intersections_host(len(t), True, lambda hits, pairs, cap, tot: L.lib().r2s_mesh_intersections(
+        pv, len(v), pt, len(t), int(device), hits, pairs, cap, tot))
+
+
+def mesh_intersections_dev(verts, tris, stream=None, *, capacity=0):
+    """mesh_intersections on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous); pairs
+    and hits_of_tri stay device tensors.  The library writes the pairs only into room for all of them: with more pairs than
+    `capacity` the call is made a second time."""
+    _mesh_tensors(verts, tris)
+    vp = ctypes.c_void_p
+    nv, nt = verts.numel() // 3, tris.numel() // 3
+    return _intersections_dev(nt, True, capacity, stream, lambda hits, pairs, cap, tot, st: L.lib().r2s_mesh_intersections_dev(
+        vp(verts.data_ptr()), nv, vp(tris.data_ptr()), nt, hits, pairs, cap, tot, st))
+
 
 class MeshShells:
     """The shells of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_shells): the raw tables and what follows from them.
@@ -1522,17 +1608,21 @@ def export_stl(filename, verts, tris):
     return filename if filename.endswith(".stl") else filename + ".stl"
 
 
-def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None):
+def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_intersections=False):
     """The triangles of a binary or ASCII STL file -> (verts (nv, 3) float32, tris (nt, 3) int32).  weld=True (needs the GPU): the
     vertices that are the same point are merged by mesh_weld(soup, snap=snap) with its defaults (collapsed triangles and unused
     vertices dropped), so the mesh tools see shared vertices; weld=False: the soup as the file holds it, 3 nt vertices and
     tris = arange.  Facet normals and attribute bytes are ignored.  orient=None: the windings as the file holds them;
     "majority" or "outward" (needs weld=True): the welded triangles go through mesh_orient(outward=(orient == "outward")), whose
-    docstring has the rules and the caveat about enclosed voids."""
+    docstring has the rules and the caveat about enclosed voids.  check_intersections=True (needs weld=True): the result is
+    (verts, tris, MeshIntersections), the self-intersections of the mesh as returned (mesh_intersections): zero pairs are what
+    the shells, the orientation, sections and thickness take for granted."""
     if orient not in (None, "majority", "outward"):
         raise L.R2SError('orient must be None, "majority" or "outward"')
     if orient is not None and not weld:
         raise L.R2SError("orient needs weld=True: a soup has no shared edges to orient across")
+    if check_intersections and not weld:
+        raise L.R2SError("check_intersections needs weld=True: in a soup every neighbour touches under different indices")
     m = L.R2SStlMesh()
     L.check(L.lib().r2s_import_stl(str(filename).encode(), ctypes.byref(m)))
     try:
@@ -1543,9 +1633,10 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None):
     if not weld:
         return soup, np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
     w = mesh_weld(soup, None, snap=snap, device=device)
-    if orient is None:
-        return w.verts, w.tris
-    return w.verts, mesh_orient(w.verts, w.tris, outward=orient == "outward", device=device).tris
+    tris = w.tris if orient is None else mesh_orient(w.verts, w.tris, outward=orient == "outward", device=device).tris
+    if check_intersections:
+        return w.verts, tris, mesh_intersections(w.verts, tris, device=device)
+    return w.verts, tris
 
 
 def exportToVTU(fileName, X, IEN, VTK_CODE=None, rho=None):

@@ -165,4 +165,8 @@ void release_weld_work();
 // frees the work buffers the orient calls keep per device; called by r2s_release_cache()
 void release_orient_work();
 
+// ---- mesh intersections (r2s_mesh_intersect.hip) ----------------------------------------------------------------------
+// frees the work buffers the intersection calls keep per device; called by r2s_release_cache()
+void release_intersect_work();
+
 }  // namespace r2s_int

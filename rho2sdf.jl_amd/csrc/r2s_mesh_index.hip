@@ -19,39 +19,15 @@
 
 #include "r2s_common.hpp"
 #include "r2s_internal.hpp"
+#include "r2s_mesh_tree.hpp"
 #include "r2s_tri_math.hpp"
 
 using namespace r2s_int;
 
-// (the Scoped members free themselves: r2s_mesh_index_destroy deletes the index with its device current)
-struct r2s_mesh_index {
-    int device = 0;
-    Scoped verts, tris;
-    MiTree tree;
-};
-
+// (r2s_mesh_index, MiNode, load_node, tri_box and MI_STACK: r2s_mesh_tree.hpp)
 namespace {
 
-constexpr int MI_STACK = 64;   // stack entries per lane; a tree of height h needs at most h (one pending sibling per level)
 constexpr uint32_t MI_ROOT = 0xffffffffu;
-
-struct MiNode {
-    float box[2][6];      // child c: lo xyz, hi xyz
-    int32_t child[2];
-    int32_t height[2];    // 0 = leaf
-};
-static_assert(sizeof(MiNode) == 64, "MiNode is read as four 16-byte words");
-
-__device__ inline MiNode load_node(const MiNode* p)
-{
-    const uint4* w = reinterpret_cast<const uint4*>(p);
-    union {
-        uint4 q[4];
-        MiNode n;
-    } u;
-    u.q[0] = w[0], u.q[1] = w[1], u.q[2] = w[2], u.q[3] = w[3];
-    return u.n;
-}
 
 __device__ inline uint32_t mi_ordered(float f)
 {
@@ -66,15 +42,6 @@ inline float mi_unordered(uint32_t u)
     return f;
 }
 
-// the AABB of the triangle with the corners a, b, c (three floats each)
-__device__ inline void tri_box(const float* a, const float* b, const float* c, float lo[3], float hi[3])
-{
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = fminf(a[k], fminf(b[k], c[k]));
-        hi[k] = fmaxf(a[k], fmaxf(b[k], c[k]));
-    }
-}
 __device__ inline void mi_tri_box(const float* __restrict__ verts, const int32_t* __restrict__ tris, int64_t t, float lo[3], float hi[3])
 {
     tri_box(verts + 3 * (int64_t)tris[3 * t], verts + 3 * (int64_t)tris[3 * t + 1], verts + 3 * (int64_t)tris[3 * t + 2], lo, hi);
@@ -478,6 +445,10 @@ __global__ void __launch_bounds__(64) mi_ray_kernel(MiRay g)
     if (g.side) g.side[i] = (int8_t)bs;
 }
 
+}  // namespace
+
+namespace r2s_int {
+
 // the traversal kernels keep one pending sibling per level on a per-lane stack of MI_STACK entries
 int check_depth(const MiTree& T)
 {
@@ -493,17 +464,9 @@ int index_on_current_device(const char* who, const r2s_mesh_index* ix)
     return 0;
 }
 
-// makes the index's device current for a host-pointer call and restores the caller's on scope exit
-struct DeviceScope {
-    int prev = -1;
-    int enter(int device)
-    {
-        HIP_TRY(hipGetDevice(&prev));
-        if (prev != device) HIP_TRY(hipSetDevice(device));
-        return 0;
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+}  // namespace r2s_int
+
+namespace {
 
 int query_args(const char* who, const r2s_mesh_index* ix, const void* points, int64_t n, const void* out)
 {

@@ -1,0 +1,68 @@
+// What the traversals of the mesh index share across files (r2s_mesh_index.hip: distance and ray queries; r2s_mesh_intersect.hip:
+// self-intersection pairs): the index object, the node of its tree and how a wavefront reads it, the box of a triangle, the
+// depth of the per-lane stack, and the host checks every entry point on an index makes.  One definition for both files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "r2s_common.hpp"
+#include "r2s_internal.hpp"
+
+// (the Scoped members free themselves: r2s_mesh_index_destroy deletes the index with its device current)
+struct r2s_mesh_index {
+    int device = 0;
+    Scoped verts, tris;
+    r2s_int::MiTree tree;
+};
+
+namespace r2s_int {
+
+constexpr int MI_STACK = 64;   // stack entries per lane; a tree of height h needs at most h (one pending sibling per level)
+
+struct MiNode {
+    float box[2][6];      // child c: lo xyz, hi xyz
+    int32_t child[2];
+    int32_t height[2];    // 0 = leaf
+};
+static_assert(sizeof(MiNode) == 64, "MiNode is read as four 16-byte words");
+
+__device__ inline MiNode load_node(const MiNode* p)
+{
+    const uint4* w = reinterpret_cast<const uint4*>(p);
+    union {
+        uint4 q[4];
+        MiNode n;
+    } u;
+    u.q[0] = w[0], u.q[1] = w[1], u.q[2] = w[2], u.q[3] = w[3];
+    return u.n;
+}
+
+// the AABB of the triangle with the corners a, b, c (three floats each)
+__device__ inline void tri_box(const float* a, const float* b, const float* c, float lo[3], float hi[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = fminf(a[k], fminf(b[k], c[k]));
+        hi[k] = fmaxf(a[k], fmaxf(b[k], c[k]));
+    }
+}
+
+// the traversal kernels keep one pending sibling per level on a per-lane stack of MI_STACK entries (r2s_mesh_index.hip)
+int check_depth(const MiTree& T);
+// R2S_ERR_ARG unless the index's device is the current one; `who` heads the error text (r2s_mesh_index.hip)
+int index_on_current_device(const char* who, const r2s_mesh_index* ix);
+
+// makes the index's device current for a host-pointer call and restores the caller's on scope exit
+struct DeviceScope {
+    int prev = -1;
+    int enter(int device)
+    {
+        HIP_TRY(hipGetDevice(&prev));
+        if (prev != device) HIP_TRY(hipSetDevice(device));
+        return 0;
+    }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+}  // namespace r2s_int

@@ -94,6 +94,41 @@ __device__ inline void build_record(double* __restrict__ r, const float* __restr
     reinterpret_cast<int64_t*>(r)[37] = (int64_t)t;
 }
 
+// component k of v by selects (an indexed register array would go to scratch)
+__device__ inline double vec_pick(Vec3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+
+// Does the segment p -> q meet the triangle a b c?  The segment test of the header (r2s_mesh_index_intersections): the ray pair
+// test, steps 1 to 7, with o = p and d = q - p, every operation rounded on its own; a hit is not mixed, det != 0 and
+// 0 <= t <= 1.  The same arithmetic as the leaf of mi_ray_kernel without its box condition.
+__device__ inline bool seg_tri_hit(Vec3 p, Vec3 q, Vec3 a, Vec3 b, Vec3 c)
+{
+#pragma clang fp contract(off)
+    const Vec3 d = sub(q, p);
+    if (d.x == 0.0 && d.y == 0.0 && d.z == 0.0) return false;
+    int kz = 0;
+    double big = fabs(d.x);
+    if (fabs(d.y) > big) kz = 1, big = fabs(d.y);
+    if (fabs(d.z) > big) kz = 2;
+    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+    const double dkz = vec_pick(d, kz);
+    if (dkz < 0.0) {
+        const int s = kx;
+        kx = ky, ky = s;
+    }
+    const double Sx = vec_pick(d, kx) / dkz, Sy = vec_pick(d, ky) / dkz, Sz = 1.0 / dkz;
+    const double okx = vec_pick(p, kx), oky = vec_pick(p, ky), okz = vec_pick(p, kz);
+    const double Az = vec_pick(a, kz) - okz, Bz = vec_pick(b, kz) - okz, Cz = vec_pick(c, kz) - okz;
+    const double Ax = (vec_pick(a, kx) - okx) - Sx * Az, Ay = (vec_pick(a, ky) - oky) - Sy * Az;
+    const double Bx = (vec_pick(b, kx) - okx) - Sx * Bz, By = (vec_pick(b, ky) - oky) - Sy * Bz;
+    const double Cx = (vec_pick(c, kx) - okx) - Sx * Cz, Cy = (vec_pick(c, ky) - oky) - Sy * Cz;
+    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    const bool mixed = (U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0);
+    const double det = (U + V) + W;
+    if (mixed || det == 0.0) return false;
+    const double t = ((U * (Sz * Az) + V * (Sz * Bz)) + W * (Sz * Cz)) / det;
+    return t >= 0.0 && t <= 1.0;
+}
+
 // element i of a float32 (f32 != 0) or float64 array, read as / stored from a double
 __device__ inline double load_real(const void* p, int f32, int64_t i)
 {

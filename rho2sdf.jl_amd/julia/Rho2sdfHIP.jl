@@ -669,22 +669,77 @@ function mesh_orient_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{
     return n[], ref, totals
 end
 
+# The self-intersections of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_index_intersections): the pairs of triangles that
+# intersect or touch.  Coplanar overlap is not reported; contact counts (a vertex on a face, equal coordinates under different
+# indices), so weld a soup first.  -> (pairs 2 x n Int32, 1-based, s < t, ascending by (s, t); hits_of_tri, the number of pairs
+# each triangle is in; totals: intersecting pairs, triangles involved, candidate pairs, candidates skipped as adjacent, candidates
+# sharing exactly one vertex index, collapsed triangles, 0, 0).  Two calls: the counts, then the pairs into room for all of them.
+function _intersections_two_calls(nt::Integer, call)
+    hits = Vector{Int32}(undef, nt)
+    totals = zeros(Int64, 8)
+    check(call(hits, C_NULL, Int64(0), totals))
+    pairs = Matrix{Int32}(undef, 2, totals[1])
+    totals[1] == 0 || check(call(hits, pairs, Int64(totals[1]), totals))
+    return (pairs = pairs .+ Int32(1), hits_of_tri = hits, totals = totals)
+end
+
+# through an index at hand; the index is not changed
+function mesh_index_intersections(ix::MeshIndexHIP)
+    nt = mesh_index_info(ix).n_tris
+    return _intersections_two_calls(nt, (hits, pairs, cap, totals) ->
+        ccall((:r2s_mesh_index_intersections, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int64}),
+              ix.handle, hits, pairs, cap, totals))
+end
+
+# without an index: verts 3 x nv Float32, tris 3 x nt 1-based; a tree is built, used and dropped
+function mesh_intersections_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}; device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    v, t0 = Matrix(verts), Int32.(tris) .- Int32(1)
+    return _intersections_two_calls(size(t0, 2), (hits, pairs, cap, totals) ->
+        ccall((:r2s_mesh_intersections, LIB[]), Cint,
+              (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int64}),
+              v, size(v, 2), t0, size(t0, 2), Int32(device), hits, pairs, cap, totals))
+end
+
+# the same on device arrays of the current device (raw pointers); d_hits_of_tri may be C_NULL, d_pairs only with pair_capacity 0;
+# the pairs are written only when pair_capacity holds all of them -> totals; indices stay 0-based on the device
+function mesh_index_intersections_dev(ix::MeshIndexHIP, d_hits_of_tri::Ptr{Cvoid}, d_pairs::Ptr{Cvoid}, pair_capacity::Integer;
+                                      stream::Ptr{Cvoid} = C_NULL)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_index_intersections_dev, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}),
+                ix.handle, d_hits_of_tri, d_pairs, Int64(pair_capacity), totals, stream))
+    return totals
+end
+
+function mesh_intersections_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer,
+                                    d_hits_of_tri::Ptr{Cvoid}, d_pairs::Ptr{Cvoid}, pair_capacity::Integer;
+                                    stream::Ptr{Cvoid} = C_NULL)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_intersections_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), d_hits_of_tri, d_pairs, Int64(pair_capacity), totals, stream))
+    return totals
+end
+
 # The triangles of a binary or ASCII STL file (r2s_import_stl) -> (verts 3 x nv Float32, tris 3 x nt 1-based).  weld = true: the
 # equal vertices are merged by mesh_weld_hip(soup; snap); weld = false: the soup as the file holds it, tris = 1:3nt.
 # orient = nothing: the windings as the file holds them; :majority or :outward (needs weld = true): the welded triangles go
-# through mesh_orient_hip (see there for the rules and the caveat about enclosed voids).
+# through mesh_orient_hip (see there for the rules and the caveat about enclosed voids).  check_intersections = true (needs
+# weld = true): -> (verts, tris, mesh_intersections_hip of the mesh as returned).
 function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real = 0.0, device::Integer = -1,
-                        orient::Union{Nothing,Symbol} = nothing)
+                        orient::Union{Nothing,Symbol} = nothing, check_intersections::Bool = false)
     orient === nothing || orient in (:majority, :outward) || error("orient must be nothing, :majority or :outward")
     orient === nothing || weld || error("orient needs weld = true")
+    !check_intersections || weld || error("check_intersections needs weld = true")
     m = R2SStlMesh(0, C_NULL)
     check(ccall((:r2s_import_stl, LIB[]), Cint, (Cstring, Ref{R2SStlMesh}), filename, m))
     soup = copy(unsafe_wrap(Array, m.verts, (3, 3 * Int(m.n_tris))))
     ccall((:r2s_free_stl_mesh, LIB[]), Cvoid, (Ref{R2SStlMesh},), m)
     weld || return soup, reshape(Int32.(1:size(soup, 2)), 3, :)
     w = mesh_weld_hip(soup; snap = snap, device = device)
-    orient === nothing && return w.verts, w.tris
-    return w.verts, mesh_orient_hip(w.verts, w.tris; outward = orient === :outward, device = device).tris
+    tris = orient === nothing ? w.tris : mesh_orient_hip(w.verts, w.tris; outward = orient === :outward, device = device).tris
+    check_intersections || return w.verts, tris
+    return w.verts, tris, mesh_intersections_hip(w.verts, tris; device = device)
 end
 
 # The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
