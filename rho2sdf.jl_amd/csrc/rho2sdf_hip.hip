@@ -2419,7 +2419,10 @@ static int iso_project_hex(r2s_plan* P, hipStream_t st, uint32_t n_items, uint32
                            const uint32_t* abort_flag)
 {
     static const int free_env = getenv("R2S_ISO_FREE") ? atoi(getenv("R2S_ISO_FREE")) : 0;   // tuning knob: fewer persistent wavefronts
-    const uint32_t resident = (uint32_t)P->n_cu * 4u * wps - (uint32_t)std::min(std::max(free_env, 0), (int)P->n_cu * 4);
+    static const int resident_env = getenv("R2S_ISO_RESIDENT") ? atoi(getenv("R2S_ISO_RESIDENT")) : 0;   // test hook: a machine of n persistent wavefronts (forced schedules on small grids)
+    uint32_t resident = (uint32_t)P->n_cu * 4u * wps - (uint32_t)std::min(std::max(free_env, 0), (int)P->n_cu * 4);
+    if (resident_env > 0) resident = std::min(resident, (uint32_t)resident_env);   // (before `group`: its rule sees the small machine)
+    resident = std::max(resident, 1u);   // (R2S_ISO_FREE with R2S_ISO_WPS=1 frees every wavefront: no division by zero, no empty grid)
     // chunks per fetch (tools/rank_share.py, R2S_ISO_GROUP): consecutive chunks mostly belong to one item, so a group costs
     // one atomic and one item record (dependent loads with every lane of the wavefront waiting) instead of one per chunk.
     // 8 when a wavefront gets a hundred chunks and more (N = 1: 4.14 -> 4.06 ms against 4), never fewer than 4: one rank
@@ -2451,7 +2454,10 @@ static int iso_project_hex(r2s_plan* P, hipStream_t st, uint32_t n_items, uint32
     P->fast_timed = true;
     // two persistent wavefronts per SIMD pull entries from the list (counters[14]); those that find none leave at once
     static const int strag_wpc = getenv("R2S_STRAG_WPC") ? std::min(std::max(atoi(getenv("R2S_STRAG_WPC")), 1), 32) : 8;   // tuning knob (4-16: +-1 %)
-    iso_straggler_kernel<<<(uint32_t)P->n_cu * (uint32_t)strag_wpc, 64, 0, st>>>(list, cap, counters + 12, erec, rho_t, res, res_xp, abort_flag, counters + 14, counters + 16);
+    static const int strag_waves_env = getenv("R2S_STRAG_WAVES") ? atoi(getenv("R2S_STRAG_WAVES")) : 0;   // test hook: quota 64 and lane refill on a list of a few thousand entries
+    uint32_t strag_grid = (uint32_t)P->n_cu * (uint32_t)strag_wpc;
+    if (strag_waves_env > 0) strag_grid = std::min(strag_grid, (uint32_t)strag_waves_env);
+    iso_straggler_kernel<<<strag_grid, 64, 0, st>>>(list, cap, counters + 12, erec, rho_t, res, res_xp, abort_flag, counters + 14, counters + 16);
     iso_sweep_kernel<<<(uint32_t)P->n_cu * 2u, 256, 0, st>>>(items, n_items, chunk_off, n_chunks, perm, erec, g, s, rho_t, res, res_xp,
                                                              counters + 13, abort_flag, counters + 16);
     return 0;
