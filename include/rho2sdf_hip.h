@@ -378,6 +378,23 @@ int r2s_rbf_smooth_dev(const double *d_sdf, const r2s_grid *grid, int32_t is_int
                        double kernel_threshold, double target_volume, float *d_fine_out, float *level_shift_out,
                        int32_t *cg_iters_out, void *stream);
 
+/* A diagnostic of the calling thread's last smoothing (r2s_rbf_smooth / _dev, r2s_rbf_field_fit, the smoothing inside
+ * r2s_rho2sdf): which kernels it planned and which tables it built.  All zero before the first one.
+ *   [0]  form of the CG's product: 0 row walk, 1 table kernels, 2 materialised matrix, 3 on the fly; -1 in approximation mode
+ *   [1]  form of the evaluations: 0 row walk, 1 table kernels, 2 on the fly
+ *   [2]  bit 0: a row-walk kernel exists for the stencil and the lattice; bit 1: the knn cap can bind
+ *   [3..5]  wavefronts per workgroup, rows per walk, workgroups per row of the product's row walk - also the grouping of the
+ *           partial sums of dot(u, K u) under every other form; 0 in approximation mode
+ *   [6..8]  the same of the row walk that evaluates the weights on the lattice; 0 when it does not run
+ *   [9]  variant slots per axis of the row walk's evaluation tables, 16 or 64, 0 = not built: bits 0-7 of the lattice's own
+ *        table, bits 8-15 of the table of the separately rounded output grid at smooth = 1
+ *   [10] distinct Float32 coordinate differences ("variants") per axis of the lattice: x in bits 0-7, y in bits 8-15, z in
+ *        bits 16-23, each the largest count over the stencil's offsets; 0 = more than a table holds, or not formed
+ *   [11] the same between the output grid at smooth = 1 and the lattice
+ * R2S_RBF_WALK_NW and R2S_RBF_WALK_L (test hooks, read per call) force the wavefronts per workgroup (1, 2, 3, 5, 9 for the
+ * product; 1, 2, 4, 8 for the evaluation) and the rows per walk (4, 8, 16, 32); other values are ignored. */
+void r2s_last_rbf_plan(int32_t out[12]);
+
 /* ---- the smoothed level-set as a function: value and gradient at arbitrary points ------------------
  * RBFs_smoothing produces f(p) = th + sum_j w_j exp(-(|p - x_j| / sigma)^2) over the coarse lattice nodes x_j
  * (rbf_interpolation_kdtree takes any array of points, RBFs4Smoothing.jl:219-248; `+ th` at :366).  A field object keeps the

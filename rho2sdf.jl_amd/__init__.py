@@ -9,7 +9,7 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   calculate_mesh_volume, calculate_volume_from_sdf, evalDistances, find_threshold_for_volume,
                   exportSdfToVTI, exportToVTU, export_sdf_results, getMesh_AABB, import_vtu_mesh, noninteractive_sdf_grid_setup,
                   remove_sdf_artifacts, rho2sdf, sdf_fused, host_array, calculate_isocontour_volume, MeshInformations,
-                  extract_isosurface, extract_isosurface_dev, export_stl, RbfField, fit_rbf_field, refine_surface,
+                  extract_isosurface, extract_isosurface_dev, export_stl, RbfField, fit_rbf_field, refine_surface, last_rbf_plan,
                   surface_curvature,
                   mesh_distance, mesh_distance_dev, redistance, redistance_dev, last_distance_stats,
                   MeshIndex, redistance_full, redistance_full_dev, surface_deviation,
@@ -24,7 +24,7 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
            "exportSdfToVTI", "exportToVTU", "export_sdf_results", "getMesh_AABB", "import_vtu_mesh", "noninteractive_sdf_grid_setup", "remove_sdf_artifacts",
            "rho2sdf", "sdf_fused", "host_array", "calculate_isocontour_volume", "MeshInformations",
-           "extract_isosurface", "extract_isosurface_dev", "export_stl", "RbfField", "fit_rbf_field", "refine_surface",
+           "extract_isosurface", "extract_isosurface_dev", "export_stl", "RbfField", "fit_rbf_field", "refine_surface", "last_rbf_plan",
            "surface_curvature",
            "mesh_distance", "mesh_distance_dev", "redistance", "redistance_dev", "last_distance_stats",
            "MeshIndex", "redistance_full", "redistance_full_dev", "surface_deviation",

@@ -138,6 +138,7 @@ SYMBOLS = [
     ("r2s_rbf_smooth", ctypes.c_int, [c_double_p, ctypes.POINTER(R2SGrid), ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_float_p, c_float_p,
                                       ctypes.POINTER(ctypes.c_int32), c_float_p]),
+    ("r2s_last_rbf_plan", None, [c_int32_p]),
     ("r2s_release_cache", None, []),
     ("r2s_export_vtu", ctypes.c_int, [ctypes.c_char_p] + _MESH + [ctypes.c_int32, ctypes.c_int32, c_double_p]),
     ("r2s_import_vtu", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(R2SVtuMesh)]),

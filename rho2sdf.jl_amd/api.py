@@ -428,6 +428,18 @@ def RBFs_smoothing(sdf, grid, Is_interpolation, smooth, target_volume, threshold
     return fine.reshape(dims[2], dims[1], dims[0])
 
 
+def last_rbf_plan():
+    """forms, row-walk plans and tables of the calling thread's last smoothing (r2s_last_rbf_plan), decoded"""
+    s = (ctypes.c_int32 * 12)()
+    L.lib().r2s_last_rbf_plan(s)
+    v = [int(x) for x in s]
+    axes = lambda w: tuple((w >> (8 * a)) & 255 for a in range(3))
+    return dict(product=(None, "walk", "lut", "k", "fly")[v[0] + 1], evaluation=("walk", "lut", "fly")[v[1]],
+                walk_ok=bool(v[2] & 1), capped=bool(v[2] & 2),
+                product_plan=dict(NW=v[3], L=v[4], nxt=v[5]), evaluation_plan=dict(NW=v[6], L=v[7], nxt=v[8]),
+                wa_nv=v[9] & 255, wa_nv_fine=(v[9] >> 8) & 255, variants=axes(v[10]), variants_fine=axes(v[11]))
+
+
 def exportSdfToVTI(filename, grid, values, value_label, smooth=None, compress=0):
     """exportSdfToVTI(filename, grid, values, value_label, smooth) - VTK ImageData (.vti)
     src/DataExport/ExportToVTI.jl:22-67: dimensions N(*smooth)+1, origin AABB_min, spacing cell_size(/smooth).

@@ -2085,6 +2085,7 @@ struct RbfPlan {
     std::vector<uint8_t> ix, iy, iz, fix, fiy, fiz;
     bool lv_ok, mv_fits, lvf_ok;
     int lutf_most;
+    int lv_most[3], lvf_most[3];          // variants per axis (rbf_lut_axis; 0: more than a table holds, or not formed)
     RbfMatvec mv;
     RbfEval ev;
 };
@@ -2137,6 +2138,7 @@ static int rbf_plan(const r2s_grid* g, int is_interp, int smooth, double kthr, R
     memset(&P.LVF, 0, sizeof P.LVF);
     P.lv_ok = P.mv_fits = P.lvf_ok = false;
     P.lutf_most = 0;
+    for (int a = 0; a < 3; ++a) P.lv_most[a] = P.lvf_most[a] = 0;
     if (G.tap_r >= 1 && G.tap_r <= 3) {
         for (RbfLutVals* V : {&P.LV, &P.LVF}) {
             V->R = G.tap_r; V->sigma = G.sigma; V->thr = G.thr; V->max_distance = G.max_distance;
@@ -2145,11 +2147,13 @@ static int rbf_plan(const r2s_grid* g, int is_interp, int smooth, double kthr, R
                   m2 = rbf_lut_axis(P.cz, P.cz, G.tap_r, P.LV.v[2], P.iz);
         P.lv_ok = m0 && m1 && m2;
         P.mv_fits = std::max(m0, std::max(m1, m2)) <= RBF_NV - 1;
+        P.lv_most[0] = m0; P.lv_most[1] = m1; P.lv_most[2] = m2;
         if (P.one_to_one) {
             const int f0 = rbf_lut_axis(P.tx, P.cx, G.tap_r, P.LVF.v[0], P.fix), f1 = rbf_lut_axis(P.ty, P.cy, G.tap_r, P.LVF.v[1], P.fiy),
                       f2 = rbf_lut_axis(P.tz, P.cz, G.tap_r, P.LVF.v[2], P.fiz);
             P.lvf_ok = f0 && f1 && f2;
             P.lutf_most = std::max(f0, std::max(f1, f2));
+            P.lvf_most[0] = f0; P.lvf_most[1] = f1; P.lvf_most[2] = f2;
         }
     }
     const char* mv_env = getenv("R2S_RBF_MATVEC");
@@ -2260,6 +2264,28 @@ int RbfTables::build(const RbfPlan& P, hipStream_t s)
         }
     }
     return 0;
+}
+
+// what the calling thread's last smoothing planned and built (r2s_last_rbf_plan; the layout is in the header)
+static thread_local int32_t g_last_rbf_plan[12];
+static void rbf_record_plan(const RbfPlan& P, int is_interp, const RbfTables& T)
+{
+    int32_t* o = g_last_rbf_plan;
+    memset(o, 0, sizeof g_last_rbf_plan);
+    o[0] = is_interp ? (int32_t)P.mv : -1;
+    o[1] = (int32_t)P.ev;
+    o[2] = (P.walk_ok ? 1 : 0) | (P.capped ? 2 : 0);
+    if (is_interp) {   // (every form of the product cuts its dot product by this plan)
+        const RbfWalkPlan W = rbf_walk_plan(P.nx, P.ny, P.nz, true);
+        o[3] = W.NW; o[4] = W.L; o[5] = W.nxt;
+    }
+    if (P.ev == RbfEval::walk && T.LG.WA) {
+        const RbfWalkPlan W = rbf_walk_plan(P.nx, P.ny, P.nz, false, rbf_walk_stage_chunks(1, T.LG.wa_nv));
+        o[6] = W.NW; o[7] = W.L; o[8] = W.nxt;
+    }
+    o[9] = (T.LG.WA ? T.LG.wa_nv : 0) | (T.LGF.WA ? T.LGF.wa_nv : 0) << 8;
+    o[10] = P.lv_most[0] | P.lv_most[1] << 8 | P.lv_most[2] << 16;
+    o[11] = P.lvf_most[0] | P.lvf_most[1] << 8 | P.lvf_most[2] << 16;
 }
 
 // the tables of the refined output grid's parity classes (smooth >= 2; one device only): F.T stays null where they do not
@@ -2433,6 +2459,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     pv_replace_kernel<<<nb, 256, 0, st>>>(d_f, n, W.cnt.as<uint32_t>());
     // ---- geometry and tables; the refined output grid's tables (R2S_RBF_APPLY=fly: on the fly, the tests compare) ----
     TRY_C(T.build(P, st));
+    rbf_record_plan(P, is_interp, T);
     TRY_C(W.fine_tab.build(P, st));
     const RbfGeom& G = T.G;
     // ---- weights ----
@@ -3011,6 +3038,7 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         if (is_interp) { SLAB_TRY(br.ensure(q, 4 * nh)); SLAB_TRY(bu.ensure(q, 4 * nh)); SLAB_TRY(bq.ensure(q, 4 * nh)); }
         SLAB_HIP(hipSetDevice(d.device));
         SLAB_TRY(tab[q].build(P, d.stream));
+        if (q == order[0]) rbf_record_plan(P, is_interp, tab[q]);   // (every slab builds the same forms)
         // process_vector pass 1 on the OWNED planes (every plane counts once for the maximum)
         SLAB_HIP(hipMemsetAsync(bcnt.b[q].p, 0, 64, d.stream));
         const int64_t no = nowned(q);
@@ -3391,6 +3419,11 @@ int r2s_rbf_smooth_dev(const double* d_sdf, const r2s_grid* grid, int32_t is_int
                              &its, nullptr, true, true);
     if (cg_iters_out) *cg_iters_out = its;
     return rc;
+}
+
+void r2s_last_rbf_plan(int32_t out[12])
+{
+    if (out) memcpy(out, g_last_rbf_plan, sizeof g_last_rbf_plan);
 }
 
 /* frees the process-wide work buffers kept between calls (the materialised RBF matrix) */

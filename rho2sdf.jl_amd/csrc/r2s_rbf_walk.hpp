@@ -507,6 +507,10 @@ static RbfWalkPlan rbf_walk_plan(int nx, int ny, int nplanes, bool dpp, int stag
     // rows per walk: long walks amortise the window of the first step, short ones fill the chip on small lattices
     P.L = RBF_WALK_LMAX;
     while (P.L > 4 && (int64_t)nplanes * ((ny + P.L - 1) / P.L) * P.nxt < 2048) P.L /= 2;
+    if (const char* e = getenv("R2S_RBF_WALK_L")) {    // (tests: the long walks of large lattices on small ones)
+        const int l = atoi(e);
+        if (l == 4 || l == 8 || l == 16 || l == 32) P.L = l;
+    }
     P.nchunk = (ny + P.L - 1) / P.L;
     return P;
 }
@@ -535,11 +539,16 @@ static void rbf_walk_launch_dpp(const RbfWalkArgs& A, int NW, unsigned nb, hipSt
     default: rbf_walk_kernel<2, 7, 0, 16, 9, 1><<<nb, 576, 0, st>>>(A); break;
     }
 }
+// 16-byte table chunks a workgroup stages per step
+static int rbf_walk_stage_chunks(int mode, int nv)
+{
+    return mode == 0 ? 420 : (nv == 16 ? 840 : 3360);
+}
 // mode 0: y = K x (T: float table, nv = 16); mode 1: evaluation (T: double table, nv = 16 or 64)
 static void rbf_walk_launch(int mode, int nv, RbfWalkArgs A, hipStream_t st)
 {
     const bool dpp = mode == 0;
-    const RbfWalkPlan P = rbf_walk_plan(A.nx, A.ny, A.nz, dpp, mode == 0 ? 420 : (nv == 16 ? 840 : 3360));
+    const RbfWalkPlan P = rbf_walk_plan(A.nx, A.ny, A.nz, dpp, rbf_walk_stage_chunks(mode, nv));
     A.L = P.L; A.nchunk = P.nchunk; A.nxt = P.nxt;
     const unsigned nb = (unsigned)((int64_t)(A.k_end - A.k_begin) * P.nchunk * P.nxt);
     if (nb == 0) return;
