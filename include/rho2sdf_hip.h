@@ -645,8 +645,8 @@ int r2s_redistance_full_dev(const void *d_values, int32_t is_float32, const int6
  *     the front (det > 0), -1 = it runs with the normal (det < 0), 0 on a miss.
  *   - a ray with a non-finite origin or direction, or a zero direction: NaN / -1 / 0.  An empty mesh: +inf / -1 / 0.
  *   - the results depend neither on the order of the triangles (the index follows a permutation wherever the minimum is
- *     unique) nor on the order of the rays; no floating-point atomics are used.  Nothing here counts crossings: no
- *     inside / outside sign is derived from the mesh.
+ *     unique) nor on the order of the rays; no floating-point atomics are used.  Nothing here counts crossings: the
+ *     inside / outside sign of the mesh is the next section's (r2s_mesh_index_winding).
  * r2s_mesh_index_raycast: host arrays, synchronous.  _raycast_dev: device arrays on the index's device, which must be
  * current; enqueues on `stream` and does not wait.  n == 0 succeeds and touches nothing.
  * R2S_ERR_ARG before any device work, outputs untouched: a NULL index or (n > 0) NULL origins / dirs / t_out, a negative n,
@@ -658,6 +658,90 @@ int r2s_mesh_index_raycast(const r2s_mesh_index *index, const void *origins, con
 int r2s_mesh_index_raycast_dev(const r2s_mesh_index *index, const void *d_origins, const void *d_dirs,
                                int32_t rays_are_float32, int64_t n, double t_min, double t_max, int32_t out_is_float32,
                                void *d_t_out, int32_t *d_tri_out, int8_t *d_side_out, void *stream);
+
+/* ---- mesh index: winding number, inside / outside and signed distance ----------------------------
+ * Is this point inside the mesh?  The sign that r2s_redistance takes from a field, taken from the mesh alone, against the same
+ * index (tree, device copies) as the distance and ray queries; the index is not changed.  The outputs are integers (and the
+ * sign of a distance the existing query returns), defined so that a loop over all triangles gives them bit for bit.
+ *   - winding(p) = minus the signed count of crossings of an AXIS ray from p (the sum of `side` below, negated).  ray, int32: 0, 1, 2 = +x, +y, +z; 3, 4, 5 = -x, -y, -z.
+ *     Only these six: for them the pair test of r2s_mesh_index_raycast needs no shear, and every cull is an exact comparison.
+ *   - pair test (point o, triangle a b c), Float64; vertices are the float32 values widened to double, points float32 or
+ *     float64 widened to double (or the lattice point, formed as r2s_mesh_index_lattice forms it); every operation rounded on its
+ *     own (no fma):
+ *       1. kz = ray % 3; kx = (kz+1) % 3, ky = (kz+2) % 3, swapped for ray >= 3; Sz = +1, or -1 for ray >= 3 (steps 1 and 2 of
+ *          the ray test with d = +-e_kz, hence Sx = Sy = 0);
+ *       2. A = a - o, Ax = A[kx], Ay = A[ky]; the same for B and C;
+ *       3. U = Cx*By - Cy*Bx, V = Ax*Cy - Ay*Cx, W = Bx*Ay - By*Ax (the values step 4 of the ray test forms for this ray);
+ *       4. the effective sign of an edge function f belongs to the directed projected edge P -> Q: B -> C for U, C -> A for V,
+ *          A -> B for W.  +1 if f > 0, -1 if f < 0; if f == 0: the sign of Qy - Py where that is non-zero, else the sign of
+ *          Px - Qx, else 0, with P and Q the vertices' own coordinates q[ky], p[ky], p[kx], q[kx] (float32 values: both
+ *          differences are exact).  This is the sign f would take with the point moved by (eps, eps^2) in the projected plane.
+ *          The two triangles at a shared edge see exact negatives, in f and in the tie, so a ray through an edge or a vertex
+ *          is given to exactly one side;
+ *       5. the pair is a crossing iff the three effective signs are equal and non-zero; `side` is that sign;
+ *       6. and both of: the own-box condition, all exact comparisons: o[kx] and o[ky] lie in the closed [lo, hi] of the
+ *          triangle's own float32 box on those axes, and the box reaches ahead: hi[kz] >= o[kz] for ray < 3, lo[kz] <= o[kz]
+ *          for ray >= 3; and det = (U+V)+W is non-zero and t = ((U*(Sz*A[kz]) + V*(Sz*B[kz])) + W*(Sz*C[kz])) / det is > 0.
+ *          The inequality is strict: A POINT ON THE SURFACE GETS A RAY-DEPENDENT ANSWER.
+ *   - crossings(p) = the number of crossings; winding(p) = - (the sum of `side` over them).  An outward-wound closed body gives
+ *     +1 inside and 0 outside; an enclosed void, wound inward, brings the inside of the void back to 0.
+ *   - a collapsed triangle (two equal vertex INDICES) takes part in nothing.  A point with a non-finite coordinate: winding 0,
+ *     crossings -1.  An empty mesh: 0 / 0.
+ *   - why the tree is exact: the own-box condition is part of the definition, float32 min / max do not round, so every
+ *     ancestor's box contains the leaf's; entering a child iff the same three comparisons hold on the child's box reaches every
+ *     pair of the definition.  No margin, no ordering.  The results follow a permutation of the triangles and of the points
+ *     exactly; integer accumulators per point, no atomics.
+ *   - known limit: a computed f has the sign of the exact f or is 0 (rounding is monotone), never the opposite sign; where a
+ *     computed 0 stands for an exact non-zero the tie rule can decide against the truth, and a ray that passes within rounding
+ *     of a vertex can then be miscounted.  tests/mesh_winding_ref.py measures this with exact rational arithmetic.
+ *   - inside rules: R2S_INSIDE_POSITIVE (winding > 0), R2S_INSIDE_NONZERO (winding != 0), R2S_INSIDE_ODD (crossings odd; the one
+ *     that survives inconsistent winding).
+ *   - signed distance = s * d: d exactly what r2s_mesh_index_query / _lattice returns for that point (the same kernel, then
+ *     signed in place), s = +1 inside, -1 outside: positive in the material, the convention of r2s_redistance.  A zero is
+ *     returned as +0; a non-finite point gives NaN; an empty mesh -inf.  closest_tri_out (may be NULL) as in the query.
+ * r2s_mesh_index_winding: n points [n][3] from host arrays (synchronous); crossings_out may be NULL.  _winding_dev: device arrays on
+ * the index's device, which must be current; enqueues on `stream` and does not wait.  n == 0 succeeds and touches nothing.
+ * r2s_mesh_index_winding_lattice(_dev): the same for the lattice of r2s_mesh_index_lattice (x fastest), by rows: all points of a row
+ * along the ray's axis share U, V, W, det and the projected comparisons, and "the box reaches ahead and t > 0" is monotone along
+ * the row (every step of t is monotone in o[kz]), so one lane traverses the tree once per row, finds each triangle's threshold
+ * index by bisection on that very predicate and adds to difference arrays kept in the outputs, which a second kernel sums.  Equal
+ * to the per-point results bit for bit; the environment variable R2S_WINDING_ROWS=0 runs the per-point kernel on 4x4x4 blocks
+ * of lattice points instead.  r2s_mesh_index_signed(_dev) / _signed_lattice(_dev): the signed distance, same rules.
+ * r2s_mesh_signed_distance / _dev: the signed lattice for a mesh without an index (host arrays and `device`, -1 = current; or
+ * device arrays on the current device, after the work queued on `stream`): a tree is built, used and dropped; synchronous.
+ * R2S_ERR_ARG before any device work, outputs untouched: a NULL index, NULL arrays with a count, a NULL output, a negative count,
+ * ray outside 0..5, rule outside 0..2, the lattice and mesh errors of r2s_mesh_index_lattice / r2s_mesh_index_build, a _dev call
+ * on another device than the index's.  R2S_ERR_UNSUPPORTED: counts beyond 32 bits, a tree deeper than the traversal stack (64
+ * levels).  No GPU: R2S_ERR_NO_DEVICE.  Not here: arbitrary ray directions, the generalized (solid-angle) winding number for
+ * open meshes, voting over rays (call three), repair. */
+#define R2S_INSIDE_POSITIVE 0
+#define R2S_INSIDE_NONZERO 1
+#define R2S_INSIDE_ODD 2
+int r2s_mesh_index_winding(const r2s_mesh_index *index, const void *points, int32_t points_are_float32, int64_t n, int32_t ray,
+                           int32_t *winding_out, int32_t *crossings_out);
+int r2s_mesh_index_winding_dev(const r2s_mesh_index *index, const void *d_points, int32_t points_are_float32, int64_t n,
+                               int32_t ray, int32_t *d_winding_out, int32_t *d_crossings_out, void *stream);
+int r2s_mesh_index_winding_lattice(const r2s_mesh_index *index, const int64_t dims[3], const double origin[3], double spacing,
+                                   int32_t ray, int32_t *winding_out, int32_t *crossings_out);
+int r2s_mesh_index_winding_lattice_dev(const r2s_mesh_index *index, const int64_t dims[3], const double origin[3],
+                                       double spacing, int32_t ray, int32_t *d_winding_out, int32_t *d_crossings_out,
+                                       void *stream);
+int r2s_mesh_index_signed(const r2s_mesh_index *index, const void *points, int32_t points_are_float32, int64_t n, int32_t rule,
+                          int32_t ray, int32_t out_is_float32, void *dist_out, int32_t *closest_tri_out);
+int r2s_mesh_index_signed_dev(const r2s_mesh_index *index, const void *d_points, int32_t points_are_float32, int64_t n,
+                              int32_t rule, int32_t ray, int32_t out_is_float32, void *d_dist_out, int32_t *d_closest_tri_out,
+                              void *stream);
+int r2s_mesh_index_signed_lattice(const r2s_mesh_index *index, const int64_t dims[3], const double origin[3], double spacing,
+                                  int32_t rule, int32_t ray, int32_t out_is_float32, void *dist_out, int32_t *closest_tri_out);
+int r2s_mesh_index_signed_lattice_dev(const r2s_mesh_index *index, const int64_t dims[3], const double origin[3], double spacing,
+                                      int32_t rule, int32_t ray, int32_t out_is_float32, void *d_dist_out,
+                                      int32_t *d_closest_tri_out, void *stream);
+int r2s_mesh_signed_distance(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, const int64_t dims[3],
+                             const double origin[3], double spacing, int32_t rule, int32_t ray, int32_t out_is_float32,
+                             int32_t device, void *out);
+int r2s_mesh_signed_distance_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris,
+                                 const int64_t dims[3], const double origin[3], double spacing, int32_t rule, int32_t ray,
+                                 int32_t out_is_float32, void *d_out, void *stream);
 
 /* ---- mesh shells: per-shell topology and mass properties ----------------------------------------
  * What a triangle mesh is: its separate bodies (shells), whether each is closed and consistently oriented, and the area,
@@ -966,7 +1050,7 @@ int r2s_mesh_orient_dev(const float *d_verts, int64_t n_verts, const int32_t *d_
  * host; _dev: the check kernel of r2s_mesh_distance_dev), an index on another device than the current one (_dev).
  * R2S_ERR_UNSUPPORTED: a tree deeper than the traversal stack (64 levels), more than 2^31 - 1 intersecting pairs.  No GPU:
  * R2S_ERR_NO_DEVICE.  Not here: coplanar overlap and fold-overs between edge neighbours, intersections between two different
- * meshes, the intersection curve, repair, any inside / outside sign. */
+ * meshes, the intersection curve, repair.  The inside / outside sign: r2s_mesh_index_winding. */
 int r2s_mesh_index_intersections(const r2s_mesh_index *index, int32_t *hits_of_tri_out, int32_t *pairs_out,
                                  int64_t pair_capacity, int64_t totals[8]);
 int r2s_mesh_index_intersections_dev(const r2s_mesh_index *index, int32_t *d_hits_of_tri, int32_t *d_pairs,

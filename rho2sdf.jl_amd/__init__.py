@@ -18,7 +18,8 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   MeshSections, mesh_sections, mesh_sections_dev,
                   MeshWeld, mesh_weld, mesh_weld_dev, import_stl,
                   MeshOrient, mesh_orient, mesh_orient_dev, flip_patches,
-                  MeshIntersections, mesh_intersections, mesh_intersections_dev)
+                  MeshIntersections, mesh_intersections, mesh_intersections_dev,
+                  mesh_signed_distance, mesh_signed_distance_dev)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
            "calculate_mesh_volume", "calculate_volume_from_sdf", "evalDistances", "find_threshold_for_volume",
@@ -34,4 +35,5 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "MeshWeld", "mesh_weld", "mesh_weld_dev", "import_stl",
            "MeshOrient", "mesh_orient", "mesh_orient_dev", "flip_patches",
            "MeshIntersections", "mesh_intersections", "mesh_intersections_dev",
+           "mesh_signed_distance", "mesh_signed_distance_dev",
            "_lib"]

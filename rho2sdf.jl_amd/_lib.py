@@ -200,6 +200,22 @@ SYMBOLS = [
                                               ctypes.c_int32, _P, c_int32_p, _P]),
     ("r2s_mesh_index_raycast_dev", ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                                                   ctypes.c_int32, _P, _P, _P, _P]),
+    ("r2s_mesh_index_winding", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_int32_p, c_int32_p]),
+    ("r2s_mesh_index_winding_dev", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _P, _P, _P]),
+    ("r2s_mesh_index_winding_lattice", ctypes.c_int, [_P, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_int32, c_int32_p, c_int32_p]),
+    ("r2s_mesh_index_winding_lattice_dev", ctypes.c_int, [_P, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_int32, _P, _P, _P]),
+    ("r2s_mesh_index_signed", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P,
+                                             c_int32_p]),
+    ("r2s_mesh_index_signed_dev", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P,
+                                                 _P, _P]),
+    ("r2s_mesh_index_signed_lattice", ctypes.c_int, [_P, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                                     ctypes.c_int32, _P, c_int32_p]),
+    ("r2s_mesh_index_signed_lattice_dev", ctypes.c_int, [_P, c_int64_p, c_double_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_int32, _P, _P, _P]),
+    ("r2s_mesh_signed_distance", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, c_int64_p, c_double_p, ctypes.c_double,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P]),
+    ("r2s_mesh_signed_distance_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, c_int64_p, c_double_p, ctypes.c_double,
+                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     ("r2s_mesh_shells", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_int32, c_int32_p, c_int64_p,
                                        c_double_p, c_int64_p]),
     ("r2s_last_mesh_shells", ctypes.c_int, [c_int64_p, c_double_p, ctypes.c_int64, c_int64_p]),

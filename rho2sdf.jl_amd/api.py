@@ -591,6 +591,18 @@ def last_distance_stats():
     return dict(zip(keys, [float(x) for x in s]))
 
 
+_INSIDE_RULES = {"positive": 0, "nonzero": 1, "odd": 2}
+
+
+def _inside_rule(rule):
+    """"positive" / "nonzero" / "odd", or the library's R2S_INSIDE_* integer 0 / 1 / 2 -> that integer"""
+    if isinstance(rule, str) and rule in _INSIDE_RULES:
+        return _INSIDE_RULES[rule]
+    if not isinstance(rule, str) and rule in (0, 1, 2):
+        return int(rule)
+    raise L.R2SError('rule must be "positive", "nonzero" or "odd" (or 0, 1, 2)')
+
+
 class MeshIndex:
     """A bounding-volume hierarchy over a triangle mesh on the device (include/rho2sdf_hip.h, r2s_mesh_index): the exact
     distance to the mesh from arbitrary points (`distance`) or from every point of a lattice (`lattice`), without a band.
@@ -738,6 +750,115 @@ class MeshIndex:
         res = (t,) + ((idx,) if want_index else ()) + ((side,) if want_side else ())
         return res if len(res) > 1 else t
 
+    def winding(self, points, ray=2, want_crossings=False):
+        """The winding number of every point ((n, 3), float32 or float64; other types are converted to float64) against the mesh
+        (include/rho2sdf_hip.h, r2s_mesh_index_winding): minus the signed count of crossings of the axis ray `ray` (0, 1, 2 = +x,
+        +y, +z; 3, 4, 5 = -x, -y, -z) -> (n,) int32: +1 inside an outward-wound closed body, 0 outside; want_crossings=True: also
+        the int32 number of crossings.  A non-finite point gives 0 / -1, an empty mesh 0 / 0; a point ON the surface gets a
+        ray-dependent answer."""
+        p = np.ascontiguousarray(points)
+        if p.dtype not in (np.float32, np.float64):
+            p = p.astype(np.float64)
+        _points_nx3("points must be (n, 3)", p)
+        w = np.empty(len(p), np.int32)
+        c = np.empty(len(p), np.int32) if want_crossings else None
+        L.check(L.lib().r2s_mesh_index_winding(self._handle(), p.ctypes.data_as(ctypes.c_void_p), int(p.dtype == np.float32), len(p),
+                                               int(ray), w.ctypes.data_as(L.c_int32_p), c.ctypes.data_as(L.c_int32_p) if want_crossings else None))
+        return (w, c) if want_crossings else w
+
+    def winding_dev(self, t, ray=2, want_crossings=False, stream=None):
+        """winding on a torch tensor of points on the index's device ((n, 3) float32 / float64, contiguous) -> int32 device
+        tensor(s); enqueued on the current stream (or `stream`)"""
+        import torch
+        _points_nx3("points must be a contiguous float32 / float64 (n, 3) device tensor", t)
+        n = t.shape[0]
+        w = torch.empty(n, dtype=torch.int32, device=t.device)
+        c = torch.empty(n, dtype=torch.int32, device=t.device) if want_crossings else None
+        if n:
+            vp = ctypes.c_void_p
+            L.check(L.lib().r2s_mesh_index_winding_dev(self._handle(), vp(t.data_ptr()), int(t.dtype == torch.float32), n, int(ray),
+                                                       vp(w.data_ptr()), vp(c.data_ptr()) if want_crossings else None, _stream(stream)))
+        return (w, c) if want_crossings else w
+
+    def winding_lattice(self, grid_or_lattice, smooth=None, ray=2, want_crossings=False):
+        """winding of every lattice point (a Grid with `smooth`, as extract_isosurface, or (dims, origin, spacing)) -> int32
+        array (nz, ny, nx); want_crossings=True: also the number of crossings"""
+        dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+        shape = (dims[2], dims[1], dims[0])
+        w = np.empty(shape, np.int32)
+        c = np.empty(shape, np.int32) if want_crossings else None
+        L.check(L.lib().r2s_mesh_index_winding_lattice(self._handle(), dims, origin, spacing, int(ray), w.ctypes.data_as(L.c_int32_p),
+                                                       c.ctypes.data_as(L.c_int32_p) if want_crossings else None))
+        return (w, c) if want_crossings else w
+
+    def winding_lattice_dev(self, grid_or_lattice, smooth=None, ray=2, want_crossings=False, stream=None):
+        """winding_lattice -> int32 torch tensor(s) on the current device (the index's); enqueued on the current stream (or `stream`)"""
+        import torch
+        dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+        shape, dev = (dims[2], dims[1], dims[0]), torch.device("cuda", torch.cuda.current_device())
+        w = torch.empty(shape, dtype=torch.int32, device=dev)
+        c = torch.empty(shape, dtype=torch.int32, device=dev) if want_crossings else None
+        vp = ctypes.c_void_p
+        L.check(L.lib().r2s_mesh_index_winding_lattice_dev(self._handle(), dims, origin, spacing, int(ray), vp(w.data_ptr()),
+                                                           vp(c.data_ptr()) if want_crossings else None, _stream(stream)))
+        return (w, c) if want_crossings else w
+
+    def contains(self, points, rule="positive", ray=2):
+        """is every point inside the mesh? -> (n,) bool.  rule: "positive" (winding > 0), "nonzero" (winding != 0) or "odd" (the
+        number of crossings is odd: the rule that survives inconsistent winding).  A non-finite point is outside."""
+        rule = _inside_rule(rule)
+        w, c = self.winding(points, ray, want_crossings=True)
+        return (w > 0, w != 0, (c > 0) & (c % 2 == 1))[rule]
+
+    def signed_distance(self, points, rule="positive", ray=2, want_index=False, dtype=np.float64):
+        """The signed distance of every point to the mesh (include/rho2sdf_hip.h, r2s_mesh_index_signed): `distance` of the same
+        points with the sign of `contains`: positive inside (in the material), negative outside, a zero is +0.  An empty mesh
+        gives -inf, a non-finite point NaN.  want_index as in `distance`."""
+        p = np.ascontiguousarray(points)
+        if p.dtype not in (np.float32, np.float64):
+            p = p.astype(np.float64)
+        _points_nx3("points must be (n, 3)", p)
+        dtype = _float_dtype(dtype, np)
+        res, p_dist, p_idx = _dist_outputs(len(p), dtype, want_index)
+        L.check(L.lib().r2s_mesh_index_signed(self._handle(), p.ctypes.data_as(ctypes.c_void_p), int(p.dtype == np.float32), len(p),
+                                              _inside_rule(rule), int(ray), int(dtype == np.float32), p_dist, p_idx))
+        return res
+
+    def signed_distance_dev(self, t, rule="positive", ray=2, want_index=False, dtype=None, stream=None):
+        """signed_distance on a torch tensor of points on the index's device ((n, 3) float32 / float64, contiguous) -> device
+        tensor(s); enqueued on the current stream (or `stream`)"""
+        import torch
+        _points_nx3("points must be a contiguous float32 / float64 (n, 3) device tensor", t)
+        dtype = _float_dtype(dtype, torch)
+        n = t.shape[0]
+        res, p_dist, p_idx = _dist_outputs(n, dtype, want_index, t.device)
+        if n:
+            L.check(L.lib().r2s_mesh_index_signed_dev(self._handle(), ctypes.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), n,
+                                                      _inside_rule(rule), int(ray), int(dtype == torch.float32), p_dist, p_idx,
+                                                      _stream(stream)))
+        return res
+
+    def signed_lattice(self, grid_or_lattice, smooth=None, rule="positive", ray=2, want_index=False, dtype=np.float64):
+        """signed_distance of every lattice point (a Grid with `smooth`, as extract_isosurface, or (dims, origin, spacing)) ->
+        array (nz, ny, nx) of `dtype`; want_index=True: also the closest triangle"""
+        dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+        dtype = _float_dtype(dtype, np)
+        res, p_dist, p_idx = _dist_outputs((dims[2], dims[1], dims[0]), dtype, want_index)
+        L.check(L.lib().r2s_mesh_index_signed_lattice(self._handle(), dims, origin, spacing, _inside_rule(rule), int(ray),
+                                                      int(dtype == np.float32), p_dist, p_idx))
+        return res
+
+    def signed_lattice_dev(self, grid_or_lattice, smooth=None, rule="positive", ray=2, want_index=False, dtype=None, stream=None):
+        """signed_lattice -> torch tensor(s) on the current device (the index's); enqueued on the current stream (or `stream`)"""
+        import torch
+        dtype = _float_dtype(dtype, torch)
+        dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        res, p_dist, p_idx = _dist_outputs((dims[2], dims[1], dims[0]), dtype, want_index, dev)
+        L.check(L.lib().r2s_mesh_index_signed_lattice_dev(self._handle(), dims, origin, spacing, _inside_rule(rule), int(ray),
+                                                          int(dtype == torch.float32), p_dist, p_idx, _stream(stream)))
+        return res
+
     def self_intersections(self, want_pairs=True):
         """The pairs of triangles of the indexed mesh that intersect or touch (include/rho2sdf_hip.h,
         r2s_mesh_index_intersections) -> MeshIntersections; want_pairs=False: counts only (`pairs` is None).  The index is not
@@ -823,6 +944,39 @@ def mesh_intersections_dev(verts, tris, stream=None, *, capacity=0):
     nv, nt = verts.numel() // 3, tris.numel() // 3
     return _intersections_dev(nt, True, capacity, stream, lambda hits, pairs, cap, tot, st: L.lib().r2s_mesh_intersections_dev(
         vp(verts.data_ptr()), nv, vp(tris.data_ptr()), nt, hits, pairs, cap, tot, st))
+
+
+def mesh_signed_distance(verts, tris, grid_or_lattice, smooth=None, *, rule="positive", ray=2, dtype=np.float64, device=-1):
+    """The signed distance from every lattice point to a closed triangle mesh, the sign taken from the mesh alone
+    (include/rho2sdf_hip.h, r2s_mesh_signed_distance): MeshIndex(verts, tris).signed_lattice(...) without keeping the index ->
+    array (nz, ny, nx) of `dtype` (float64 or float32), positive inside.  The lattice is that of extract_isosurface for a Grid
+    and `smooth`, or an explicit (dims, origin, spacing); rule and ray as in MeshIndex.contains.  The mesh should be closed,
+    consistently wound outward (mesh_orient(outward=True)) and free of self-intersections (mesh_intersections); with windings
+    that cannot be trusted use rule="odd"."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+    dtype = _float_dtype(dtype, np)
+    out = np.empty((dims[2], dims[1], dims[0]), dtype)
+    L.check(L.lib().r2s_mesh_signed_distance(_f(v), len(v), t.ctypes.data_as(L.c_int32_p), len(t), dims, origin, spacing,
+                                             _inside_rule(rule), int(ray), int(dtype == np.float32), int(device),
+                                             out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def mesh_signed_distance_dev(verts, tris, grid_or_lattice, smooth=None, *, rule="positive", ray=2, dtype=None, stream=None):
+    """mesh_signed_distance on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous) -> a
+    device tensor (nz, ny, nx) of `dtype` (float64 by default, or float32).  Reads after the work queued on the current stream
+    (or `stream`); synchronous."""
+    import torch
+    _mesh_tensors(verts, tris)
+    dtype = _float_dtype(dtype, torch)
+    dims, origin, spacing = _dist_lattice(grid_or_lattice, smooth)
+    out = torch.empty((dims[2], dims[1], dims[0]), dtype=dtype, device=verts.device)
+    L.check(L.lib().r2s_mesh_signed_distance_dev(ctypes.c_void_p(verts.data_ptr()), verts.numel() // 3, ctypes.c_void_p(tris.data_ptr()),
+                                                 tris.numel() // 3, dims, origin, spacing, _inside_rule(rule), int(ray),
+                                                 int(dtype == torch.float32), ctypes.c_void_p(out.data_ptr()), _stream(stream)))
+    return out
 
 
 class MeshShells:
@@ -1628,7 +1782,15 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     "majority" or "outward" (needs weld=True): the welded triangles go through mesh_orient(outward=(orient == "outward")), whose
     docstring has the rules and the caveat about enclosed voids.  check_intersections=True (needs weld=True): the result is
     (verts, tris, MeshIntersections), the self-intersections of the mesh as returned (mesh_intersections): zero pairs are what
-    the shells, the orientation, sections and thickness take for granted."""
+    the shells, the orientation, sections and thickness take for granted.
+
+    From an STL file to the signed-distance volume everything else here produces:
+
+        verts, tris, x = import_stl("part.stl", orient="outward", check_intersections=True)   # weld -> orient(outward)
+        assert len(x) == 0                                        # the surface does not pass through itself
+        grid = Grid(verts.min(0), verts.max(0), 128)              # 128 cells along the longest side, 3 cells of margin
+        sdf = mesh_signed_distance(verts, tris, grid)             # (nz, ny, nx), positive inside
+        exportSdfToVTI("part_sdf", grid, sdf, "distance")"""
     if orient not in (None, "majority", "outward"):
         raise L.R2SError('orient must be None, "majority" or "outward"')
     if orient is not None and not weld:

@@ -505,33 +505,6 @@ int mi_raycast(const MiTree& T, const void* d_org, const void* d_dir, bool rays_
     return 0;
 }
 
-// One array of a host-pointer call: `bytes` on the device, uploaded from `in`, downloaded to `out` (both null: not wanted, no buffer)
-struct HostIo {
-    const void* in;
-    void* out;
-    size_t bytes;
-};
-
-// a host-pointer call: on the index's device, stage the arrays, run `enqueue` on their buffers (null stream), wait, copy the results back
-template <class F>
-int staged_call(const r2s_mesh_index* ix, const std::vector<HostIo>& io, F enqueue)
-{
-    int rc = check_device(0);
-    if (rc) return rc;
-    DeviceScope scope;
-    if ((rc = scope.enter(ix->device))) return rc;
-    std::vector<Scoped> buf(io.size());   // (freed before the caller's device is current again)
-    for (size_t k = 0; k < io.size(); ++k) {
-        if (io[k].in || io[k].out) ENSURE(buf[k], io[k].bytes);
-        if (io[k].in) HIP_TRY(hipMemcpy(buf[k].p, io[k].in, io[k].bytes, hipMemcpyHostToDevice));
-    }
-    if ((rc = enqueue(buf.data()))) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    for (size_t k = 0; k < io.size(); ++k)
-        if (io[k].out) HIP_TRY(hipMemcpy(io[k].out, buf[k].p, io[k].bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 // the new index of a mesh that `fill` uploads and builds the tree of, on the current device
 template <class F>
 int new_index(r2s_mesh_index** out, F fill)

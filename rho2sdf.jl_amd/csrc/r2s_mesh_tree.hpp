@@ -1,10 +1,12 @@
 // What the traversals of the mesh index share across files (r2s_mesh_index.hip: distance and ray queries; r2s_mesh_intersect.hip:
-// self-intersection pairs): the index object, the node of its tree and how a wavefront reads it, the box of a triangle, the
-// depth of the per-lane stack, and the host checks every entry point on an index makes.  One definition for both files.
+// self-intersection pairs; r2s_mesh_winding.hip: winding number and signed distance): the index object, the node of its tree and how
+// a wavefront reads it, the box of a triangle, the depth of the per-lane stack, the host checks every entry point on an index makes
+// and the staging of a host-pointer call.  One definition for all files.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "r2s_common.hpp"
 #include "r2s_internal.hpp"
@@ -64,5 +66,33 @@ struct DeviceScope {
     }
     ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+
+// One array of a host-pointer call: `bytes` on the device, uploaded from `in`, downloaded to `out` (both null: not wanted, no buffer)
+struct HostIo {
+    const void* in;
+    void* out;
+    size_t bytes;
+};
+
+// a host-pointer call: on the index's device, stage the arrays, run `enqueue` on their buffers (null stream), wait, copy the results back
+template <class F>
+int staged_call(const r2s_mesh_index* ix, const std::vector<HostIo>& io, F enqueue)
+{
+    int rc = check_device(0);
+    if (rc) return rc;
+    DeviceScope scope;
+    if ((rc = scope.enter(ix->device))) return rc;
+    std::vector<Scoped> buf(io.size());   // (freed before the caller's device is current again)
+    for (size_t k = 0; k < io.size(); ++k) {
+        if (io[k].in || io[k].out) ENSURE(buf[k], io[k].bytes);
+        if (io[k].in) HIP_TRY(hipMemcpy(buf[k].p, io[k].in, io[k].bytes, hipMemcpyHostToDevice));
+    }
+    if ((rc = enqueue(buf.data()))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (size_t k = 0; k < io.size(); ++k)
+        if (io[k].out) HIP_TRY(hipMemcpy(io[k].out, buf[k].p, io[k].bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 }  // namespace r2s_int

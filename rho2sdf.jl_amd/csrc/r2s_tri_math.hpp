@@ -129,6 +129,63 @@ __device__ inline bool seg_tri_hit(Vec3 p, Vec3 q, Vec3 a, Vec3 b, Vec3 c)
     return t >= 0.0 && t <= 1.0;
 }
 
+// The effective sign of the edge function f of the directed projected edge P -> Q (the header, r2s_mesh_index_winding, step 4):
+// the sign of f, and for f == 0 the sign f would take with the point moved by (eps, eps^2): that of Qy - Py, else of Px - Qx.
+// P and Q are the vertices' own float32 coordinates widened to double, so the two differences are exact.
+__device__ inline int edge_sign(double f, double px, double py, double qx, double qy)
+{
+    if (f != 0.0) return f > 0.0 ? 1 : -1;
+    if (qy != py) return qy > py ? 1 : -1;
+    return px > qx ? 1 : (px < qx ? -1 : 0);
+}
+
+// Does the axis ray from o along +e_KZ (neg: -e_KZ) cross the triangle a b c (float32 corners)?  The pair test of the header
+// (r2s_mesh_index_winding, steps 1 to 6) in two halves, so that a lattice row, whose points share the first, runs the same
+// arithmetic as a single point.  The caller has set collapsed triangles aside.  Every operation is rounded on its own.
+// First half, what depends on o[kx], o[ky] only (o1, o2 = o[(KZ+1)%3], o[(KZ+2)%3]): the two projected comparisons of the own-box
+// condition, U, V, W and their effective signs, det != 0.  -> 0 = no crossing for any o[kz], else `side`.
+template <int KZ>
+__device__ inline int axis_cross_2d(double o1, double o2, bool neg, const float* __restrict__ fa, const float* __restrict__ fb,
+                                    const float* __restrict__ fc, double& U, double& V, double& W)
+{
+#pragma clang fp contract(off)
+    constexpr int K1 = (KZ + 1) % 3, K2 = (KZ + 2) % 3;
+    if (!((double)fminf(fa[K1], fminf(fb[K1], fc[K1])) <= o1 && o1 <= (double)fmaxf(fa[K1], fmaxf(fb[K1], fc[K1])))) return 0;
+    if (!((double)fminf(fa[K2], fminf(fb[K2], fc[K2])) <= o2 && o2 <= (double)fmaxf(fa[K2], fmaxf(fb[K2], fc[K2])))) return 0;
+    // kx, ky = K1, K2, swapped for a ray along -e_KZ
+    const double okx = neg ? o2 : o1, oky = neg ? o1 : o2;
+    const double ax = (double)(neg ? fa[K2] : fa[K1]), ay = (double)(neg ? fa[K1] : fa[K2]);
+    const double bx = (double)(neg ? fb[K2] : fb[K1]), by = (double)(neg ? fb[K1] : fb[K2]);
+    const double cx = (double)(neg ? fc[K2] : fc[K1]), cy = (double)(neg ? fc[K1] : fc[K2]);
+    const double Ax = ax - okx, Ay = ay - oky, Bx = bx - okx, By = by - oky, Cx = cx - okx, Cy = cy - oky;
+    U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    const int su = edge_sign(U, bx, by, cx, cy), sv = edge_sign(V, cx, cy, ax, ay), sw = edge_sign(W, ax, ay, bx, by);
+    if (su == 0 || su != sv || su != sw) return 0;
+    return (U + V) + W != 0.0 ? su : 0;
+}
+// Second half, what depends on oz = o[KZ]: the box reaches ahead of the point, and t > 0.  Monotone in oz (true up to a threshold
+// for +e_KZ, from a threshold on for -e_KZ): the subtraction, the product with a factor of fixed sign, the sum and the quotient are.
+template <int KZ>
+__device__ inline bool axis_cross_1d(double oz, bool neg, const float* __restrict__ fa, const float* __restrict__ fb,
+                                     const float* __restrict__ fc, double U, double V, double W)
+{
+#pragma clang fp contract(off)
+    if (neg ? !((double)fminf(fa[KZ], fminf(fb[KZ], fc[KZ])) <= oz) : !((double)fmaxf(fa[KZ], fmaxf(fb[KZ], fc[KZ])) >= oz)) return false;
+    const double det = (U + V) + W;
+    const double Sz = neg ? -1.0 : 1.0;
+    const double Az = (double)fa[KZ] - oz, Bz = (double)fb[KZ] - oz, Cz = (double)fc[KZ] - oz;
+    const double t = ((U * (Sz * Az) + V * (Sz * Bz)) + W * (Sz * Cz)) / det;
+    return t > 0.0;
+}
+// the whole pair test for one point: 0 = no crossing, else `side`, the common effective sign of U, V, W
+template <int KZ>
+__device__ inline int axis_cross(Vec3 o, bool neg, const float* __restrict__ fa, const float* __restrict__ fb, const float* __restrict__ fc)
+{
+    double U, V, W;
+    const int side = axis_cross_2d<KZ>(vec_pick(o, (KZ + 1) % 3), vec_pick(o, (KZ + 2) % 3), neg, fa, fb, fc, U, V, W);
+    return side != 0 && axis_cross_1d<KZ>(vec_pick(o, KZ), neg, fa, fb, fc, U, V, W) ? side : 0;
+}
+
 // element i of a float32 (f32 != 0) or float64 array, read as / stored from a double
 __device__ inline double load_real(const void* p, int f32, int64_t i)
 {

@@ -721,6 +721,91 @@ function mesh_intersections_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tri
     return totals
 end
 
+# ---- winding number, inside / outside and signed distance from the mesh (include/rho2sdf_hip.h, r2s_mesh_index_winding) ----------
+# ray: 0, 1, 2 = +x, +y, +z; 3, 4, 5 = -x, -y, -z.  rule: :positive (winding > 0), :nonzero, :odd (crossings odd).
+const _INSIDE_RULES = Dict(:positive => Int32(0), :nonzero => Int32(1), :odd => Int32(2))
+_inside_rule(rule::Symbol) = get(() -> error("rule must be :positive, :nonzero or :odd"), _INSIDE_RULES, rule)
+
+# the winding number of the points (3 x n, Float32 or Float64) -> (winding, crossings), Vector{Int32}: +1 inside an outward-wound
+# closed body; a non-finite point gives 0 / -1; a point ON the surface gets a ray-dependent answer
+function mesh_index_winding(ix::MeshIndexHIP, points::AbstractMatrix{T}; ray::Integer = 2) where {T<:Union{Float32,Float64}}
+    size(points, 1) == 3 || error("points must be 3 x n")
+    n = size(points, 2)
+    winding, crossings = Vector{Int32}(undef, n), Vector{Int32}(undef, n)
+    check(ccall((:r2s_mesh_index_winding, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Int32}, Ptr{Int32}),
+                ix.handle, Matrix(points), Int32(T == Float32), n, Int32(ray), winding, crossings))
+    return winding, crossings
+end
+
+# distance of the points with the sign of the inside rule: positive inside (in the material) -> Vector{Float64}
+function mesh_index_signed_distance(ix::MeshIndexHIP, points::AbstractMatrix{T}; rule::Symbol = :positive,
+                                    ray::Integer = 2) where {T<:Union{Float32,Float64}}
+    size(points, 1) == 3 || error("points must be 3 x n")
+    n = size(points, 2)
+    dist = Vector{Float64}(undef, n)
+    check(ccall((:r2s_mesh_index_signed, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Int32}),
+                ix.handle, Matrix(points), Int32(T == Float32), n, _inside_rule(rule), Int32(ray), Int32(0), dist, C_NULL))
+    return dist
+end
+
+# winding and crossings on every point of the lattice of extract_isosurface_hip for (grid, smooth) -> two Array{Int32,3} (x fastest)
+function mesh_index_winding_lattice(ix::MeshIndexHIP, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing; ray::Integer = 2)
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    winding, crossings = Array{Int32,3}(undef, dims...), Array{Int32,3}(undef, dims...)
+    check(ccall((:r2s_mesh_index_winding_lattice, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Float64, Int32, Ptr{Int32}, Ptr{Int32}),
+                ix.handle, collect(dims), collect(Float64.(grid.AABB_min)), spacing, Int32(ray), winding, crossings))
+    return winding, crossings
+end
+
+# the signed distance on every point of that lattice -> Array{Float64,3}
+function mesh_index_signed_lattice(ix::MeshIndexHIP, grid::MeshGrid.Grid, smooth::Union{Int,Nothing} = nothing;
+                                   rule::Symbol = :positive, ray::Integer = 2)
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    dist = Array{Float64,3}(undef, dims...)
+    check(ccall((:r2s_mesh_index_signed_lattice, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Float64, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Int32}),
+                ix.handle, collect(dims), collect(Float64.(grid.AABB_min)), spacing, _inside_rule(rule), Int32(ray), Int32(0), dist, C_NULL))
+    return dist
+end
+
+# without an index: verts 3 x nv Float32, tris 3 x nt 1-based; a tree is built, used and dropped.  STL -> .vti:
+# import_stl_hip(file; orient = :outward) -> mesh_signed_distance_hip -> the .vti export of the same grid
+function mesh_signed_distance_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}, grid::MeshGrid.Grid,
+                                  smooth::Union{Int,Nothing} = nothing; rule::Symbol = :positive, ray::Integer = 2, device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    v, t0 = Matrix(verts), Int32.(tris) .- Int32(1)
+    s = smooth === nothing ? 1 : smooth
+    dims = Int64.((grid.N .* s) .+ 1)
+    spacing = smooth === nothing ? Float64(grid.cell_size) : Float64(grid.cell_size) / s
+    dist = Array{Float64,3}(undef, dims...)
+    check(ccall((:r2s_mesh_signed_distance, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Float64}, Float64, Int32, Int32, Int32, Int32, Ptr{Cvoid}),
+                v, size(v, 2), t0, size(t0, 2), collect(dims), collect(Float64.(grid.AABB_min)), spacing, _inside_rule(rule), Int32(ray),
+                Int32(0), Int32(device), dist))
+    return dist
+end
+
+# the device-pointer forms (raw pointers on the index's device, which must be current; enqueued on `stream`, not waited for)
+function mesh_index_winding_dev(ix::MeshIndexHIP, d_points::Ptr{Cvoid}, points_are_float32::Bool, n::Integer, d_winding::Ptr{Cvoid},
+                                d_crossings::Ptr{Cvoid}; ray::Integer = 2, stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:r2s_mesh_index_winding_dev, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                ix.handle, d_points, Int32(points_are_float32), Int64(n), Int32(ray), d_winding, d_crossings, stream))
+end
+
+function mesh_index_signed_dev(ix::MeshIndexHIP, d_points::Ptr{Cvoid}, points_are_float32::Bool, n::Integer, d_dist::Ptr{Cvoid},
+                               out_is_float32::Bool; rule::Symbol = :positive, ray::Integer = 2, d_closest_tri::Ptr{Cvoid} = C_NULL,
+                               stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:r2s_mesh_index_signed_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                ix.handle, d_points, Int32(points_are_float32), Int64(n), _inside_rule(rule), Int32(ray), Int32(out_is_float32), d_dist,
+                d_closest_tri, stream))
+end
+
 # The triangles of a binary or ASCII STL file (r2s_import_stl) -> (verts 3 x nv Float32, tris 3 x nt 1-based).  weld = true: the
 # equal vertices are merged by mesh_weld_hip(soup; snap); weld = false: the soup as the file holds it, tris = 1:3nt.
 # orient = nothing: the windings as the file holds them; :majority or :outward (needs weld = true): the welded triangles go
