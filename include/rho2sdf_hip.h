@@ -37,7 +37,7 @@
  *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
  *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
  *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev,
- *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev.
+ *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev, r2s_mesh_fans_dev.
  *     A caller should still order its consumers on `stream`, not on that wait.
  *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
  *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
@@ -500,7 +500,8 @@ int r2s_rbf_field_project_dev(const r2s_rbf_field *f, float *d_points_inout, int
  *     (v1-v0)x(v2-v0) point from the interior to the exterior.  Closed where the interior does not touch the lattice
  *     border; there is no capping and coincident vertices (exact-iso points) are not welded here.  The mesh is topologically
  *     closed as it stands; r2s_mesh_weld merges the coincident vertices on request, which collapses the zero-area triangles
- *     between them and can leave non-manifold vertices or edges that r2s_mesh_shells reports - so it is offered, not applied.
+ *     between them and can leave non-manifold edges, which r2s_mesh_shells reports, and non-manifold (pinched) vertices, which
+ *     the shells cannot see and r2s_mesh_fans reports and splits - so it is offered, not applied.
  *   - >= 2^31 vertices: R2S_ERR_UNSUPPORTED.  Any dim < 2, a non-positive or non-finite spacing or a NaN iso: R2S_ERR_ARG
  *     before any device work.
  * Host variant: *n_verts / *n_tris are always the full counts; the first min(capacity, n) entries are written (verts_out
@@ -917,7 +918,9 @@ int r2s_mesh_sections_dev(const float *d_verts, int64_t n_verts, const int32_t *
  * R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  n_verts == 0 or n_tris == 0 succeed.
  * The same input gives the same output on every call and from both variants (no result depends on an atomic's arrival order).
  * Caveat for meshes of r2s_extract_isosurface: they are topologically closed WITHOUT welding; welding their exact-iso vertices
- * collapses the zero-area triangles between them and can leave non-manifold vertices or edges, which r2s_mesh_shells reports.
+ * collapses the zero-area triangles between them and can leave non-manifold edges, which r2s_mesh_shells reports, and
+ * non-manifold vertices, which only r2s_mesh_fans below reports (the shells join triangles over edges and cannot see a vertex
+ * whose triangles fall into several fans); weld, then split with r2s_mesh_fans, gives a mesh whose every vertex is manifold.
  * Not here: distance-tolerance welding, hole filling, decimation; flipped triangles are re-oriented by r2s_mesh_orient below. */
 #define R2S_WELD_DROP_COLLAPSED 1
 #define R2S_WELD_DROP_DUPLICATES 2
@@ -997,6 +1000,71 @@ int r2s_last_mesh_orient(int64_t *counts_out, double *volume_out, int64_t capaci
 int r2s_mesh_orient_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, int32_t flags,
                         int32_t *d_tris_out, int32_t *d_flip_out, int32_t *d_patch_of_tri, int64_t *d_counts, double *d_volume,
                         int64_t patch_capacity, int64_t *n_patches, double ref_point[3], int64_t totals[8], void *stream);
+
+/* ---- mesh fans: non-manifold vertices, found and split ------------------------------------------
+ * Is every vertex a manifold vertex?  r2s_mesh_shells classifies EDGES; two bodies touching in one point, a surface pinched onto
+ * itself in one point or a welded iso-surface that passes through a lattice point have clean edge counts and are still refused by
+ * slicers, mesh Booleans and every half-edge structure.  The fans find such vertices and, on request, give every fan its own copy
+ * of the vertex: the one repair that never changes geometry.  With the shells this decides "closed 2-manifold": the shells say
+ * the edges are regular, the fans say the vertices are (the Euler characteristic and genus of a shell mean something only then).
+ * verts float32 [n_verts][3], tris int32 [n_tris][3], 0-based; collapsed triangles, half-edges, undirected keys and edge classes
+ * are exactly those of r2s_mesh_shells.  Integer and copy work only: there is no floating-point sum in this tool.
+ *   - corner k = 3t + c: corner c of the non-collapsed triangle t; its vertex is v = tris[k].  Its two edges at v are half-edge c
+ *     (i_c -> i_((c+1)%3)) and half-edge (c+2)%3 (i_((c+2)%3) -> i_c).  A collapsed triangle has no corners.
+ *   - adjacent corners: two corners of the SAME vertex whose triangles share an undirected edge incident to that vertex, of any
+ *     class.  All triangles on a non-manifold edge are therefore joined at both of its ends, as the shells join them.
+ *   - fan: a connected component of the corners of one vertex.  Fans are numbered by ascending vertex, and within a vertex by
+ *     ascending smallest corner id.  fan_of_corner[k] is that number, -1 for the three entries of a collapsed triangle.
+ *   - integer record of a fan, int64[8]: [0] vertex, [1] first_corner (its smallest corner id), [2] n_corners (= triangles),
+ *     [3] n_edges (distinct undirected edges at the vertex among the fan's triangles), [4] n_boundary, [5] n_flipped,
+ *     [6] n_nonmanifold (those edges by class), [7] class: 2 complex if [6] > 0, else 1 open if [4] > 0, else 0 closed.
+ *   - invariants: a closed fan is a single cycle, n_edges == n_corners; an open fan is a single path, n_boundary == 2 and
+ *     n_edges == n_corners + 1.  (Without non-manifold edges every corner has two distinct edges at v and every edge one or two
+ *     corners: a connected graph of degree <= 2.)
+ *   - fans_of_vert[v], int32: 0 unused (unreferenced, or referenced by collapsed triangles only), 1 an ordinary vertex (if its
+ *     fan is not complex), >= 2 a PINCHED vertex.
+ *   - totals, int64[8]: [0] fans, [1] triangles (n_tris), [2] collapsed triangles, [3] used vertices, [4] unused vertices,
+ *     [5] pinched vertices (two or more fans), [6] complex fans, [7] open fans.
+ *   - split (requested by passing tris_out): the first fan of a vertex keeps index v; every further fan f gets index
+ *     n_verts + (the number of non-first fans with a smaller fan number).  n_verts_out = n_verts + fans - used vertices.
+ *     verts_out[j] is the source vertex bit for bit; vert_of_out[j] is j for j < n_verts, else the source index;
+ *     tris_out[t][c] is the index of the fan of corner 3t + c.  Collapsed triangles and unused vertices are copied unchanged;
+ *     triangle order and winding are untouched.
+ *   - consequences.  No undirected edge is merged or divided by the split, because all corners of v on an edge (v, w) are in one
+ *     fan.  On the output mesh r2s_mesh_shells therefore gives the same shell_of_tri, the same edge counts and classes, the same
+ *     ref_point and bit-equal Float64 sums; only the vertex counts grow: totals[7] by n_verts_out - n_verts, and n_verts of a
+ *     shell to the number of its fans (a shell pinched onto itself gains a vertex; a vertex at which two shells touch was
+ *     counted in both already, so neither gains one).  The split is idempotent: on its output fans_of_vert <= 1 everywhere and a second split adds nothing.  Complex fans are NOT
+ *     repaired: non-manifold edges stay.
+ *   - determinism: the union-find hooks the larger root under the smaller, the counts are integer sums; no result depends on an
+ *     atomic's arrival order.  Under a permutation of the triangles the partition follows exactly, and so does every record
+ *     once first_corner is mapped.
+ * r2s_mesh_fans: host arrays, `device` (-1 = current).  fan_of_corner_out [n_tris][3] and fans_of_vert_out [n_verts] may be NULL.
+ * The split is written when tris_out [n_tris][3], verts_out [vert_capacity][3] and vert_of_out [vert_capacity] are given (all
+ * three or none; with n_tris == 0 tris_out may be NULL) AND vert_capacity >= *n_verts_out; otherwise the three are left untouched
+ * (ask without them, then call again).  *n_fans, *n_verts_out and totals are always written on success; the records become the
+ * calling thread's last result, read with r2s_last_mesh_fans: counts_out [capacity][8]; *n_fans is always the full count, the
+ * first min(capacity, n) records are written; counts_out may be NULL only with capacity == 0.
+ * r2s_mesh_fans_dev: device arrays on the current device, read after the work queued on `stream`, which is the only stream the
+ * call queues on; d_fan_of_corner, d_fans_of_vert (both may be NULL), d_counts [fan_capacity][8] and the three split outputs are
+ * device pointers, n_fans / n_verts_out / totals host pointers.  The counts are always returned; the records are written only
+ * when fan_capacity >= *n_fans, the split only when vert_capacity >= *n_verts_out (else they are left untouched: ask, then call
+ * again).  Synchronous on return; it does not touch the thread's last result.  Work buffers are kept per device and freed by
+ * r2s_release_cache.
+ * R2S_ERR_ARG before any output is touched, as by r2s_mesh_shells: NULL arrays with a count, a negative count or capacity, NULL
+ * n_fans / n_verts_out / totals, NULL records with a capacity, tris_out without verts_out / vert_of_out (or the reverse), an
+ * output that overlaps an input, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the host; _dev:
+ * the check kernel of r2s_mesh_distance_dev).  3 * n_tris >= 2^31, n_verts beyond 32 bits or an *n_verts_out beyond them:
+ * R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 fans and, under the split, the vertices copied.
+ * Not here: splitting along non-manifold edges, hole filling, anything geometric. */
+int r2s_mesh_fans(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
+                  int32_t *fan_of_corner_out, int32_t *fans_of_vert_out, int32_t *tris_out, float *verts_out,
+                  int32_t *vert_of_out, int64_t vert_capacity, int64_t *n_fans, int64_t *n_verts_out, int64_t totals[8]);
+int r2s_last_mesh_fans(int64_t *counts_out, int64_t capacity, int64_t *n_fans);
+int r2s_mesh_fans_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, int32_t *d_fan_of_corner,
+                      int32_t *d_fans_of_vert, int64_t *d_counts, int64_t fan_capacity, int32_t *d_tris_out, float *d_verts_out,
+                      int32_t *d_vert_of_out, int64_t vert_capacity, int64_t *n_fans, int64_t *n_verts_out, int64_t totals[8],
+                      void *stream);
 
 /* ---- mesh index: self-intersection pairs --------------------------------------------------------
  * Does the surface pass through itself?  The shells' volume and "void" verdict, OUTWARD orientation, "material on the left" of a

@@ -18,6 +18,7 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   MeshSections, mesh_sections, mesh_sections_dev,
                   MeshWeld, mesh_weld, mesh_weld_dev, import_stl,
                   MeshOrient, mesh_orient, mesh_orient_dev, flip_patches,
+                  MeshFans, mesh_fans, mesh_fans_dev,
                   MeshIntersections, mesh_intersections, mesh_intersections_dev,
                   mesh_signed_distance, mesh_signed_distance_dev)
 
@@ -34,6 +35,7 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "MeshSections", "mesh_sections", "mesh_sections_dev",
            "MeshWeld", "mesh_weld", "mesh_weld_dev", "import_stl",
            "MeshOrient", "mesh_orient", "mesh_orient_dev", "flip_patches",
+           "MeshFans", "mesh_fans", "mesh_fans_dev",
            "MeshIntersections", "mesh_intersections", "mesh_intersections_dev",
            "mesh_signed_distance", "mesh_signed_distance_dev",
            "_lib"]

@@ -1113,7 +1113,8 @@ def mesh_weld(verts, tris=None, *, snap=0.0, drop_collapsed=True, drop_duplicate
     triangles with two equal indices after the weld, drop_duplicates all but the first of the triangles equal up to a rotation
     of their corners, drop_unused the vertices no surviving triangle references.
     The mesh of extract_isosurface is already topologically closed; welding its exact-iso vertices collapses zero-area triangles
-    and can leave non-manifold vertices that mesh_shells reports, so the weld is offered, not applied by default."""
+    and can leave non-manifold edges, which mesh_shells reports, and non-manifold (pinched) vertices, which mesh_shells cannot
+    see: mesh_fans reports them and mesh_fans(split=True) repairs them.  So the weld is offered, not applied by default."""
     v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
     t = None if tris is None else np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
     if t is None and len(v) % 3:
@@ -1272,6 +1273,102 @@ def flip_patches(tris, patch_of_tri, which):
     rev = (pot >= 0) & np.concatenate([sel, [False]])[pot]
     t[rev] = t[rev][:, [0, 2, 1]]
     return t
+
+
+class MeshFans:
+    """The result of mesh_fans (include/rho2sdf_hip.h, r2s_mesh_fans): `fan_of_corner` (nt, 3) int32, the fan of every triangle
+    corner (-1 in a collapsed triangle); `fans_of_vert` (nv,) int32 (0 unused, 1 ordinary, >= 2 pinched); `counts` (n, 8) int64
+    (vertex, first_corner, n_corners, n_edges, n_boundary, n_flipped, n_nonmanifold, class 0 closed / 1 open / 2 complex);
+    `totals` (8,) int64 (fans, triangles, collapsed, used vertices, unused vertices, pinched vertices, complex fans, open
+    fans).  With split=True also `verts` (nv_out, 3) float32, `tris` (nt, 3) int32 and `vert_of` (nv_out,) int32 (the source
+    vertex of every output vertex), else None.  numpy arrays from mesh_fans; mesh_fans_dev keeps fan_of_corner, fans_of_vert,
+    verts, tris and vert_of on the device.  Derived on the host: the masks `closed`, `open`, `complex` per fan, `pinched` (the
+    vertex indices with two or more fans) and `vertex_manifold` (no pinched vertex and no complex fan)."""
+
+    def __init__(self, fan_of_corner, fans_of_vert, counts, totals, n_verts_in, verts=None, tris=None, vert_of=None):
+        self.fan_of_corner, self.fans_of_vert, self.counts, self.totals = fan_of_corner, fans_of_vert, counts, totals
+        self.verts, self.tris, self.vert_of, self._nv = verts, tris, vert_of, int(n_verts_in)
+
+    n_fans = property(lambda s: len(s.counts))
+    n_added = property(lambda s: int(s.totals[0] - s.totals[3]))
+    n_verts_out = property(lambda s: s._nv + s.n_added)
+    vertex = property(lambda s: s.counts[:, 0])
+    first_corner = property(lambda s: s.counts[:, 1])
+    n_corners = property(lambda s: s.counts[:, 2])
+    closed = property(lambda s: s.counts[:, 7] == 0)
+    open = property(lambda s: s.counts[:, 7] == 1)
+    complex = property(lambda s: s.counts[:, 7] == 2)
+    vertex_manifold = property(lambda s: bool(s.totals[5] == 0 and s.totals[6] == 0))
+
+    @property
+    def pinched(self):
+        v = self.counts[:, 0]
+        return np.unique(v[1:][v[1:] == v[:-1]])
+
+    def __len__(self):
+        return len(self.counts)
+
+
+def mesh_fans(verts, tris, *, split=False, device=-1):
+    """The fans of a triangle mesh (verts (nv, 3) float32, tris (nt, 3) int32, 0-based) -> MeshFans: the corners of every vertex
+    fall into fans, connected over the edges their triangles share at that vertex; a vertex with two or more fans is PINCHED
+    (non-manifold although every edge may be regular: two bodies touching in a point, a welded iso-surface through a lattice
+    point), which mesh_shells cannot see.  split=True also returns the repaired mesh: the first fan of a vertex keeps its index,
+    every further fan gets a copy of the vertex appended behind the input vertices, in fan order; no coordinate, edge or winding
+    changes.  Fans on a non-manifold edge (complex) are reported, not repaired.  One library call (a second one when the split
+    needs more than a little room) and a copy of the thread's last records."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    foc, fov = np.empty((len(t), 3), np.int32), np.empty(len(v), np.int32)
+    n, nvo = ctypes.c_int64(), ctypes.c_int64()
+    tot = np.zeros(8, np.int64)
+    ip = lambda a: a.ctypes.data_as(L.c_int32_p)
+    cap = len(v) + 1024 if split else 0
+    while True:
+        to, vo, vof = np.empty((len(t), 3), np.int32), np.empty((max(cap, 1), 3), np.float32), np.empty(max(cap, 1), np.int32)
+        L.check(L.lib().r2s_mesh_fans(_f(v) if len(v) else None, len(v), ip(t) if len(t) else None, len(t), int(device), ip(foc), ip(fov),
+                                      ip(to) if split else None, _f(vo) if split else None, ip(vof) if split else None, cap,
+                                      ctypes.byref(n), ctypes.byref(nvo), _i(tot)))
+        if not split or nvo.value <= cap:
+            break
+        cap = nvo.value
+    counts = np.empty((n.value, 8), np.int64)
+    if n.value:
+        L.check(L.lib().r2s_last_mesh_fans(_i(counts), n.value, ctypes.byref(n)))
+    if not split:
+        return MeshFans(foc, fov, counts, tot, len(v))
+    return MeshFans(foc, fov, counts, tot, len(v), vo[:nvo.value].copy(), to, vof[:nvo.value].copy())
+
+
+def mesh_fans_dev(verts, tris, stream=None, *, split=False, capacity=0):
+    """mesh_fans on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous).  The records come
+    back as a numpy array; fan_of_corner, fans_of_vert and, with split=True, verts, tris and vert_of stay device tensors.  The
+    library writes the records only into room for all fans and the split only into room for all output vertices: with more fans
+    than `capacity`, or a split that needs more than a little room, the call is made a second time."""
+    import torch
+    _mesh_tensors(verts, tris)
+    st = _stream(stream)
+    dev = verts.device
+    nv, nt = verts.numel() // 3, tris.numel() // 3
+    foc, fov = torch.empty((nt, 3), dtype=torch.int32, device=dev), torch.empty(nv, dtype=torch.int32, device=dev)
+    n, nvo = ctypes.c_int64(), ctypes.c_int64()
+    tot = np.zeros(8, np.int64)
+    cap, vcap = int(capacity), (nv + 1024 if split else 0)
+    vp = lambda x: ctypes.c_void_p(x.data_ptr()) if x.numel() else None   # noqa: E731
+    while True:
+        counts = torch.empty((cap, 8), dtype=torch.int64, device=dev)
+        to = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        vo, vof = torch.empty((max(vcap, 1), 3), dtype=torch.float32, device=dev), torch.empty(max(vcap, 1), dtype=torch.int32, device=dev)
+        L.check(L.lib().r2s_mesh_fans_dev(vp(verts), nv, vp(tris), nt, vp(foc), vp(fov), vp(counts), cap, vp(to) if split else None,
+                                          vp(vo) if split else None, vp(vof) if split else None, vcap, ctypes.byref(n), ctypes.byref(nvo),
+                                          _i(tot), st))
+        if n.value <= cap and (not split or nvo.value <= vcap):
+            break
+        cap, vcap = max(cap, n.value), (max(vcap, nvo.value) if split else 0)
+    counts = counts[:n.value].cpu().numpy()
+    if not split:
+        return MeshFans(foc, fov, counts, tot, nv)
+    return MeshFans(foc, fov, counts, tot, nv, vo[:nvo.value], to, vof[:nvo.value])
 
 
 class MeshSections:
@@ -1774,7 +1871,7 @@ def export_stl(filename, verts, tris):
     return filename if filename.endswith(".stl") else filename + ".stl"
 
 
-def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_intersections=False):
+def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_intersections=False, split_vertices=False):
     """The triangles of a binary or ASCII STL file -> (verts (nv, 3) float32, tris (nt, 3) int32).  weld=True (needs the GPU): the
     vertices that are the same point are merged by mesh_weld(soup, snap=snap) with its defaults (collapsed triangles and unused
     vertices dropped), so the mesh tools see shared vertices; weld=False: the soup as the file holds it, 3 nt vertices and
@@ -1782,7 +1879,9 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     "majority" or "outward" (needs weld=True): the welded triangles go through mesh_orient(outward=(orient == "outward")), whose
     docstring has the rules and the caveat about enclosed voids.  check_intersections=True (needs weld=True): the result is
     (verts, tris, MeshIntersections), the self-intersections of the mesh as returned (mesh_intersections): zero pairs are what
-    the shells, the orientation, sections and thickness take for granted.
+    the shells, the orientation, sections and thickness take for granted.  split_vertices=True (needs weld=True): after the weld,
+    and after the orient if one is asked for, the vertices the weld left pinched (two bodies touching in a point) are split by
+    mesh_fans(split=True), so that every vertex of the result has a single fan unless it lies on a non-manifold edge.
 
     From an STL file to the signed-distance volume everything else here produces:
 
@@ -1795,6 +1894,8 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
         raise L.R2SError('orient must be None, "majority" or "outward"')
     if orient is not None and not weld:
         raise L.R2SError("orient needs weld=True: a soup has no shared edges to orient across")
+    if split_vertices and not weld:
+        raise L.R2SError("split_vertices needs weld=True: in a soup no vertex is shared")
     if check_intersections and not weld:
         raise L.R2SError("check_intersections needs weld=True: in a soup every neighbour touches under different indices")
     m = L.R2SStlMesh()
@@ -1807,10 +1908,14 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     if not weld:
         return soup, np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
     w = mesh_weld(soup, None, snap=snap, device=device)
-    tris = w.tris if orient is None else mesh_orient(w.verts, w.tris, outward=orient == "outward", device=device).tris
+    verts = w.verts
+    tris = w.tris if orient is None else mesh_orient(verts, w.tris, outward=orient == "outward", device=device).tris
+    if split_vertices:
+        f = mesh_fans(verts, tris, split=True, device=device)
+        verts, tris = f.verts, f.tris
     if check_intersections:
-        return w.verts, tris, mesh_intersections(w.verts, tris, device=device)
-    return w.verts, tris
+        return verts, tris, mesh_intersections(verts, tris, device=device)
+    return verts, tris
 
 
 def exportToVTU(fileName, X, IEN, VTK_CODE=None, rho=None):

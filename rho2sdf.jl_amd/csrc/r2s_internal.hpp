@@ -165,6 +165,10 @@ void release_weld_work();
 // frees the work buffers the orient calls keep per device; called by r2s_release_cache()
 void release_orient_work();
 
+// ---- mesh fans (r2s_mesh_fans.hip) ------------------------------------------------------------------------------------
+// frees the work buffers the fan calls keep per device; called by r2s_release_cache()
+void release_fans_work();
+
 // ---- mesh intersections (r2s_mesh_intersect.hip) ----------------------------------------------------------------------
 // frees the work buffers the intersection calls keep per device; called by r2s_release_cache()
 void release_intersect_work();

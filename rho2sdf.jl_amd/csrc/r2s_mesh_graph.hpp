@@ -1,6 +1,6 @@
-// What r2s_mesh_shells.hip, r2s_mesh_sections.hip and r2s_mesh_orient.hip share: the box of the vertices behind the reference
-// point, the collapsed-triangle test, the integer union-find with min-root and (shells, orient) the per-group integer
-// counting.  r2s_mesh_weld.hip takes the order-preserving bit pattern
+// What r2s_mesh_shells.hip, r2s_mesh_sections.hip, r2s_mesh_orient.hip and r2s_mesh_fans.hip share: the box of the vertices
+// behind the reference point, the collapsed-triangle test, the integer union-find with min-root, (shells, orient, fans) the
+// per-group integer counting and (orient, fans) the size of a run of sorted half-edges.  r2s_mesh_weld.hip takes the order-preserving bit pattern
 // of a float32 and the launch / bit-count helpers from here.  Everything has internal linkage: each file gets its own copy of
 // the kernel.
 #pragma once
@@ -88,6 +88,18 @@ __device__ inline void ms_union(uint32_t* L, uint32_t a, uint32_t b)
         if (a < b) { const uint32_t t = a; a = b; b = t; }   // link the larger root under the smaller
         if (atomicCAS(&L[a], a, b) == a) return;             // a was still a root
     }
+}
+
+// (orient, fans) the sorted half-edge keys are (min << 33) | (max << 1) | direction, the collapsed triangles' keys behind them.
+// The number of members of the run of sorted half-edge i, capped at 3 (i is a real half-edge: keys[i] < ckey)
+__device__ inline int ms_run_size(const uint64_t* __restrict__ keys, int64_t i, int64_t nh, bool& head)
+{
+    const uint64_t e = keys[i] >> 1;
+    const bool p1 = i >= 1 && (keys[i - 1] >> 1) == e, p2 = p1 && i >= 2 && (keys[i - 2] >> 1) == e;
+    const bool n1 = i + 1 < nh && (keys[i + 1] >> 1) == e, n2 = n1 && i + 2 < nh && (keys[i + 2] >> 1) == e;
+    head = !p1;
+    if (!p1 && !n1) return 1;
+    return (p2 || (p1 && n1) || n2) ? 3 : 2;
 }
 
 // adds 1 to counts[group][col0 + k] (rows of STRIDE) for every k < NC with add[k] set, over the workgroup's active threads: once

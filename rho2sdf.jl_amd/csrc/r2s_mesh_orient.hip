@@ -71,17 +71,6 @@ __global__ void __launch_bounds__(256) mo_key_kernel(const int32_t* __restrict__
     if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MO_COLLAPSED], (unsigned long long)__popcll(m));
 }
 
-// the number of members of the run of sorted half-edge i, capped at 3 (i is a real half-edge: keys[i] < ckey)
-__device__ inline int mo_run_size(const uint64_t* __restrict__ keys, int64_t i, int64_t nh, bool& head)
-{
-    const uint64_t e = keys[i] >> 1;
-    const bool p1 = i >= 1 && (keys[i - 1] >> 1) == e, p2 = p1 && i >= 2 && (keys[i - 2] >> 1) == e;
-    const bool n1 = i + 1 < nh && (keys[i + 1] >> 1) == e, n2 = n1 && i + 2 < nh && (keys[i + 2] >> 1) == e;
-    head = !p1;
-    if (!p1 && !n1) return 1;
-    return (p2 || (p1 && n1) || n2) ? 3 : 2;
-}
-
 // one thread per sorted half-edge: the second member of a run of exactly two joins the two triangles on the doubled graph
 __global__ void __launch_bounds__(256) mo_union_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
                                                         uint64_t ckey, uint32_t* parent)
@@ -91,7 +80,7 @@ __global__ void __launch_bounds__(256) mo_union_kernel(const uint64_t* __restric
     const uint64_t k = keys[i];
     if (k >= ckey) return;
     bool head;
-    if (mo_run_size(keys, i, nh, head) != 2 || head) return;
+    if (ms_run_size(keys, i, nh, head) != 2 || head) return;
     const uint32_t a = vals[i - 1] / 3u, b = vals[i] / 3u;
     const uint32_t same = (uint32_t)(((keys[i - 1] ^ k) & 1ull) == 0ull);   // equal directions: a flipped edge, the parities differ
     ms_union(parent, 2u * a, 2u * b + same);
@@ -253,7 +242,7 @@ __global__ void __launch_bounds__(256) mo_edge_kernel(const uint64_t* __restrict
     bool any = false;
     if (i < nh && keys[i] < ckey) {
         bool head;
-        const int size = mo_run_size(keys, i, nh, head);
+        const int size = ms_run_size(keys, i, nh, head);
         add[0] = size == 1;
         add[1] = size == 3;
         add[2] = size == 2 && head && ((keys[i + 1] ^ keys[i]) & 1ull) == 0ull;
@@ -322,7 +311,7 @@ __global__ void __launch_bounds__(256) mo_remain_kernel(const uint64_t* __restri
     bool left = false;
     if (i < nh && keys[i] < ckey) {
         bool head;
-        if (mo_run_size(keys, i, nh, head) == 2 && head) {
+        if (ms_run_size(keys, i, nh, head) == 2 && head) {
             const uint32_t da = (uint32_t)(keys[i] & 1ull) ^ (uint32_t)flip[vals[i] / 3u];
             const uint32_t db = (uint32_t)(keys[i + 1] & 1ull) ^ (uint32_t)flip[vals[i + 1] / 3u];
             left = da == db;

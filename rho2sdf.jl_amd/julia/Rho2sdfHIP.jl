@@ -567,8 +567,8 @@ end
 # equal as Float32; snap > 0: iff they fall into the same cell floor(v / snap) per axis - grid snapping, not a distance tolerance.
 # -> (verts 3 x nv_out, every column an input vertex bit for bit in first-occurrence order, tris 3 x nt_out 1-based, vert_map and
 # tri_map 1-based with 0 for what was dropped, totals).  The mesh of extract_isosurface_hip is closed without welding; welding its
-# exact-iso vertices collapses zero-area triangles and can leave non-manifold vertices that mesh_shells_hip reports: offered, not
-# applied by default.
+# exact-iso vertices collapses zero-area triangles and can leave non-manifold edges, which mesh_shells_hip reports, and pinched
+# vertices, which only mesh_fans_hip reports (and splits): offered, not applied by default.
 function mesh_weld_hip(verts::AbstractMatrix{Float32}, tris::Union{Nothing,AbstractMatrix{<:Integer}} = nothing; snap::Real = 0.0,
                        drop_collapsed::Bool = true, drop_duplicates::Bool = false, drop_unused::Bool = true, device::Integer = -1)
     size(verts, 1) == 3 && (tris === nothing ? size(verts, 2) % 3 == 0 : size(tris, 1) == 3) ||
@@ -667,6 +667,67 @@ function mesh_orient_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{
                 d_verts, Int64(n_verts), d_tris, Int64(n_tris), outward ? ORIENT_OUTWARD : Int32(0), d_tris_out, d_flip, d_patch_of_tri,
                 d_counts, d_volume, Int64(patch_capacity), n, ref, totals, stream))
     return n[], ref, totals
+end
+
+# The fans of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_fans): verts 3 x nv Float32, tris 3 x nt 1-based.  The corners of
+# every vertex fall into fans, connected over the edges their triangles share at that vertex; a vertex with two or more fans is
+# pinched (non-manifold, although every edge may be regular), which mesh_shells_hip cannot see.  split = true also returns the
+# repaired mesh: the first fan of a vertex keeps its index, every further fan gets a copy of the vertex appended behind the input
+# vertices; fans on a non-manifold edge (complex) are reported, not repaired.
+# -> (fan_of_corner 3 x nt (1-based fan number, 0 = collapsed triangle), fans_of_vert (0 unused, 1 ordinary, >= 2 pinched),
+# counts 8 x n Int64 (vertex and first_corner 1-based, n_corners, n_edges, boundary, flipped, non-manifold edges, class 0 closed /
+# 1 open / 2 complex), totals (fans, triangles, collapsed, used, unused, pinched vertices, complex fans, open fans) and, with
+# split, verts 3 x nv_out, tris 3 x nt 1-based, vert_of (1-based source vertex))
+function mesh_fans_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}; split::Bool = false, device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    t0 = Int32.(tris) .- Int32(1)
+    nv = size(verts, 2); nt = size(t0, 2)
+    foc = Matrix{Int32}(undef, 3, nt); fov = Vector{Int32}(undef, nv)
+    n = Ref{Int64}(0); nvo = Ref{Int64}(0)
+    totals = zeros(Int64, 8)
+    cap = split ? nv + 1024 : 0
+    tout = Matrix{Int32}(undef, 3, nt)
+    while true
+        vout = Matrix{Float32}(undef, 3, max(cap, 1)); vof = Vector{Int32}(undef, max(cap, 1))
+        check(ccall((:r2s_mesh_fans, LIB[]), Cint,
+                    (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Int64,
+                     Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                    Matrix(verts), nv, t0, nt, Int32(device), foc, fov, split ? tout : C_NULL, split ? vout : C_NULL,
+                    split ? vof : C_NULL, Int64(cap), n, nvo, totals))
+        if !split || nvo[] <= cap
+            counts = last_mesh_fans_hip(n[])
+            base = (fan_of_corner = foc .+ Int32(1), fans_of_vert = fov, counts = counts, totals = totals)
+            return split ? merge(base, (verts = vout[:, 1:nvo[]], tris = tout .+ Int32(1), vert_of = vof[1:nvo[]] .+ Int32(1))) : base
+        end
+        cap = nvo[]
+    end
+end
+
+# the calling thread's last fan records (r2s_last_mesh_fans): counts 8 x n (vertex and first_corner made 1-based)
+function last_mesh_fans_hip(capacity::Integer)
+    counts = Matrix{Int64}(undef, 8, capacity)
+    n = Ref{Int64}(0)
+    check(ccall((:r2s_last_mesh_fans, LIB[]), Cint, (Ptr{Int64}, Int64, Ptr{Int64}),
+                capacity == 0 ? C_NULL : counts, Int64(capacity), n))
+    counts[1:2, :] .+= 1
+    return counts
+end
+
+# the same on device arrays of the current device (raw pointers, e.g. of AMDGPU.jl ROCArrays); d_fan_of_corner and d_fans_of_vert
+# may be C_NULL; the records are written only when fan_capacity holds all fans, the split (d_tris_out, d_verts_out, d_vert_of_out:
+# all three or C_NULL) only when vert_capacity holds all output vertices -> (n_fans, n_verts_out, totals); indices stay 0-based
+function mesh_fans_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer, d_fan_of_corner::Ptr{Cvoid},
+                           d_fans_of_vert::Ptr{Cvoid}, d_counts::Ptr{Cvoid}, fan_capacity::Integer, d_tris_out::Ptr{Cvoid} = C_NULL,
+                           d_verts_out::Ptr{Cvoid} = C_NULL, d_vert_of_out::Ptr{Cvoid} = C_NULL, vert_capacity::Integer = 0;
+                           stream::Ptr{Cvoid} = C_NULL)
+    n = Ref{Int64}(0); nvo = Ref{Int64}(0)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_fans_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+                 Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), d_fan_of_corner, d_fans_of_vert, d_counts, Int64(fan_capacity), d_tris_out,
+                d_verts_out, d_vert_of_out, Int64(vert_capacity), n, nvo, totals, stream))
+    return n[], nvo[], totals
 end
 
 # The self-intersections of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_index_intersections): the pairs of triangles that
@@ -810,11 +871,13 @@ end
 # equal vertices are merged by mesh_weld_hip(soup; snap); weld = false: the soup as the file holds it, tris = 1:3nt.
 # orient = nothing: the windings as the file holds them; :majority or :outward (needs weld = true): the welded triangles go
 # through mesh_orient_hip (see there for the rules and the caveat about enclosed voids).  check_intersections = true (needs
-# weld = true): -> (verts, tris, mesh_intersections_hip of the mesh as returned).
+# weld = true): -> (verts, tris, mesh_intersections_hip of the mesh as returned).  split_vertices = true (needs weld = true): the
+# vertices the weld left pinched are split by mesh_fans_hip(split = true), after the orient if one is asked for.
 function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real = 0.0, device::Integer = -1,
-                        orient::Union{Nothing,Symbol} = nothing, check_intersections::Bool = false)
+                        orient::Union{Nothing,Symbol} = nothing, check_intersections::Bool = false, split_vertices::Bool = false)
     orient === nothing || orient in (:majority, :outward) || error("orient must be nothing, :majority or :outward")
     orient === nothing || weld || error("orient needs weld = true")
+    !split_vertices || weld || error("split_vertices needs weld = true")
     !check_intersections || weld || error("check_intersections needs weld = true")
     m = R2SStlMesh(0, C_NULL)
     check(ccall((:r2s_import_stl, LIB[]), Cint, (Cstring, Ref{R2SStlMesh}), filename, m))
@@ -823,8 +886,13 @@ function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real 
     weld || return soup, reshape(Int32.(1:size(soup, 2)), 3, :)
     w = mesh_weld_hip(soup; snap = snap, device = device)
     tris = orient === nothing ? w.tris : mesh_orient_hip(w.verts, w.tris; outward = orient === :outward, device = device).tris
-    check_intersections || return w.verts, tris
-    return w.verts, tris, mesh_intersections_hip(w.verts, tris; device = device)
+    verts = w.verts
+    if split_vertices
+        f = mesh_fans_hip(verts, tris; split = true, device = device)
+        verts, tris = f.verts, f.tris
+    end
+    check_intersections || return verts, tris
+    return verts, tris, mesh_intersections_hip(verts, tris; device = device)
 end
 
 # The signed distance to the iso-surface of `values` on the whole lattice (r2s_redistance_full): redistance_hip without a band;
