@@ -37,7 +37,7 @@
  *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
  *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
  *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev,
- *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev, r2s_mesh_fans_dev.
+ *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev, r2s_mesh_fans_dev, r2s_mesh_holes_dev.
  *     A caller should still order its consumers on `stream`, not on that wait.
  *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
  *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
@@ -1056,7 +1056,7 @@ int r2s_mesh_orient_dev(const float *d_verts, int64_t n_verts, const int32_t *d_
  * output that overlaps an input, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the host; _dev:
  * the check kernel of r2s_mesh_distance_dev).  3 * n_tris >= 2^31, n_verts beyond 32 bits or an *n_verts_out beyond them:
  * R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 fans and, under the split, the vertices copied.
- * Not here: splitting along non-manifold edges, hole filling, anything geometric. */
+ * Not here: splitting along non-manifold edges, anything geometric; hole filling is r2s_mesh_holes below. */
 int r2s_mesh_fans(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
                   int32_t *fan_of_corner_out, int32_t *fans_of_vert_out, int32_t *tris_out, float *verts_out,
                   int32_t *vert_of_out, int64_t vert_capacity, int64_t *n_fans, int64_t *n_verts_out, int64_t totals[8]);
@@ -1065,6 +1065,95 @@ int r2s_mesh_fans_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tr
                       int32_t *d_fans_of_vert, int64_t *d_counts, int64_t fan_capacity, int32_t *d_tris_out, float *d_verts_out,
                       int32_t *d_vert_of_out, int64_t vert_capacity, int64_t *n_fans, int64_t *n_verts_out, int64_t totals[8],
                       void *stream);
+
+/* ---- mesh holes: boundary loops, found, measured and capped ---------------------------------------
+ * Where is the mesh open, how large is each opening, and can it be closed?  r2s_mesh_shells COUNTS boundary edges; the winding
+ * number, the OUTWARD rule and the signed distance mean something only on closed shells, and an STL with one missing triangle is
+ * not one.  The holes report the RIMS of a mesh - its boundary loops and chains - and, on request, return a mesh in which every
+ * selected closed rim is capped.  verts float32 [n_verts][3], tris int32 [n_tris][3], 0-based; collapsed triangles, half-edges,
+ * undirected keys and edge classes are exactly those of r2s_mesh_shells.
+ *   - boundary half-edge: half-edge h = 3t + c of a non-collapsed triangle whose undirected edge group has exactly one half-edge.
+ *     It runs FROM tris[3t + c] TO tris[3t + (c + 1) % 3].
+ *   - node: a vertex that is an end of at least one boundary half-edge.  Its class is taken over the ends at the vertex (a FROM
+ *     end is outgoing, a TO end incoming), worded like the sections' classes: one outgoing and one incoming end REGULAR, one end
+ *     OPEN, two ends of the same kind FLIPPED, three or more ends BRANCH.
+ *   - rim: a connected component of the boundary half-edges; two are adjacent when they share a node of any class.  A rim is
+ *     CLOSED iff all its nodes are regular; it is then one simple cycle of distinct vertex indices with n_edges == n_nodes >= 3
+ *     (every node has one way in and one way out; a cycle of two would be one undirected edge with two half-edges, which is not
+ *     a boundary edge).  Rims are numbered by ascending smallest half-edge id.
+ *   - output order: inside a closed rim, from its smallest half-edge id along the successors (the successor of a half-edge is the
+ *     half-edge whose FROM is this one's TO); inside any other rim, ascending half-edge id - no walk is promised there.
+ *   - tables: rim_start int64 [n_rims + 1]; rim_edge int32 per output position, the half-edge id; per rim the integer record
+ *     int64[8]: [0] first half-edge id, [1] n_edges, [2] n_nodes, [3] open, [4] flipped, [5] branch nodes, [6] status (0 not
+ *     closed, 1 closed and not filled, 2 filled with one triangle, 3 filled with a fan), [7] index of the added vertex or -1;
+ *     per rim the Float64 record double[7] about the shells' reference point r (the same definition, returned in ref_point):
+ *     [0] length = sum sqrt((Dx Dx + Dy Dy) + Dz Dz), [1..3] sum A x B = (Ay Bz - Az By, Az Bx - Ax Bz, Ax By - Ay Bx),
+ *     [4..6] sum A, with A = from - r, B = to - r, D = B - A, each coordinate widened to double; every operation is rounded on
+ *     its own (no fma).  Of a closed rim 0.5 |sum A x B| is the area of its vector-area projection and r + sum A / n_edges the
+ *     mean of its vertices.
+ *   - summation: the sections' scheme on the output order.  Blocks of 256 consecutive output positions (block j = positions
+ *     [256 j, 256 j + 256) of the whole table; a rim's first and last block may be shared with its neighbours, whose terms do
+ *     not enter) are summed in a fixed binary tree: in round d = 1, 2, .., 128 position p takes position p + d when that lies in
+ *     the same block and rim.  The nb block partials of a rim are cut into up to 64 runs of ceil(nb / 64) consecutive partials,
+ *     each summed in ascending order; the run sums are joined in a fixed tree (round d = 1, 2, .., 32: run l takes run l + d).
+ *     No floating-point atomic, no library reduction: the same input gives the same bits on every call and from both variants.
+ *     Each sum is within (n_edges + K) 2^-53 T of the exact sum of the exact terms, T = the sum of the absolute values of the
+ *     term's monomials, K = 5 (length), 4 (A x B), 1 (A): the roundings on the term's longest chain.
+ *   - totals, int64[8]: [0] rims, [1] boundary half-edges, [2] collapsed triangles, [3] nodes, [4] open + flipped + branch nodes,
+ *     [5] closed rims, [6] filled rims, [7] added triangles.
+ *   - fill (requested by passing tris_out and verts_out): max_edges selects the rims - negative: every closed rim, 0: none,
+ *     k > 0: the closed rims with n_edges <= k.  A selected rim of exactly 3 edges a -> b -> c -> a (a -> b its first half-edge)
+ *     gets the one triangle (b, a, c) and no new vertex.  A longer selected rim gets one new vertex w and n_edges triangles
+ *     (b, a, w), one per boundary half-edge a -> b, in output order.  w is computed per axis as r_a + S_a / n_edges in double
+ *     (S = the rim's [4..6]; one division, one addition) and rounded to the nearest float32.  Added vertices follow the input
+ *     vertices in rim order, added triangles follow the input triangles in rim order; input vertices and triangles are copied
+ *     unchanged, bit for bit.  Non-closed rims are never filled.  Status and added vertex of the records, n_verts_out,
+ *     n_tris_out and totals[6..7] state the selection whether or not the outputs had room; without a fill request nothing is
+ *     selected.
+ *   - consequences.  The cap of a rim is wound against it: every boundary half-edge a -> b of a filled rim meets exactly one new
+ *     half-edge b -> a, so every filled boundary edge becomes a regular edge; every added edge {a, w} has exactly two opposite
+ *     half-edges (a -> w from the triangle of the boundary half-edge that leaves a, w -> a from the one that arrives at a); no
+ *     other edge gains or loses a half-edge.  On the output mesh r2s_mesh_shells therefore reports the boundary-edge total lower
+ *     by exactly the filled edges, unchanged flipped and non-manifold totals and an unchanged shell_of_tri for the input
+ *     triangles; r2s_mesh_fans reports one closed fan at each w and unchanged fans_of_vert at the input vertices.  The fill is
+ *     idempotent under the same max_edges: the filled rims are gone, the others are untouched.
+ *   - determinism: the union-find hooks the larger root under the smaller, the counts are integer sums, the Float64 sums have a
+ *     fixed order; no result depends on an atomic's arrival order.  Under a permutation of the triangles or a rotation of their
+ *     corners the partition and every integer follow once the half-edge ids are mapped; a closed rim is the same cycle from
+ *     another start, so its sums may differ by the bound above.
+ * r2s_mesh_holes: host arrays, `device` (-1 = current).  The fill is asked for by tris_out [tri_capacity][3] and verts_out
+ * [vert_capacity][3] (both or none); verts_out is written when vert_capacity >= *n_verts_out, tris_out when tri_capacity >=
+ * *n_tris_out, otherwise that array is left untouched (ask, then call again).  *n_rims, *n_edges (boundary half-edges),
+ * *n_verts_out, *n_tris_out, ref_point and totals are always written on success; the tables become the calling thread's last
+ * result, read with r2s_last_mesh_holes: rim_start_out [rim_capacity + 1], counts_out [rim_capacity][8], sums_out
+ * [rim_capacity][7], rim_edge_out [edge_capacity]; the counts are always the full ones, the first min(capacity, n) entries of
+ * each group are written (rim_start_out: one more); a group may be NULL only with capacity == 0.
+ * r2s_mesh_holes_dev: device arrays on the current device, read after the work queued on `stream`, which is the only stream the
+ * call queues on; the tables and the two fill outputs are device pointers, the counts, ref_point and totals host pointers.  The
+ * counts are always returned; each group is written only when its capacity suffices - d_rim_start [rim_capacity + 1], d_counts
+ * and d_sums when rim_capacity >= *n_rims, d_rim_edge when edge_capacity >= *n_edges, d_verts_out when vert_capacity >=
+ * *n_verts_out, d_tris_out when tri_capacity >= *n_tris_out - else it is left untouched.  Synchronous on return; it does not
+ * touch the thread's last result.  Work buffers are kept per device and freed by r2s_release_cache.
+ * R2S_ERR_ARG before any output is touched, as by r2s_mesh_fans: NULL arrays with a count, a negative count or capacity, NULL
+ * count / ref_point / totals pointers, NULL tables with a capacity, tris_out without verts_out (or the reverse), an output that
+ * overlaps an input, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the host; _dev: the check
+ * kernel of r2s_mesh_distance_dev).  3 * n_tris >= 2^31, n_verts beyond 32 bits or an *n_verts_out beyond them:
+ * R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with nothing and, under the fill, the vertices copied.
+ * Not here: a pinched boundary vertex (two holes touching in a point) is a branch node and blocks the fill - the fans' split
+ * makes it regular, so the recipe is weld -> orient -> split -> fill; rims through flipped nodes need the orient first; a fan cap
+ * of a non-planar or non-star-shaped rim can intersect the surface, and r2s_mesh_intersections is the check.  Not offered:
+ * filling only the rims a user names, planar caps with nesting (an iso-surface cut by the lattice border), caps without a
+ * Steiner point, refinement or fairing of a cap. */
+int r2s_mesh_holes(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device, int64_t max_edges,
+                   int32_t *tris_out, float *verts_out, int64_t vert_capacity, int64_t tri_capacity, int64_t *n_rims,
+                   int64_t *n_edges, int64_t *n_verts_out, int64_t *n_tris_out, double ref_point[3], int64_t totals[8]);
+int r2s_last_mesh_holes(int64_t *rim_start_out, int64_t *counts_out, double *sums_out, int64_t rim_capacity, int32_t *rim_edge_out,
+                        int64_t edge_capacity, int64_t *n_rims, int64_t *n_edges);
+int r2s_mesh_holes_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, int64_t max_edges,
+                       int64_t *d_rim_start, int64_t *d_counts, double *d_sums, int64_t rim_capacity, int32_t *d_rim_edge,
+                       int64_t edge_capacity, int32_t *d_tris_out, float *d_verts_out, int64_t vert_capacity, int64_t tri_capacity,
+                       int64_t *n_rims, int64_t *n_edges, int64_t *n_verts_out, int64_t *n_tris_out, double ref_point[3],
+                       int64_t totals[8], void *stream);
 
 /* ---- mesh index: self-intersection pairs --------------------------------------------------------
  * Does the surface pass through itself?  The shells' volume and "void" verdict, OUTWARD orientation, "material on the left" of a

@@ -19,6 +19,7 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   MeshWeld, mesh_weld, mesh_weld_dev, import_stl,
                   MeshOrient, mesh_orient, mesh_orient_dev, flip_patches,
                   MeshFans, mesh_fans, mesh_fans_dev,
+                  MeshHoles, mesh_holes, mesh_holes_dev,
                   MeshIntersections, mesh_intersections, mesh_intersections_dev,
                   mesh_signed_distance, mesh_signed_distance_dev)
 
@@ -36,6 +37,7 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "MeshWeld", "mesh_weld", "mesh_weld_dev", "import_stl",
            "MeshOrient", "mesh_orient", "mesh_orient_dev", "flip_patches",
            "MeshFans", "mesh_fans", "mesh_fans_dev",
+           "MeshHoles", "mesh_holes", "mesh_holes_dev",
            "MeshIntersections", "mesh_intersections", "mesh_intersections_dev",
            "mesh_signed_distance", "mesh_signed_distance_dev",
            "_lib"]

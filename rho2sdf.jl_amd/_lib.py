@@ -241,6 +241,14 @@ SYMBOLS = [
     ("r2s_last_mesh_fans", ctypes.c_int, [c_int64_p, ctypes.c_int64, c_int64_p]),
     ("r2s_mesh_fans_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64,
                                          c_int64_p, c_int64_p, c_int64_p, _P]),
+    ("r2s_mesh_holes", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_int32_p,
+                                      c_float_p, ctypes.c_int64, ctypes.c_int64, c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_double_p,
+                                      c_int64_p]),
+    ("r2s_last_mesh_holes", ctypes.c_int, [c_int64_p, c_int64_p, c_double_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, c_int64_p,
+                                           c_int64_p]),
+    ("r2s_mesh_holes_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P,
+                                          ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_int64, c_int64_p, c_int64_p, c_int64_p, c_int64_p,
+                                          c_double_p, c_int64_p, _P]),
     ("r2s_mesh_index_intersections", ctypes.c_int, [_P, c_int32_p, c_int32_p, ctypes.c_int64, c_int64_p]),
     ("r2s_mesh_index_intersections_dev", ctypes.c_int, [_P, _P, _P, ctypes.c_int64, c_int64_p, _P]),
     ("r2s_mesh_intersections", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_int32, c_int32_p, c_int32_p,

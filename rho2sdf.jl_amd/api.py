@@ -1371,6 +1371,107 @@ def mesh_fans_dev(verts, tris, stream=None, *, split=False, capacity=0):
     return MeshFans(foc, fov, counts, tot, nv, vo[:nvo.value], to, vof[:nvo.value])
 
 
+class MeshHoles:
+    """The result of mesh_holes (include/rho2sdf_hip.h, r2s_mesh_holes): the RIMS of a mesh, the connected components of its
+    boundary half-edges.  `rim_start` (n + 1,) int64, `rim_edge` (m,) int32 (the half-edge id 3 t + c of every output position:
+    it runs from tris[t, c] to tris[t, (c + 1) % 3]; a closed rim is listed along its cycle from its smallest half-edge, any
+    other rim in ascending id), `counts` (n, 8) int64 (first half-edge, n_edges, n_nodes, open, flipped, branch nodes, status
+    0 not closed / 1 closed / 2 filled with one triangle / 3 filled with a fan, added vertex or -1), `sums` (n, 7) float64
+    (length, sum A x B, sum A about `ref_point`), `ref_point` (3,), `totals` (8,) int64 (rims, boundary half-edges, collapsed
+    triangles, nodes, open + flipped + branch nodes, closed rims, filled rims, added triangles).  With a fill also `verts`
+    (nv_out, 3) float32 and `tris` (nt_out, 3) int32, else None.  numpy arrays from mesh_holes; mesh_holes_dev keeps rim_edge,
+    verts and tris on the device.  Derived on the host: `closed`, `filled` masks, `length`, `area` (0.5 |sum A x B|, the area of
+    a closed rim's vector-area projection), `centroid` (ref_point + sum A / n_edges, the mean of a rim's FROM vertices) and
+    `watertight` (no boundary half-edge at all)."""
+
+    def __init__(self, rim_start, rim_edge, counts, sums, ref_point, totals, verts=None, tris=None):
+        self.rim_start, self.rim_edge, self.counts, self.sums = rim_start, rim_edge, counts, sums
+        self.ref_point, self.totals, self.verts, self.tris = ref_point, totals, verts, tris
+
+    n_rims = property(lambda s: len(s.counts))
+    first_edge = property(lambda s: s.counts[:, 0])
+    n_edges = property(lambda s: s.counts[:, 1])
+    closed = property(lambda s: s.counts[:, 6] >= 1)
+    filled = property(lambda s: s.counts[:, 6] >= 2)
+    length = property(lambda s: s.sums[:, 0])
+    area = property(lambda s: 0.5 * np.sqrt((s.sums[:, 1:4] ** 2).sum(-1)))
+    centroid = property(lambda s: s.ref_point[None, :] + s.sums[:, 4:7] / np.maximum(s.counts[:, 1:2], 1))
+    watertight = property(lambda s: bool(s.totals[1] == 0))
+
+    def __len__(self):
+        return len(self.counts)
+
+
+def mesh_holes(verts, tris, *, fill=None, device=-1):
+    """The rims (boundary loops and chains) of a triangle mesh (verts (nv, 3) float32, tris (nt, 3) int32, 0-based) -> MeshHoles.
+    A boundary half-edge is alone on its undirected edge; a rim is a connected component of them, CLOSED when every vertex on
+    it has one incoming and one outgoing boundary half-edge (then it is one simple loop: a hole).  fill=None reports only;
+    fill=-1 caps every closed rim, fill=k > 0 those of at most k edges, fill=0 none (the mesh is copied): a rim of three gets
+    one triangle, a longer one a new vertex at the mean of its vertices and a fan of n_edges triangles, wound against the
+    boundary so that every filled edge becomes a regular edge.  Rims that are not closed (a pinched boundary vertex, flipped
+    neighbours, a fin) are never filled: weld -> orient -> mesh_fans(split=True) first.  A fan cap of a rim that is far from
+    planar or not star-shaped can pass through the surface; mesh_intersections is the check."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    nr, nb, nvo, nto = (ctypes.c_int64() for _ in range(4))
+    tot, r = np.zeros(8, np.int64), np.zeros(3, np.float64)
+    ip = lambda a: a.ctypes.data_as(L.c_int32_p)   # noqa: E731
+    do_fill = fill is not None
+    vcap, tcap = (len(v) + 1024, len(t) + 4096) if do_fill else (0, 0)
+    while True:
+        vo, to = np.empty((max(vcap, 1), 3), np.float32), np.empty((max(tcap, 1), 3), np.int32)
+        L.check(L.lib().r2s_mesh_holes(_f(v) if len(v) else None, len(v), ip(t) if len(t) else None, len(t), int(device),
+                                       int(fill) if do_fill else 0, ip(to) if do_fill else None, _f(vo) if do_fill else None, vcap, tcap,
+                                       ctypes.byref(nr), ctypes.byref(nb), ctypes.byref(nvo), ctypes.byref(nto), _d(r), _i(tot)))
+        if not do_fill or (nvo.value <= vcap and nto.value <= tcap):
+            break
+        vcap, tcap = max(vcap, nvo.value), max(tcap, nto.value)
+    start, counts, sums = np.zeros(nr.value + 1, np.int64), np.empty((nr.value, 8), np.int64), np.empty((nr.value, 7), np.float64)
+    edge = np.empty(nb.value, np.int32)
+    if nr.value:
+        L.check(L.lib().r2s_last_mesh_holes(_i(start), _i(counts), _d(sums), nr.value, ip(edge), nb.value, ctypes.byref(nr), ctypes.byref(nb)))
+    if not do_fill:
+        return MeshHoles(start, edge, counts, sums, r, tot)
+    return MeshHoles(start, edge, counts, sums, r, tot, vo[:nvo.value].copy(), to[:nto.value].copy())
+
+
+def mesh_holes_dev(verts, tris, stream=None, *, fill=None, capacity=0, edge_capacity=0):
+    """mesh_holes on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous).  rim_start,
+    the records and the sums come back as numpy arrays; rim_edge and, with a fill, verts and tris stay device tensors.  The
+    library writes each group only into room for all of it: with more rims than `capacity`, more boundary half-edges than
+    `edge_capacity` or a fill that needs more than a little room, the call is made a second time."""
+    import torch
+    _mesh_tensors(verts, tris)
+    st = _stream(stream)
+    dev = verts.device
+    nv, nt = verts.numel() // 3, tris.numel() // 3
+    nr, nb, nvo, nto = (ctypes.c_int64() for _ in range(4))
+    tot, r = np.zeros(8, np.int64), np.zeros(3, np.float64)
+    do_fill = fill is not None
+    cap, ecap = int(capacity), int(edge_capacity)
+    vcap, tcap = (nv + 1024, nt + 4096) if do_fill else (0, 0)
+    vp = lambda x: ctypes.c_void_p(x.data_ptr()) if x.numel() else None   # noqa: E731
+    while True:
+        start = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        counts = torch.empty((cap, 8), dtype=torch.int64, device=dev)
+        sums = torch.empty((cap, 7), dtype=torch.float64, device=dev)
+        edge = torch.empty(ecap, dtype=torch.int32, device=dev)
+        vo = torch.empty((max(vcap, 1), 3), dtype=torch.float32, device=dev)
+        to = torch.empty((max(tcap, 1), 3), dtype=torch.int32, device=dev)
+        L.check(L.lib().r2s_mesh_holes_dev(vp(verts), nv, vp(tris), nt, int(fill) if do_fill else 0, vp(start) if cap else None, vp(counts),
+                                           vp(sums), cap, vp(edge), ecap, vp(to) if do_fill else None, vp(vo) if do_fill else None, vcap,
+                                           tcap, ctypes.byref(nr), ctypes.byref(nb), ctypes.byref(nvo), ctypes.byref(nto), _d(r), _i(tot), st))
+        if nr.value <= cap and nb.value <= ecap and (not do_fill or (nvo.value <= vcap and nto.value <= tcap)):
+            break
+        cap, ecap = max(cap, nr.value), max(ecap, nb.value)
+        if do_fill:
+            vcap, tcap = max(vcap, nvo.value), max(tcap, nto.value)
+    out = (start[:nr.value + 1].cpu().numpy(), edge[:nb.value], counts[:nr.value].cpu().numpy(), sums[:nr.value].cpu().numpy(), r, tot)
+    if not do_fill:
+        return MeshHoles(*out)
+    return MeshHoles(*out, vo[:nvo.value], to[:nto.value])
+
+
 class MeshSections:
     """The plane sections of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_sections): the raw tables and what follows from
     them.  Raw: `normal` (3,), `levels` (n_levels,), `contour_start` (n + 1,) int64, `counts` (n, 8) int64 (level, first segment id,
@@ -1871,7 +1972,8 @@ def export_stl(filename, verts, tris):
     return filename if filename.endswith(".stl") else filename + ".stl"
 
 
-def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_intersections=False, split_vertices=False):
+def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_intersections=False, split_vertices=False,
+               fill_holes=None):
     """The triangles of a binary or ASCII STL file -> (verts (nv, 3) float32, tris (nt, 3) int32).  weld=True (needs the GPU): the
     vertices that are the same point are merged by mesh_weld(soup, snap=snap) with its defaults (collapsed triangles and unused
     vertices dropped), so the mesh tools see shared vertices; weld=False: the soup as the file holds it, 3 nt vertices and
@@ -1882,11 +1984,16 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     the shells, the orientation, sections and thickness take for granted.  split_vertices=True (needs weld=True): after the weld,
     and after the orient if one is asked for, the vertices the weld left pinched (two bodies touching in a point) are split by
     mesh_fans(split=True), so that every vertex of the result has a single fan unless it lies on a non-manifold edge.
+    fill_holes=k (needs weld=True): after the weld, the orient and the split, the closed rims of the mesh are capped by
+    mesh_holes(fill=k): -1 every hole, k > 0 the holes of at most k edges.  The intersections are those of the filled mesh.
 
-    From an STL file to the signed-distance volume everything else here produces:
+    From an STL file to the signed-distance volume everything else here produces (the full repair recipe: weld -> orient ->
+    split pinched vertices -> fill holes -> check):
 
-        verts, tris, x = import_stl("part.stl", orient="outward", check_intersections=True)   # weld -> orient(outward)
-        assert len(x) == 0                                        # the surface does not pass through itself
+        verts, tris, x = import_stl("part.stl", orient="majority", split_vertices=True, fill_holes=-1, check_intersections=True)
+        assert len(x) == 0                                        # the surface, caps included, does not pass through itself
+        assert mesh_holes(verts, tris).watertight                 # no rim was left open (a fin, a non-manifold edge)
+        tris = mesh_orient(verts, tris, outward=True).tris        # the sign of a closed shell: outward
         grid = Grid(verts.min(0), verts.max(0), 128)              # 128 cells along the longest side, 3 cells of margin
         sdf = mesh_signed_distance(verts, tris, grid)             # (nz, ny, nx), positive inside
         exportSdfToVTI("part_sdf", grid, sdf, "distance")"""
@@ -1898,6 +2005,8 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
         raise L.R2SError("split_vertices needs weld=True: in a soup no vertex is shared")
     if check_intersections and not weld:
         raise L.R2SError("check_intersections needs weld=True: in a soup every neighbour touches under different indices")
+    if fill_holes is not None and not weld:
+        raise L.R2SError("fill_holes needs weld=True: in a soup every triangle is a hole of its own")
     m = L.R2SStlMesh()
     L.check(L.lib().r2s_import_stl(str(filename).encode(), ctypes.byref(m)))
     try:
@@ -1913,6 +2022,9 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     if split_vertices:
         f = mesh_fans(verts, tris, split=True, device=device)
         verts, tris = f.verts, f.tris
+    if fill_holes is not None:
+        h = mesh_holes(verts, tris, fill=int(fill_holes), device=device)
+        verts, tris = h.verts, h.tris
     if check_intersections:
         return verts, tris, mesh_intersections(verts, tris, device=device)
     return verts, tris

@@ -169,6 +169,10 @@ void release_orient_work();
 // frees the work buffers the fan calls keep per device; called by r2s_release_cache()
 void release_fans_work();
 
+// ---- mesh holes (r2s_mesh_holes.hip) ----------------------------------------------------------------------------------
+// frees the work buffers the hole calls keep per device; called by r2s_release_cache()
+void release_holes_work();
+
 // ---- mesh intersections (r2s_mesh_intersect.hip) ----------------------------------------------------------------------
 // frees the work buffers the intersection calls keep per device; called by r2s_release_cache()
 void release_intersect_work();

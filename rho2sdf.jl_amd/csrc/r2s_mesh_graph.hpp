@@ -1,6 +1,6 @@
-// What r2s_mesh_shells.hip, r2s_mesh_sections.hip, r2s_mesh_orient.hip and r2s_mesh_fans.hip share: the box of the vertices
-// behind the reference point, the collapsed-triangle test, the integer union-find with min-root, (shells, orient, fans) the
-// per-group integer counting and (orient, fans) the size of a run of sorted half-edges.  r2s_mesh_weld.hip takes the order-preserving bit pattern
+// What r2s_mesh_shells.hip, r2s_mesh_sections.hip, r2s_mesh_orient.hip, r2s_mesh_fans.hip and r2s_mesh_holes.hip share: the box
+// of the vertices behind the reference point, the collapsed-triangle test, the integer union-find with min-root, (shells, orient,
+// fans, holes) the per-group integer counting and (orient, fans, holes) the size of a run of sorted half-edges.  r2s_mesh_weld.hip takes the order-preserving bit pattern
 // of a float32 and the launch / bit-count helpers from here.  Everything has internal linkage: each file gets its own copy of
 // the kernel.
 #pragma once
@@ -90,7 +90,7 @@ __device__ inline void ms_union(uint32_t* L, uint32_t a, uint32_t b)
     }
 }
 
-// (orient, fans) the sorted half-edge keys are (min << 33) | (max << 1) | direction, the collapsed triangles' keys behind them.
+// (orient, fans, holes) the sorted half-edge keys are (min << 33) | (max << 1) | direction, the collapsed triangles' keys behind them.
 // The number of members of the run of sorted half-edge i, capped at 3 (i is a real half-edge: keys[i] < ckey)
 __device__ inline int ms_run_size(const uint64_t* __restrict__ keys, int64_t i, int64_t nh, bool& head)
 {

@@ -1,0 +1,826 @@
+// Mesh holes: the rims of a triangle mesh (its boundary loops and chains), per rim the integer record and the Float64 length /
+// area vector / vertex sum, and the fill that caps every selected closed rim (include/rho2sdf_hip.h, r2s_mesh_holes; DESIGN.md
+// "Mesh holes").  The sections' machinery on the boundary half-edges: the graph is on half-edges, the nodes are vertices.
+//   mh_key_kernel      one half-edge key per corner, the shells' keys, payload 3t + c -> rocPRIM radix sort of pairs
+//   mh_flag_kernel     a run of size one (ms_run_size) is a boundary half-edge: the flag goes to its half-edge id
+//   -> rocPRIM exclusive scan -> mh_compact_kernel: the boundary half-edges b = 0 .. n_b - 1 in ascending half-edge id
+//   mh_end_kernel      the two ends of every boundary half-edge, keyed by vertex (end 2b: FROM, outgoing; end 2b + 1: TO, incoming);
+//                      parent = successor = itself -> stable radix sort of the ends by vertex: a run is a node
+//   mh_link_kernel     every member of a run joins the member before it (the shells' union-find: the larger root under the smaller,
+//                      so a rim's root is its first half-edge); the head of a regular run writes the successor
+//   mh_flatten_kernel  parent = root, root flags -> scan: the roots in ascending half-edge id are the rim numbers
+//   mh_number_kernel   rim of every half-edge, first half-edge and n_edges of every rim;  mh_node_kernel: the runs again, the class
+//                      of every node counted into its rim
+//   mh_closed_kernel   closed flags, the longest closed rim (integer atomicMax), the totals, what the fill adds per rim
+//   -> two exclusive scans (added vertices, added triangles) -> mh_fill_kernel: status and added vertex of every rim
+//   mh_rank_init_kernel / mh_jump_kernel   distance to the first half-edge by pointer jumping, ping-pong buffers,
+//                      ceil(log2(longest closed rim)) rounds
+//   -> stable radix sort of the half-edges by rim -> mh_start_kernel -> mh_place_kernel: closed rims are laid out by rank, the
+//      others keep ascending half-edge id
+//   mh_sum_kernel      blocks of 256 output positions, the 7 terms of every half-edge, a segmented fixed tree in LDS, one partial
+//                      per (block, rim);  mh_combine_kernel: one wavefront per rim, as the sections'
+//   mh_apply_*         the fill: the added vertices and the added triangles (the input mesh is copied by the copy engine)
+// Integer counts use integer atomics; no floating-point atomic and no library reduction touches the Float64 sums.
+// Registers of the gfx950 build (hipcc -O3 -ffp-contract=off, -Rpass-analysis=kernel-resource-usage) are listed in DESIGN.md:
+// no kernel uses scratch.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "r2s_common.hpp"
+#include "r2s_internal.hpp"
+#include "r2s_mesh_graph.hpp"
+
+using namespace r2s_int;
+
+namespace {
+
+constexpr int MH_BLOCK = 256;   // output positions per block of the Float64 sums (the header's definition)
+constexpr int MH_NSUM = 7, MH_NCNT = 8;
+constexpr int64_t MH_MAX_TRIS = (((int64_t)1 << 31) - 1) / 3;   // 3 n_tris < 2^31: half-edge ids are int32
+// slots of the small device array: [0..5] the bounds, then
+constexpr int MH_COLLAPSED = 6, MH_NB = 7, MH_NRIMS = 8, MH_MAXLOOP = 9, MH_NODES = 10, MH_IRREGULAR = 11, MH_CLOSED = 12, MH_FILLED = 13,
+              MH_ADDT = 14, MH_ADDV = 15;
+constexpr int MH_SMALL = 16;
+// columns of the per-rim record
+constexpr int MH_FIRST = 0, MH_NEDGES = 1, MH_NNODES = 2, MH_STATUS = 6, MH_ADDED = 7;
+
+// one thread per triangle: its three half-edge keys, the collapsed count
+__global__ void __launch_bounds__(256) mh_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ vals, uint64_t* __restrict__ small)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool col = false;
+    if (t < n) {
+        int32_t i[3];
+        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
+            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
+            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
+            vals[3 * t + c] = (uint32_t)(3 * t + c);
+        }
+    }
+    const unsigned long long m = __ballot(col);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MH_COLLAPSED], (unsigned long long)__popcll(m));
+}
+
+// one thread per sorted half-edge: bflag[its id] = it is alone in its edge run (every id is written once)
+__global__ void __launch_bounds__(256) mh_flag_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
+                                                       uint64_t ckey, int32_t* __restrict__ bflag)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nh) return;
+    bool head = false;
+    bflag[vals[i]] = (keys[i] < ckey && ms_run_size(keys, i, nh, head) == 1) ? 1 : 0;
+}
+
+// bpos = the exclusive scan of bflag: the boundary half-edges in ascending id; n_b
+__global__ void __launch_bounds__(256) mh_compact_kernel(int64_t nh, const int32_t* __restrict__ bflag, const int32_t* __restrict__ bpos,
+                                                          uint32_t* __restrict__ bh, uint64_t* __restrict__ small)
+{
+    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (h >= nh) return;
+    const int32_t f = bflag[h], p = bpos[h];
+    if (f) bh[p] = (uint32_t)h;
+    if (h == nh - 1) small[MH_NB] = (uint64_t)(p + f);
+}
+
+// the vertices half-edge h runs from and to
+__device__ inline void mh_from_to(const int32_t* __restrict__ tris, uint32_t h, int32_t& from, int32_t& to)
+{
+    from = tris[h];
+    to = tris[h % 3u == 2u ? h - 2u : h + 1u];
+}
+
+// one thread per boundary half-edge b: its two ends keyed by vertex, parent[b] = succ[b] = b
+__global__ void __launch_bounds__(256) mh_end_kernel(const int32_t* __restrict__ tris, const uint32_t* __restrict__ bh, int64_t nb,
+                                                      uint32_t* __restrict__ ekey, uint32_t* __restrict__ eval, uint32_t* __restrict__ parent,
+                                                      uint32_t* __restrict__ succ)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nb) return;
+    int32_t from, to;
+    mh_from_to(tris, bh[b], from, to);
+    ekey[2 * b] = (uint32_t)from, eval[2 * b] = (uint32_t)(2 * b);
+    ekey[2 * b + 1] = (uint32_t)to, eval[2 * b + 1] = (uint32_t)(2 * b + 1);
+    parent[b] = (uint32_t)b;
+    succ[b] = (uint32_t)b;
+}
+
+// the class of the node whose run of sorted ends holds position i: 0 regular, 1 open, 2 flipped, 3 branch (valid at the head of
+// the run; the low bit of an end is its kind, 0 outgoing, 1 incoming)
+__device__ inline int mh_node_class(const uint32_t* __restrict__ ekey, const uint32_t* __restrict__ eval, int64_t i, int64_t n2, bool& head)
+{
+    const uint32_t v = ekey[i];
+    head = i == 0 || ekey[i - 1] != v;
+    const bool n1 = i + 1 < n2 && ekey[i + 1] == v, n2nd = n1 && i + 2 < n2 && ekey[i + 2] == v;
+    if (!n1) return 1;
+    if (n2nd) return 3;
+    return ((eval[i] ^ eval[i + 1]) & 1u) ? 0 : 2;
+}
+
+// one thread per sorted end: a member of a run joins the member before it, whatever the node's class; the head of a regular run
+// writes the successor of the incoming half-edge
+__global__ void __launch_bounds__(256) mh_link_kernel(const uint32_t* __restrict__ ekey, const uint32_t* __restrict__ eval, int64_t n2,
+                                                       uint32_t* parent, uint32_t* __restrict__ succ)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n2) return;
+    bool head = false;
+    const int cls = mh_node_class(ekey, eval, i, n2, head);
+    if (!head) {
+        ms_union(parent, eval[i - 1] >> 1, eval[i] >> 1);
+        return;
+    }
+    if (cls == 0) {
+        const uint32_t e0 = eval[i], e1 = eval[i + 1];
+        const uint32_t in = (e0 & 1u) ? e0 : e1, out = (e0 & 1u) ? e1 : e0;
+        succ[in >> 1] = out >> 1;
+    }
+}
+
+__global__ void __launch_bounds__(256) mh_flatten_kernel(int64_t nb, uint32_t* parent, int32_t* __restrict__ flag)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nb) return;
+    const uint32_t r = ms_find(parent, (uint32_t)b);
+    if (r != (uint32_t)b) atomicMin(&parent[b], r);
+    flag[b] = r == (uint32_t)b ? 1 : 0;
+}
+
+// num = the exclusive scan of flag: the rim of every half-edge, the sort pairs, first half-edge and n_edges of every rim; n_rims
+__global__ void __launch_bounds__(256) mh_number_kernel(int64_t nb, const uint32_t* __restrict__ parent, const int32_t* __restrict__ flag,
+                                                         const int32_t* __restrict__ num, const uint32_t* __restrict__ bh,
+                                                         uint32_t* __restrict__ skey, uint32_t* __restrict__ sval, int64_t* __restrict__ counts,
+                                                         uint64_t* __restrict__ small)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool active = b < nb;
+    int32_t rim = -1;
+    if (active) {
+        rim = num[parent[b]];   // (mh_flatten_kernel left parent = root)
+        skey[b] = (uint32_t)rim;
+        sval[b] = (uint32_t)b;
+        if (flag[b]) counts[(int64_t)rim * MH_NCNT + MH_FIRST] = (int64_t)bh[b];
+        if (b == nb - 1) small[MH_NRIMS] = (uint64_t)(num[b] + flag[b]);
+    }
+    const bool add[1] = {true};
+    ms_count<1, MH_NCNT>(active, rim, add, MH_NEDGES, counts);
+}
+
+// one thread per sorted end; the head of a run counts the node and its class into the rim of its half-edge
+__global__ void __launch_bounds__(256) mh_node_kernel(const uint32_t* __restrict__ ekey, const uint32_t* __restrict__ eval, int64_t n2,
+                                                       const uint32_t* __restrict__ skey, int64_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool head = false;
+    bool add[4] = {true, false, false, false};   // node, open, flipped, branch
+    int32_t rim = -1;
+    if (i < n2) {
+        const int cls = mh_node_class(ekey, eval, i, n2, head);
+        if (head) {
+            add[1] = cls == 1, add[2] = cls == 2, add[3] = cls == 3;
+            rim = (int32_t)skey[eval[i] >> 1];
+        }
+    }
+    ms_count<4, MH_NCNT>(head, rim, add, MH_NNODES, counts);
+}
+
+// one thread per possible rim c < n_b (n_rims is read on the device): closed flag, the longest closed rim, the totals, and what the
+// fill adds for the rim (0 beyond n_rims, so that the scans run over n_b entries)
+__global__ void __launch_bounds__(256) mh_closed_kernel(int64_t nb, int32_t fill, int64_t max_edges, int64_t* __restrict__ counts,
+                                                         int32_t* __restrict__ closed, int32_t* __restrict__ addv, int64_t* __restrict__ addt,
+                                                         uint64_t* __restrict__ small)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t nr = (int64_t)small[MH_NRIMS];
+    long long v[4] = {0, 0, 0, 0};   // nodes, irregular nodes, closed rims, filled rims
+    long long loop = 0;
+    if (c < nb) {
+        int32_t av = 0;
+        int64_t at = 0;
+        if (c < nr) {
+            int64_t* rec = counts + c * MH_NCNT;
+            const int64_t ne = rec[MH_NEDGES];
+            v[0] = rec[MH_NNODES];
+            v[1] = rec[3] + rec[4] + rec[5];
+            const bool cl = v[1] == 0;
+            closed[c] = cl ? 1 : 0;
+            v[2] = cl ? 1 : 0;
+            loop = cl ? ne : 0;
+            const bool sel = cl && fill && (max_edges < 0 || ne <= max_edges);
+            v[3] = sel ? 1 : 0;
+            av = sel && ne > 3 ? 1 : 0;
+            at = sel ? (ne > 3 ? ne : 1) : 0;
+            rec[MH_STATUS] = cl ? 1 : 0;
+            rec[MH_ADDED] = -1;
+        }
+        addv[c] = av;
+        addt[c] = at;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const long long o = __shfl_xor(loop, d, 64);
+        loop = o > loop ? o : loop;
+    }
+    if ((threadIdx.x & 63) == 0 && loop) atomicMax((unsigned long long*)&small[MH_MAXLOOP], (unsigned long long)loop);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d, 64);
+        if ((threadIdx.x & 63) == 0 && v[k]) atomicAdd((unsigned long long*)&small[MH_NODES + k], (unsigned long long)v[k]);
+    }
+}
+
+// voff / toff = the exclusive scans of addv / addt: status and added vertex of every selected rim, the added counts
+__global__ void __launch_bounds__(256) mh_fill_kernel(int64_t nb, int64_t n_verts, const int32_t* __restrict__ addv, const int32_t* __restrict__ voff,
+                                                       const int64_t* __restrict__ addt, const int64_t* __restrict__ toff,
+                                                       int64_t* __restrict__ counts, uint64_t* __restrict__ small)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nb) return;
+    if (addt[c] > 0) {
+        counts[c * MH_NCNT + MH_STATUS] = addv[c] ? 3 : 2;
+        counts[c * MH_NCNT + MH_ADDED] = addv[c] ? n_verts + (int64_t)voff[c] : -1;
+    }
+    if (c == nb - 1) {
+        small[MH_ADDV] = (uint64_t)((int64_t)voff[c] + addv[c]);
+        small[MH_ADDT] = (uint64_t)(toff[c] + addt[c]);
+    }
+}
+
+// (distance << 32) | pointer: a half-edge of a closed rim points at its successor at distance 1, the rim's first half-edge (its
+// root) and every half-edge of another rim at itself at distance 0
+__global__ void __launch_bounds__(256) mh_rank_init_kernel(int64_t nb, const uint32_t* __restrict__ skey, const int32_t* __restrict__ closed,
+                                                            const uint32_t* __restrict__ parent, const uint32_t* __restrict__ succ,
+                                                            uint64_t* __restrict__ pp)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nb) return;
+    const bool walks = closed[skey[b]] && parent[b] != (uint32_t)b;
+    pp[b] = walks ? ((1ull << 32) | (uint64_t)succ[b]) : (uint64_t)b;
+}
+
+// one round of pointer jumping from `in` to `out`
+__global__ void __launch_bounds__(256) mh_jump_kernel(int64_t nb, const uint64_t* __restrict__ in, uint64_t* __restrict__ out)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nb) return;
+    const uint64_t v = in[b], w = in[(uint32_t)v];
+    out[b] = (((v >> 32) + (w >> 32)) << 32) | (uint64_t)(uint32_t)w;
+}
+
+// start[c] = the first sorted position of rim c, start[n_rims] = n_b
+__global__ void __launch_bounds__(256) mh_start_kernel(const uint32_t* __restrict__ skey, int64_t nb, int64_t nr, int64_t* __restrict__ start)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nb) return;
+    const uint32_t c = skey[i];
+    if (i == 0 || skey[i - 1] != c) start[c] = i;
+    if (i == 0) start[nr] = nb;
+}
+
+// the output order: the stable sort left every rim in ascending half-edge id; a closed rim is laid out by rank instead
+// (rank 0 = its first half-edge, rank r = n - distance to it along the successors)
+__global__ void __launch_bounds__(256) mh_place_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval, int64_t nb,
+                                                        const int32_t* __restrict__ closed, const int64_t* __restrict__ counts,
+                                                        const int64_t* __restrict__ start, const uint64_t* __restrict__ pp,
+                                                        const uint32_t* __restrict__ bh, int32_t* __restrict__ rim_edge)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nb) return;
+    const uint32_t c = skey[i], b = sval[i];
+    int64_t pos = i;
+    if (closed[c]) {
+        const int64_t n = counts[(int64_t)c * MH_NCNT + MH_NEDGES], d = (int64_t)(pp[b] >> 32);
+        const int64_t rank = d ? n - d : 0;
+        if (rank < 0 || rank >= n) return;   // (cannot happen on a cycle; keeps the store inside the rim's range)
+        pos = start[c] + rank;
+    }
+    rim_edge[pos] = (int32_t)bh[b];
+}
+
+// block j: the output positions [256 j, 256 j + 256); the partial of (block j, rim c) goes to slot j + c (both only grow along
+// the output order, so the slots are distinct; there are fewer than blocks + rims of them)
+__global__ void __launch_bounds__(MH_BLOCK) mh_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
+                                                           const uint32_t* __restrict__ skey, const int32_t* __restrict__ rim_edge, int64_t nb,
+                                                           double rx, double ry, double rz, double* __restrict__ partial)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_v[MH_NSUM][MH_BLOCK];
+    __shared__ uint32_t s_key[MH_BLOCK];
+    const int j = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MH_BLOCK + j;
+    const bool active = i < nb;
+    uint32_t key = 0xffffffffu;
+    double v[MH_NSUM];
+#pragma unroll
+    for (int q = 0; q < MH_NSUM; ++q) v[q] = 0.0;
+    if (active) {
+        key = skey[i];
+        int32_t from, to;
+        mh_from_to(tris, (uint32_t)rim_edge[i], from, to);
+        const float *pa = verts + 3 * (int64_t)from, *pb = verts + 3 * (int64_t)to;
+        const double Ax = (double)pa[0] - rx, Ay = (double)pa[1] - ry, Az = (double)pa[2] - rz;
+        const double Bx = (double)pb[0] - rx, By = (double)pb[1] - ry, Bz = (double)pb[2] - rz;
+        const double Dx = Bx - Ax, Dy = By - Ay, Dz = Bz - Az;
+        v[0] = sqrt((Dx * Dx + Dy * Dy) + Dz * Dz);
+        v[1] = Ay * Bz - Az * By;
+        v[2] = Az * Bx - Ax * Bz;
+        v[3] = Ax * By - Ay * Bx;
+        v[4] = Ax, v[5] = Ay, v[6] = Az;
+    }
+    s_key[j] = key;
+#pragma unroll
+    for (int q = 0; q < MH_NSUM; ++q) s_v[q][j] = v[q];
+    __syncthreads();
+    const bool head = active && (j == 0 || s_key[j - 1] != key);
+#pragma unroll
+    for (int d = 1; d < MH_BLOCK; d <<= 1) {
+        const bool take = active && j + d < MH_BLOCK && s_key[j + d] == key;
+        double o[MH_NSUM];
+#pragma unroll
+        for (int q = 0; q < MH_NSUM; ++q) o[q] = take ? s_v[q][j + d] : 0.0;
+        __syncthreads();
+        if (take) {
+#pragma unroll
+            for (int q = 0; q < MH_NSUM; ++q) {
+                v[q] = v[q] + o[q];
+                s_v[q][j] = v[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (head) {
+        double* out = partial + ((int64_t)blockIdx.x + (int64_t)key) * MH_NSUM;
+#pragma unroll
+        for (int q = 0; q < MH_NSUM; ++q) out[q] = v[q];
+    }
+}
+
+// one wavefront per rim: lane l sums the l-th run of `chunk` consecutive block partials in ascending block order, then the run
+// sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while that lane has a run)
+__global__ void __launch_bounds__(256) mh_combine_kernel(const int64_t* __restrict__ start, int64_t nr, const double* __restrict__ partial,
+                                                          double* __restrict__ sums)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= nr) return;   // (the whole wavefront)
+    const int64_t lo_pos = start[c], end = start[c + 1];
+    const int64_t b0 = lo_pos / MH_BLOCK, nblk = (end - 1) / MH_BLOCK - b0 + 1;
+    const int64_t chunk = (nblk + 63) / 64;
+    const int m = (int)((nblk + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
+    double v[MH_NSUM];
+#pragma unroll
+    for (int q = 0; q < MH_NSUM; ++q) v[q] = 0.0;
+    if (lane < m) {
+        const int64_t lo = lane * chunk, hi = lo + chunk < nblk ? lo + chunk : nblk;
+        const double* p = partial + (b0 + lo + c) * MH_NSUM;
+#pragma unroll
+        for (int q = 0; q < MH_NSUM; ++q) v[q] = p[q];
+        for (int64_t b = lo + 1; b < hi; ++b) {
+            p += MH_NSUM;
+#pragma unroll
+            for (int q = 0; q < MH_NSUM; ++q) v[q] = v[q] + p[q];
+        }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (int q = 0; q < MH_NSUM; ++q) {
+            const double o = __shfl_down(v[q], d, 64);
+            if (lane + d < m) v[q] = v[q] + o;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < MH_NSUM; ++q) sums[c * MH_NSUM + q] = v[q];
+    }
+}
+
+// the fill, one thread per rim: the added vertex of a fan cap, per axis r + S / n_edges in double, rounded to float32
+__global__ void __launch_bounds__(256) mh_apply_vert_kernel(int64_t nr, const int64_t* __restrict__ counts, const double* __restrict__ sums,
+                                                             double rx, double ry, double rz, float* __restrict__ verts_out)
+{
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nr || counts[c * MH_NCNT + MH_STATUS] != 3) return;
+    const int64_t j = counts[c * MH_NCNT + MH_ADDED];
+    const double n = (double)counts[c * MH_NCNT + MH_NEDGES];
+    const double* S = sums + c * MH_NSUM + 4;
+    verts_out[3 * j] = (float)(rx + S[0] / n);
+    verts_out[3 * j + 1] = (float)(ry + S[1] / n);
+    verts_out[3 * j + 2] = (float)(rz + S[2] / n);
+}
+
+// the fill, one thread per output position: boundary half-edge a -> b of a fan cap adds (b, a, w); the first half-edge a -> b of
+// a filled rim of three, a -> b -> c -> a, adds (b, a, c)
+__global__ void __launch_bounds__(256) mh_apply_cap_kernel(const int32_t* __restrict__ tris, const uint32_t* __restrict__ skey,
+                                                            const int32_t* __restrict__ rim_edge, int64_t nb, const int64_t* __restrict__ counts,
+                                                            const int64_t* __restrict__ start, const int64_t* __restrict__ toff, int64_t n_tris,
+                                                            int32_t* __restrict__ tris_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nb) return;
+    const int64_t c = (int64_t)skey[i], status = counts[c * MH_NCNT + MH_STATUS], rank = i - start[c];
+    if (status < 2 || (status == 2 && rank != 0)) return;
+    int32_t a, b, third = (int32_t)counts[c * MH_NCNT + MH_ADDED];
+    mh_from_to(tris, (uint32_t)rim_edge[i], a, b);
+    if (status == 2) {
+        int32_t b2;
+        mh_from_to(tris, (uint32_t)rim_edge[i + 1], b2, third);   // (a rim of three: position i + 1 is inside it)
+    }
+    int32_t* out = tris_out + 3 * (n_tris + toff[c] + rank);
+    out[0] = b, out[1] = a, out[2] = third;
+}
+
+// work buffers of the hole calls, kept per device between calls (r2s_release_cache frees them)
+struct HoleWork {
+    DevBuf verts, tris, flag, small, keys, keys2, vals, vals2, temp, bflag, bpos, bh, ekey, ekey2, eval, eval2, parent, succ, rflag, num, skey,
+        skey2, sval, sval2, counts, closed, addv, voff, addt, toff, pp0, pp1, start, rim_edge, partial, sums, tris_out, verts_out;
+    void release()
+    {
+        DevBuf* all[] = {&verts, &tris, &flag, &small, &keys, &keys2, &vals, &vals2, &temp, &bflag, &bpos, &bh, &ekey, &ekey2, &eval, &eval2,
+                         &parent, &succ, &rflag, &num, &skey, &skey2, &sval, &sval2, &counts, &closed, &addv, &voff, &addt, &toff, &pp0, &pp1,
+                         &start, &rim_edge, &partial, &sums, &tris_out, &verts_out};
+        for (DevBuf* b : all) b->release();
+    }
+};
+std::mutex g_holes_mu;
+std::map<int, HoleWork> g_holes_work;
+
+struct HoleTables {
+    std::vector<int64_t> start;     // [n_rims + 1] (empty without rims)
+    std::vector<int64_t> counts;    // [n_rims][8]
+    std::vector<double> sums;       // [n_rims][7]
+    std::vector<int32_t> rim_edge;  // [n_b]
+};
+thread_local HoleTables g_last_holes;
+
+struct HoleSizes {
+    int64_t n_rims = 0, n_edges = 0, n_verts_out = 0, n_tris_out = 0;
+    double r[3] = {0.0, 0.0, 0.0};
+    int64_t totals[8] = {};
+};
+
+// The rims of the device mesh on the current device, after the work queued on `st`; synchronous.  Leaves the tables in w.start
+// [n_rims + 1], w.counts / w.sums [n_rims], w.rim_edge [n_b] and what holes_apply needs in w.skey2 / w.toff.
+int holes_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, bool fill, int64_t max_edges, hipStream_t st,
+               HoleWork& w, HoleSizes& out)
+{
+    uint64_t h_small[MH_SMALL] = {};
+    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
+    ENSURE(w.small, sizeof h_small);
+    uint64_t* small = w.small.as<uint64_t>();
+    HIP_TRY(hipMemcpyAsync(small, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
+    if (n_verts > 0) {
+        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, small);
+        HIP_TRY(hipGetLastError());
+    }
+    const int64_t nh = 3 * n;
+    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    size_t tb = 0, sb = 0, sb2 = 0;
+    if (n > 0) {
+        ENSURE(w.keys, sizeof(uint64_t) * (size_t)nh);
+        ENSURE(w.keys2, sizeof(uint64_t) * (size_t)nh);
+        ENSURE(w.vals, sizeof(uint32_t) * (size_t)nh);
+        ENSURE(w.vals2, sizeof(uint32_t) * (size_t)nh);
+        ENSURE(w.bflag, sizeof(int32_t) * (size_t)nh);
+        ENSURE(w.bpos, sizeof(int32_t) * (size_t)nh);
+        ENSURE(w.bh, sizeof(uint32_t) * (size_t)nh);
+        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
+        uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>();
+        int32_t *bflag = w.bflag.as<int32_t>(), *bpos = w.bpos.as<int32_t>();
+        mh_key_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ckey, keys, vals, small);
+        HIP_TRY(hipGetLastError());
+        const unsigned ebits = std::min(33u + ms_bits((uint64_t)n_verts), 64u);   // (the collapsed key included)
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
+        HIP_TRY(rocprim::exclusive_scan(nullptr, sb, bflag, bpos, (int32_t)0, (size_t)nh, rocprim::plus<int32_t>(), st));
+        ENSURE(w.temp, std::max<size_t>(std::max(tb, sb), 16));
+        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
+        mh_flag_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, bflag);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::exclusive_scan(w.temp.p, sb, bflag, bpos, (int32_t)0, (size_t)nh, rocprim::plus<int32_t>(), st));
+        mh_compact_kernel<<<ms_blocks(nh), 256, 0, st>>>(nh, bflag, bpos, w.bh.as<uint32_t>(), small);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ms_ref_point(h_small, n_verts, out.r);
+    const int64_t nb = (int64_t)h_small[MH_NB], n2 = 2 * nb;
+    int64_t nr = 0;
+    if (nb > 0) {
+        // n_rims <= n_b: everything per rim is sized for n_b of them, and the number of rims is read with the totals
+        const int64_t nblk = (nb + MH_BLOCK - 1) / MH_BLOCK;
+        ENSURE(w.ekey, sizeof(uint32_t) * (size_t)n2);
+        ENSURE(w.ekey2, sizeof(uint32_t) * (size_t)n2);
+        ENSURE(w.eval, sizeof(uint32_t) * (size_t)n2);
+        ENSURE(w.eval2, sizeof(uint32_t) * (size_t)n2);
+        ENSURE(w.parent, sizeof(uint32_t) * (size_t)nb);
+        ENSURE(w.succ, sizeof(uint32_t) * (size_t)nb);
+        ENSURE(w.rflag, sizeof(int32_t) * (size_t)nb);
+        ENSURE(w.num, sizeof(int32_t) * (size_t)nb);
+        ENSURE(w.skey, sizeof(uint32_t) * (size_t)nb);
+        ENSURE(w.skey2, sizeof(uint32_t) * (size_t)nb);
+        ENSURE(w.sval, sizeof(uint32_t) * (size_t)nb);
+        ENSURE(w.sval2, sizeof(uint32_t) * (size_t)nb);
+        ENSURE(w.counts, sizeof(int64_t) * MH_NCNT * (size_t)nb);
+        ENSURE(w.closed, sizeof(int32_t) * (size_t)nb);
+        ENSURE(w.addv, sizeof(int32_t) * (size_t)nb);
+        ENSURE(w.voff, sizeof(int32_t) * (size_t)nb);
+        ENSURE(w.addt, sizeof(int64_t) * (size_t)nb);
+        ENSURE(w.toff, sizeof(int64_t) * (size_t)nb);
+        ENSURE(w.pp0, sizeof(uint64_t) * (size_t)nb);
+        ENSURE(w.pp1, sizeof(uint64_t) * (size_t)nb);
+        ENSURE(w.start, sizeof(int64_t) * (size_t)(nb + 1));
+        ENSURE(w.rim_edge, sizeof(int32_t) * (size_t)nb);
+        ENSURE(w.partial, sizeof(double) * MH_NSUM * (size_t)(nblk + nb));
+        ENSURE(w.sums, sizeof(double) * MH_NSUM * (size_t)nb);
+        uint32_t *ekey = w.ekey.as<uint32_t>(), *ekey2 = w.ekey2.as<uint32_t>(), *eval = w.eval.as<uint32_t>(), *eval2 = w.eval2.as<uint32_t>();
+        uint32_t *parent = w.parent.as<uint32_t>(), *succ = w.succ.as<uint32_t>(), *bh = w.bh.as<uint32_t>();
+        uint32_t *skey = w.skey.as<uint32_t>(), *skey2 = w.skey2.as<uint32_t>(), *sval = w.sval.as<uint32_t>(), *sval2 = w.sval2.as<uint32_t>();
+        int32_t *rflag = w.rflag.as<int32_t>(), *num = w.num.as<int32_t>(), *closed = w.closed.as<int32_t>();
+        int32_t *addv = w.addv.as<int32_t>(), *voff = w.voff.as<int32_t>();
+        int64_t *addt = w.addt.as<int64_t>(), *toff = w.toff.as<int64_t>(), *counts = w.counts.as<int64_t>();
+        const unsigned vbits = ms_bits((uint64_t)n_verts);
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, ekey, ekey2, eval, eval2, (size_t)n2, 0u, vbits, st));
+        HIP_TRY(rocprim::exclusive_scan(nullptr, sb, rflag, num, (int32_t)0, (size_t)nb, rocprim::plus<int32_t>(), st));
+        HIP_TRY(rocprim::exclusive_scan(nullptr, sb2, addt, toff, (int64_t)0, (size_t)nb, rocprim::plus<int64_t>(), st));
+        ENSURE(w.temp, std::max<size_t>(std::max(tb, std::max(sb, sb2)), 16));
+        mh_end_kernel<<<ms_blocks(nb), 256, 0, st>>>(d_tris, bh, nb, ekey, eval, parent, succ);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, ekey, ekey2, eval, eval2, (size_t)n2, 0u, vbits, st));
+        mh_link_kernel<<<ms_blocks(n2), 256, 0, st>>>(ekey2, eval2, n2, parent, succ);
+        HIP_TRY(hipGetLastError());
+        mh_flatten_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, parent, rflag);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::exclusive_scan(w.temp.p, sb, rflag, num, (int32_t)0, (size_t)nb, rocprim::plus<int32_t>(), st));
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * MH_NCNT * (size_t)nb, st));
+        mh_number_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, parent, rflag, num, bh, skey, sval, counts, small);
+        HIP_TRY(hipGetLastError());
+        mh_node_kernel<<<ms_blocks(n2), 256, 0, st>>>(ekey2, eval2, n2, skey, counts);
+        HIP_TRY(hipGetLastError());
+        mh_closed_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, fill ? 1 : 0, max_edges, counts, closed, addv, addt, small);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::exclusive_scan(w.temp.p, sb, addv, voff, (int32_t)0, (size_t)nb, rocprim::plus<int32_t>(), st));
+        HIP_TRY(rocprim::exclusive_scan(w.temp.p, sb2, addt, toff, (int64_t)0, (size_t)nb, rocprim::plus<int64_t>(), st));
+        mh_fill_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, n_verts, addv, voff, addt, toff, counts, small);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        nr = (int64_t)h_small[MH_NRIMS];
+
+        // the round count comes from the longest closed rim the device found: 2^rounds >= that length
+        uint64_t *pin = w.pp0.as<uint64_t>(), *pout = w.pp1.as<uint64_t>();
+        mh_rank_init_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, skey, closed, parent, succ, pin);
+        HIP_TRY(hipGetLastError());
+        for (uint64_t reach = 1; reach < h_small[MH_MAXLOOP]; reach <<= 1) {
+            mh_jump_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, pin, pout);
+            HIP_TRY(hipGetLastError());
+            std::swap(pin, pout);
+        }
+        const unsigned rbits = ms_bits((uint64_t)nr);
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)nb, 0u, rbits, st));
+        ENSURE(w.temp, std::max<size_t>(tb, 16));
+        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)nb, 0u, rbits, st));
+        HIP_TRY(hipMemsetAsync(w.rim_edge.p, 0, sizeof(int32_t) * (size_t)nb, st));
+        mh_start_kernel<<<ms_blocks(nb), 256, 0, st>>>(skey2, nb, nr, w.start.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+        mh_place_kernel<<<ms_blocks(nb), 256, 0, st>>>(skey2, sval2, nb, closed, counts, w.start.as<int64_t>(), pin, bh, w.rim_edge.as<int32_t>());
+        HIP_TRY(hipGetLastError());
+        mh_sum_kernel<<<(unsigned)nblk, MH_BLOCK, 0, st>>>(d_verts, d_tris, skey2, w.rim_edge.as<int32_t>(), nb, out.r[0], out.r[1], out.r[2],
+                                                          w.partial.as<double>());
+        HIP_TRY(hipGetLastError());
+        mh_combine_kernel<<<(unsigned)((nr + 3) / 4), 256, 0, st>>>(w.start.as<int64_t>(), nr, w.partial.as<double>(), w.sums.as<double>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const int64_t addv = nb > 0 ? (int64_t)h_small[MH_ADDV] : 0, addt = nb > 0 ? (int64_t)h_small[MH_ADDT] : 0;
+    if (n_verts + addv > INT32_MAX)
+        return fail(R2S_ERR_UNSUPPORTED, "mesh_holes: the fill needs %lld vertices, beyond 32-bit indices", (long long)(n_verts + addv));
+    out.n_rims = nr, out.n_edges = nb, out.n_verts_out = n_verts + addv, out.n_tris_out = n + addt;
+    out.totals[0] = nr, out.totals[1] = nb, out.totals[2] = (int64_t)h_small[MH_COLLAPSED];
+    out.totals[3] = nb > 0 ? (int64_t)h_small[MH_NODES] : 0, out.totals[4] = nb > 0 ? (int64_t)h_small[MH_IRREGULAR] : 0;
+    out.totals[5] = nb > 0 ? (int64_t)h_small[MH_CLOSED] : 0, out.totals[6] = nb > 0 ? (int64_t)h_small[MH_FILLED] : 0, out.totals[7] = addt;
+    return 0;
+}
+
+// queues the filled mesh of the mesh holes_core has just analysed on `st`: the vertices when d_verts_out is given, the triangles
+// when d_tris_out is (room for n_verts_out / n_tris_out is the caller's business)
+int holes_apply(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, const HoleSizes& s, hipStream_t st, HoleWork& w,
+                int32_t* d_tris_out, float* d_verts_out)
+{
+    if (d_verts_out) {
+        if (n_verts > 0) HIP_TRY(hipMemcpyAsync(d_verts_out, d_verts, vert_bytes(n_verts), hipMemcpyDeviceToDevice, st));
+        if (s.n_verts_out > n_verts) {
+            mh_apply_vert_kernel<<<ms_blocks(s.n_rims), 256, 0, st>>>(s.n_rims, w.counts.as<int64_t>(), w.sums.as<double>(), s.r[0], s.r[1],
+                                                                     s.r[2], d_verts_out);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (d_tris_out) {
+        if (n > 0) HIP_TRY(hipMemcpyAsync(d_tris_out, d_tris, tri_bytes(n), hipMemcpyDeviceToDevice, st));
+        if (s.n_tris_out > n) {
+            mh_apply_cap_kernel<<<ms_blocks(s.n_edges), 256, 0, st>>>(d_tris, w.skey2.as<uint32_t>(), w.rim_edge.as<int32_t>(), s.n_edges,
+                                                                     w.counts.as<int64_t>(), w.start.as<int64_t>(), w.toff.as<int64_t>(), n,
+                                                                     d_tris_out);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
+{
+    if (!a || !b || !abytes || !bbytes) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+struct Span {
+    const void* p;
+    size_t bytes;
+};
+
+// the checks that need no device; *fill: the fill was asked for
+int holes_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tris, const void* tris_out, const void* verts_out,
+               int64_t vert_capacity, int64_t tri_capacity, const int64_t* n_rims, const int64_t* n_edges, const int64_t* n_verts_out,
+               const int64_t* n_tris_out, const double* ref_point, const int64_t* totals, const Span* tables, int n_tables, bool* fill)
+{
+    const int rc = mesh_args("mesh_holes", verts, n_verts, tris, n_tris);
+    if (rc) return rc;
+    if (n_tris > MH_MAX_TRIS) return fail(R2S_ERR_UNSUPPORTED, "mesh_holes: 3 * %lld half-edges reach 2^31", (long long)n_tris);
+    if (!n_rims || !n_edges || !n_verts_out || !n_tris_out || !ref_point || !totals)
+        return fail(R2S_ERR_ARG, "mesh_holes: null n_rims / n_edges / n_verts_out / n_tris_out / ref_point / totals");
+    if (vert_capacity < 0 || tri_capacity < 0) return fail(R2S_ERR_ARG, "mesh_holes: negative vert_capacity / tri_capacity");
+    *fill = tris_out || verts_out;
+    if (*fill && (!tris_out || !verts_out)) return fail(R2S_ERR_ARG, "mesh_holes: the fill needs tris_out and verts_out together");
+    const Span in[2] = {{verts, vert_bytes(n_verts)}, {tris, tri_bytes(n_tris)}};
+    const Span out[2] = {{tris_out, tri_bytes(tri_capacity)}, {verts_out, vert_bytes(vert_capacity)}};
+    for (const auto& i : in) {
+        for (const auto& o : out)
+            if (overlaps(o.p, o.bytes, i.p, i.bytes)) return fail(R2S_ERR_ARG, "mesh_holes: an output overlaps an input");
+        for (int k = 0; k < n_tables; ++k)
+            if (overlaps(tables[k].p, tables[k].bytes, i.p, i.bytes)) return fail(R2S_ERR_ARG, "mesh_holes: an output overlaps an input");
+    }
+    return 0;
+}
+
+int table_args(const char* who, const void* start, const void* counts, const void* sums, int64_t rim_capacity, const void* rim_edge,
+               int64_t edge_capacity)
+{
+    if (rim_capacity < 0 || edge_capacity < 0 || (rim_capacity > 0 && (!start || !counts || !sums)) || (edge_capacity > 0 && !rim_edge))
+        return fail(R2S_ERR_ARG, "%s: null tables or a negative capacity", who);
+    return 0;
+}
+
+HoleWork* holes_work_of_current_device(int& rc)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
+        return nullptr;
+    }
+    rc = 0;
+    return &g_holes_work[dev];
+}
+
+void holes_return(const HoleSizes& s, int64_t* n_rims, int64_t* n_edges, int64_t* n_verts_out, int64_t* n_tris_out, double ref_point[3],
+                  int64_t totals[8])
+{
+    *n_rims = s.n_rims, *n_edges = s.n_edges, *n_verts_out = s.n_verts_out, *n_tris_out = s.n_tris_out;
+    std::memcpy(ref_point, s.r, sizeof s.r);
+    std::memcpy(totals, s.totals, sizeof s.totals);
+}
+
+}  // namespace
+
+namespace r2s_int {
+
+void release_holes_work()
+{
+    std::lock_guard<std::mutex> lock(g_holes_mu);
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+    for (auto& kv : g_holes_work) {
+        (void)hipSetDevice(kv.first);
+        kv.second.release();
+    }
+    g_holes_work.clear();
+    if (cur >= 0) (void)hipSetDevice(cur);
+    (void)hipGetLastError();
+}
+
+}  // namespace r2s_int
+
+extern "C" {
+
+int r2s_mesh_holes(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, int32_t device, int64_t max_edges,
+                   int32_t* tris_out, float* verts_out, int64_t vert_capacity, int64_t tri_capacity, int64_t* n_rims, int64_t* n_edges,
+                   int64_t* n_verts_out, int64_t* n_tris_out, double ref_point[3], int64_t totals[8])
+{
+    bool fill = false;
+    int rc = holes_args(verts, n_verts, tris, n_tris, tris_out, verts_out, vert_capacity, tri_capacity, n_rims, n_edges, n_verts_out,
+                        n_tris_out, ref_point, totals, nullptr, 0, &fill);
+    if (rc) return rc;
+    if ((rc = check_mesh_host("mesh_holes", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
+    std::lock_guard<std::mutex> lock(g_holes_mu);
+    HoleWork* w = holes_work_of_current_device(rc);
+    if (rc) return rc;
+    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
+    HoleSizes s;
+    if ((rc = holes_core(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, fill, max_edges, nullptr, *w, s))) return rc;
+    const bool vroom = fill && vert_capacity >= s.n_verts_out, troom = fill && tri_capacity >= s.n_tris_out;
+    if (vroom) ENSURE(w->verts_out, vert_bytes(std::max<int64_t>(s.n_verts_out, 1)));
+    if (troom) ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(s.n_tris_out, 1)));
+    if ((vroom || troom) && (rc = holes_apply(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, s, nullptr, *w,
+                                              troom ? w->tris_out.as<int32_t>() : nullptr, vroom ? w->verts_out.as<float>() : nullptr)))
+        return rc;
+    HoleTables tab;
+    if (s.n_rims > 0) {
+        tab.start.resize((size_t)s.n_rims + 1);
+        tab.counts.resize((size_t)s.n_rims * MH_NCNT);
+        tab.sums.resize((size_t)s.n_rims * MH_NSUM);
+        tab.rim_edge.resize((size_t)s.n_edges);
+        HIP_TRY(hipMemcpy(tab.start.data(), w->start.p, sizeof(int64_t) * tab.start.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tab.sums.data(), w->sums.p, sizeof(double) * tab.sums.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tab.rim_edge.data(), w->rim_edge.p, sizeof(int32_t) * tab.rim_edge.size(), hipMemcpyDeviceToHost));
+    }
+    if (vroom && s.n_verts_out > 0) HIP_TRY(hipMemcpy(verts_out, w->verts_out.p, vert_bytes(s.n_verts_out), hipMemcpyDeviceToHost));
+    if (troom && s.n_tris_out > 0) HIP_TRY(hipMemcpy(tris_out, w->tris_out.p, tri_bytes(s.n_tris_out), hipMemcpyDeviceToHost));
+    g_last_holes = std::move(tab);
+    holes_return(s, n_rims, n_edges, n_verts_out, n_tris_out, ref_point, totals);
+    return 0;
+}
+
+int r2s_last_mesh_holes(int64_t* rim_start_out, int64_t* counts_out, double* sums_out, int64_t rim_capacity, int32_t* rim_edge_out,
+                        int64_t edge_capacity, int64_t* n_rims, int64_t* n_edges)
+{
+    if (!n_rims || !n_edges) return fail(R2S_ERR_ARG, "last_mesh_holes: null n_rims / n_edges");
+    const int rc = table_args("last_mesh_holes", rim_start_out, counts_out, sums_out, rim_capacity, rim_edge_out, edge_capacity);
+    if (rc) return rc;
+    const HoleTables& t = g_last_holes;
+    const int64_t nr = (int64_t)(t.counts.size() / MH_NCNT), nb = (int64_t)t.rim_edge.size();
+    const int64_t mr = std::min(rim_capacity, nr), mb = std::min(edge_capacity, nb);
+    *n_rims = nr;
+    *n_edges = nb;
+    if (mr > 0) {
+        std::memcpy(rim_start_out, t.start.data(), sizeof(int64_t) * (size_t)(mr + 1));
+        std::memcpy(counts_out, t.counts.data(), sizeof(int64_t) * MH_NCNT * (size_t)mr);
+        std::memcpy(sums_out, t.sums.data(), sizeof(double) * MH_NSUM * (size_t)mr);
+    }
+    if (mb > 0) std::memcpy(rim_edge_out, t.rim_edge.data(), sizeof(int32_t) * (size_t)mb);
+    return 0;
+}
+
+int r2s_mesh_holes_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n_tris, int64_t max_edges, int64_t* d_rim_start,
+                       int64_t* d_counts, double* d_sums, int64_t rim_capacity, int32_t* d_rim_edge, int64_t edge_capacity,
+                       int32_t* d_tris_out, float* d_verts_out, int64_t vert_capacity, int64_t tri_capacity, int64_t* n_rims,
+                       int64_t* n_edges, int64_t* n_verts_out, int64_t* n_tris_out, double ref_point[3], int64_t totals[8], void* stream)
+{
+    bool fill = false;
+    int rc = table_args("mesh_holes", d_rim_start, d_counts, d_sums, rim_capacity, d_rim_edge, edge_capacity);
+    if (rc) return rc;
+    const Span tables[4] = {{d_rim_start, sizeof(int64_t) * ((size_t)rim_capacity + 1)},
+                            {d_counts, sizeof(int64_t) * MH_NCNT * (size_t)rim_capacity},
+                            {d_sums, sizeof(double) * MH_NSUM * (size_t)rim_capacity},
+                            {d_rim_edge, sizeof(int32_t) * (size_t)edge_capacity}};
+    if ((rc = holes_args(d_verts, n_verts, d_tris, n_tris, d_tris_out, d_verts_out, vert_capacity, tri_capacity, n_rims, n_edges, n_verts_out,
+                         n_tris_out, ref_point, totals, tables, rim_capacity > 0 || edge_capacity > 0 ? 4 : 0, &fill)))
+        return rc;
+    if ((rc = check_device(0))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g_holes_mu);
+    HoleWork* w = holes_work_of_current_device(rc);
+    if (rc) return rc;
+    if ((rc = check_mesh_dev("mesh_holes", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
+    HoleSizes s;
+    if ((rc = holes_core(d_verts, n_verts, d_tris, n_tris, fill, max_edges, st, *w, s))) return rc;
+    if (s.n_rims > 0 && rim_capacity >= s.n_rims) {
+        HIP_TRY(hipMemcpyAsync(d_rim_start, w->start.p, sizeof(int64_t) * (size_t)(s.n_rims + 1), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MH_NCNT * (size_t)s.n_rims, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_sums, w->sums.p, sizeof(double) * MH_NSUM * (size_t)s.n_rims, hipMemcpyDeviceToDevice, st));
+    }
+    if (s.n_edges > 0 && edge_capacity >= s.n_edges)
+        HIP_TRY(hipMemcpyAsync(d_rim_edge, w->rim_edge.p, sizeof(int32_t) * (size_t)s.n_edges, hipMemcpyDeviceToDevice, st));
+    const bool vroom = fill && vert_capacity >= s.n_verts_out, troom = fill && tri_capacity >= s.n_tris_out;
+    if ((vroom || troom) &&
+        (rc = holes_apply(d_verts, n_verts, d_tris, n_tris, s, st, *w, troom ? d_tris_out : nullptr, vroom ? d_verts_out : nullptr)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    holes_return(s, n_rims, n_edges, n_verts_out, n_tris_out, ref_point, totals);
+    return 0;
+}
+
+}  // extern "C"

@@ -3441,6 +3441,7 @@ void r2s_release_cache(void)
     r2s_int::release_weld_work();
     r2s_int::release_orient_work();
     r2s_int::release_fans_work();
+    r2s_int::release_holes_work();
     r2s_int::release_intersect_work();
     r2s_int::release_host_sessions();
 }

@@ -730,6 +730,71 @@ function mesh_fans_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cv
     return n[], nvo[], totals
 end
 
+# The rims (boundary loops and chains) of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_holes): verts 3 x nv Float32, tris
+# 3 x nt 1-based.  A rim is a connected component of the boundary half-edges, closed when every vertex on it has one incoming and
+# one outgoing boundary half-edge.  fill = nothing reports only; fill = -1 caps every closed rim, fill = k > 0 those of at most k
+# edges (a rim of three gets one triangle, a longer one a new vertex at the mean of its vertices and a fan).  Rims that are not
+# closed are never filled: weld, orient and split the pinched vertices (mesh_fans_hip) first.
+# -> (rim_start (0-based offsets, n + 1), rim_edge (0-based half-edge id 3 (t - 1) + (c - 1) per output position), counts 8 x n
+# Int64 (first half-edge 0-based, n_edges, n_nodes, open, flipped, branch nodes, status 0 not closed / 1 closed / 2 one triangle /
+# 3 fan, added vertex 1-based or 0), sums 7 x n (length, sum A x B, sum A about ref_point), ref_point, totals (rims, boundary
+# half-edges, collapsed, nodes, irregular nodes, closed rims, filled rims, added triangles) and, with a fill, verts 3 x nv_out and
+# tris 3 x nt_out 1-based)
+function mesh_holes_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}; fill::Union{Nothing, Integer} = nothing,
+                        device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    t0 = Int32.(tris) .- Int32(1)
+    nv = size(verts, 2); nt = size(t0, 2)
+    nr = Ref{Int64}(0); nb = Ref{Int64}(0); nvo = Ref{Int64}(0); nto = Ref{Int64}(0)
+    r = zeros(Float64, 3); totals = zeros(Int64, 8)
+    dofill = fill !== nothing
+    vcap = dofill ? nv + 1024 : 0; tcap = dofill ? nt + 4096 : 0
+    while true
+        vout = Matrix{Float32}(undef, 3, max(vcap, 1)); tout = Matrix{Int32}(undef, 3, max(tcap, 1))
+        check(ccall((:r2s_mesh_holes, LIB[]), Cint,
+                    (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Int32, Int64, Ptr{Int32}, Ptr{Float32}, Int64, Int64, Ptr{Int64}, Ptr{Int64},
+                     Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                    Matrix(verts), nv, t0, nt, Int32(device), Int64(dofill ? fill : 0), dofill ? tout : C_NULL, dofill ? vout : C_NULL,
+                    Int64(vcap), Int64(tcap), nr, nb, nvo, nto, r, totals))
+        if !dofill || (nvo[] <= vcap && nto[] <= tcap)
+            base = merge(last_mesh_holes_hip(nr[], nb[]), (ref_point = r, totals = totals))
+            return dofill ? merge(base, (verts = vout[:, 1:nvo[]], tris = tout[:, 1:nto[]] .+ Int32(1))) : base
+        end
+        vcap = max(vcap, nvo[]); tcap = max(tcap, nto[])
+    end
+end
+
+# the calling thread's last rim tables (r2s_last_mesh_holes); the added vertex is made 1-based (0: none)
+function last_mesh_holes_hip(rim_capacity::Integer, edge_capacity::Integer)
+    start = zeros(Int64, rim_capacity + 1); counts = Matrix{Int64}(undef, 8, rim_capacity); sums = Matrix{Float64}(undef, 7, rim_capacity)
+    edge = Vector{Int32}(undef, edge_capacity)
+    nr = Ref{Int64}(0); nb = Ref{Int64}(0)
+    check(ccall((:r2s_last_mesh_holes, LIB[]), Cint, (Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int64}),
+                rim_capacity == 0 ? C_NULL : start, rim_capacity == 0 ? C_NULL : counts, rim_capacity == 0 ? C_NULL : sums,
+                Int64(rim_capacity), edge_capacity == 0 ? C_NULL : edge, Int64(edge_capacity), nr, nb))
+    counts[8, :] .+= 1
+    return (rim_start = start, rim_edge = edge, counts = counts, sums = sums)
+end
+
+# the same on device arrays of the current device (raw pointers, e.g. of AMDGPU.jl ROCArrays); each group is written only when its
+# capacity holds all of it: d_rim_start (rim_capacity + 1), d_counts, d_sums / d_rim_edge / d_verts_out / d_tris_out (both or
+# C_NULL: no fill) -> (n_rims, n_edges, n_verts_out, n_tris_out, ref_point, totals); indices stay 0-based
+function mesh_holes_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer, max_edges::Integer,
+                            d_rim_start::Ptr{Cvoid}, d_counts::Ptr{Cvoid}, d_sums::Ptr{Cvoid}, rim_capacity::Integer,
+                            d_rim_edge::Ptr{Cvoid}, edge_capacity::Integer, d_tris_out::Ptr{Cvoid} = C_NULL,
+                            d_verts_out::Ptr{Cvoid} = C_NULL, vert_capacity::Integer = 0, tri_capacity::Integer = 0;
+                            stream::Ptr{Cvoid} = C_NULL)
+    nr = Ref{Int64}(0); nb = Ref{Int64}(0); nvo = Ref{Int64}(0); nto = Ref{Int64}(0)
+    r = zeros(Float64, 3); totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_holes_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid},
+                 Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), Int64(max_edges), d_rim_start, d_counts, d_sums, Int64(rim_capacity),
+                d_rim_edge, Int64(edge_capacity), d_tris_out, d_verts_out, Int64(vert_capacity), Int64(tri_capacity), nr, nb, nvo, nto, r,
+                totals, stream))
+    return nr[], nb[], nvo[], nto[], r, totals
+end
+
 # The self-intersections of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_index_intersections): the pairs of triangles that
 # intersect or touch.  Coplanar overlap is not reported; contact counts (a vertex on a face, equal coordinates under different
 # indices), so weld a soup first.  -> (pairs 2 x n Int32, 1-based, s < t, ascending by (s, t); hits_of_tri, the number of pairs
@@ -872,13 +937,17 @@ end
 # orient = nothing: the windings as the file holds them; :majority or :outward (needs weld = true): the welded triangles go
 # through mesh_orient_hip (see there for the rules and the caveat about enclosed voids).  check_intersections = true (needs
 # weld = true): -> (verts, tris, mesh_intersections_hip of the mesh as returned).  split_vertices = true (needs weld = true): the
-# vertices the weld left pinched are split by mesh_fans_hip(split = true), after the orient if one is asked for.
+# vertices the weld left pinched are split by mesh_fans_hip(split = true), after the orient if one is asked for.  fill_holes = k
+# (needs weld = true): after that the closed rims are capped by mesh_holes_hip(fill = k), -1 every hole, k > 0 those of at most
+# k edges; the intersections are those of the filled mesh.
 function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real = 0.0, device::Integer = -1,
-                        orient::Union{Nothing,Symbol} = nothing, check_intersections::Bool = false, split_vertices::Bool = false)
+                        orient::Union{Nothing,Symbol} = nothing, check_intersections::Bool = false, split_vertices::Bool = false,
+                        fill_holes::Union{Nothing,Integer} = nothing)
     orient === nothing || orient in (:majority, :outward) || error("orient must be nothing, :majority or :outward")
     orient === nothing || weld || error("orient needs weld = true")
     !split_vertices || weld || error("split_vertices needs weld = true")
     !check_intersections || weld || error("check_intersections needs weld = true")
+    fill_holes === nothing || weld || error("fill_holes needs weld = true")
     m = R2SStlMesh(0, C_NULL)
     check(ccall((:r2s_import_stl, LIB[]), Cint, (Cstring, Ref{R2SStlMesh}), filename, m))
     soup = copy(unsafe_wrap(Array, m.verts, (3, 3 * Int(m.n_tris))))
@@ -890,6 +959,10 @@ function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real 
     if split_vertices
         f = mesh_fans_hip(verts, tris; split = true, device = device)
         verts, tris = f.verts, f.tris
+    end
+    if fill_holes !== nothing
+        h = mesh_holes_hip(verts, tris; fill = fill_holes, device = device)
+        verts, tris = h.verts, h.tris
     end
     check_intersections || return verts, tris
     return verts, tris, mesh_intersections_hip(verts, tris; device = device)
