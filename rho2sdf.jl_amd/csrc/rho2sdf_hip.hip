@@ -882,6 +882,94 @@ __device__ __forceinline__ uint32_t tile_count(const int lo[3], const int hi[3])
 {
     return (uint32_t)(hi[0] - lo[0] + 1) * (uint32_t)(hi[1] - lo[1] + 1) * (uint32_t)(hi[2] - lo[2] + 1);
 }
+__device__ __forceinline__ void tile_xyz(const int lo[3], const int hi[3], uint32_t q, int& tx, int& ty, int& tz)
+{
+    const uint32_t n0 = (uint32_t)(hi[0] - lo[0] + 1), n1 = (uint32_t)(hi[1] - lo[1] + 1);
+    const uint32_t z = q / (n0 * n1), r = q - z * (n0 * n1), y = r / n0;
+    tx = lo[0] + (int)(r - y * n0);
+    ty = lo[1] + (int)y;
+    tz = lo[2] + (int)z;
+}
+
+// lattice box of an element's inverse maps in the HEX8 sign pass (sign_box_kernel, sign_project_kernel)
+struct alignas(16) SignBox {
+    int32_t lo[3];    // first lattice index per axis (Z: local plane of the slab)
+    int32_t dim[3];   // 0 in any axis = no box (element irrelevant for the sign pass)
+    double rmax;      // max nodal density (SignDetection.jl:33-36): all the ordered gather needs of an element
+};
+
+// ---- what the gather needs of a (tile, list entry) pair, written when the lists are sorted ----------------
+// The 64 voxels of a tile differ only by their 4x4x4 position, so "is this voxel inside the entry's range" is a
+// product of three 4-bit masks: bit p of axis ax (bit 4 ax + p of the word) is set when the voxel plane 4 t_ax + p of
+// the tile passes the test the reference applies on that axis (Z: LOCAL planes of the slab, as everywhere in the
+// tile numbering).  The gather broadcasts the words of an entry and tests its own three bits (gather_lane_bits).
+//   band entry: x = storage chunk of the tile inside the item's result array (iso items; tile_chunk), y = kind << 12 | mask
+//   sign entry (HEX8): x = storage chunk inside the element's inverse-map results, y = mask, z/w = rmax (lo, hi word)
+#define ENT_MASK_BITS 12
+__host__ __device__ __forceinline__ uint32_t gather_lane_bits(int lane)
+{
+    return (1u << (lane & 3)) | (1u << (4 + ((lane >> 2) & 3))) | (1u << (8 + (lane >> 4)));
+}
+__host__ __device__ __forceinline__ bool entry_mask_hits(uint32_t m)   // some voxel position passes on all three axes
+{
+    return (m & 0xfu) && (m & 0xf0u) && (m & 0xf00u);
+}
+// band: the cell index (Grid.jl:58) of the voxel's coordinate lies in the item's cell box [imin, imax]
+__device__ __forceinline__ uint32_t band_entry_mask(const GridDev& g, const SlabInfo& s, const int32_t imin[3],
+                                                    const int32_t imax[3], int tx, int ty, int tz)
+{
+    const int t[3] = {tx, ty, tz};
+    uint32_t m = 0;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int l = 4 * t[ax] + p;
+            const int c = (int)cell_of(g, ax, grid_coord(g, ax, ax == 2 ? slab_global_k(s, l) : l));
+            if (c >= imin[ax] && c <= imax[ax]) m |= 1u << (4 * ax + p);
+        }
+    return m;
+}
+// sign (HEX8): the lattice index lies in the element's box [lo, lo + dim)
+__device__ __forceinline__ uint32_t sign_entry_mask(const int32_t lo[3], const int32_t dim[3], int tx, int ty, int tz)
+{
+    const int t[3] = {tx, ty, tz};
+    uint32_t m = 0;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if ((uint32_t)(4 * t[ax] + p - lo[ax]) < (uint32_t)dim[ax]) m |= 1u << (4 * ax + p);
+    return m;
+}
+// the words of one entry, made in the write-out of the list sort (bin_sort_*_kernel), where tile and id are both at hand
+struct BandEntryMaker {
+    typedef uint2 Out;
+    const BandItem* items;
+    GridDev g;
+    __device__ __forceinline__ uint2 operator()(uint32_t it, const SlabInfo& s, int tx, int ty, int tz) const
+    {
+        const BandItem& T = items[it];
+        const uint32_t kind = (uint32_t)T.kind;
+        const uint32_t m = band_entry_mask(g, s, T.imin, T.imax, tx, ty, tz);
+        // (no voxel of the tile in range: the chunk is never looked up, and the tile may lie outside the item's tile box)
+        const uint32_t chunk = (kind == 0 && entry_mask_hits(m)) ? tile_chunk(T.store_off, tile_box(T.lo, T.dim), tx, ty, tz) : 0u;
+        return make_uint2(chunk, (kind << ENT_MASK_BITS) | m);
+    }
+};
+struct SignEntryMaker {
+    typedef uint4 Out;
+    const SignBox* sbox;
+    const uint32_t* s_store_off;
+    __device__ __forceinline__ uint4 operator()(uint32_t el, const SlabInfo&, int tx, int ty, int tz) const
+    {
+        const SignBox B = sbox[el];
+        // (the tile range of the list is wider by one than the element's exact box: such entries get an empty mask)
+        const uint32_t m = sign_entry_mask(B.lo, B.dim, tx, ty, tz);
+        const uint32_t chunk = entry_mask_hits(m) ? tile_chunk(s_store_off[el], tile_box(B.lo, B.dim), tx, ty, tz) : 0u;
+        return make_uint4(chunk, m, (uint32_t)__double2loint(B.rmax), (uint32_t)__double2hiint(B.rmax));
+    }
+};
 
 template <bool FILL>
 __global__ void band_bin_kernel(const BandItem* __restrict__ items, uint32_t nitems, GridDev g, SlabInfo s,
@@ -920,14 +1008,6 @@ __device__ __forceinline__ bool tile_clear_of(const TetRec& E, const GridDev& g,
         clear = clear || (t - r > E.fo[f]);
     }
     return clear;
-}
-__device__ __forceinline__ void tile_xyz(const int lo[3], const int hi[3], uint32_t q, int& tx, int& ty, int& tz)
-{
-    const uint32_t n0 = (uint32_t)(hi[0] - lo[0] + 1), n1 = (uint32_t)(hi[1] - lo[1] + 1);
-    const uint32_t z = q / (n0 * n1), r = q - z * (n0 * n1), y = r / n0;
-    tx = lo[0] + (int)(r - y * n0);
-    ty = lo[1] + (int)y;
-    tz = lo[2] + (int)z;
 }
 
 // a voxel is only examined when some candidate reaches rho_t (SignDetection.jl:36): tiles whose lists
@@ -1512,11 +1592,7 @@ __global__ void __launch_bounds__(256) iso_sweep_kernel(const BandItem* __restri
 // inverse map for each (SignDetection.jl:27-70).  Here the inverse maps are computed element-major
 // (sign_project_kernel: element record in SGPRs, lanes = lattice points of the element's AABB box, dense
 // lanes) into `sres`, and the ordered per-voxel state machine (sdf_tiles_kernel) only looks them up.
-struct alignas(16) SignBox {
-    int32_t lo[3];    // first lattice index per axis (Z: local plane of the slab)
-    int32_t dim[3];   // 0 in any axis = no box (element irrelevant for the sign pass)
-    double rmax;      // max nodal density (SignDetection.jl:33-36): all the ordered gather needs of an element
-};
+// (struct SignBox: with the tile binning, whose list sort reads the boxes)
 
 // lattice indices i with mn <= grid_coord(i) <= mx: exactly the reference's AABB comparisons
 __device__ __forceinline__ bool coord_range(const GridDev& g, int ax, double mn, double mx, int nmax, int& a, int& b)
@@ -1773,11 +1849,16 @@ __global__ void __launch_bounds__(256) active_tiles_kernel(const uint32_t* __res
 
 // short lists (<= 64 entries): SORT_LANES lanes per active tile, rank sort (every lane ranks every SORT_LANES-th
 // entry; the lanes of a group read the same addresses in the inner loop)
+// The write-out also makes the words the gather reads of the entry (`make`: BandEntryMaker / SignEntryMaker) - tile and
+// id are both at hand here, and the lanes of a tile work on different entries; `out` may be nullptr where nothing reads
+// the sorted ids (HEX8 sign lists).
 #define SORT_LANES 8
+template <class MAKE>
 __global__ void __launch_bounds__(256) bin_sort_small_kernel(const uint32_t* __restrict__ active, uint32_t n_active,
                                                             const uint32_t* __restrict__ off,
-                                                            const uint32_t* __restrict__ in,
-                                                            uint32_t* __restrict__ out, const uint32_t* __restrict__ abort_flag)
+                                                            const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                            MAKE make, SlabInfo s, typename MAKE::Out* __restrict__ aout,
+                                                            const uint32_t* __restrict__ abort_flag)
 {
     if (*abort_flag) return;   // speculated sizes of this call did not hold (run_impl)
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1786,20 +1867,24 @@ __global__ void __launch_bounds__(256) bin_sort_small_kernel(const uint32_t* __r
     const uint32_t t = active[w];
     const uint32_t b = off[t], n = off[t + 1] - b;
     if (n > 64) return;
+    const int tx = t % s.ntx, ty = (t / s.ntx) % s.nty, tz = t / (s.ntx * s.nty);
     for (uint32_t i = sub; i < n; i += SORT_LANES) {
         const uint32_t v = in[b + i];
         uint32_t rank = 0;
         for (uint32_t j = 0; j < n; ++j) rank += (in[b + j] < v) ? 1u : 0u;
-        out[b + rank] = v;
+        if (out) out[b + rank] = v;
+        aout[b + rank] = make(v, s, tx, ty, tz);
     }
 }
 
 // one wavefront per active tile: rank-sort both lists ascending (the reference visits
 // elements 1..nel in order; the ordered gather needs the same order).
+template <class MAKE>
 __global__ void __launch_bounds__(256) bin_sort_kernel(const uint32_t* __restrict__ active, uint32_t n_active,
                                                       const uint32_t* __restrict__ off,
-                                                      const uint32_t* __restrict__ in,
-                                                      uint32_t* __restrict__ out, const uint32_t* __restrict__ abort_flag)
+                                                      const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                      MAKE make, SlabInfo s, typename MAKE::Out* __restrict__ aout,
+                                                      const uint32_t* __restrict__ abort_flag)
 {
     if (*abort_flag) return;   // speculated sizes of this call did not hold (run_impl)
     const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1808,11 +1893,13 @@ __global__ void __launch_bounds__(256) bin_sort_kernel(const uint32_t* __restric
     const uint32_t t = active[w];
     const uint32_t b = off[t], n = off[t + 1] - b;
     if (n <= 64) return;   // handled by bin_sort_small_kernel
+    const int tx = t % s.ntx, ty = (t / s.ntx) % s.nty, tz = t / (s.ntx * s.nty);
     for (uint32_t i = lane; i < n; i += 64) {
         const uint32_t v = in[b + i];
         uint32_t rank = 0;
         for (uint32_t j = 0; j < n; ++j) rank += (in[b + j] < v) ? 1u : 0u;
-        out[b + rank] = v;
+        if (out) out[b + rank] = v;
+        aout[b + rank] = make(v, s, tx, ty, tz);
     }
 }
 
@@ -1841,9 +1928,11 @@ struct MainArgs {
     const uint32_t* active;
     uint32_t n_active;
     const uint32_t* band_off;
-    const uint32_t* band_ent;
+    const uint32_t* band_ent;   // item ids in list order (the triangle code fetches its item through them)
+    const uint2* band_aux;      // per band entry: storage chunk, kind << 12 | mask (BandEntryMaker)
     const uint32_t* sign_off;
-    const uint32_t* sign_ent;
+    const uint32_t* sign_ent;   // TET4: candidate elements
+    const uint4* sign_aux;      // HEX8, per sign entry: storage chunk, mask, rmax (SignEntryMaker)
     const BandItem* items;
     const void* erec;   // ElemRec[] or TetRec[]
     double* dist;
@@ -1852,9 +1941,7 @@ struct MainArgs {
     double* xp;
     const double* iso_res;     // per (iso item, box voxel) distances from iso_project_kernel
     const double* iso_res_xp;  // projection points (only when xp is requested)
-    const void* sbox;          // HEX8: per-element boxes / chunk offsets / results of sign_project_kernel
-    const uint32_t* s_store_off;
-    const double* sres;
+    const double* sres;        // HEX8: results of sign_project_kernel
     const uint8_t* hot;        // per tile: some candidate reaches rho_t
     const uint32_t* abort_flag;   // set on the device when the speculated sizes of this call did not hold (run_impl)
     int true_min;  // order-independent semantics (see write_value / process_triangle)
@@ -1891,28 +1978,22 @@ __global__ void __launch_bounds__(256) sdf_tiles_kernel(MainArgs A)
     VoxState st;
     st.cur = 1.0e10;
     st.xp[0] = st.xp[1] = st.xp[2] = 0.0;
+    // the three mask bits of this lane's position in the tile (band_entry_mask / sign_entry_mask); a voxel off the
+    // grid asks for bits no entry has
+    const uint32_t lane_bits = valid ? gather_lane_bits(lane) : ~0u;
     if (DO_DIST) {
-        const int ci = (int)cell_of(A.g, 0, x[0]), cj = (int)cell_of(A.g, 1, x[1]),
-                  ck = (int)cell_of(A.g, 2, x[2]);
         const uint32_t b = A.band_off[t], e = A.band_off[t + 1];
-        // Lane l fetches the header of list entry l (two dependent vector loads for the whole list instead of
-        // two dependent scalar loads per item); the headers are then broadcast item by item (v_readlane) and
-        // the iso look-ups of four items are issued together.  Items are consumed in list order, which is all
-        // the update rules depend on.
+        // Lane l fetches the two words of list entry l (one vector load for the whole list); they are then broadcast
+        // item by item (v_readlane), a voxel lies in the item's cell box when the entry's mask holds its three
+        // bits, and the iso look-ups of four items are issued together.  Items are consumed in list order, which
+        // is all the update rules depend on.
         for (uint32_t p0 = b; p0 < e; p0 += 64u) {
             const uint32_t n = (e - p0 < 64u) ? e - p0 : 64u;
             int32_t my_it = 0;
-            int32_t h[15];   // imin[3], imax[3], el, kind, lo[3], dim[3], store_off
-#pragma unroll
-            for (int q = 0; q < 15; ++q) h[q] = 0;
+            uint2 my = make_uint2(0u, 0u);   // storage chunk, kind << 12 | mask
             if ((uint32_t)lane < n) {
-                my_it = (int32_t)A.band_ent[p0 + lane];
-                const int32_t* w = reinterpret_cast<const int32_t*>(&A.items[my_it]);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) h[q] = w[q];
-#pragma unroll
-                for (int q = 0; q < 6; ++q) h[8 + q] = w[offsetof(BandItem, lo) / 4 + q];
-                h[14] = w[offsetof(BandItem, store_off) / 4];
+                my = A.band_aux[p0 + lane];
+                if constexpr (TRI) my_it = (int32_t)A.band_ent[p0 + lane];
             }
             for (uint32_t q0 = 0; q0 < n; q0 += 4u) {
                 bool in[4];
@@ -1923,17 +2004,14 @@ __global__ void __launch_bounds__(256) sdf_tiles_kernel(MainArgs A)
                 for (int u = 0; u < 4; ++u) {
                     const bool ok = q0 + u < n;
                     const int qq = (int)(ok ? q0 + u : n - 1u);
-                    int32_t hh[15];
-#pragma unroll
-                    for (int q = 0; q < 15; ++q) hh[q] = __builtin_amdgcn_readlane(h[q], qq);
-                    in[u] = valid && ok && ci >= hh[0] && ci <= hh[3] && cj >= hh[1] && cj <= hh[4] && ck >= hh[2] &&
-                            ck <= hh[5];
-                    kind[u] = hh[7];
+                    const uint32_t chunk = (uint32_t)__builtin_amdgcn_readlane((int)my.x, qq);
+                    const uint32_t km = (uint32_t)__builtin_amdgcn_readlane((int)my.y, qq);
+                    in[u] = ok && (km & lane_bits) == lane_bits;
+                    kind[u] = (int)(km >> ENT_MASK_BITS);
                     slot[u] = 0;
                     d[u] = INFINITY;
                     if (kind[u] == 0) {
-                        const int32_t lo3[3] = {hh[8], hh[9], hh[10]}, dim3[3] = {hh[11], hh[12], hh[13]};
-                        slot[u] = (size_t)tile_chunk((uint32_t)hh[14], tile_box(lo3, dim3), tx, ty, tz) * 64u + (uint32_t)lane;
+                        slot[u] = (size_t)chunk * 64u + (uint32_t)lane;
                         if (in[u]) d[u] = A.iso_res[slot[u]];
                     }
                 }
@@ -1971,24 +2049,16 @@ __global__ void __launch_bounds__(256) sdf_tiles_kernel(MainArgs A)
             // sign_project_kernel, so a visit is a lookup.  The state machine (:41-70) runs while the
             // candidates' max density is collected; the test of :36 is applied at the end (same result).
             if (A.hot[t]) {
-                const SignBox* __restrict__ sbox = static_cast<const SignBox*>(A.sbox);
                 bool any = false, done = false;
                 double cmax = -INFINITY, max_local = 10.0;
-                // lane l fetches the record of candidate l; records are broadcast one by one (v_readlane), four
+                // lane l fetches the four words of candidate l; they are broadcast one by one (v_readlane), four
                 // look-ups are issued together, and the state machine consumes them in order.  "Point inside the element's AABB"
-                // (SignDetection.jl:30) == "lattice index inside the element's box" by construction of the box.
+                // (SignDetection.jl:30) == "lattice index inside the element's box" by construction of the box ==
+                // "the entry's mask holds the three bits of the voxel" (sign_entry_mask).
                 for (uint32_t p0 = b; p0 < e; p0 += 64u) {
                     const uint32_t n = (e - p0 < 64u) ? e - p0 : 64u;
-                    int32_t hs[9];   // lo[3], dim[3], rmax (2 words), store_off of candidate l
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) hs[q] = 0;
-                    if ((uint32_t)lane < n) {
-                        const uint32_t el = A.sign_ent[p0 + lane];
-                        const int32_t* w = reinterpret_cast<const int32_t*>(&sbox[el]);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) hs[q] = w[q];
-                        hs[8] = (int32_t)A.s_store_off[el];
-                    }
+                    uint4 my = make_uint4(0u, 0u, 0u, 0u);   // storage chunk, mask, rmax (lo, hi word) of candidate l
+                    if ((uint32_t)lane < n) my = A.sign_aux[p0 + lane];
                     for (uint32_t q0 = 0; q0 < n; q0 += 4u) {
                         bool in[4];
                         double v[4], rmax[4];
@@ -1996,16 +2066,13 @@ __global__ void __launch_bounds__(256) sdf_tiles_kernel(MainArgs A)
                         for (int u = 0; u < 4; ++u) {
                             const bool ok = q0 + u < n;
                             const int qq = (int)(ok ? q0 + u : n - 1u);
-                            int32_t hh[9];
-#pragma unroll
-                            for (int q = 0; q < 9; ++q) hh[q] = __builtin_amdgcn_readlane(hs[q], qq);
-                            const int32_t lo3[3] = {hh[0], hh[1], hh[2]}, dim3[3] = {hh[3], hh[4], hh[5]};
-                            const uint32_t di = (uint32_t)(i - lo3[0]), dj = (uint32_t)(j - lo3[1]), dk = (uint32_t)(kl - lo3[2]);
-                            in[u] = valid && ok && di < (uint32_t)dim3[0] && dj < (uint32_t)dim3[1] && dk < (uint32_t)dim3[2];
-                            rmax[u] = __hiloint2double(hh[7], hh[6]);
+                            const uint32_t chunk = (uint32_t)__builtin_amdgcn_readlane((int)my.x, qq);
+                            const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)my.y, qq);
+                            in[u] = ok && (m & lane_bits) == lane_bits;
+                            rmax[u] = __hiloint2double(__builtin_amdgcn_readlane((int)my.w, qq), __builtin_amdgcn_readlane((int)my.z, qq));
                             v[u] = INFINITY;
                             if (in[u] && !done)   // a lane that is done (as of the previous batch) needs no more look-ups
-                                v[u] = A.sres[(size_t)tile_chunk((uint32_t)hh[8], tile_box(lo3, dim3), tx, ty, tz) * 64u + (uint32_t)lane];
+                                v[u] = A.sres[(size_t)chunk * 64u + (uint32_t)lane];
                         }
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
@@ -2198,6 +2265,7 @@ struct r2s_plan {
     int n_cu = 256;
     DevBuf deg, ine_ptr, ine, cursor, erec, cls, fmask, nitems, item_off, items;
     DevBuf band_cnt, band_off, band_raw, band_ent, sign_cnt, sign_off, sign_raw, sign_ent;
+    DevBuf band_aux, sign_aux;   // the words the gather reads per list entry, in list order
     DevBuf active, active_sign, active_any, active_sonly, active_lean, active_tri, tri, hot, counters, scan_tmp[3], scan_tmp2[3], nchunks, chunk_off, iso_res, iso_res_xp, strag;
     DevBuf perm, wchunks, hardflag;   // work order of the persistent projection kernel (HEX8)
     DevBuf sbox, s_nchunks, s_chunk_off, sres;   // item-major inverse maps of the sign pass (HEX8)
@@ -2381,7 +2449,7 @@ void r2s_plan_destroy(r2s_plan* P)
     (void)hipSetDevice(P->device);
     DevBuf* all[] = {&P->deg, &P->ine_ptr, &P->ine, &P->cursor, &P->erec, &P->cls, &P->fmask, &P->nitems,
                      &P->item_off, &P->items, &P->band_cnt, &P->band_off, &P->band_raw, &P->band_ent,
-                     &P->sign_cnt, &P->sign_off, &P->sign_raw, &P->sign_ent, &P->active, &P->active_sign, &P->active_any, &P->active_sonly, &P->active_lean, &P->active_tri, &P->tri,
+                     &P->sign_cnt, &P->sign_off, &P->sign_raw, &P->sign_ent, &P->band_aux, &P->sign_aux, &P->active, &P->active_sign, &P->active_any, &P->active_sonly, &P->active_lean, &P->active_tri, &P->tri,
                      &P->hot, &P->counters, &P->nchunks, &P->chunk_off, &P->iso_res, &P->iso_res_xp, &P->strag,
                      &P->perm, &P->wchunks, &P->hardflag, &P->sbox, &P->s_nchunks, &P->s_chunk_off, &P->sres, &P->nstore, &P->store_off, &P->s_nstore, &P->s_store_off,
                      &P->scan_tmp[0], &P->scan_tmp[1], &P->scan_tmp[2], &P->scan_tmp2[0], &P->scan_tmp2[1], &P->scan_tmp2[2]};
@@ -2773,8 +2841,13 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
     if (mode & R2S_OUT_XP) ENSURE(P->iso_res_xp, sizeof(double) * 192 * (size_t)std::max<uint32_t>(n_store, 1));
     ENSURE(P->band_raw, sizeof(uint32_t) * (size_t)std::max<uint32_t>(n_band, 1));
     ENSURE(P->band_ent, sizeof(uint32_t) * (size_t)std::max<uint32_t>(n_band, 1));
-    ENSURE(P->sign_raw, sizeof(uint32_t) * (size_t)std::max<uint32_t>(n_sign, 1));
-    ENSURE(P->sign_ent, sizeof(uint32_t) * (size_t)std::max<uint32_t>(n_sign, 1));
+    ENSURE(P->band_aux, sizeof(uint2) * (size_t)std::max<uint32_t>(n_band, 1));
+    if (HEX) {   // (the sorted element ids of the HEX8 sign lists are read by nobody: the gather has all it needs in sign_aux)
+        ENSURE(P->sign_raw, sizeof(uint32_t) * (size_t)std::max<uint32_t>(n_sign, 1));
+        ENSURE(P->sign_aux, sizeof(uint4) * (size_t)std::max<uint32_t>(n_sign, 1));
+    } else {
+        ENSURE(P->sign_ent, sizeof(uint32_t) * (size_t)std::max<uint32_t>(n_sign, 1));
+    }
     zero_many(bs, {{P->band_cnt.p, sizeof(uint32_t) * (size_t)(ntiles + 1)}, {P->sign_cnt.p, sizeof(uint32_t) * (size_t)(ntiles + 1)}});
     if (n_items)
         band_bin_kernel<true><<<(n_items * BIN_LANES + 127) / 128, 128, 0, bs>>>(P->items.as<BandItem>(), n_items, g, s, P->band_cnt.as<uint32_t>(), P->band_off.as<uint32_t>(), P->band_raw.as<uint32_t>(), nullptr, abort_flag);
@@ -2784,14 +2857,17 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
     // only ends the search - so the order of a list does not matter and the lists are used as filled)
     // lists longer than 64 entries only occur when the grid is coarse relative to the mesh (few tiles)
     if (n_active) {
-        bin_sort_small_kernel<<<(n_active * SORT_LANES + 255) / 256, 256, 0, bs>>>(P->active.as<uint32_t>(), n_active, P->band_off.as<uint32_t>(), P->band_raw.as<uint32_t>(), P->band_ent.as<uint32_t>(), abort_flag);
+        const BandEntryMaker mk{P->items.as<BandItem>(), g};
+        bin_sort_small_kernel<BandEntryMaker><<<(n_active * SORT_LANES + 255) / 256, 256, 0, bs>>>(P->active.as<uint32_t>(), n_active, P->band_off.as<uint32_t>(), P->band_raw.as<uint32_t>(), P->band_ent.as<uint32_t>(), mk, s, P->band_aux.as<uint2>(), abort_flag);
         if (cnt[6] > 64u)
-            bin_sort_kernel<<<(n_active + 3) / 4, 256, 0, bs>>>(P->active.as<uint32_t>(), n_active, P->band_off.as<uint32_t>(), P->band_raw.as<uint32_t>(), P->band_ent.as<uint32_t>(), abort_flag);
+            bin_sort_kernel<BandEntryMaker><<<(n_active + 3) / 4, 256, 0, bs>>>(P->active.as<uint32_t>(), n_active, P->band_off.as<uint32_t>(), P->band_raw.as<uint32_t>(), P->band_ent.as<uint32_t>(), mk, s, P->band_aux.as<uint2>(), abort_flag);
     }
     if (n_active_sign && HEX) {
-        bin_sort_small_kernel<<<(n_active_sign * SORT_LANES + 255) / 256, 256, 0, bs>>>(P->active_sign.as<uint32_t>(), n_active_sign, P->sign_off.as<uint32_t>(), P->sign_raw.as<uint32_t>(), P->sign_ent.as<uint32_t>(), abort_flag);
+        // (boxes and storage offsets are complete since the count pass - ev2[7], which `bs` has waited for)
+        const SignEntryMaker mk{P->sbox.as<SignBox>(), P->s_store_off.as<uint32_t>()};
+        bin_sort_small_kernel<SignEntryMaker><<<(n_active_sign * SORT_LANES + 255) / 256, 256, 0, bs>>>(P->active_sign.as<uint32_t>(), n_active_sign, P->sign_off.as<uint32_t>(), P->sign_raw.as<uint32_t>(), nullptr, mk, s, P->sign_aux.as<uint4>(), abort_flag);
         if (cnt[7] > 64u)
-            bin_sort_kernel<<<(n_active_sign + 3) / 4, 256, 0, bs>>>(P->active_sign.as<uint32_t>(), n_active_sign, P->sign_off.as<uint32_t>(), P->sign_raw.as<uint32_t>(), P->sign_ent.as<uint32_t>(), abort_flag);
+            bin_sort_kernel<SignEntryMaker><<<(n_active_sign + 3) / 4, 256, 0, bs>>>(P->active_sign.as<uint32_t>(), n_active_sign, P->sign_off.as<uint32_t>(), P->sign_raw.as<uint32_t>(), nullptr, mk, s, P->sign_aux.as<uint4>(), abort_flag);
     }
     HIP_TRY(hipEventRecord(P->ev[2], bs));
 
@@ -2833,13 +2909,13 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
         MainArgs A;
         A.g = g; A.s = s; A.rho_t = rho_t;
         A.true_min = prm.true_min ? 1 : 0;
-        A.band_off = P->band_off.as<uint32_t>(); A.band_ent = P->band_ent.as<uint32_t>();
-        A.sign_off = P->sign_off.as<uint32_t>(); A.sign_ent = P->sign_ent.as<uint32_t>();
+        A.band_off = P->band_off.as<uint32_t>(); A.band_ent = P->band_ent.as<uint32_t>(); A.band_aux = P->band_aux.as<uint2>();
+        A.sign_off = P->sign_off.as<uint32_t>(); A.sign_ent = P->sign_ent.as<uint32_t>(); A.sign_aux = P->sign_aux.as<uint4>();
         A.items = P->items.as<BandItem>(); A.erec = P->erec.as<typename ET::Rec>();
         A.dist = (mode & R2S_OUT_DIST) ? d_dist : nullptr;
         A.sign = (mode & R2S_OUT_SIGN) ? d_sign : nullptr;
         A.sdf = (mode & R2S_OUT_SDF) ? d_sdf : nullptr;
-        A.sbox = P->sbox.p; A.s_store_off = P->s_store_off.as<uint32_t>(); A.sres = P->sres.as<double>();
+        A.sres = P->sres.as<double>();
         A.hot = P->hot.as<uint8_t>();
         A.abort_flag = abort_flag;
         if constexpr (HEX) {
