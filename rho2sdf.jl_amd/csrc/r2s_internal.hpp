@@ -4,11 +4,50 @@
 #pragma once
 #include <cstdint>
 #include <functional>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "r2s_common.hpp"
 
 namespace r2s_int {
+
+// ---- per-device work caches ----------------------------------------------------------------------------------------------
+// The work buffers a family of entry points keeps between calls, one W per device.  W holds its device buffers as Scoped
+// members, so that destroying an entry frees every one of them: there is no second list of the members to keep in step.
+// A call locks `mu` for as long as it uses its entry.  The map is never destroyed: at process exit the HIP runtime may be
+// gone before a static destructor runs, and the driver reclaims the memory anyway.
+template <class W>
+class PerDevice {
+public:
+    std::mutex mu;
+    // the entry of `device` (empty on first use); the caller holds mu
+    W& of(int device) { return map_[device]; }
+    // the entry of the current device, or nullptr and the error in rc; the caller holds mu
+    W* current(int& rc)
+    {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) {
+            rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
+            return nullptr;
+        }
+        rc = 0;
+        return &map_[dev];
+    }
+    // frees every entry with its own device current, then makes the caller's device current again
+    void release_all()
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+        for (auto it = map_.begin(); it != map_.end(); it = map_.erase(it)) (void)hipSetDevice(it->first);
+        if (cur >= 0) (void)hipSetDevice(cur);
+        (void)hipGetLastError();
+    }
+
+private:
+    std::map<int, W>& map_ = *new std::map<int, W>;
+};
 
 // The three volume forms below read X and rho_n through dIEN unchecked: the caller has validated the connectivity
 // (dense_in_nodes_dev does; the host-pointer entry points of r2s_pre.hip run a flag pass after the upload).

@@ -1,7 +1,8 @@
 // Mesh fans: the fans of triangle corners round every vertex of a triangle mesh, the non-manifold (pinched) vertices, and the
 // split that gives every fan its own copy of the vertex (include/rho2sdf_hip.h, r2s_mesh_fans; DESIGN.md "Mesh fans").
-//   mf_key_kernel      one half-edge key per corner, the orient's keys (min << 33 | max << 1 | direction), payload 3t + c;
-//                      parent[k] = k on the graph of the 3 n_tris CORNERS -> rocPRIM radix sort of pairs
+//   ms_sort_half_edges (r2s_mesh_graph.hpp) ms_key_kernel<3, false>: one half-edge key per corner, the orient's keys
+//                      (min << 33 | max << 1 | direction), payload 3t + c; parent[k] = k on the graph of the 3 n_tris CORNERS
+//                      -> rocPRIM radix sort of pairs
 //   mf_union_kernel    every member of an edge run but its first: at each end of the edge, this triangle's corner at that end
 //                      joins the predecessor's corner at that end (the shells' union-find: larger root under the smaller, so a
 //                      fan's root is its smallest corner)
@@ -21,7 +22,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -43,28 +43,6 @@ constexpr int MF_SMALL = 8;
 constexpr int MF_VERTEX = 0, MF_FIRST = 1, MF_NCORNERS = 2, MF_NEDGES = 3, MF_NONMANIFOLD = 6, MF_CLASS = 7;
 
 __device__ inline uint32_t mf_next(uint32_t k) { return k % 3u == 2u ? k - 2u : k + 1u; }   // the next corner of k's triangle
-
-// one thread per triangle: its three half-edge keys, parent[k] = k for its corners, the collapsed count
-__global__ void __launch_bounds__(256) mf_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
-                                                      uint32_t* __restrict__ vals, uint32_t* __restrict__ parent, uint64_t* __restrict__ small)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool col = false;
-    if (t < n) {
-        int32_t i[3];
-        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
-            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
-            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
-            vals[3 * t + c] = (uint32_t)(3 * t + c);
-            parent[3 * t + c] = (uint32_t)(3 * t + c);
-        }
-    }
-    const unsigned long long m = __ballot(col);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MF_COLLAPSED], (unsigned long long)__popcll(m));
-}
 
 // the corners of half-edge (key, k = 3t + c) at the smaller and at the larger vertex of its edge: the half-edge leaves corner c
 // and arrives at corner (c + 1) % 3; direction bit 0: it leaves the smaller vertex
@@ -249,18 +227,11 @@ __global__ void __launch_bounds__(256) mf_apply_further_kernel(const uint32_t* _
 }
 
 // work buffers of the fan calls, kept per device between calls (r2s_release_cache frees them)
-struct FanWork {
-    DevBuf verts, tris, flag, small, keys, keys2, vals, vals2, temp, parent, label, rflag, pos, rkey, rkey2, rval, rval2, fan_at, further, extra,
-        index_of, foc, fov, counts, tris_out, verts_out, vert_of;
-    void release()
-    {
-        DevBuf* all[] = {&verts, &tris, &flag, &small, &keys, &keys2, &vals, &vals2, &temp, &parent, &label, &rflag, &pos, &rkey, &rkey2,
-                         &rval, &rval2, &fan_at, &further, &extra, &index_of, &foc, &fov, &counts, &tris_out, &verts_out, &vert_of};
-        for (DevBuf* b : all) b->release();
-    }
+struct FanWork : MsHalfEdgeBufs {
+    Scoped verts, tris, flag, small, parent, label, rflag, pos, rkey, rkey2, rval, rval2, fan_at, further, extra, index_of, foc, fov, counts,
+        tris_out, verts_out, vert_of;
 };
-std::mutex g_fans_mu;
-std::map<int, FanWork> g_fans_work;
+PerDevice<FanWork> g_fans_work;
 
 thread_local std::vector<int64_t> g_last_fans;   // [n][8]
 
@@ -277,13 +248,9 @@ int fans_core(int64_t n_verts, const int32_t* d_tris, int64_t n, hipStream_t st,
     ENSURE(w.fov, sizeof(int32_t) * (size_t)std::max<int64_t>(n_verts, 1));
     if (n_verts > 0) HIP_TRY(hipMemsetAsync(w.fov.p, 0, sizeof(int32_t) * (size_t)n_verts, st));
     const int64_t nh = 3 * n;
-    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    const uint64_t ckey = ms_collapsed_key(n_verts);
     int64_t nf = 0;
     if (n > 0) {
-        ENSURE(w.keys, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.keys2, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.vals, sizeof(uint32_t) * (size_t)nh);
-        ENSURE(w.vals2, sizeof(uint32_t) * (size_t)nh);
         ENSURE(w.parent, sizeof(uint32_t) * (size_t)nh);
         ENSURE(w.label, sizeof(uint32_t) * (size_t)nh);
         ENSURE(w.rflag, sizeof(int32_t) * (size_t)nh);
@@ -292,17 +259,14 @@ int fans_core(int64_t n_verts, const int32_t* d_tris, int64_t n, hipStream_t st,
         ENSURE(w.rval, sizeof(uint32_t) * (size_t)nh);
         ENSURE(w.fan_at, sizeof(int32_t) * (size_t)nh);
         ENSURE(w.foc, sizeof(int32_t) * (size_t)nh);
-        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
-        uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>(), *parent = w.parent.as<uint32_t>();
-        mf_key_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ckey, keys, vals, parent, small);
-        HIP_TRY(hipGetLastError());
-        const unsigned ebits = std::min(33u + ms_bits((uint64_t)n_verts), 64u);   // (the collapsed key included)
+        uint32_t* parent = w.parent.as<uint32_t>();
         size_t tb = 0, sb = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
         HIP_TRY(rocprim::exclusive_scan(nullptr, sb, w.rflag.as<int32_t>(), w.pos.as<int32_t>(), (int32_t)0, (size_t)nh,
                                         rocprim::plus<int32_t>(), st));
-        ENSURE(w.temp, std::max<size_t>(std::max(tb, sb), 16));
-        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
+        int rc = ms_sort_half_edges<3, false>(w, d_tris, n, n_verts, parent, nullptr, small + MF_COLLAPSED, sb, st);
+        if (rc) return rc;
+        const uint64_t* keys2 = w.keys2.as<uint64_t>();
+        const uint32_t* vals2 = w.vals2.as<uint32_t>();
         mf_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, parent);
         HIP_TRY(hipGetLastError());
         mf_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.label.as<uint32_t>(), w.rflag.as<int32_t>());
@@ -410,34 +374,11 @@ int fans_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tr
     return 0;
 }
 
-FanWork* fans_work_of_current_device(int& rc)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
-        return nullptr;
-    }
-    rc = 0;
-    return &g_fans_work[dev];
-}
-
 }  // namespace
 
 namespace r2s_int {
 
-void release_fans_work()
-{
-    std::lock_guard<std::mutex> lock(g_fans_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_fans_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_fans_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_fans_work() { g_fans_work.release_all(); }
 
 }  // namespace r2s_int
 
@@ -452,8 +393,8 @@ int r2s_mesh_fans(const float* verts, int64_t n_verts, const int32_t* tris, int6
                        n_fans, n_verts_out, totals, &split);
     if (rc) return rc;
     if ((rc = check_mesh_host("mesh_fans", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_fans_mu);
-    FanWork* w = fans_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_fans_work.mu);
+    FanWork* w = g_fans_work.current(rc);
     if (rc) return rc;
     if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
     int64_t nf = 0, nvo = 0, tot[8];
@@ -506,8 +447,8 @@ int r2s_mesh_fans_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tr
     if (fan_capacity < 0 || (fan_capacity > 0 && !d_counts)) return fail(R2S_ERR_ARG, "mesh_fans: null table or negative fan_capacity");
     if ((rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_fans_mu);
-    FanWork* w = fans_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_fans_work.mu);
+    FanWork* w = g_fans_work.current(rc);
     if (rc) return rc;
     if ((rc = check_mesh_dev("mesh_fans", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
     int64_t nf = 0, nvo = 0, tot[8];

@@ -1,15 +1,33 @@
-// What r2s_mesh_shells.hip, r2s_mesh_sections.hip, r2s_mesh_orient.hip, r2s_mesh_fans.hip and r2s_mesh_holes.hip share: the box
-// of the vertices behind the reference point, the collapsed-triangle test, the integer union-find with min-root, (shells, orient,
-// fans, holes) the per-group integer counting and (orient, fans, holes) the size of a run of sorted half-edges.  r2s_mesh_weld.hip takes the order-preserving bit pattern
-// of a float32 and the launch / bit-count helpers from here.  Everything has internal linkage: each file gets its own copy of
-// the kernel.
+// What r2s_mesh_shells.hip, r2s_mesh_sections.hip, r2s_mesh_orient.hip, r2s_mesh_fans.hip and r2s_mesh_holes.hip share:
+//   the box of the vertices behind the reference point (ms_bounds_kernel, ms_ref_point) and the collapsed-triangle test;
+//   the half-edge table: ms_half_edge_keys writes the keys of one triangle, ms_key_kernel is the one key launch of shells,
+//     orient, fans and holes (sections writes its keys in sx_tri_kernel with the same function), ms_sort_half_edges sizes the
+//     buffers (MsHalfEdgeBufs), launches the keys and sorts the pairs; ms_run_size reads the sorted runs;
+//   the integer union-find with min-root (ms_find, ms_union) and the per-group integer counting (ms_count);
+//   the segmented Float64 sum every Float64 table of these tools is defined by (include/rho2sdf_hip.h): ms_block_sum, the tree
+//     over 256 consecutive sorted items with one partial per (block, segment) at slot block + segment, and ms_combine_kernel,
+//     one wavefront per segment; ms_segment_kernel finds the segment starts of shells and orient.
+// r2s_mesh_weld.hip takes the order-preserving bit pattern of a float32 and the launch / bit-count helpers from here.
+// Everything has internal linkage: each file gets its own copy of a kernel, and a template only where it is used.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 
+#include "r2s_common.hpp"
+
 namespace {
+
+inline unsigned ms_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+inline unsigned ms_bits(uint64_t max_value)
+{
+    unsigned b = 1;
+    while (b < 64 && (max_value >> b)) ++b;
+    return b;
+}
 
 __device__ inline uint32_t ms_ordered(float f)
 {
@@ -90,7 +108,7 @@ __device__ inline void ms_union(uint32_t* L, uint32_t a, uint32_t b)
     }
 }
 
-// (orient, fans, holes) the sorted half-edge keys are (min << 33) | (max << 1) | direction, the collapsed triangles' keys behind them.
+// The sorted half-edge keys are (min << 33) | (max << 1) | direction, the collapsed triangles' keys behind them (below).
 // The number of members of the run of sorted half-edge i, capped at 3 (i is a real half-edge: keys[i] < ckey)
 __device__ inline int ms_run_size(const uint64_t* __restrict__ keys, int64_t i, int64_t nh, bool& head)
 {
@@ -134,12 +152,194 @@ __device__ inline void ms_count(bool active, int32_t group, const bool add[NC], 
         atomicAdd((unsigned long long*)&counts[(int64_t)s_group * STRIDE + col0 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
-inline unsigned ms_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline unsigned ms_bits(uint64_t max_value)
+// ---- the half-edge table -------------------------------------------------------------------------------------------------
+// The three half-edges of triangle t: key (min << 33) | (max << 1) | direction of the edge from corner c to corner c + 1
+// (direction 1: it leaves the larger vertex), payload 3t + c.  A collapsed triangle gets ckey three times.  Returns whether t
+// is collapsed; i = its vertices.
+__device__ inline bool ms_half_edge_keys(const int32_t* __restrict__ tris, int64_t t, uint64_t ckey, uint64_t* __restrict__ keys,
+                                         uint32_t* __restrict__ vals, int32_t i[3])
 {
-    unsigned b = 1;
-    while (b < 64 && (max_value >> b)) ++b;
-    return b;
+    const bool col = ms_collapsed(tris, t, i[0], i[1], i[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
+        const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
+        keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
+        vals[3 * t + c] = (uint32_t)(3 * t + c);
+    }
+    return col;
 }
 
+// adds the wavefront's collapsed triangles to *n_collapsed.  Called by all 64 lanes.
+__device__ inline void ms_count_collapsed(bool col, uint64_t* __restrict__ n_collapsed)
+{
+    const unsigned long long m = __ballot(col);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)n_collapsed, (unsigned long long)__popcll(m));
+}
+
+// one thread per triangle: its three half-edges, the collapsed count, and what the tool's graph needs in the same launch:
+// parent[x] = x for the NPARENT nodes of the triangle (1: the triangle, 2: its two parities, 3: its corners, 0: no parent
+// array), VFLAG: the flag of every vertex a real triangle names
+template <int NPARENT, bool VFLAG>
+__global__ void __launch_bounds__(256) ms_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ vals, uint32_t* __restrict__ parent, int32_t* __restrict__ vflag,
+                                                      uint64_t* __restrict__ n_collapsed)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool col = false;
+    if (t < n) {
+        int32_t i[3];
+        col = ms_half_edge_keys(tris, t, ckey, keys, vals, i);
+#pragma unroll
+        for (int k = 0; k < NPARENT; ++k) parent[NPARENT * t + k] = (uint32_t)(NPARENT * t + k);
+        if (VFLAG && !col) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) vflag[i[c]] = 1;
+        }
+    }
+    ms_count_collapsed(col, n_collapsed);
+}
+
+// the key of every half-edge of a collapsed triangle: above every key of a real edge (min < n_verts), so the sort leaves the
+// collapsed triangles behind the real runs
+inline uint64_t ms_collapsed_key(int64_t n_verts) { return (uint64_t)n_verts << 33; }
+// the key bits the sort has to look at, the collapsed key included; n_verts < 2^31 keeps 33 + bits(n_verts) within the 64 bits
+// of the key, and the clamp says so to rocPRIM whatever the argument checks admit
+inline unsigned ms_key_bits(int64_t n_verts) { return std::min(33u + ms_bits((uint64_t)n_verts), 64u); }
+
+// the buffers of the half-edge table: keys / vals as written, keys2 / vals2 sorted, temp for rocPRIM (a tool's work struct
+// derives from this and uses temp for its other sorts and scans too)
+struct MsHalfEdgeBufs {
+    Scoped keys, keys2, vals, vals2, temp;
+};
+
+// The sorted half-edge table of n > 0 device triangles on `st`: sizes the buffers, launches ms_key_kernel<NPARENT, VFLAG>
+// (parent / vflag: the caller's arrays, null where the tool has none) and sorts the pairs by key into keys2 / vals2.  temp is
+// sized for the sort and for `extra_temp` bytes, what the caller's scan behind the sort asks for, so that both share one
+// allocation.
+template <int NPARENT, bool VFLAG>
+int ms_sort_half_edges(MsHalfEdgeBufs& b, const int32_t* d_tris, int64_t n, int64_t n_verts, uint32_t* parent, int32_t* vflag,
+                       uint64_t* n_collapsed, size_t extra_temp, hipStream_t st)
+{
+    const size_t nh = 3 * (size_t)n;
+    ENSURE(b.keys, sizeof(uint64_t) * nh);
+    ENSURE(b.keys2, sizeof(uint64_t) * nh);
+    ENSURE(b.vals, sizeof(uint32_t) * nh);
+    ENSURE(b.vals2, sizeof(uint32_t) * nh);
+    uint64_t *keys = b.keys.as<uint64_t>(), *keys2 = b.keys2.as<uint64_t>();
+    uint32_t *vals = b.vals.as<uint32_t>(), *vals2 = b.vals2.as<uint32_t>();
+    ms_key_kernel<NPARENT, VFLAG><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ms_collapsed_key(n_verts), keys, vals, parent, vflag, n_collapsed);
+    HIP_TRY(hipGetLastError());
+    const unsigned ebits = ms_key_bits(n_verts);
+    size_t tb = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, nh, 0u, ebits, st));
+    ENSURE(b.temp, std::max<size_t>(std::max(tb, extra_temp), 16));
+    HIP_TRY(rocprim::radix_sort_pairs(b.temp.p, tb, keys, keys2, vals, vals2, nh, 0u, ebits, st));
+    return 0;
+}
+
+// ---- the segmented Float64 sum ---------------------------------------------------------------------------------------------
+constexpr int MS_BLOCK = 256;   // sorted items per block of the Float64 sums (the header's definition)
+
+// seg[s] = the first sorted position of segment s, seg[n_segments] = nvalid; counts[s][0] = the segment's first item
+// (rows of STRIDE)
+template <int STRIDE>
+__global__ void __launch_bounds__(256) ms_segment_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval, int64_t nvalid,
+                                                          int64_t n_segments, int64_t* __restrict__ seg, int64_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvalid) return;
+    const uint32_t s = skey[i];
+    if (i == 0 || skey[i - 1] != s) {
+        seg[s] = i;
+        counts[(int64_t)s * STRIDE] = (int64_t)sval[i];
+    }
+    if (i == 0) seg[n_segments] = nvalid;
+}
+
+// Block b holds the sorted positions [256 b, 256 b + 256); `key` is the segment of the thread's item, v its NSUM terms.  A
+// segmented fixed tree in LDS (round d = 1, 2, .., 128: an item takes the item d places on while that one is in its
+// segment), then the first item of every segment in the block writes the partial of (block b, segment s) to slot b + s (both
+// only grow along the sorted order, so the slots are distinct; there are fewer than blocks + segments of them).  Called by
+// all 256 threads; v comes back changed.
+template <int NSUM>
+__device__ inline void ms_block_sum(bool active, uint32_t key, double v[NSUM], double* __restrict__ partial)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_v[NSUM][MS_BLOCK];
+    __shared__ uint32_t s_key[MS_BLOCK];
+    const int j = threadIdx.x;
+    if (!active) key = 0xffffffffu;
+    s_key[j] = key;
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q) s_v[q][j] = v[q];
+    __syncthreads();
+    const bool head = active && (j == 0 || s_key[j - 1] != key);
+#pragma unroll
+    for (int d = 1; d < MS_BLOCK; d <<= 1) {
+        const bool take = active && j + d < MS_BLOCK && s_key[j + d] == key;
+        double o[NSUM];
+#pragma unroll
+        for (int q = 0; q < NSUM; ++q) o[q] = take ? s_v[q][j + d] : 0.0;
+        __syncthreads();
+        if (take) {
+#pragma unroll
+            for (int q = 0; q < NSUM; ++q) {
+                v[q] = v[q] + o[q];
+                s_v[q][j] = v[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (head) {
+        double* out = partial + ((int64_t)blockIdx.x + (int64_t)key) * NSUM;
+#pragma unroll
+        for (int q = 0; q < NSUM; ++q) out[q] = v[q];
+    }
+}
+
+// one wavefront per segment [start[s], start[s + 1]): lane l sums the l-th run of `chunk` consecutive block partials in
+// ascending block order, then the run sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while
+// that lane has a run).  n_items (optional): the segment's length goes to n_items[s * item_stride], the count column of shells
+// and orient, at no launch of its own.
+template <int NSUM>
+__global__ void __launch_bounds__(256) ms_combine_kernel(const int64_t* __restrict__ start, int64_t n_segments, const double* __restrict__ partial,
+                                                          double* __restrict__ sums, int64_t* __restrict__ n_items, int item_stride)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= n_segments) return;   // (the whole wavefront)
+    const int64_t first = start[s], end = start[s + 1];
+    const int64_t b0 = first / MS_BLOCK, nb = (end - 1) / MS_BLOCK - b0 + 1;
+    const int64_t chunk = (nb + 63) / 64;
+    const int m = (int)((nb + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
+    double v[NSUM];
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q) v[q] = 0.0;
+    if (lane < m) {
+        const int64_t lo = lane * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
+        const double* p = partial + (b0 + lo + s) * NSUM;
+#pragma unroll
+        for (int q = 0; q < NSUM; ++q) v[q] = p[q];
+        for (int64_t b = lo + 1; b < hi; ++b) {
+            p += NSUM;
+#pragma unroll
+            for (int q = 0; q < NSUM; ++q) v[q] = v[q] + p[q];
+        }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (int q = 0; q < NSUM; ++q) {
+            const double o = __shfl_down(v[q], d, 64);
+            if (lane + d < m) v[q] = v[q] + o;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NSUM; ++q) sums[s * NSUM + q] = v[q];
+        if (n_items) n_items[s * item_stride] = end - first;
+    }
+}
 }  // namespace

@@ -1,7 +1,8 @@
 // Mesh holes: the rims of a triangle mesh (its boundary loops and chains), per rim the integer record and the Float64 length /
 // area vector / vertex sum, and the fill that caps every selected closed rim (include/rho2sdf_hip.h, r2s_mesh_holes; DESIGN.md
 // "Mesh holes").  The sections' machinery on the boundary half-edges: the graph is on half-edges, the nodes are vertices.
-//   mh_key_kernel      one half-edge key per corner, the shells' keys, payload 3t + c -> rocPRIM radix sort of pairs
+//   ms_sort_half_edges (r2s_mesh_graph.hpp) ms_key_kernel<0, false>: one half-edge key per corner, the shells' keys, payload
+//                      3t + c -> rocPRIM radix sort of pairs
 //   mh_flag_kernel     a run of size one (ms_run_size) is a boundary half-edge: the flag goes to its half-edge id
 //   -> rocPRIM exclusive scan -> mh_compact_kernel: the boundary half-edges b = 0 .. n_b - 1 in ascending half-edge id
 //   mh_end_kernel      the two ends of every boundary half-edge, keyed by vertex (end 2b: FROM, outgoing; end 2b + 1: TO, incoming);
@@ -17,8 +18,9 @@
 //                      ceil(log2(longest closed rim)) rounds
 //   -> stable radix sort of the half-edges by rim -> mh_start_kernel -> mh_place_kernel: closed rims are laid out by rank, the
 //      others keep ascending half-edge id
-//   mh_sum_kernel      blocks of 256 output positions, the 7 terms of every half-edge, a segmented fixed tree in LDS, one partial
-//                      per (block, rim);  mh_combine_kernel: one wavefront per rim, as the sections'
+//   mh_sum_kernel      blocks of 256 output positions, the 7 terms of every half-edge -> ms_block_sum<7> (r2s_mesh_graph.hpp): a
+//                      segmented fixed tree in LDS, one partial per (block, rim);  ms_combine_kernel<7> (r2s_mesh_graph.hpp): one
+//                      wavefront per rim
 //   mh_apply_*         the fill: the added vertices and the added triangles (the input mesh is copied by the copy engine)
 // Integer counts use integer atomics; no floating-point atomic and no library reduction touches the Float64 sums.
 // Registers of the gfx950 build (hipcc -O3 -ffp-contract=off, -Rpass-analysis=kernel-resource-usage) are listed in DESIGN.md:
@@ -30,7 +32,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -42,7 +43,6 @@ using namespace r2s_int;
 
 namespace {
 
-constexpr int MH_BLOCK = 256;   // output positions per block of the Float64 sums (the header's definition)
 constexpr int MH_NSUM = 7, MH_NCNT = 8;
 constexpr int64_t MH_MAX_TRIS = (((int64_t)1 << 31) - 1) / 3;   // 3 n_tris < 2^31: half-edge ids are int32
 // slots of the small device array: [0..5] the bounds, then
@@ -51,27 +51,6 @@ constexpr int MH_COLLAPSED = 6, MH_NB = 7, MH_NRIMS = 8, MH_MAXLOOP = 9, MH_NODE
 constexpr int MH_SMALL = 16;
 // columns of the per-rim record
 constexpr int MH_FIRST = 0, MH_NEDGES = 1, MH_NNODES = 2, MH_STATUS = 6, MH_ADDED = 7;
-
-// one thread per triangle: its three half-edge keys, the collapsed count
-__global__ void __launch_bounds__(256) mh_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
-                                                      uint32_t* __restrict__ vals, uint64_t* __restrict__ small)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool col = false;
-    if (t < n) {
-        int32_t i[3];
-        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
-            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
-            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
-            vals[3 * t + c] = (uint32_t)(3 * t + c);
-        }
-    }
-    const unsigned long long m = __ballot(col);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MH_COLLAPSED], (unsigned long long)__popcll(m));
-}
 
 // one thread per sorted half-edge: bflag[its id] = it is alone in its edge run (every id is written once)
 __global__ void __launch_bounds__(256) mh_flag_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
@@ -309,17 +288,13 @@ __global__ void __launch_bounds__(256) mh_place_kernel(const uint32_t* __restric
     rim_edge[pos] = (int32_t)bh[b];
 }
 
-// block j: the output positions [256 j, 256 j + 256); the partial of (block j, rim c) goes to slot j + c (both only grow along
-// the output order, so the slots are distinct; there are fewer than blocks + rims of them)
-__global__ void __launch_bounds__(MH_BLOCK) mh_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
+// one thread per output position: the 7 terms of its half-edge into the segmented sum of its block (ms_block_sum: slot block + rim)
+__global__ void __launch_bounds__(MS_BLOCK) mh_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
                                                            const uint32_t* __restrict__ skey, const int32_t* __restrict__ rim_edge, int64_t nb,
                                                            double rx, double ry, double rz, double* __restrict__ partial)
 {
 #pragma clang fp contract(off)
-    __shared__ double s_v[MH_NSUM][MH_BLOCK];
-    __shared__ uint32_t s_key[MH_BLOCK];
-    const int j = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * MH_BLOCK + j;
+    const int64_t i = (int64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     const bool active = i < nb;
     uint32_t key = 0xffffffffu;
     double v[MH_NSUM];
@@ -339,73 +314,7 @@ __global__ void __launch_bounds__(MH_BLOCK) mh_sum_kernel(const float* __restric
         v[3] = Ax * By - Ay * Bx;
         v[4] = Ax, v[5] = Ay, v[6] = Az;
     }
-    s_key[j] = key;
-#pragma unroll
-    for (int q = 0; q < MH_NSUM; ++q) s_v[q][j] = v[q];
-    __syncthreads();
-    const bool head = active && (j == 0 || s_key[j - 1] != key);
-#pragma unroll
-    for (int d = 1; d < MH_BLOCK; d <<= 1) {
-        const bool take = active && j + d < MH_BLOCK && s_key[j + d] == key;
-        double o[MH_NSUM];
-#pragma unroll
-        for (int q = 0; q < MH_NSUM; ++q) o[q] = take ? s_v[q][j + d] : 0.0;
-        __syncthreads();
-        if (take) {
-#pragma unroll
-            for (int q = 0; q < MH_NSUM; ++q) {
-                v[q] = v[q] + o[q];
-                s_v[q][j] = v[q];
-            }
-        }
-        __syncthreads();
-    }
-    if (head) {
-        double* out = partial + ((int64_t)blockIdx.x + (int64_t)key) * MH_NSUM;
-#pragma unroll
-        for (int q = 0; q < MH_NSUM; ++q) out[q] = v[q];
-    }
-}
-
-// one wavefront per rim: lane l sums the l-th run of `chunk` consecutive block partials in ascending block order, then the run
-// sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while that lane has a run)
-__global__ void __launch_bounds__(256) mh_combine_kernel(const int64_t* __restrict__ start, int64_t nr, const double* __restrict__ partial,
-                                                          double* __restrict__ sums)
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= nr) return;   // (the whole wavefront)
-    const int64_t lo_pos = start[c], end = start[c + 1];
-    const int64_t b0 = lo_pos / MH_BLOCK, nblk = (end - 1) / MH_BLOCK - b0 + 1;
-    const int64_t chunk = (nblk + 63) / 64;
-    const int m = (int)((nblk + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
-    double v[MH_NSUM];
-#pragma unroll
-    for (int q = 0; q < MH_NSUM; ++q) v[q] = 0.0;
-    if (lane < m) {
-        const int64_t lo = lane * chunk, hi = lo + chunk < nblk ? lo + chunk : nblk;
-        const double* p = partial + (b0 + lo + c) * MH_NSUM;
-#pragma unroll
-        for (int q = 0; q < MH_NSUM; ++q) v[q] = p[q];
-        for (int64_t b = lo + 1; b < hi; ++b) {
-            p += MH_NSUM;
-#pragma unroll
-            for (int q = 0; q < MH_NSUM; ++q) v[q] = v[q] + p[q];
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int q = 0; q < MH_NSUM; ++q) {
-            const double o = __shfl_down(v[q], d, 64);
-            if (lane + d < m) v[q] = v[q] + o;
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < MH_NSUM; ++q) sums[c * MH_NSUM + q] = v[q];
-    }
+    ms_block_sum<MH_NSUM>(active, key, v, partial);
 }
 
 // the fill, one thread per rim: the added vertex of a fan cap, per axis r + S / n_edges in double, rounded to float32
@@ -445,19 +354,11 @@ __global__ void __launch_bounds__(256) mh_apply_cap_kernel(const int32_t* __rest
 }
 
 // work buffers of the hole calls, kept per device between calls (r2s_release_cache frees them)
-struct HoleWork {
-    DevBuf verts, tris, flag, small, keys, keys2, vals, vals2, temp, bflag, bpos, bh, ekey, ekey2, eval, eval2, parent, succ, rflag, num, skey,
-        skey2, sval, sval2, counts, closed, addv, voff, addt, toff, pp0, pp1, start, rim_edge, partial, sums, tris_out, verts_out;
-    void release()
-    {
-        DevBuf* all[] = {&verts, &tris, &flag, &small, &keys, &keys2, &vals, &vals2, &temp, &bflag, &bpos, &bh, &ekey, &ekey2, &eval, &eval2,
-                         &parent, &succ, &rflag, &num, &skey, &skey2, &sval, &sval2, &counts, &closed, &addv, &voff, &addt, &toff, &pp0, &pp1,
-                         &start, &rim_edge, &partial, &sums, &tris_out, &verts_out};
-        for (DevBuf* b : all) b->release();
-    }
+struct HoleWork : MsHalfEdgeBufs {
+    Scoped verts, tris, flag, small, bflag, bpos, bh, ekey, ekey2, eval, eval2, parent, succ, rflag, num, skey, skey2, sval, sval2, counts,
+        closed, addv, voff, addt, toff, pp0, pp1, start, rim_edge, partial, sums, tris_out, verts_out;
 };
-std::mutex g_holes_mu;
-std::map<int, HoleWork> g_holes_work;
+PerDevice<HoleWork> g_holes_work;
 
 struct HoleTables {
     std::vector<int64_t> start;     // [n_rims + 1] (empty without rims)
@@ -488,27 +389,17 @@ int holes_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int
         HIP_TRY(hipGetLastError());
     }
     const int64_t nh = 3 * n;
-    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    const uint64_t ckey = ms_collapsed_key(n_verts);
     size_t tb = 0, sb = 0, sb2 = 0;
     if (n > 0) {
-        ENSURE(w.keys, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.keys2, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.vals, sizeof(uint32_t) * (size_t)nh);
-        ENSURE(w.vals2, sizeof(uint32_t) * (size_t)nh);
         ENSURE(w.bflag, sizeof(int32_t) * (size_t)nh);
         ENSURE(w.bpos, sizeof(int32_t) * (size_t)nh);
         ENSURE(w.bh, sizeof(uint32_t) * (size_t)nh);
-        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
-        uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>();
         int32_t *bflag = w.bflag.as<int32_t>(), *bpos = w.bpos.as<int32_t>();
-        mh_key_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ckey, keys, vals, small);
-        HIP_TRY(hipGetLastError());
-        const unsigned ebits = std::min(33u + ms_bits((uint64_t)n_verts), 64u);   // (the collapsed key included)
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
         HIP_TRY(rocprim::exclusive_scan(nullptr, sb, bflag, bpos, (int32_t)0, (size_t)nh, rocprim::plus<int32_t>(), st));
-        ENSURE(w.temp, std::max<size_t>(std::max(tb, sb), 16));
-        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
-        mh_flag_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, bflag);
+        int rc = ms_sort_half_edges<0, false>(w, d_tris, n, n_verts, nullptr, nullptr, small + MH_COLLAPSED, sb, st);
+        if (rc) return rc;
+        mh_flag_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, bflag);
         HIP_TRY(hipGetLastError());
         HIP_TRY(rocprim::exclusive_scan(w.temp.p, sb, bflag, bpos, (int32_t)0, (size_t)nh, rocprim::plus<int32_t>(), st));
         mh_compact_kernel<<<ms_blocks(nh), 256, 0, st>>>(nh, bflag, bpos, w.bh.as<uint32_t>(), small);
@@ -521,7 +412,7 @@ int holes_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int
     int64_t nr = 0;
     if (nb > 0) {
         // n_rims <= n_b: everything per rim is sized for n_b of them, and the number of rims is read with the totals
-        const int64_t nblk = (nb + MH_BLOCK - 1) / MH_BLOCK;
+        const int64_t nblk = (nb + MS_BLOCK - 1) / MS_BLOCK;
         ENSURE(w.ekey, sizeof(uint32_t) * (size_t)n2);
         ENSURE(w.ekey2, sizeof(uint32_t) * (size_t)n2);
         ENSURE(w.eval, sizeof(uint32_t) * (size_t)n2);
@@ -598,10 +489,11 @@ int holes_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int
         HIP_TRY(hipGetLastError());
         mh_place_kernel<<<ms_blocks(nb), 256, 0, st>>>(skey2, sval2, nb, closed, counts, w.start.as<int64_t>(), pin, bh, w.rim_edge.as<int32_t>());
         HIP_TRY(hipGetLastError());
-        mh_sum_kernel<<<(unsigned)nblk, MH_BLOCK, 0, st>>>(d_verts, d_tris, skey2, w.rim_edge.as<int32_t>(), nb, out.r[0], out.r[1], out.r[2],
+        mh_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, skey2, w.rim_edge.as<int32_t>(), nb, out.r[0], out.r[1], out.r[2],
                                                           w.partial.as<double>());
         HIP_TRY(hipGetLastError());
-        mh_combine_kernel<<<(unsigned)((nr + 3) / 4), 256, 0, st>>>(w.start.as<int64_t>(), nr, w.partial.as<double>(), w.sums.as<double>());
+        ms_combine_kernel<MH_NSUM><<<(unsigned)((nr + 3) / 4), 256, 0, st>>>(w.start.as<int64_t>(), nr, w.partial.as<double>(), w.sums.as<double>(),
+                                                                          nullptr, 0);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -684,17 +576,6 @@ int table_args(const char* who, const void* start, const void* counts, const voi
     return 0;
 }
 
-HoleWork* holes_work_of_current_device(int& rc)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
-        return nullptr;
-    }
-    rc = 0;
-    return &g_holes_work[dev];
-}
-
 void holes_return(const HoleSizes& s, int64_t* n_rims, int64_t* n_edges, int64_t* n_verts_out, int64_t* n_tris_out, double ref_point[3],
                   int64_t totals[8])
 {
@@ -707,19 +588,7 @@ void holes_return(const HoleSizes& s, int64_t* n_rims, int64_t* n_edges, int64_t
 
 namespace r2s_int {
 
-void release_holes_work()
-{
-    std::lock_guard<std::mutex> lock(g_holes_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_holes_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_holes_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_holes_work() { g_holes_work.release_all(); }
 
 }  // namespace r2s_int
 
@@ -734,8 +603,8 @@ int r2s_mesh_holes(const float* verts, int64_t n_verts, const int32_t* tris, int
                         n_tris_out, ref_point, totals, nullptr, 0, &fill);
     if (rc) return rc;
     if ((rc = check_mesh_host("mesh_holes", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_holes_mu);
-    HoleWork* w = holes_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_holes_work.mu);
+    HoleWork* w = g_holes_work.current(rc);
     if (rc) return rc;
     if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
     HoleSizes s;
@@ -801,8 +670,8 @@ int r2s_mesh_holes_dev(const float* d_verts, int64_t n_verts, const int32_t* d_t
         return rc;
     if ((rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_holes_mu);
-    HoleWork* w = holes_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_holes_work.mu);
+    HoleWork* w = g_holes_work.current(rc);
     if (rc) return rc;
     if ((rc = check_mesh_dev("mesh_holes", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
     HoleSizes s;

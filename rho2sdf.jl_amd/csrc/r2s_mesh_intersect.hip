@@ -17,7 +17,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 
 #include "r2s_common.hpp"
@@ -201,26 +200,9 @@ __global__ void __launch_bounds__(256) mx_unpack_kernel(const uint64_t* __restri
 
 // work buffers of the intersection calls, kept per device between calls (r2s_release_cache frees them)
 struct IsectWork {
-    DevBuf verts, tris, flag, small, hits, keys, keys2, temp, pairs;
-    void release()
-    {
-        DevBuf* all[] = {&verts, &tris, &flag, &small, &hits, &keys, &keys2, &temp, &pairs};
-        for (DevBuf* b : all) b->release();
-    }
+    Scoped verts, tris, flag, small, hits, keys, keys2, temp, pairs;
 };
-std::mutex g_mx_mu;
-std::map<int, IsectWork> g_mx_work;
-
-IsectWork* work_of_current_device(int& rc)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
-        return nullptr;
-    }
-    rc = 0;
-    return &g_mx_work[dev];
-}
+PerDevice<IsectWork> g_mx_work;
 
 inline unsigned mx_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 inline unsigned mx_bits(uint64_t max_value)
@@ -319,19 +301,7 @@ int isect_copy_dev(IsectWork& w, int64_t n_tris, int32_t* d_hits, hipStream_t st
 
 namespace r2s_int {
 
-void release_intersect_work()
-{
-    std::lock_guard<std::mutex> lock(g_mx_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_mx_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_mx_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_intersect_work() { g_mx_work.release_all(); }
 
 }  // namespace r2s_int
 
@@ -345,8 +315,8 @@ int r2s_mesh_index_intersections(const r2s_mesh_index* ix, int32_t* hits_of_tri_
     if (rc || (rc = check_device(0))) return rc;
     DeviceScope scope;
     if ((rc = scope.enter(ix->device))) return rc;
-    std::lock_guard<std::mutex> lock(g_mx_mu);
-    IsectWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_mx_work.mu);
+    IsectWork* w = g_mx_work.current(rc);
     if (rc) return rc;
     int64_t tot[8];
     if ((rc = isect_core(ix->tree, nullptr, *w, nullptr, pair_capacity, tot))) return rc;
@@ -362,8 +332,8 @@ int r2s_mesh_index_intersections_dev(const r2s_mesh_index* ix, int32_t* d_hits_o
     int rc = isect_args(d_pairs, pair_capacity, totals);
     if (rc || (rc = check_device(0)) || (rc = index_on_current_device("mesh_index_intersections", ix))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_mx_mu);
-    IsectWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_mx_work.mu);
+    IsectWork* w = g_mx_work.current(rc);
     if (rc) return rc;
     int64_t tot[8];
     if ((rc = isect_core(ix->tree, st, *w, pair_capacity > 0 ? d_pairs : nullptr, pair_capacity, tot))) return rc;
@@ -378,8 +348,8 @@ int r2s_mesh_intersections(const float* verts, int64_t n_verts, const int32_t* t
     int rc = mesh_args("mesh_intersections", verts, n_verts, tris, n_tris);
     if (rc || (rc = isect_args(pairs_out, pair_capacity, totals))) return rc;
     if ((rc = check_mesh_host("mesh_intersections", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_mx_mu);
-    IsectWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_mx_work.mu);
+    IsectWork* w = g_mx_work.current(rc);
     if (rc) return rc;
     if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
     MiTree T;   // (built, used and dropped: the nodes free themselves)
@@ -397,8 +367,8 @@ int r2s_mesh_intersections_dev(const float* d_verts, int64_t n_verts, const int3
     int rc = mesh_args("mesh_intersections", d_verts, n_verts, d_tris, n_tris);
     if (rc || (rc = isect_args(d_pairs, pair_capacity, totals)) || (rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_mx_mu);
-    IsectWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_mx_work.mu);
+    IsectWork* w = g_mx_work.current(rc);
     if (rc) return rc;
     if ((rc = check_mesh_dev("mesh_intersections", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
     MiTree T;

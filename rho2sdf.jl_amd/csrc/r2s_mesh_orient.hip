@@ -1,17 +1,20 @@
 // Mesh orient: the orientable patches of a triangle mesh, a consistent winding for each, and the choice of that winding by the
 // signed volume or by the majority (include/rho2sdf_hip.h, r2s_mesh_orient; DESIGN.md "Mesh orient").
 //   ms_bounds_kernel   the box of all vertices -> the reference point (the shells' kernel)
-//   mo_key_kernel      one half-edge key per corner, the shells' keys, payload 3t + c; parent[x] = x on the DOUBLED graph of
-//                      2 n_tris nodes, node 2t + s = "triangle t with parity s" -> rocPRIM radix sort of pairs
+//   ms_sort_half_edges (r2s_mesh_graph.hpp) ms_key_kernel<2, false>: one half-edge key per corner, the shells' keys, payload
+//                      3t + c; parent[x] = x on the DOUBLED graph of 2 n_tris nodes, node 2t + s = "triangle t with parity s"
+//                      -> rocPRIM radix sort of pairs
 //   mo_union_kernel    the second member of every run of EXACTLY two: opposite directions join (2a, 2b) and (2a+1, 2b+1), equal
 //                      directions join (2a, 2b+1) and (2a+1, 2b) (the shells' union-find: larger root under the smaller)
 //   mo_flatten_kernel  root(2t) = 2f + rel[t] in an orientable patch with first triangle f, root(2t) = root(2t+1) = 2f in a
 //                      non-orientable one: first triangle, parity and orientability of every triangle; root flags
 //   -> rocPRIM exclusive scan (integers) -> mo_number_kernel: patch numbers, sort keys
-//   -> stable radix sort of the triangle ids by patch -> mo_segment_kernel: where each patch starts, its first triangle
-//   mo_sum_kernel      blocks of 256 consecutive sorted triangles, the volume term negated where rel = 1, a segmented fixed
-//                      tree in LDS, one partial per (block, patch) at slot block + patch
-//   mo_combine_kernel  one wavefront per patch: up to 64 equal runs of its block partials in ascending order, then a fixed tree
+//   -> stable radix sort of the triangle ids by patch -> ms_segment_kernel (r2s_mesh_graph.hpp): where each patch starts, its
+//      first triangle
+//   mo_sum_kernel      blocks of 256 consecutive sorted triangles, the volume term negated where rel = 1 -> ms_block_sum<1>
+//                      (r2s_mesh_graph.hpp): a segmented fixed tree in LDS, one partial per (block, patch) at slot block + patch
+//   ms_combine_kernel<1> (r2s_mesh_graph.hpp) one wavefront per patch: up to 64 equal runs of its block partials in ascending
+//                      order, then a fixed tree; n_tris of the patch
 //   mo_parity_kernel   n1 per patch; mo_edge_kernel: the sorted edge runs again, boundary / non-manifold half-edges and the
 //                      flipped edges of the input per patch
 //   mo_decide_kernel   one thread per patch: closed, the whole-patch flip g, the record, the totals
@@ -25,7 +28,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -37,7 +39,6 @@ using namespace r2s_int;
 
 namespace {
 
-constexpr int MO_BLOCK = 256;   // triangles per block of the volume sums (the shells' definition)
 constexpr int MO_NCNT = 8;
 constexpr int64_t MO_MAX_TRIS = (int64_t)1 << 30;
 constexpr int32_t MO_FLAGS = 1;   // R2S_ORIENT_OUTWARD
@@ -47,29 +48,6 @@ constexpr int MO_COLLAPSED = 6, MO_NPATCHES = 7, MO_TOT = 8;   // [MO_TOT .. MO_
 constexpr int MO_SMALL = 16;
 // columns of the per-patch record
 constexpr int MO_FIRST = 0, MO_NTRIS = 1, MO_NFLIP = 2, MO_STATUS = 3, MO_BOUNDARY = 4, MO_NONMANIFOLD = 5, MO_FLIPPED_IN = 6;
-
-// one thread per triangle: its three half-edge keys, parent[x] = x for both of its nodes, the collapsed count
-__global__ void __launch_bounds__(256) mo_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
-                                                      uint32_t* __restrict__ vals, uint32_t* __restrict__ parent, uint64_t* __restrict__ small)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool col = false;
-    if (t < n) {
-        int32_t i[3];
-        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
-        parent[2 * t] = (uint32_t)(2 * t);
-        parent[2 * t + 1] = (uint32_t)(2 * t + 1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
-            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
-            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
-            vals[3 * t + c] = (uint32_t)(3 * t + c);
-        }
-    }
-    const unsigned long long m = __ballot(col);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MO_COLLAPSED], (unsigned long long)__popcll(m));
-}
 
 // one thread per sorted half-edge: the second member of a run of exactly two joins the two triangles on the doubled graph
 __global__ void __launch_bounds__(256) mo_union_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
@@ -121,20 +99,6 @@ __global__ void __launch_bounds__(256) mo_number_kernel(const int32_t* __restric
     if (t == n - 1) small[MO_NPATCHES] = (uint64_t)np;
 }
 
-// seg[s] = the first sorted position of patch s, seg[n_patches] = nvalid; the patch's first triangle
-__global__ void __launch_bounds__(256) mo_segment_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ stri, int64_t nvalid,
-                                                          int64_t np, int64_t* __restrict__ seg, int64_t* __restrict__ counts)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nvalid) return;
-    const uint32_t s = skey[i];
-    if (i == 0 || skey[i - 1] != s) {
-        seg[s] = i;
-        counts[(int64_t)s * MO_NCNT + MO_FIRST] = (int64_t)stri[i];
-    }
-    if (i == 0) seg[np] = nvalid;
-}
-
 // the shells' volume term of one triangle, in the header's operation order
 __device__ inline double mo_volume_term(const float* __restrict__ verts, int32_t i0, int32_t i1, int32_t i2, double rx, double ry, double rz)
 {
@@ -147,73 +111,24 @@ __device__ inline double mo_volume_term(const float* __restrict__ verts, int32_t
     return det / 6.0;
 }
 
-// block b: the sorted positions [256 b, 256 b + 256); the partial of (block b, patch s) goes to slot b + s (the shells' scheme)
-__global__ void __launch_bounds__(MO_BLOCK) mo_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
+// one thread per sorted triangle: its volume term into the segmented sum of its block (ms_block_sum: slot block + patch)
+__global__ void __launch_bounds__(MS_BLOCK) mo_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
                                                            const uint32_t* __restrict__ info, const uint32_t* __restrict__ skey,
                                                            const uint32_t* __restrict__ stri, int64_t nvalid, double rx, double ry, double rz,
                                                            double* __restrict__ partial)
 {
 #pragma clang fp contract(off)
-    __shared__ double s_v[MO_BLOCK];
-    __shared__ uint32_t s_key[MO_BLOCK];
-    const int j = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * MO_BLOCK + j;
+    const int64_t i = (int64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     const bool active = i < nvalid;
     uint32_t key = 0xffffffffu;
-    double v = 0.0;
+    double v[1] = {0.0};
     if (active) {
         key = skey[i];
         const int64_t t = (int64_t)stri[i];
-        v = mo_volume_term(verts, tris[3 * t], tris[3 * t + 1], tris[3 * t + 2], rx, ry, rz);
-        if (info[t] & 1u) v = -v;   // (a non-orientable patch has rel = 0 everywhere: the plain sum)
+        v[0] = mo_volume_term(verts, tris[3 * t], tris[3 * t + 1], tris[3 * t + 2], rx, ry, rz);
+        if (info[t] & 1u) v[0] = -v[0];   // (a non-orientable patch has rel = 0 everywhere: the plain sum)
     }
-    s_key[j] = key;
-    s_v[j] = v;
-    __syncthreads();
-    const bool head = active && (j == 0 || s_key[j - 1] != key);
-#pragma unroll
-    for (int d = 1; d < MO_BLOCK; d <<= 1) {
-        const bool take = active && j + d < MO_BLOCK && s_key[j + d] == key;
-        const double o = take ? s_v[j + d] : 0.0;
-        __syncthreads();
-        if (take) {
-            v = v + o;
-            s_v[j] = v;
-        }
-        __syncthreads();
-    }
-    if (head) partial[(int64_t)blockIdx.x + (int64_t)key] = v;
-}
-
-// one wavefront per patch: lane l sums the l-th run of `chunk` consecutive block partials in ascending block order, then the
-// run sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while that lane has a run)
-__global__ void __launch_bounds__(256) mo_combine_kernel(const int64_t* __restrict__ seg, int64_t np, const double* __restrict__ partial,
-                                                          double* __restrict__ vol, int64_t* __restrict__ counts)
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= np) return;   // (the whole wavefront)
-    const int64_t start = seg[s], end = seg[s + 1];
-    const int64_t b0 = start / MO_BLOCK, nb = (end - 1) / MO_BLOCK - b0 + 1;
-    const int64_t chunk = (nb + 63) / 64;
-    const int m = (int)((nb + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
-    double v = 0.0;
-    if (lane < m) {
-        const int64_t lo = lane * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
-        const double* p = partial + (b0 + lo + s);
-        v = p[0];
-        for (int64_t b = lo + 1; b < hi; ++b) v = v + p[b - lo];
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double o = __shfl_down(v, d, 64);
-        if (lane + d < m) v = v + o;
-    }
-    if (lane == 0) {
-        vol[s] = v;
-        counts[s * MO_NCNT + MO_NTRIS] = end - start;
-    }
+    ms_block_sum<1>(active, key, v, partial);
 }
 
 // one thread per triangle: n1 of its patch, kept in column MO_NFLIP until mo_decide_kernel turns it into the flipped count
@@ -322,18 +237,10 @@ __global__ void __launch_bounds__(256) mo_remain_kernel(const uint64_t* __restri
 }
 
 // work buffers of the orient calls, kept per device between calls (r2s_release_cache frees them)
-struct OrientWork {
-    DevBuf verts, tris, tris_out, flag, small, keys, keys2, vals, vals2, temp, parent, info, rflag, num, patch, flip, skey, skey2, sval, sval2,
-        seg, partial, counts, vol, gflag;
-    void release()
-    {
-        DevBuf* all[] = {&verts, &tris, &tris_out, &flag, &small, &keys, &keys2, &vals, &vals2, &temp, &parent, &info, &rflag, &num, &patch,
-                         &flip, &skey, &skey2, &sval, &sval2, &seg, &partial, &counts, &vol, &gflag};
-        for (DevBuf* b : all) b->release();
-    }
+struct OrientWork : MsHalfEdgeBufs {
+    Scoped verts, tris, tris_out, flag, small, parent, info, rflag, num, patch, flip, skey, skey2, sval, sval2, seg, partial, counts, vol, gflag;
 };
-std::mutex g_orient_mu;
-std::map<int, OrientWork> g_orient_work;
+PerDevice<OrientWork> g_orient_work;
 
 struct OrientTables {
     std::vector<int64_t> counts;   // [n][8]
@@ -357,13 +264,9 @@ int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         HIP_TRY(hipGetLastError());
     }
     const int64_t nh = 3 * n;
-    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    const uint64_t ckey = ms_collapsed_key(n_verts);
     size_t scan_bytes = 0;
     if (n > 0) {
-        ENSURE(w.keys, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.keys2, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.vals, sizeof(uint32_t) * (size_t)nh);
-        ENSURE(w.vals2, sizeof(uint32_t) * (size_t)nh);
         ENSURE(w.parent, sizeof(uint32_t) * 2 * (size_t)n);
         ENSURE(w.info, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
@@ -374,18 +277,12 @@ int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         ENSURE(w.skey2, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.sval, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.sval2, sizeof(uint32_t) * (size_t)n);
-        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
-        uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>(), *parent = w.parent.as<uint32_t>();
-        mo_key_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ckey, keys, vals, parent, small);
-        HIP_TRY(hipGetLastError());
-        const unsigned ebits = 33u + ms_bits((uint64_t)n_verts);   // (the collapsed key included)
-        size_t tb = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
+        uint32_t* parent = w.parent.as<uint32_t>();
         HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n,
                                         rocprim::plus<int32_t>(), st));
-        ENSURE(w.temp, std::max<size_t>(std::max(tb, scan_bytes), 16));
-        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
-        mo_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, parent);
+        int rc = ms_sort_half_edges<2, false>(w, d_tris, n, n_verts, parent, nullptr, small + MO_COLLAPSED, scan_bytes, st);
+        if (rc) return rc;
+        mo_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, parent);
         HIP_TRY(hipGetLastError());
         mo_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.info.as<uint32_t>(), w.rflag.as<int32_t>());
         HIP_TRY(hipGetLastError());
@@ -401,7 +298,7 @@ int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
     ms_ref_point(h_small, n_verts, r);
     const int64_t np = (int64_t)h_small[MO_NPATCHES], ncol = (int64_t)h_small[MO_COLLAPSED], nvalid = n - ncol;
     if (n > 0) {
-        const int64_t nblk = (nvalid + MO_BLOCK - 1) / MO_BLOCK;
+        const int64_t nblk = (nvalid + MS_BLOCK - 1) / MS_BLOCK;
         ENSURE(w.seg, sizeof(int64_t) * (size_t)(np + 1));
         ENSURE(w.partial, sizeof(double) * (size_t)(nblk + np + 1));
         ENSURE(w.counts, sizeof(int64_t) * MO_NCNT * (size_t)std::max<int64_t>(np, 1));
@@ -418,12 +315,13 @@ int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
             HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
             ENSURE(w.temp, std::max<size_t>(tb, 16));
             HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
-            mo_segment_kernel<<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, np, w.seg.as<int64_t>(), counts);
+            ms_segment_kernel<MO_NCNT><<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, np, w.seg.as<int64_t>(), counts);
             HIP_TRY(hipGetLastError());
-            mo_sum_kernel<<<(unsigned)nblk, MO_BLOCK, 0, st>>>(d_verts, d_tris, info, skey2, sval2, nvalid, r[0], r[1], r[2],
+            mo_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, info, skey2, sval2, nvalid, r[0], r[1], r[2],
                                                               w.partial.as<double>());
             HIP_TRY(hipGetLastError());
-            mo_combine_kernel<<<(unsigned)((np + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), np, w.partial.as<double>(), w.vol.as<double>(), counts);
+            ms_combine_kernel<1><<<(unsigned)((np + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), np, w.partial.as<double>(), w.vol.as<double>(),
+                                                                        counts + MO_NTRIS, MO_NCNT);
             HIP_TRY(hipGetLastError());
             mo_parity_kernel<<<ms_blocks(n), 256, 0, st>>>(n, info, patch, counts);
             HIP_TRY(hipGetLastError());
@@ -461,34 +359,11 @@ int orient_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_
     return 0;
 }
 
-OrientWork* orient_work_of_current_device(int& rc)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
-        return nullptr;
-    }
-    rc = 0;
-    return &g_orient_work[dev];
-}
-
 }  // namespace
 
 namespace r2s_int {
 
-void release_orient_work()
-{
-    std::lock_guard<std::mutex> lock(g_orient_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_orient_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_orient_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_orient_work() { g_orient_work.release_all(); }
 
 }  // namespace r2s_int
 
@@ -501,8 +376,8 @@ int r2s_mesh_orient(const float* verts, int64_t n_verts, const int32_t* tris, in
     int rc = orient_args(verts, n_verts, tris, n_tris, flags, tris_out, n_patches, ref_point, totals);
     if (rc) return rc;
     if ((rc = check_mesh_host("mesh_orient", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_orient_mu);
-    OrientWork* w = orient_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_orient_work.mu);
+    OrientWork* w = g_orient_work.current(rc);
     if (rc) return rc;
     if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
     ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)));
@@ -553,8 +428,8 @@ int r2s_mesh_orient_dev(const float* d_verts, int64_t n_verts, const int32_t* d_
         return fail(R2S_ERR_ARG, "mesh_orient: null tables or negative patch_capacity");
     if ((rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_orient_mu);
-    OrientWork* w = orient_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_orient_work.mu);
+    OrientWork* w = g_orient_work.current(rc);
     if (rc) return rc;
     if ((rc = check_mesh_dev("mesh_orient", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
     int64_t np = 0, tot[8];

@@ -4,7 +4,8 @@
 // is on segments, nodes take the place of edges.
 //   sx_height_kernel   h(v) per vertex;  ms_bounds_kernel (r2s_mesh_graph.hpp): the box of the vertices -> the reference point
 //   sx_tri_kernel      per triangle the range of crossed levels (two binary searches in `levels`) and its three half-edge keys
-//                      as in the shells' ms_key_kernel -> rocPRIM exclusive scan (int64): segment offsets; radix sort of pairs
+//                      (ms_half_edge_keys, r2s_mesh_graph.hpp) -> rocPRIM exclusive scan (int64): segment offsets; radix sort
+//                      of pairs
 //   sx_expand_kernel   per segment its triangle (binary search in the offsets) and level, parent = successor = itself
 //   sx_link_kernel     one thread per sorted half-edge with the member before it in the same run: both see the level range of
 //                      the EDGE, so for every level in it the segments of the two triangles are united (integer union-find,
@@ -18,14 +19,15 @@
 //                      ceil(log2(longest closed loop)) rounds
 //   -> stable radix sort of the segment ids by contour -> sx_start_kernel -> sx_place_kernel: closed contours are laid out by
 //      rank, the others keep ascending segment id
-//   sx_sum_kernel      blocks of 256 output positions: the two points and the 7 terms of every segment, a segmented fixed tree
-//                      in LDS, one partial per (block, contour);  sx_combine_kernel: one wavefront per contour, as the shells'
+//   sx_sum_kernel      blocks of 256 output positions: the two points and the 7 terms of every segment -> ms_block_sum<7>
+//                      (r2s_mesh_graph.hpp): a segmented fixed tree in LDS, one partial per (block, contour);
+//                      ms_combine_kernel<7> (r2s_mesh_graph.hpp): one wavefront per contour
 // Integer counts use integer atomics (one per wavefront and contour); no floating-point atomic and no library reduction
 // touches the Float64 sums.
 // Registers of the gfx950 build (hipcc -O3 -ffp-contract=off, -Rpass-analysis=kernel-resource-usage), VGPRs / scratch bytes:
-//   sx_height 8 / 0, sx_tri 21 / 0, sx_expand 13 / 0, sx_link 22 / 0, sx_flatten 12 / 0, sx_rootkey 8 / 0, sx_contour 10 / 0,
+//   sx_height 8 / 0, sx_tri 28 / 0, sx_expand 13 / 0, sx_link 22 / 0, sx_flatten 12 / 0, sx_rootkey 8 / 0, sx_contour 10 / 0,
 //   sx_number 10 / 0, sx_node 22 / 0, sx_closed 23 / 0, sx_rank_init 6 / 0, sx_jump 8 / 0, sx_start 6 / 0, sx_place 12 / 0,
-//   sx_sum 63 / 0 (15 KiB of LDS), sx_combine 38 / 0, ms_bounds 18 / 0: no kernel uses scratch, all run 8 waves per SIMD.
+//   sx_sum 63 / 0 (15 KiB of LDS), ms_combine<7> 42 / 0, ms_bounds 18 / 0: no kernel uses scratch, all run 8 waves per SIMD.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -34,7 +36,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -46,7 +47,6 @@ using namespace r2s_int;
 
 namespace {
 
-constexpr int SX_BLOCK = 256;   // output positions per block of the Float64 sums (the header's definition)
 constexpr int SX_NSUM = 7, SX_NCNT = 8;
 constexpr int64_t SX_MAX_TRIS = (int64_t)1 << 30, SX_MAX_LEVELS = (int64_t)1 << 30, SX_MAX_SEGS = 0x7fffffffll;
 // slots of the small device array: [0..5] the bounds, then
@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(256) sx_tri_kernel(const int32_t* __restrict__
     if (t == n) cnt[n] = 0;
     if (t < n) {
         int32_t i[3];
-        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
+        col = ms_half_edge_keys(tris, t, ckey, keys, vals, i);
         int32_t f = 0, e = 0;
         if (!col) {
             const double h0 = h[i[0]], h1 = h[i[1]], h2 = h[i[2]];
@@ -98,16 +98,8 @@ __global__ void __launch_bounds__(256) sx_tri_kernel(const int32_t* __restrict__
         }
         first[t] = f;
         cnt[t] = (int64_t)(e - f);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
-            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
-            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
-            vals[3 * t + c] = (uint32_t)(3 * t + c);
-        }
     }
-    const unsigned long long m = __ballot(col);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[SX_COLLAPSED], (unsigned long long)__popcll(m));
+    ms_count_collapsed(col, &small[SX_COLLAPSED]);
 }
 
 // one thread per segment: its triangle is the last one whose offset is <= s (a triangle without segments shares its offset
@@ -361,9 +353,9 @@ __device__ inline void sx_node_point(int32_t iu, int32_t iw, double hu, double h
     }
 }
 
-// block b: the output positions [256 b, 256 b + 256); the partial of (block b, contour c) goes to slot b + c (both only grow
-// along the output order, so the slots are distinct; there are fewer than blocks + contours of them)
-__global__ void __launch_bounds__(SX_BLOCK) sx_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
+// one thread per output position: the two points of its segment, and its 7 terms into the segmented sum of its block
+// (ms_block_sum: slot block + contour)
+__global__ void __launch_bounds__(MS_BLOCK) sx_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
                                                            const double* __restrict__ h, const double* __restrict__ levels,
                                                            const uint32_t* __restrict__ skey, const uint32_t* __restrict__ order,
                                                            const int32_t* __restrict__ tri_of, const int32_t* __restrict__ level_of, int64_t nseg,
@@ -371,10 +363,7 @@ __global__ void __launch_bounds__(SX_BLOCK) sx_sum_kernel(const float* __restric
                                                            int32_t* __restrict__ seg_tri, double* __restrict__ points, double* __restrict__ partial)
 {
 #pragma clang fp contract(off)
-    __shared__ double s_v[SX_NSUM][SX_BLOCK];
-    __shared__ uint32_t s_key[SX_BLOCK];
-    const int j = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * SX_BLOCK + j;
+    const int64_t i = (int64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     const bool active = i < nseg;
     uint32_t key = 0xffffffffu;
     double v[SX_NSUM];
@@ -425,89 +414,15 @@ __global__ void __launch_bounds__(SX_BLOCK) sx_sum_kernel(const float* __restric
         v[5] = w * (Ay + By);
         v[6] = w * (Az + Bz);
     }
-    s_key[j] = key;
-#pragma unroll
-    for (int q = 0; q < SX_NSUM; ++q) s_v[q][j] = v[q];
-    __syncthreads();
-    const bool head = active && (j == 0 || s_key[j - 1] != key);
-#pragma unroll
-    for (int d = 1; d < SX_BLOCK; d <<= 1) {
-        const bool take = active && j + d < SX_BLOCK && s_key[j + d] == key;
-        double o[SX_NSUM];
-#pragma unroll
-        for (int q = 0; q < SX_NSUM; ++q) o[q] = take ? s_v[q][j + d] : 0.0;
-        __syncthreads();
-        if (take) {
-#pragma unroll
-            for (int q = 0; q < SX_NSUM; ++q) {
-                v[q] = v[q] + o[q];
-                s_v[q][j] = v[q];
-            }
-        }
-        __syncthreads();
-    }
-    if (head) {
-        double* out = partial + ((int64_t)blockIdx.x + (int64_t)key) * SX_NSUM;
-#pragma unroll
-        for (int q = 0; q < SX_NSUM; ++q) out[q] = v[q];
-    }
-}
-
-// one wavefront per contour: lane l sums the l-th run of `chunk` consecutive block partials in ascending block order, then the
-// run sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while that lane has a run)
-__global__ void __launch_bounds__(256) sx_combine_kernel(const int64_t* __restrict__ start, int64_t nc, const double* __restrict__ partial,
-                                                          double* __restrict__ sums)
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= nc) return;   // (the whole wavefront)
-    const int64_t lo_pos = start[c], end = start[c + 1];
-    const int64_t b0 = lo_pos / SX_BLOCK, nb = (end - 1) / SX_BLOCK - b0 + 1;
-    const int64_t chunk = (nb + 63) / 64;
-    const int m = (int)((nb + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
-    double v[SX_NSUM];
-#pragma unroll
-    for (int q = 0; q < SX_NSUM; ++q) v[q] = 0.0;
-    if (lane < m) {
-        const int64_t lo = lane * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
-        const double* p = partial + (b0 + lo + c) * SX_NSUM;
-#pragma unroll
-        for (int q = 0; q < SX_NSUM; ++q) v[q] = p[q];
-        for (int64_t b = lo + 1; b < hi; ++b) {
-            p += SX_NSUM;
-#pragma unroll
-            for (int q = 0; q < SX_NSUM; ++q) v[q] = v[q] + p[q];
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int q = 0; q < SX_NSUM; ++q) {
-            const double o = __shfl_down(v[q], d, 64);
-            if (lane + d < m) v[q] = v[q] + o;
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < SX_NSUM; ++q) sums[c * SX_NSUM + q] = v[q];
-    }
+    ms_block_sum<SX_NSUM>(active, key, v, partial);
 }
 
 // work buffers of the section calls, kept per device between calls (r2s_release_cache frees them)
-struct SectionWork {
-    DevBuf verts, tris, flag, small, levels, h, first, cnt, offset, keys, keys2, vals, vals2, temp, tri_of, level_of, parent, succ, rflag,
-        num, rkeys, rkeys2, skey, skey2, sval, sval2, pp0, pp1, closed, start, order, partial, counts, sums, seg_tri, points;
-    void release()
-    {
-        DevBuf* all[] = {&verts, &tris, &flag, &small, &levels, &h, &first, &cnt, &offset, &keys, &keys2, &vals, &vals2, &temp, &tri_of,
-                         &level_of, &parent, &succ, &rflag, &num, &rkeys, &rkeys2, &skey, &skey2, &sval, &sval2, &pp0, &pp1, &closed,
-                         &start, &order, &partial, &counts, &sums, &seg_tri, &points};
-        for (DevBuf* b : all) b->release();
-    }
+struct SectionWork : MsHalfEdgeBufs {
+    Scoped verts, tris, flag, small, levels, h, first, cnt, offset, tri_of, level_of, parent, succ, rflag, num, rkeys, rkeys2, skey, skey2,
+        sval, sval2, pp0, pp1, closed, start, order, partial, counts, sums, seg_tri, points;
 };
-std::mutex g_section_mu;
-std::map<int, SectionWork> g_section_work;
+PerDevice<SectionWork> g_section_work;
 
 struct SectionTables {
     std::vector<int64_t> start;    // [n_contours + 1] (empty without contours)
@@ -536,7 +451,7 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
     }
     const int64_t nh = 3 * n;
     const int32_t nl = (int32_t)n_levels;
-    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    const uint64_t ckey = ms_collapsed_key(n_verts);
     int64_t nseg = 0;
     if (n > 0) {
         ENSURE(w.levels, sizeof(double) * (size_t)std::max<int64_t>(n_levels, 1));
@@ -593,7 +508,7 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
         uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
         uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>(), *parent = w.parent.as<uint32_t>(), *succ = w.succ.as<uint32_t>();
         int32_t *rflag = w.rflag.as<int32_t>(), *num = w.num.as<int32_t>();
-        const unsigned ebits = std::min(33u + ms_bits((uint64_t)n_verts), 64u);   // (the collapsed key included)
+        const unsigned ebits = ms_key_bits(n_verts);
         size_t tb = 0, tb2 = 0;
         HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
         HIP_TRY(rocprim::exclusive_scan(nullptr, tb2, rflag, num, (int32_t)0, (size_t)nseg, rocprim::plus<int32_t>(), st));
@@ -612,7 +527,7 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
         HIP_TRY(hipStreamSynchronize(st));
         nc = (int64_t)last[0] + last[1];
 
-        const int64_t nblk = (nseg + SX_BLOCK - 1) / SX_BLOCK;
+        const int64_t nblk = (nseg + MS_BLOCK - 1) / MS_BLOCK;
         ENSURE(w.rkeys, sizeof(uint64_t) * (size_t)nc);
         ENSURE(w.rkeys2, sizeof(uint64_t) * (size_t)nc);
         ENSURE(w.closed, sizeof(int32_t) * (size_t)nc);
@@ -658,11 +573,12 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
         sx_place_kernel<<<ms_blocks(nseg), 256, 0, st>>>(skey2, sval2, nseg, w.closed.as<int32_t>(), counts, w.start.as<int64_t>(), pin,
                                                        w.order.as<uint32_t>());
         HIP_TRY(hipGetLastError());
-        sx_sum_kernel<<<(unsigned)nblk, SX_BLOCK, 0, st>>>(d_verts, d_tris, h, levels, skey2, w.order.as<uint32_t>(), w.tri_of.as<int32_t>(),
+        sx_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, h, levels, skey2, w.order.as<uint32_t>(), w.tri_of.as<int32_t>(),
                                                           w.level_of.as<int32_t>(), nseg, nrm[0], nrm[1], nrm[2], r[0], r[1], r[2],
                                                           w.seg_tri.as<int32_t>(), w.points.as<double>(), w.partial.as<double>());
         HIP_TRY(hipGetLastError());
-        sx_combine_kernel<<<(unsigned)((nc + 3) / 4), 256, 0, st>>>(w.start.as<int64_t>(), nc, w.partial.as<double>(), w.sums.as<double>());
+        ms_combine_kernel<SX_NSUM><<<(unsigned)((nc + 3) / 4), 256, 0, st>>>(w.start.as<int64_t>(), nc, w.partial.as<double>(), w.sums.as<double>(),
+                                                                          nullptr, 0);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -707,34 +623,11 @@ int table_args(const void* start, const void* counts, const void* sums, int64_t 
     return 0;
 }
 
-SectionWork* work_of_current_device(int& rc)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
-        return nullptr;
-    }
-    rc = 0;
-    return &g_section_work[dev];
-}
-
 }  // namespace
 
 namespace r2s_int {
 
-void release_section_work()
-{
-    std::lock_guard<std::mutex> lock(g_section_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_section_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_section_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_section_work() { g_section_work.release_all(); }
 
 }  // namespace r2s_int
 
@@ -746,8 +639,8 @@ int r2s_mesh_sections(const float* verts, int64_t n_verts, const int32_t* tris, 
     int rc = sections_args(verts, n_verts, tris, n_tris, normal, levels, n_levels, n_contours, n_segments, ref_point, totals);
     if (rc) return rc;
     if ((rc = check_mesh_host("mesh_sections", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_section_mu);
-    SectionWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_section_work.mu);
+    SectionWork* w = g_section_work.current(rc);
     if (rc) return rc;
     if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
     int64_t nc = 0, nseg = 0, tot[8];
@@ -809,8 +702,8 @@ int r2s_mesh_sections_dev(const float* d_verts, int64_t n_verts, const int32_t* 
     if ((rc = table_args(d_contour_start, d_counts, d_sums, contour_capacity, d_seg_tri, d_seg_points, segment_capacity))) return rc;
     if ((rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_section_mu);
-    SectionWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_section_work.mu);
+    SectionWork* w = g_section_work.current(rc);
     if (rc) return rc;
     if ((rc = check_mesh_dev("mesh_sections", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
     int64_t nc = 0, nseg = 0, tot[8];

@@ -1,16 +1,18 @@
 // Mesh shells: the connected components of a triangle mesh over shared edges, the edge classes, and per shell the integer
 // record and the Float64 area / volume / moments (include/rho2sdf_hip.h, r2s_mesh_shells; DESIGN.md "Mesh shells").
 //   ms_bounds_kernel   the box of all vertices (integer atomics on order-preserving bit patterns) -> the reference point
-//   ms_key_kernel      one half-edge key per corner, (min << 33) | (max << 1) | direction, payload 3t + c; collapsed
-//                      triangles get a key above every real one -> rocPRIM radix sort of pairs
+//   ms_sort_half_edges (r2s_mesh_graph.hpp) ms_key_kernel<1, true>: one half-edge key per corner, (min << 33) | (max << 1) |
+//                      direction, payload 3t + c, parent[t] = t, the referenced-vertex flags; collapsed triangles get a key
+//                      above every real one -> rocPRIM radix sort of pairs
 //   ms_union_kernel    one union per run member with the member before it (integer union-find: the larger root is hooked
 //                      under the smaller with a compare-and-swap, paths are halved with atomicMin, so the final root of a
 //                      component is its smallest triangle whatever the race)
 //   ms_flatten_kernel  label = root, root flags -> rocPRIM exclusive scan (integers) -> ms_number_kernel: shell numbers
-//   -> stable radix sort of the triangle ids by shell number -> ms_segment_kernel: where each shell starts
-//   ms_sum_kernel      blocks of 256 consecutive sorted triangles, the 11 terms per triangle, a segmented fixed tree in LDS,
-//                      one partial per (block, shell) at slot block + shell
-//   ms_combine_kernel  one wavefront per shell: up to 64 equal runs of its block partials in ascending order, then a fixed tree
+//   -> stable radix sort of the triangle ids by shell number -> ms_segment_kernel (r2s_mesh_graph.hpp): where each shell starts
+//   ms_sum_kernel      blocks of 256 consecutive sorted triangles, the 11 terms per triangle -> ms_block_sum<11>
+//                      (r2s_mesh_graph.hpp): a segmented fixed tree in LDS, one partial per (block, shell) at slot block + shell
+//   ms_combine_kernel<11> (r2s_mesh_graph.hpp) one wavefront per shell: up to 64 equal runs of its block partials in ascending
+//                      order, then a fixed tree; n_tris of the shell
 //   ms_edge_kernel     the sorted edge runs again: class of each run, counted into the shell of its first half-edge
 //   ms_vkey_kernel     (shell << 32) | vertex per corner -> radix sort of keys -> ms_vcount_kernel: distinct vertices per shell
 //   ms_totals_kernel   the column sums of the integer table and the number of referenced vertices
@@ -24,7 +26,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -36,36 +37,11 @@ using namespace r2s_int;
 
 namespace {
 
-constexpr int MS_BLOCK = 256;   // triangles per block of the Float64 sums (the header's definition)
 constexpr int MS_NSUM = 11, MS_NCNT = 8;
 constexpr int64_t MS_MAX_TRIS = (int64_t)1 << 30;
 // slots of the small device array: [0..5] the bounds, then
 constexpr int MS_COLLAPSED = 6, MS_NSHELLS = 7, MS_TOT = 8;   // [MS_TOT .. MS_TOT + 4]: edges, boundary, flipped, non-manifold, vertices
 constexpr int MS_SMALL = 16;
-
-// one thread per triangle: its three half-edge keys, parent[t] = t, the referenced-vertex flags, the collapsed count
-__global__ void __launch_bounds__(256) ms_key_kernel(const int32_t* __restrict__ tris, int64_t n, uint64_t ckey, uint64_t* __restrict__ keys,
-                                                      uint32_t* __restrict__ vals, uint32_t* __restrict__ parent, int32_t* __restrict__ vflag,
-                                                      uint64_t* __restrict__ small)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool col = false;
-    if (t < n) {
-        int32_t i[3];
-        col = ms_collapsed(tris, t, i[0], i[1], i[2]);
-        parent[t] = (uint32_t)t;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const uint32_t u = (uint32_t)i[c], w = (uint32_t)i[c == 2 ? 0 : c + 1];
-            const uint64_t mn = u < w ? u : w, mx = u < w ? w : u;
-            keys[3 * t + c] = col ? ckey : ((mn << 33) | (mx << 1) | (uint64_t)(u > w));
-            vals[3 * t + c] = (uint32_t)(3 * t + c);
-            if (!col) vflag[i[c]] = 1;
-        }
-    }
-    const unsigned long long m = __ballot(col);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&small[MS_COLLAPSED], (unsigned long long)__popcll(m));
-}
 
 // one thread per sorted half-edge: joins its triangle to that of the member before it in the same run
 __global__ void __launch_bounds__(256) ms_union_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t nh,
@@ -109,20 +85,6 @@ __global__ void __launch_bounds__(256) ms_number_kernel(const int32_t* __restric
     if (t == n - 1) small[MS_NSHELLS] = (uint64_t)nsh;
 }
 
-// seg[s] = the first sorted position of shell s, seg[n_shells] = nvalid; the shell's first triangle
-__global__ void __launch_bounds__(256) ms_segment_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ stri, int64_t nvalid,
-                                                          int64_t nsh, int64_t* __restrict__ seg, int64_t* __restrict__ counts)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nvalid) return;
-    const uint32_t s = skey[i];
-    if (i == 0 || skey[i - 1] != s) {
-        seg[s] = i;
-        counts[(int64_t)s * MS_NCNT] = (int64_t)stri[i];
-    }
-    if (i == 0) seg[nsh] = nvalid;
-}
-
 // the 11 terms of one triangle in the header's operation order
 __device__ inline void ms_terms(const float* __restrict__ verts, int32_t i0, int32_t i1, int32_t i2, double rx, double ry, double rz, double v[MS_NSUM])
 {
@@ -148,17 +110,13 @@ __device__ inline void ms_terms(const float* __restrict__ verts, int32_t i0, int
     v[10] = (det * (((Ay * Az + By * Bz) + Cy * Cz) + Sy * Sz)) / 120.0;
 }
 
-// block b: the sorted positions [256 b, 256 b + 256); the partial of (block b, shell s) goes to slot b + s (both only grow
-// along the sorted order, so the slots are distinct; there are fewer than blocks + shells of them)
+// one thread per sorted triangle: its 11 terms into the segmented sum of its block (ms_block_sum: slot block + shell)
 __global__ void __launch_bounds__(MS_BLOCK) ms_sum_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tris,
                                                            const uint32_t* __restrict__ skey, const uint32_t* __restrict__ stri, int64_t nvalid,
                                                            double rx, double ry, double rz, double* __restrict__ partial)
 {
 #pragma clang fp contract(off)
-    __shared__ double s_v[MS_NSUM][MS_BLOCK];
-    __shared__ uint32_t s_key[MS_BLOCK];
-    const int j = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * MS_BLOCK + j;
+    const int64_t i = (int64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     const bool active = i < nvalid;
     uint32_t key = 0xffffffffu;
     double v[MS_NSUM];
@@ -169,74 +127,7 @@ __global__ void __launch_bounds__(MS_BLOCK) ms_sum_kernel(const float* __restric
         const int64_t t = (int64_t)stri[i];
         ms_terms(verts, tris[3 * t], tris[3 * t + 1], tris[3 * t + 2], rx, ry, rz, v);
     }
-    s_key[j] = key;
-#pragma unroll
-    for (int q = 0; q < MS_NSUM; ++q) s_v[q][j] = v[q];
-    __syncthreads();
-    const bool head = active && (j == 0 || s_key[j - 1] != key);
-#pragma unroll
-    for (int d = 1; d < MS_BLOCK; d <<= 1) {
-        const bool take = active && j + d < MS_BLOCK && s_key[j + d] == key;
-        double o[MS_NSUM];
-#pragma unroll
-        for (int q = 0; q < MS_NSUM; ++q) o[q] = take ? s_v[q][j + d] : 0.0;
-        __syncthreads();
-        if (take) {
-#pragma unroll
-            for (int q = 0; q < MS_NSUM; ++q) {
-                v[q] = v[q] + o[q];
-                s_v[q][j] = v[q];
-            }
-        }
-        __syncthreads();
-    }
-    if (head) {
-        double* out = partial + ((int64_t)blockIdx.x + (int64_t)key) * MS_NSUM;
-#pragma unroll
-        for (int q = 0; q < MS_NSUM; ++q) out[q] = v[q];
-    }
-}
-
-// one wavefront per shell: lane l sums the l-th run of `chunk` consecutive block partials in ascending block order, then the
-// run sums are joined in a fixed tree (round d = 1, 2, .., 32: lane l takes lane l + d while that lane has a run)
-__global__ void __launch_bounds__(256) ms_combine_kernel(const int64_t* __restrict__ seg, int64_t nsh, const double* __restrict__ partial,
-                                                          double* __restrict__ sums, int64_t* __restrict__ counts)
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= nsh) return;   // (the whole wavefront)
-    const int64_t start = seg[s], end = seg[s + 1];
-    const int64_t b0 = start / MS_BLOCK, nb = (end - 1) / MS_BLOCK - b0 + 1;
-    const int64_t chunk = (nb + 63) / 64;
-    const int m = (int)((nb + chunk - 1) / chunk);   // lanes with a run: 1 .. 64
-    double v[MS_NSUM];
-#pragma unroll
-    for (int q = 0; q < MS_NSUM; ++q) v[q] = 0.0;
-    if (lane < m) {
-        const int64_t lo = lane * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
-        const double* p = partial + (b0 + lo + s) * MS_NSUM;
-#pragma unroll
-        for (int q = 0; q < MS_NSUM; ++q) v[q] = p[q];
-        for (int64_t b = lo + 1; b < hi; ++b) {
-            p += MS_NSUM;
-#pragma unroll
-            for (int q = 0; q < MS_NSUM; ++q) v[q] = v[q] + p[q];
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int q = 0; q < MS_NSUM; ++q) {
-            const double o = __shfl_down(v[q], d, 64);
-            if (lane + d < m) v[q] = v[q] + o;
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < MS_NSUM; ++q) sums[s * MS_NSUM + q] = v[q];
-        counts[s * MS_NCNT + 1] = end - start;
-    }
+    ms_block_sum<MS_NSUM>(active, key, v, partial);
 }
 
 // one thread per sorted half-edge; the first member of a run classifies it and counts it into the shell of its triangle
@@ -307,18 +198,10 @@ __global__ void __launch_bounds__(256) ms_totals_kernel(const int64_t* __restric
 }
 
 // work buffers of the shell calls, kept per device between calls (r2s_release_cache frees them)
-struct ShellWork {
-    DevBuf verts, tris, flag, small, keys, keys2, vals, vals2, temp, parent, rflag, num, shell, skey, skey2, sval, sval2, seg, partial,
-        counts, sums, vflag;
-    void release()
-    {
-        DevBuf* all[] = {&verts, &tris, &flag, &small, &keys, &keys2, &vals, &vals2, &temp, &parent, &rflag, &num, &shell, &skey, &skey2,
-                         &sval, &sval2, &seg, &partial, &counts, &sums, &vflag};
-        for (DevBuf* b : all) b->release();
-    }
+struct ShellWork : MsHalfEdgeBufs {
+    Scoped verts, tris, flag, small, parent, rflag, num, shell, skey, skey2, sval, sval2, seg, partial, counts, sums, vflag;
 };
-std::mutex g_shell_mu;
-std::map<int, ShellWork> g_shell_work;
+PerDevice<ShellWork> g_shell_work;
 
 struct ShellTables {
     std::vector<int64_t> counts;   // [n][8]
@@ -341,12 +224,8 @@ int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         HIP_TRY(hipGetLastError());
     }
     const int64_t nh = 3 * n;
-    const uint64_t ckey = (uint64_t)n_verts << 33;   // above every key of a real edge (min < n_verts)
+    const uint64_t ckey = ms_collapsed_key(n_verts);
     if (n > 0) {
-        ENSURE(w.keys, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.keys2, sizeof(uint64_t) * (size_t)nh);
-        ENSURE(w.vals, sizeof(uint32_t) * (size_t)nh);
-        ENSURE(w.vals2, sizeof(uint32_t) * (size_t)nh);
         ENSURE(w.parent, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
         ENSURE(w.num, sizeof(int32_t) * (size_t)n);
@@ -357,17 +236,12 @@ int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         ENSURE(w.sval2, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.vflag, sizeof(int32_t) * (size_t)std::max<int64_t>(n_verts, 1));
         HIP_TRY(hipMemsetAsync(w.vflag.p, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(n_verts, 1), st));
-        uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
-        uint32_t *vals = w.vals.as<uint32_t>(), *vals2 = w.vals2.as<uint32_t>(), *parent = w.parent.as<uint32_t>();
-        ms_key_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, ckey, keys, vals, parent, w.vflag.as<int32_t>(), small);
-        HIP_TRY(hipGetLastError());
-        const unsigned ebits = 33u + ms_bits((uint64_t)n_verts);   // (the collapsed key included)
-        size_t tb = 0, tb2 = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
+        uint32_t* parent = w.parent.as<uint32_t>();
+        size_t tb2 = 0;
         HIP_TRY(rocprim::exclusive_scan(nullptr, tb2, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
-        ENSURE(w.temp, std::max<size_t>(std::max(tb, tb2), 16));
-        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, std::min(ebits, 64u), st));
-        ms_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, parent);
+        int rc = ms_sort_half_edges<1, true>(w, d_tris, n, n_verts, parent, w.vflag.as<int32_t>(), small + MS_COLLAPSED, tb2, st);
+        if (rc) return rc;
+        ms_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, parent);
         HIP_TRY(hipGetLastError());
         ms_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.rflag.as<int32_t>());
         HIP_TRY(hipGetLastError());
@@ -397,11 +271,12 @@ int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         HIP_TRY(rocprim::radix_sort_keys(nullptr, tb2, keys, keys2, (size_t)nh, 0u, vbits, st));
         ENSURE(w.temp, std::max<size_t>(std::max(tb, tb2), 16));
         HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
-        ms_segment_kernel<<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, nsh, w.seg.as<int64_t>(), counts);
+        ms_segment_kernel<MS_NCNT><<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, nsh, w.seg.as<int64_t>(), counts);
         HIP_TRY(hipGetLastError());
         ms_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, skey2, sval2, nvalid, r[0], r[1], r[2], w.partial.as<double>());
         HIP_TRY(hipGetLastError());
-        ms_combine_kernel<<<(unsigned)((nsh + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), nsh, w.partial.as<double>(), w.sums.as<double>(), counts);
+        ms_combine_kernel<MS_NSUM><<<(unsigned)((nsh + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), nsh, w.partial.as<double>(), w.sums.as<double>(),
+                                                                           counts + 1, MS_NCNT);
         HIP_TRY(hipGetLastError());
         // (keys2 / vals2 still hold the sorted half-edges)
         ms_edge_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, w.vals2.as<uint32_t>(), nh, ckey, w.shell.as<int32_t>(), counts);
@@ -433,34 +308,11 @@ int shells_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_
     return 0;
 }
 
-ShellWork* work_of_current_device(int& rc)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
-        return nullptr;
-    }
-    rc = 0;
-    return &g_shell_work[dev];
-}
-
 }  // namespace
 
 namespace r2s_int {
 
-void release_shell_work()
-{
-    std::lock_guard<std::mutex> lock(g_shell_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_shell_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_shell_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_shell_work() { g_shell_work.release_all(); }
 
 }  // namespace r2s_int
 
@@ -472,8 +324,8 @@ int r2s_mesh_shells(const float* verts, int64_t n_verts, const int32_t* tris, in
     int rc = shells_args(verts, n_verts, tris, n_tris, n_shells, ref_point, totals);
     if (rc) return rc;
     if ((rc = check_mesh_host("mesh_shells", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_shell_mu);
-    ShellWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_shell_work.mu);
+    ShellWork* w = g_shell_work.current(rc);
     if (rc) return rc;
     if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
     int64_t nsh = 0, tot[8];
@@ -517,8 +369,8 @@ int r2s_mesh_shells_dev(const float* d_verts, int64_t n_verts, const int32_t* d_
         return fail(R2S_ERR_ARG, "mesh_shells: null tables or negative shell_capacity");
     if ((rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_shell_mu);
-    ShellWork* w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_shell_work.mu);
+    ShellWork* w = g_shell_work.current(rc);
     if (rc) return rc;
     if ((rc = check_mesh_dev("mesh_shells", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
     int64_t nsh = 0, tot[8];

@@ -27,7 +27,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 
 #include "r2s_common.hpp"
@@ -232,17 +231,10 @@ __global__ void __launch_bounds__(256) mw_tout_kernel(const int32_t* __restrict_
 
 // work buffers of the weld calls, kept per device between calls (r2s_release_cache frees them)
 struct WeldWork {
-    DevBuf verts, tris, verts_out, tris_out, flag, small, k32, k32b, k64, g64, s64, idx, idx2, temp, hp, hp2, rep, is_rep, num, class_of,
-        is_dup, keep, tnum, used, unum, final_of, vert_map, tri_map;
-    void release()
-    {
-        DevBuf* all[] = {&verts, &tris, &verts_out, &tris_out, &flag, &small, &k32, &k32b, &k64, &g64, &s64, &idx, &idx2, &temp, &hp,
-                         &hp2, &rep, &is_rep, &num, &class_of, &is_dup, &keep, &tnum, &used, &unum, &final_of, &vert_map, &tri_map};
-        for (DevBuf* b : all) b->release();
-    }
+    Scoped verts, tris, verts_out, tris_out, flag, small, k32, k32b, k64, g64, s64, idx, idx2, temp, hp, hp2, rep, is_rep, num, class_of, is_dup,
+        keep, tnum, used, unum, final_of, vert_map, tri_map;
 };
-std::mutex g_weld_mu;
-std::map<int, WeldWork> g_weld_work;
+PerDevice<WeldWork> g_weld_work;
 
 // sorts n (z / high word, index) records of w.k32 / w.k64 / w.idx by the 64-bit word, then the 32-bit word, stably: the order
 // ends in w.idx, the sorted 64-bit words in w.s64
@@ -391,34 +383,11 @@ int weld_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tr
     return 0;
 }
 
-WeldWork* weld_work_of_current_device(int& rc)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        rc = fail(R2S_ERR_HIP, "hipGetDevice failed");
-        return nullptr;
-    }
-    rc = 0;
-    return &g_weld_work[dev];
-}
-
 }  // namespace
 
 namespace r2s_int {
 
-void release_weld_work()
-{
-    std::lock_guard<std::mutex> lock(g_weld_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_weld_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_weld_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_weld_work() { g_weld_work.release_all(); }
 
 }  // namespace r2s_int
 
@@ -431,8 +400,8 @@ int r2s_mesh_weld(const float* verts, int64_t n_verts, const int32_t* tris, int6
     int rc = weld_args(verts, n_verts, tris, n_tris, snap, flags, verts_out, tris_out, totals, &nt);
     if (rc) return rc;
     if ((rc = check_mesh_host("mesh_weld", verts, n_verts, tris, tris ? nt : 0)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_weld_mu);
-    WeldWork* w = weld_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_weld_work.mu);
+    WeldWork* w = g_weld_work.current(rc);
     if (rc) return rc;
     if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, tris ? nt : 0, false, nullptr))) return rc;
     ENSURE(w->verts_out, vert_bytes(std::max<int64_t>(n_verts, 1)));
@@ -458,8 +427,8 @@ int r2s_mesh_weld_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tr
     if (rc) return rc;
     if ((rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_weld_mu);
-    WeldWork* w = weld_work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_weld_work.mu);
+    WeldWork* w = g_weld_work.current(rc);
     if (rc) return rc;
     if ((rc = check_mesh_dev("mesh_weld", d_verts, n_verts, d_tris, d_tris ? nt : 0, w->flag, st))) return rc;
     int64_t tot[8];

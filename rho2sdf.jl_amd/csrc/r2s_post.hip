@@ -437,23 +437,13 @@ static int ccl_table(const uint32_t* L, const uint32_t* size, uint32_t n, DevBuf
 // the work arrays of remove_artifacts_dev / analyze_components_dev, kept between calls per device (r2s_release_cache
 // frees them): allocating and freeing 1.6 GB per call cost as much as a kernel of the stage
 struct CclWork {
-    DevBuf L, size, roots, cnt, blk, tab;
+    Scoped L, size, roots, cnt, blk, tab;
 };
-static std::mutex g_ccl_mutex;
-static std::map<int, CclWork> g_ccl_work;
-static void release_ccl_work()
-{
-    std::lock_guard<std::mutex> lock(g_ccl_mutex);
-    for (auto& kv : g_ccl_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.L.release(); kv.second.size.release(); kv.second.roots.release(); kv.second.cnt.release();
-        kv.second.blk.release(); kv.second.tab.release();
-    }
-    g_ccl_work.clear();
-}
+static r2s_int::PerDevice<CclWork> g_ccl_work;
+static void release_ccl_work() { g_ccl_work.release_all(); }
 
 // The labelling of {sdf >= threshold} shared by removal and analysis, on the device's work arrays (the caller holds
-// g_ccl_mutex): afterwards L[v] is v's head (or root, or NOLABEL) and size[r] the size of every root r.  h[8] comes back
+// g_ccl_work.mu): afterwards L[v] is v's head (or root, or NOLABEL) and size[r] the size of every root r.  h[8] comes back
 // with [4] = number of roots and, when `counters`, [0] largest size, [1] smallest root having it, [3] interior count
 // (from the list of roots, or from the sweeps over all counters when the list overflowed).
 static int ccl_label(const double* d_sdf, uint32_t n, int nx, int ny, int nz, double threshold, hipStream_t st, CclWork& Wk,
@@ -514,8 +504,8 @@ static int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double thresho
     const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_ccl_mutex);   // (one call at a time uses the device's work arrays)
-    CclWork& Wk = g_ccl_work[dev];
+    std::lock_guard<std::mutex> lock(g_ccl_work.mu);   // (one call at a time uses the device's work arrays)
+    CclWork& Wk = g_ccl_work.of(dev);
     uint32_t h[8];
     int rc = ccl_label(d_sdf, n, nx, ny, nz, threshold, st, Wk, true, h);
     if (rc) return rc;
@@ -549,8 +539,8 @@ static int analyze_components_dev(const double* d_sdf, const r2s_grid* g, double
     const int nx = (int)g->N[0] + 1, ny = (int)g->N[1] + 1, nz = (int)g->N[2] + 1;
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_ccl_mutex);
-    CclWork& Wk = g_ccl_work[dev];
+    std::lock_guard<std::mutex> lock(g_ccl_work.mu);
+    CclWork& Wk = g_ccl_work.of(dev);
     uint32_t h[8];
     int rc = ccl_label(d_sdf, n, nx, ny, nz, threshold, st, Wk, false, h);
     if (rc) return rc;

@@ -26,7 +26,6 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -231,16 +230,10 @@ __global__ void __launch_bounds__(256) md_tile_kernel(const float* __restrict__ 
 
 // work buffers of the distance calls, kept per device between calls (r2s_release_cache frees them)
 struct DistWork {
-    DevBuf cnt, off, list, flag;            // binning
-    DevBuf verts, tris, out, idx, field;   // host-pointer variants / the extracted surface
-    void release()
-    {
-        DevBuf* all[] = {&cnt, &off, &list, &flag, &verts, &tris, &out, &idx, &field};
-        for (DevBuf* b : all) b->release();
-    }
+    Scoped cnt, off, list, flag;            // binning
+    Scoped verts, tris, out, idx, field;   // host-pointer variants / the extracted surface
 };
-std::mutex g_dist_mu;
-std::map<int, DistWork> g_dist_work;
+PerDevice<DistWork> g_dist_work;
 
 // [0] ms surface extraction, [1] ms binning (count, scan, fills), [2] ms tile kernel, [3] tile/triangle pairs, [4] batches,
 // [5] triangles, [6] tiles, [7] tiles with triangles
@@ -250,19 +243,7 @@ thread_local double g_dist_stats[8];
 
 namespace r2s_int {
 
-void release_dist_work()
-{
-    std::lock_guard<std::mutex> lock(g_dist_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    for (auto& kv : g_dist_work) {
-        (void)hipSetDevice(kv.first);
-        kv.second.release();
-    }
-    g_dist_work.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+void release_dist_work() { g_dist_work.release_all(); }
 
 int lattice_args(const char* who, const int64_t dims[3], const double origin[3], double spacing, double band)
 {
@@ -445,13 +426,6 @@ int mesh_distance_core(const float* d_verts, const int32_t* d_tris, int64_t n_tr
     return 0;
 }
 
-DistWork& work_of_current_device(int& rc)
-{
-    int dev = 0;
-    rc = hipGetDevice(&dev) == hipSuccess ? 0 : fail(R2S_ERR_HIP, "hipGetDevice failed");
-    return g_dist_work[dev];
-}
-
 // the iso-surface of the device field into w.verts / w.tris (count, size the buffers, fill); nv / nt: its vertices / triangles
 int extract_surface(const char* who, const void* d_values, bool f32, const int64_t dims[3], const double origin[3], double spacing,
                     double iso, hipStream_t st, DistWork& w, int64_t& nv, int64_t& nt)
@@ -506,9 +480,10 @@ int redistance_call(const char* who, bool banded, bool host, const void* values,
     if (std::isnan(iso)) return fail(R2S_ERR_ARG, "%s: iso is NaN", who);
     if (!values || !out) return fail(R2S_ERR_ARG, "%s: null values / output", who);
     if ((rc = host ? use_device(device) : check_device(0))) return rc;
-    std::lock_guard<std::mutex> lock(g_dist_mu);
-    DistWork& w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_dist_work.mu);
+    DistWork* wp = g_dist_work.current(rc);
     if (rc) return rc;
+    DistWork& w = *wp;
     const size_t bytes = real_bytes(is_float32) * (size_t)(dims[0] * dims[1] * dims[2]);
     const void* d_values = values;
     void* d_out = out;
@@ -537,9 +512,10 @@ int r2s_mesh_distance(const float* verts, int64_t n_verts, const int32_t* tris, 
     if (rc || (rc = mesh_args("mesh_distance", verts, n_verts, tris, n_tris))) return rc;
     if (!dist_out) return fail(R2S_ERR_ARG, "mesh_distance: null output");
     if ((rc = check_mesh_host("mesh_distance", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_dist_mu);
-    DistWork& w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_dist_work.mu);
+    DistWork* wp = g_dist_work.current(rc);
     if (rc) return rc;
+    DistWork& w = *wp;
     const size_t nvox = (size_t)(dims[0] * dims[1] * dims[2]), esz = real_bytes(out_is_float32);
     ENSURE(w.out, esz * nvox);
     if (closest_tri_out) ENSURE(w.idx, sizeof(int32_t) * nvox);
@@ -561,9 +537,10 @@ int r2s_mesh_distance_dev(const float* d_verts, int64_t n_verts, const int32_t* 
     if (rc || (rc = mesh_args("mesh_distance", d_verts, n_verts, d_tris, n_tris))) return rc;
     if (!d_dist_out) return fail(R2S_ERR_ARG, "mesh_distance: null output");
     if ((rc = check_device(0))) return rc;
-    std::lock_guard<std::mutex> lock(g_dist_mu);
-    DistWork& w = work_of_current_device(rc);
+    std::lock_guard<std::mutex> lock(g_dist_work.mu);
+    DistWork* wp = g_dist_work.current(rc);
     if (rc) return rc;
+    DistWork& w = *wp;
     const hipStream_t st = (hipStream_t)stream;
     if ((rc = check_mesh_dev("mesh_distance", d_verts, n_verts, d_tris, n_tris, w.flag, st))) return rc;
     g_dist_stats[0] = 0.0;

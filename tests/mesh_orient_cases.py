@@ -66,6 +66,11 @@ def ribbon_alternating(n=3000):
     return V, reverse(T, np.arange(1, n, 2))
 
 
+def _first(mesh, n):
+    """the mesh with its first n triangles only"""
+    return mesh[0], mesh[1][:n]
+
+
 def ribbon_alternating_shuffled():
     return S.permuted(ribbon_alternating(), 21)[0]
 
@@ -80,6 +85,11 @@ HAND = {"empty": S.empty, "one_triangle": S.one_triangle, "all_collapsed": S.all
         "torus": lambda: S.torus(100, 100)}
 EXTRACTED = ("sphere33", "nested41")
 ALL = tuple(HAND) + EXTRACTED
+# one patch of 65 blocks of 256 sorted triangles (the first with two block partials per lane of the combine) and one of 129
+# blocks (the last lane's run is short): named for tests/test_mesh_segsum_gpu.py, too long for the plain-Python restatement of
+# every test that walks ALL
+LONG = {"ribbon16385": lambda: _first(ribbon_alternating(16386), 16385),
+        "ribbon32769": lambda: _first(ribbon_alternating(32770), 32769)}
 TIE_FREE = ("cube_one_reversed", "moebius_and_tetrahedron", "torus", "nested41")   # (their scrambled copies too)
 
 _cases = {}
@@ -89,7 +99,7 @@ def case(name, scrambled=False):
     """the named mesh; scrambled: a seeded random 30 % of its triangles have corners 1 and 2 swapped"""
     key = (name, bool(scrambled))
     if key not in _cases:
-        V, T = HAND[name]() if name in HAND else S.extracted(name)
+        V, T = HAND[name]() if name in HAND else LONG[name]() if name in LONG else S.extracted(name)
         if scrambled:
             pick = np.random.default_rng(zlib.crc32(name.encode())).random(len(T)) < 0.3
             T = reverse(T, pick)
