@@ -8,10 +8,70 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 
 namespace r2s {
 
 #define R2S_DEV __device__ __forceinline__
+
+// fmin / fmax as the bare v_min_f64 / v_max_f64.  For fmin(a, b) the compiler puts a self-max in front of every operand it
+// cannot prove canonical (anything that comes through a phi node of a lane machine, LDS or memory): v_max_f64 x, x, x only
+// turns a signalling NaN into a quiet one, which the IEEE-mode min / max that follows would need to return the OTHER operand
+// for it.  For every other input - numbers, infinities, either zero, quiet NaNs - the instruction alone returns the same
+// bits as the pair: one quiet-NaN operand gives the other operand, two give NaN, and (+0, -0) is decided by the same
+// instruction as before.  Signalling NaNs are the only inputs that change behaviour, and none can reach these helpers: no
+// arithmetic instruction produces one (every result NaN is quiet), the library never writes a NaN bit pattern itself, and
+// its inputs are validated finite numbers.  The asm statements are not volatile: the compiler may still merge, hoist and
+// drop them like any pure expression.  fmax_abs_hw and fmax_neg_hw keep the source modifiers the compiler would have folded.
+// For per-lane operands only: an asm result is a vector register, so a wave-uniform min / max (the gather kernels, the
+// sign pass) would be copied out of its scalar registers and its branches would become divergent - those keep fmin / fmax.
+#if defined(__HIP_DEVICE_COMPILE__)
+R2S_DEV double fmin_hw(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+R2S_DEV double fmax_hw(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+R2S_DEV double fmax_abs_hw(double a, double b)   // fmax(|a|, |b|)
+{
+    double r;
+    asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+R2S_DEV double fmax_neg_hw(double a, double b)   // fmax(a, -b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, -%2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// constant operands are written into the instruction (inline constants of the encoding): a "v" operand would cost moves
+R2S_DEV double clamp1_hw(double x)   // fmin(fmax(x, -1.0), 1.0)
+{
+    double r;
+    asm("v_max_f64 %0, %1, -1.0" : "=v"(r) : "v"(x));
+    asm("v_min_f64 %0, %1, 1.0" : "=v"(r) : "v"(r));
+    return r;
+}
+R2S_DEV double fmin2_hw(double x)   // fmin(2.0, x)
+{
+    double r;
+    asm("v_min_f64 %0, 2.0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+#else   // host pass over the shared headers: the same functions in plain C++
+__host__ __device__ inline double fmin_hw(double a, double b) { return ::fmin(a, b); }
+__host__ __device__ inline double fmax_hw(double a, double b) { return ::fmax(a, b); }
+__host__ __device__ inline double fmax_abs_hw(double a, double b) { return ::fmax(::fabs(a), ::fabs(b)); }
+__host__ __device__ inline double fmax_neg_hw(double a, double b) { return ::fmax(a, -b); }
+__host__ __device__ inline double clamp1_hw(double x) { return ::fmin(::fmax(x, -1.0), 1.0); }
+__host__ __device__ inline double fmin2_hw(double x) { return ::fmin(2.0, x); }
+#endif
 
 // One pre-gathered HEX8 element: X[:, IEN[:, el]] and rho_n[IEN[:, el]] plus the
 // element AABB (SignDetection.jl:16-21) and max nodal density (SignDetection.jl:33-36).
@@ -458,7 +518,7 @@ R2S_DEV int qp_pattern(int pat, const Sym3& H, const double g[3], const double a
             if (!(o.d[i] >= lo[i] - 1e-12 && o.d[i] <= hi[i] + 1e-12)) {
                 ok = false;
                 const double below = (lo[i] - 1e-12) - o.d[i], above = o.d[i] - (hi[i] + 1e-12);
-                const double viol = fmax(below, above);
+                const double viol = fmax_hw(below, above);
                 if (viol > worst) { worst = viol; o.next = pat + ((above > below) ? 2 : 1) * pw[i]; }
             }
         }
@@ -1502,8 +1562,8 @@ R2S_DEV void iso_lane_bounds(const IsoLane& s, double lo[3], double hi[3])
 {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        lo[i] = fmax(-1.0 - s.xi[i], -s.Delta);
-        hi[i] = fmin(1.0 - s.xi[i], s.Delta);
+        lo[i] = fmax_neg_hw(-1.0 - s.xi[i], s.Delta);
+        hi[i] = fmin_hw(1.0 - s.xi[i], s.Delta);
     }
 }
 
@@ -1567,8 +1627,8 @@ R2S_DEV void iso_lane_eval(const ER& E, double rt, double rtol, IsoLane& s)
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const double p = s.a[i] * lo[i], q = s.a[i] * hi[i];
-        mplus += fmax(p, q);
-        mminus += fmin(p, q);
+        mplus += fmax_hw(p, q);
+        mminus += fmin_hw(p, q);
     }
     const double trG = G[0][0] + G[1][1] + G[2][2];
     const double aa2 = dot3(s.a[0], s.a[1], s.a[2], s.a[0], s.a[1], s.a[2]);
@@ -1591,8 +1651,8 @@ R2S_DEV void iso_lane_eval(const ER& E, double rt, double rtol, IsoLane& s)
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const double p = s.a[i] * (-1.0 - s.xi[i]), q = s.a[i] * (1.0 - s.xi[i]);
-            bp += fmax(p, q);
-            bm += fmin(p, q);
+            bp += fmax_hw(p, q);
+            bm += fmin_hw(p, q);
         }
         const bool stall = (e > 0.0) ? !(bp > 0.05 * e) : !(bm < 0.05 * e);
         double Gd[3];
@@ -1624,7 +1684,7 @@ R2S_DEV void iso_lane_qp(IsoLane& s)
         // pattern when the step is accepted - until then xi, mu, Delta, pat are the state at the iteration's start,
         // which is what a hand-over passes on)
 #pragma unroll
-        for (int i = 0; i < 3; ++i) s.d[i] = fmin(fmax(o.d[i], lo[i]), hi[i]);
+        for (int i = 0; i < 3; ++i) s.d[i] = fmin_hw(fmax_hw(o.d[i], lo[i]), hi[i]);
         s.lam_new = o.lam;
         s.phase = ISO_FINISH;
     } else if (rc == 0) {
@@ -1639,7 +1699,7 @@ R2S_DEV void iso_lane_qp(IsoLane& s)
 template <class ER>
 R2S_DEV void iso_lane_finish(const ER& E, double rt, double rtol, IsoLane& s)
 {
-    const double dmax = fmax(fabs(s.d[0]), fmax(fabs(s.d[1]), fabs(s.d[2])));
+    const double dmax = fmax_abs_hw(s.d[0], fmax_abs_hw(s.d[1], s.d[2]));
     const bool near_feas = (fabs(s.c) <= 1e4 * rtol);
     if (!(dmax > R2S_ISO_TOL)) {
         if (s.corner && !near_feas) { s.phase = ISO_BAIL; return; }   // stuck off the iso-surface: restoration
@@ -1648,7 +1708,7 @@ R2S_DEV void iso_lane_finish(const ER& E, double rt, double rtol, IsoLane& s)
         const double pred_c = fabs(s.c) - fabs(s.c + ad);
         const double gd = dot3(s.g[0], s.g[1], s.g[2], s.d[0], s.d[1], s.d[2]);
         const double mu_keep = (fabs(s.c) <= 1e10 * rtol) ? 0.5 : 1.0;
-        double mu_t = s.corner ? s.mu : fmax(mu_keep * s.mu, 2.0 * fabs(s.lam_new));
+        double mu_t = s.corner ? s.mu : fmax_hw(mu_keep * s.mu, 2.0 * fabs(s.lam_new));
         if (s.corner && pred_c > 0.0) {
             // a step that only buys feasibility: the merit function pays for the growth of f including its curvature
             const double need = 2.0 * fma(0.5, s.se, gd) / pred_c;
@@ -1667,11 +1727,11 @@ R2S_DEV void iso_lane_finish(const ER& E, double rt, double rtol, IsoLane& s)
         const double phi0 = fma(mu_t, fabs(s.c), s.f);
         double xt[3], ft, ct;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) xt[i] = fmin(fmax(fma(1.0, s.d[i], s.xi[i]), -1.0), 1.0);
+        for (int i = 0; i < 3; ++i) xt[i] = clamp1_hw(fma(1.0, s.d[i], s.xi[i]));
         iso_eval_fc(E, s.x, rt, xt, ft, ct);
         if (!(fma(mu_t, fabs(ct), ft) <= fma(1e-4 * 1.0, D, phi0))) { s.phase = ISO_BAIL; return; }   // correction / back-tracking
         s.mu = mu_t;
-        s.Delta = fmin(2.0, fmax(s.Delta, 2.0 * dmax));
+        s.Delta = fmin2_hw(fmax_hw(s.Delta, 2.0 * dmax));
         if (!s.corner) s.pat = s.p;
         s.seen = s.seen || (s.c == 0.0);
 #pragma unroll
@@ -1681,9 +1741,9 @@ R2S_DEV void iso_lane_finish(const ER& E, double rt, double rtol, IsoLane& s)
         return;
     }
     // converged: the last (tiny) step is applied
-    s.Delta = fmin(2.0, fmax(s.Delta, 2.0 * dmax));
+    s.Delta = fmin2_hw(fmax_hw(s.Delta, 2.0 * dmax));
 #pragma unroll
-    for (int i = 0; i < 3; ++i) s.xi[i] = fmin(fmax(fma(1.0, s.d[i], s.xi[i]), -1.0), 1.0);
+    for (int i = 0; i < 3; ++i) s.xi[i] = clamp1_hw(fma(1.0, s.d[i], s.xi[i]));
     s.phase = ISO_DONE;
 }
 
