@@ -1293,6 +1293,12 @@ int r2s_import_mat(const char *filename, r2s_vtu_mesh *out);
  * Must not run concurrently with any other call of the library (it destroys the sessions other calls lock). */
 void r2s_release_cache(void);
 
+/* ---- diagnostics ---- */
+/* bytes of device memory the library's own buffers hold at this moment, over all devices and threads (what the calls in
+ * flight, the caches and the live handles have allocated and not yet freed); after r2s_release_cache with no handle alive
+ * and no call running it is what it was before the first call */
+int64_t r2s_live_device_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

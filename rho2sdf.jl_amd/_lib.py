@@ -140,6 +140,7 @@ SYMBOLS = [
                                       ctypes.POINTER(ctypes.c_int32), c_float_p]),
     ("r2s_last_rbf_plan", None, [c_int32_p]),
     ("r2s_release_cache", None, []),
+    ("r2s_live_device_bytes", ctypes.c_int64, []),
     ("r2s_export_vtu", ctypes.c_int, [ctypes.c_char_p] + _MESH + [ctypes.c_int32, ctypes.c_int32, c_double_p]),
     ("r2s_import_vtu", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(R2SVtuMesh)]),
     ("r2s_free_vtu_mesh", None, [ctypes.POINTER(R2SVtuMesh)]),

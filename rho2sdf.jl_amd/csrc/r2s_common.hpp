@@ -2,9 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <string>
+#include <utility>
 
 #include "../../include/rho2sdf_hip.h"
 
@@ -27,15 +30,33 @@ inline int fail(int code, const char* fmt, ...)
                         __FILE__, __LINE__);                                               \
     } while (0)
 
+// bytes of device memory that live DevBufs hold (r2s_live_device_bytes); touched on growth and free only
+inline std::atomic<int64_t> g_live_device_bytes{0};
+
+// A device buffer.  It owns what it points to: it frees in its destructor (on whichever device is current when it dies)
+// and moves by stealing the pointer.  An object of static storage duration must not hold one by value - the HIP runtime
+// may be gone before a static destructor runs (see PerDevice in r2s_internal.hpp).
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p;
+            cap = o.cap;
+            o.p = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int ensure(size_t bytes)
     {
         if (bytes <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         size_t want = bytes + bytes / 4 + 256;
         if (hipMalloc(&p, want) != hipSuccess) {
             (void)hipGetLastError();
@@ -43,24 +64,25 @@ struct DevBuf {
             want = bytes;
         }
         cap = want;
+        g_live_device_bytes += (int64_t)cap;
         return 0;
     }
     int ensure_exact(size_t bytes)   // no growth margin (very large buffers)
     {
         if (bytes <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         if (hipMalloc(&p, bytes) != hipSuccess) {
             (void)hipGetLastError();
             return -1;
         }
         cap = bytes;
+        g_live_device_bytes += (int64_t)cap;
         return 0;
     }
     void release()
     {
         if (p) (void)hipFree(p);
+        g_live_device_bytes -= (int64_t)cap;
         p = nullptr;
         cap = 0;
     }
@@ -69,13 +91,44 @@ struct DevBuf {
     template <class T>
     const T* as() const { return reinterpret_cast<const T*>(p); }
 };
-// a DevBuf that frees itself (on whichever device is current when it dies)
-struct Scoped : DevBuf {
-    Scoped() = default;
-    Scoped(const Scoped&) = delete;
-    Scoped& operator=(const Scoped&) = delete;
-    ~Scoped() { release(); }
+
+// a pinned host block that frees itself
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
+    hipError_t ensure(size_t bytes, unsigned flags = hipHostMallocDefault)
+    {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&p, bytes, flags);
+        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return e; }
+        cap = bytes;
+        return hipSuccess;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
 };
+
+// an event / a stream that destroys itself: created into .h, read as the plain handle
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
 
 inline int check_device(int device)
 {

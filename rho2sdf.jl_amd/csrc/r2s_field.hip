@@ -446,7 +446,6 @@ int project_dev(const r2s_rbf_field* f, float* d_points, int64_t n, int max_iter
 // host arrays <-> temporaries on the field's device
 struct HostIo {
     DevBuf b[5];
-    void release() { for (DevBuf& x : b) x.release(); }
     int up(int i, const void* src, size_t bytes)
     {
         ENSURE(b[i], bytes);
@@ -528,9 +527,8 @@ void r2s_rbf_field_destroy(r2s_rbf_field* f)
     if (!f) return;
     int cur = -1;
     const bool sw = hipGetDevice(&cur) == hipSuccess && cur != f->device && hipSetDevice(f->device) == hipSuccess;
-    f->w.release(); f->cx.release(); f->cy.release(); f->cz.release();
+    delete f;   // (its buffers free themselves, on the field's device)
     if (sw) (void)hipSetDevice(cur);
-    delete f;
 }
 
 int r2s_rbf_field_eval_dev(const r2s_rbf_field* f, const float* d_points, int64_t n, float* d_val, float* d_grad, int32_t* d_taps,
@@ -557,7 +555,6 @@ int r2s_rbf_field_eval(const r2s_rbf_field* f, const float* points, int64_t n, f
     if (!rc) rc = io.down(1, val_out, 4 * N);
     if (!rc) rc = io.down(2, grad_out, 12 * N);
     if (!rc) rc = io.down(3, taps_out, 4 * N);
-    io.release();
     return rc;
 }
 
@@ -588,7 +585,6 @@ int r2s_rbf_field_hessian(const r2s_rbf_field* f, const float* points, int64_t n
     if (!rc) rc = io.down(2, grad_out, 12 * N);
     if (!rc) rc = io.down(3, taps_out, 4 * N);
     if (!rc) rc = io.down(4, hess_out, 24 * N);
-    io.release();
     return rc;
 }
 
@@ -619,7 +615,6 @@ int r2s_rbf_field_curvature(const r2s_rbf_field* f, const float* points, int64_t
     if (!rc) rc = io.down(1, curv_out, 16 * N);
     if (!rc) rc = io.down(2, grad_out, 12 * N);
     if (!rc) rc = io.down(3, hess_out, 24 * N);
-    io.release();
     return rc;
 }
 
@@ -644,7 +639,6 @@ int r2s_rbf_field_normals(const r2s_rbf_field* f, const float* points, int64_t n
     if (!rc) rc = io.up(1, nullptr, 12 * N);
     if (!rc) rc = normals_dev(f, io.b[0].as<float>(), n, io.b[1].as<float>(), nullptr);
     if (!rc) rc = io.down(1, normals_out, 12 * N);
-    io.release();
     return rc;
 }
 
@@ -674,7 +668,6 @@ int r2s_rbf_field_project(const r2s_rbf_field* f, float* points_inout, int64_t n
     if (!rc) rc = io.down(1, status_out, 4 * N);
     if (!rc) rc = io.down(2, resid_out, 4 * N);
     if (!rc) rc = io.down(3, iters_out, 4 * N);
-    io.release();
     return rc;
 }
 

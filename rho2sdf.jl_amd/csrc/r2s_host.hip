@@ -28,6 +28,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <pthread.h>
 #include <sched.h>
@@ -172,6 +173,22 @@ class CopyPool {
 
 constexpr size_t STAGE_BYTES = 32u << 20;
 
+struct HostZone {   // a pinned landing zone from r2s_host_alloc that frees itself
+    void* p = nullptr;
+    size_t cap = 0;
+    HostZone() = default;
+    HostZone(const HostZone&) = delete;
+    HostZone& operator=(const HostZone&) = delete;
+    ~HostZone() { r2s_host_free(p); }
+    bool regrow(size_t bytes)   // a fresh block of `bytes` (the contents are not kept)
+    {
+        r2s_host_free(p);
+        cap = (p = r2s_host_alloc(bytes)) ? bytes : 0;
+        if (!p) (void)hipGetLastError();
+        return p != nullptr;
+    }
+};
+
 struct HostSession {
     int device = 0;
     std::mutex mu;   // one host call at a time per device
@@ -180,17 +197,15 @@ struct HostSession {
     DevBuf pre_ws[7];   // node -> element lists and centroids of the nodal densities, element volumes (r2s_rho2sdf)
     DevBuf out[4];   // dist, sign, sdf, xp
     DevBuf fine, raw, slab;
-    void* stage[2] = {nullptr, nullptr};
-    hipStream_t cs = nullptr;   // copy stream
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> evf;   // one per forwarded chunk of the smoothed field (r2s_rho2sdf)
+    PinnedBuf stage[2];
+    Stream cs;   // copy stream
+    Event ev[2];
+    std::vector<Event> evf;        // one per forwarded chunk of the smoothed field (r2s_rho2sdf)
     void* rbf_ws = nullptr;        // buffers of the smoothing stage, kept between r2s_rho2sdf calls
-    CopyPool* pool = nullptr;
+    std::unique_ptr<CopyPool> pool;
     DevBuf pk;                     // packed tiles of the sparse download (device)
-    void* pk_host = nullptr;       // ... and their pinned landing zone
-    size_t pk_host_cap = 0;
-    void* fine_host = nullptr;     // pinned landing zone of the smoothed field before its level shift (r2s_rho2sdf)
-    size_t fine_host_cap = 0;
+    HostZone pk_host;              // ... and their pinned landing zone
+    HostZone fine_host;            // pinned landing zone of the smoothed field before its level shift (r2s_rho2sdf)
     r2s_int::IsoWork iso;          // work buffers of the iso-surface of the smoothed field (r2s_rho2sdf, extract_surface)
 
     int init(int dev)
@@ -199,7 +214,7 @@ struct HostSession {
         HIP_TRY(hipSetDevice(dev));
         int rc = r2s_plan_create(dev, &plan);
         if (rc) return rc;
-        HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&cs.h, hipStreamNonBlocking));
         {   // direct xGMI peer copies for the multi-device gather (no-op on a one-GPU box)
             int n = 0;
             if (hipGetDeviceCount(&n) != hipSuccess) n = 0;
@@ -210,40 +225,16 @@ struct HostSession {
             (void)hipGetLastError();
         }
         for (int i = 0; i < 2; ++i) {
-            HIP_TRY(hipHostMalloc(&stage[i], STAGE_BYTES, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+            HIP_TRY(stage[i].ensure(STAGE_BYTES));
+            HIP_TRY(hipEventCreateWithFlags(&ev[i].h, hipEventDisableTiming));
         }
         return 0;
     }
-    void release()
+    ~HostSession()   // (runs before the members free themselves)
     {
         (void)hipSetDevice(device);
-        if (plan) r2s_plan_destroy(plan);
-        plan = nullptr;
-        DevBuf* all[] = {&dX, &dI, &dR, &dE, &out[0], &out[1], &out[2], &out[3], &fine, &raw, &slab, &pk,
-                         &pre_ws[0], &pre_ws[1], &pre_ws[2], &pre_ws[3], &pre_ws[4], &pre_ws[5], &pre_ws[6]};
-        for (DevBuf* b : all) b->release();
-        iso.release();
-        if (pk_host) r2s_host_free(pk_host);
-        pk_host = nullptr;
-        if (fine_host) r2s_host_free(fine_host);
-        fine_host = nullptr;
-        fine_host_cap = 0;
-        pk_host_cap = 0;
-        for (int i = 0; i < 2; ++i) {
-            if (stage[i]) (void)hipHostFree(stage[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-            stage[i] = nullptr;
-            ev[i] = nullptr;
-        }
-        for (hipEvent_t e : evf) (void)hipEventDestroy(e);
-        evf.clear();
+        r2s_plan_destroy(plan);
         r2s_int::rbf_workspace_release(rbf_ws);
-        rbf_ws = nullptr;
-        if (cs) (void)hipStreamDestroy(cs);
-        cs = nullptr;
-        delete pool;
-        pool = nullptr;
     }
 };
 
@@ -280,7 +271,6 @@ int get_session(int key, HostSession** out)
     HostSession* S = new HostSession();
     int rc = S->init(device);
     if (rc) {
-        S->release();
         delete S;
         return rc;
     }
@@ -351,7 +341,7 @@ void ensure_pool(HostSession* S)
     // (default: 16, or the CPU quota of the container if that is smaller; a host without a quota: half of its CPUs at most)
     const unsigned all = std::max(1u, std::thread::hardware_concurrency());
     static const bool spread_env = !(getenv("R2S_HOST_SPREAD") && atoi(getenv("R2S_HOST_SPREAD")) == 0);
-    S->pool = new CopyPool(env > 0 ? std::min(env, 64) : (int)std::min(16u, std::max(2u, hw < all ? hw : all / 2)), spread_env);
+    S->pool.reset(new CopyPool(env > 0 ? std::min(env, 64) : (int)std::min(16u, std::max(2u, hw < all ? hw : all / 2)), spread_env));
 }
 
 // device -> host.  Pinned destination: plain DMA.  Pageable: DMA into the two staging buffers, each staged chunk
@@ -371,15 +361,15 @@ int download(HostSession* S, const std::vector<Segment>& segs, bool pinned)
             chunks.push_back({g.dst + o, g.src + o, std::min(STAGE_BYTES, g.bytes - o)});
     const size_t n = chunks.size();
     if (!n) return 0;
-    HIP_TRY(hipMemcpyAsync(S->stage[0], chunks[0].src, chunks[0].bytes, hipMemcpyDeviceToHost, S->cs));
+    HIP_TRY(hipMemcpyAsync(S->stage[0].p, chunks[0].src, chunks[0].bytes, hipMemcpyDeviceToHost, S->cs));
     HIP_TRY(hipEventRecord(S->ev[0], S->cs));
     for (size_t c = 0; c < n; ++c) {
         if (c + 1 < n) {   // (its staging buffer was drained by the copy of chunk c-1, which has returned)
-            HIP_TRY(hipMemcpyAsync(S->stage[(c + 1) & 1], chunks[c + 1].src, chunks[c + 1].bytes, hipMemcpyDeviceToHost, S->cs));
+            HIP_TRY(hipMemcpyAsync(S->stage[(c + 1) & 1].p, chunks[c + 1].src, chunks[c + 1].bytes, hipMemcpyDeviceToHost, S->cs));
             HIP_TRY(hipEventRecord(S->ev[(c + 1) & 1], S->cs));
         }
         HIP_TRY(hipEventSynchronize(S->ev[c & 1]));
-        S->pool->copy(chunks[c].dst, S->stage[c & 1], chunks[c].bytes);
+        S->pool->copy(chunks[c].dst, S->stage[c & 1].p, chunks[c].bytes);
     }
     return 0;
 }
@@ -490,17 +480,9 @@ int run_host_device(const HostCall& c, int device, int G, int r, r2s_stats* stat
         const size_t bytes = off_mids + (((size_t)nm * 4 + 7) & ~(size_t)7);
         auto bail = [&](int code) { S->pool->wait(); return code; };
         if (S->pk.ensure(std::max<size_t>(bytes, 8))) return bail(fail(R2S_ERR_NOMEM, "hipMalloc of the packed tiles failed"));
-        if (S->pk_host_cap < bytes) {
-            if (S->pk_host) r2s_host_free(S->pk_host);
-            S->pk_host = nullptr;
-            S->pk_host_cap = 0;
-            const size_t want = bytes + bytes / 4 + 4096;
-            if (!(S->pk_host = r2s_host_alloc(want))) {   // (pages interleaved over the NUMA nodes: the scatter threads are spread)
-                (void)hipGetLastError();
-                return bail(fail(R2S_ERR_NOMEM, "hipHostMalloc of the landing zone of the packed tiles failed"));
-            }
-            S->pk_host_cap = want;
-        }
+        // (pages interleaved over the NUMA nodes: the scatter threads are spread)
+        if (S->pk_host.cap < bytes && !S->pk_host.regrow(bytes + bytes / 4 + 4096))
+            return bail(fail(R2S_ERR_NOMEM, "hipHostMalloc of the landing zone of the packed tiles failed"));
         char* const dpk = (char*)S->pk.p;
         int64_t nf2 = 0, nm2 = 0;
         rc = r2s_plan_pack_tiles2_dev(S->plan, S->out[2].as<double>(), (double*)dpk, (uint32_t*)(dpk + off_ids), nf,
@@ -519,11 +501,11 @@ int run_host_device(const HostCall& c, int device, int G, int r, r2s_stats* stat
         static const int nt_force = getenv("R2S_HOST_NT") ? atoi(getenv("R2S_HOST_NT")) : -1;
         const bool nt_env = nt_force >= 0 ? nt_force != 0 : is_pinned(c.sdf);
         while (S->evf.size() < (size_t)NPIECE) {   // (an event joins the list only once it exists)
-            hipEvent_t e = nullptr;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(fail(R2S_ERR_HIP, "hipEventCreate failed"));
-            S->evf.push_back(e);
+            Event e;
+            if (hipEventCreateWithFlags(&e.h, hipEventDisableTiming) != hipSuccess) return bail(fail(R2S_ERR_HIP, "hipEventCreate failed"));
+            S->evf.push_back(std::move(e));
         }
-        char* const hpk_w = (char*)S->pk_host;
+        char* const hpk_w = (char*)S->pk_host.p;
         const int64_t f0[NPIECE + 1] = {0, 0, nf}, m0[NPIECE + 1] = {0, nm, nm};   // phase 0: masks, phase 1: band tiles
         if (bytes > off_masks && hipMemcpyAsync(hpk_w + off_masks, dpk + off_masks, bytes - off_masks, hipMemcpyDeviceToHost, S->cs) != hipSuccess)
             return bail(fail(R2S_ERR_HIP, "copy of the packed tiles failed"));
@@ -534,7 +516,7 @@ int run_host_device(const HostCall& c, int device, int G, int r, r2s_stats* stat
         const double t3 = now_ms();
         S->pool->wait();   // the sentinel is everywhere
         const double t4 = now_ms();
-        const char* const hpk = (const char*)S->pk_host;
+        const char* const hpk = (const char*)S->pk_host.p;
         double* const out = c.sdf;
         const int ntx = (nx + 3) / 4, nty = (ny + 3) / 4;
         const int64_t nzz = nz;
@@ -709,10 +691,9 @@ void release_host_sessions()
 {
     std::lock_guard<std::mutex> l(g_sessions_mu);
     for (auto& kv : g_sessions) {
-        std::lock_guard<std::mutex> l2(kv.second->mu);
-        kv.second->release();
+        { std::lock_guard<std::mutex> l2(kv.second->mu); }   // (a call that still holds the session finishes first)
+        delete kv.second;
     }
-    for (auto& kv : g_sessions) delete kv.second;
     g_sessions.clear();
 }
 }  // namespace r2s_int
@@ -1122,13 +1103,7 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     // only); the host threads add the level shift afterwards.  Needs pinned memory for the field without its shift.
     static const bool early_env = !(getenv("R2S_FINE_EARLY") && atoi(getenv("R2S_FINE_EARLY")) == 0);
     bool early = early_env && !o.skip_rbf && fine_sdf_out && nfine >= ((size_t)1 << 22);
-    if (early && !pin_f && S->fine_host_cap < sizeof(float) * nfine) {
-        if (S->fine_host) r2s_host_free(S->fine_host);
-        S->fine_host = nullptr;
-        S->fine_host_cap = 0;
-        if ((S->fine_host = r2s_host_alloc(sizeof(float) * nfine))) S->fine_host_cap = sizeof(float) * nfine;
-        else { (void)hipGetLastError(); early = false; }
-    }
+    if (early && !pin_f && S->fine_host.cap < sizeof(float) * nfine && !S->fine_host.regrow(sizeof(float) * nfine)) early = false;
     if (sdf_dists_out && pin_d) {
         HIP_TRY(hipMemcpyAsync(sdf_dists_out, S->out[2].p, sizeof(double) * (size_t)ngp, hipMemcpyDeviceToHost, S->cs));
         dists_in_flight = true;
@@ -1153,7 +1128,7 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
                 if (hipEventSynchronize(c.ev) != hipSuccess) { dl_fail(R2S_ERR_HIP, "hipEventSynchronize failed"); return; }
                 // (early: the chunk lands in pinned memory - the caller's array if it is pinned, else the landing zone - and gets its
                 //  level shift from the host threads once the level is known)
-                float* land = early ? (pin_f ? fine_sdf_out : (float*)S->fine_host) : fine_sdf_out;
+                float* land = early ? (pin_f ? fine_sdf_out : (float*)S->fine_host.p) : fine_sdf_out;
                 std::vector<Segment> segs{{(char*)(land + c.t0), (const char*)(S->fine.as<float>() + c.t0), sizeof(float) * (size_t)(c.t1 - c.t0)}};
                 if (const int rc2 = download(S, segs, early ? true : pin_f)) { dl_fail(rc2, g_err); return; }
                 if (early) {
@@ -1185,9 +1160,9 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
         size_t n_ev = 0;
         const std::function<int(int64_t, int64_t)> forward = [&](int64_t t0, int64_t t1) -> int {
             if (n_ev >= S->evf.size()) {
-                hipEvent_t e = nullptr;
-                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(R2S_ERR_HIP, "hipEventCreate failed");
-                S->evf.push_back(e);
+                Event e;
+                if (hipEventCreateWithFlags(&e.h, hipEventDisableTiming) != hipSuccess) return fail(R2S_ERR_HIP, "hipEventCreate failed");
+                S->evf.push_back(std::move(e));
             }
             hipEvent_t e = S->evf[n_ev++];
             if (hipEventRecord(e, nullptr) != hipSuccess) return fail(R2S_ERR_HIP, "hipEventRecord failed");   // (the smoothing's stream)
@@ -1221,7 +1196,7 @@ int r2s_rho2sdf(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, c
     if (early) {   // the level shift: fine = raw + th (Float32), by the host threads, chunk by chunk as the chunks arrive
         ensure_pool(S);
         const float th = ri.level_shift;
-        const float* src = pin_f ? fine_sdf_out : (const float*)S->fine_host;
+        const float* src = pin_f ? fine_sdf_out : (const float*)S->fine_host.p;
         float* dst = fine_sdf_out;
         {
             std::lock_guard<std::mutex> lk(qmu);

@@ -13,8 +13,8 @@
 namespace r2s_int {
 
 // ---- per-device work caches ----------------------------------------------------------------------------------------------
-// The work buffers a family of entry points keeps between calls, one W per device.  W holds its device buffers as Scoped
-// members, so that destroying an entry frees every one of them: there is no second list of the members to keep in step.
+// The work buffers a family of entry points keeps between calls, one W per device.  W holds its device buffers as DevBuf
+// members (which free themselves), so that destroying an entry frees every one of them: there is no second list of the members to keep in step.
 // A call locks `mu` for as long as it uses its entry.  The map is never destroyed: at process exit the HIP runtime may be
 // gone before a static destructor runs, and the driver reclaims the memory anyway.
 template <class W>
@@ -139,7 +139,6 @@ void set_last_surface(Surface&& s);
 // device work buffers of one extraction (kept by the caller between calls on the CURRENT device)
 struct IsoWork {
     DevBuf rows, tiles, tot, field, verts, tris;
-    void release();
 };
 // the surface of a device field (Float32 or Float64, x fastest) on the current device, after the work queued on `st`;
 // has_shift: Float32 values are read as f + shift (float32 sum), the level shift the host adds to an early fine field
@@ -161,7 +160,7 @@ struct MiTree {
     const float* verts = nullptr;
     const int32_t* tris = nullptr;
     int64_t n_verts = 0, n_tris = 0;
-    Scoped nodes;
+    DevBuf nodes;
     int32_t root = 0;
     int32_t depth = 0;
     double absmax = 0.0;

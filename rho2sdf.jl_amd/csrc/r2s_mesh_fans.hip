@@ -228,7 +228,7 @@ __global__ void __launch_bounds__(256) mf_apply_further_kernel(const uint32_t* _
 
 // work buffers of the fan calls, kept per device between calls (r2s_release_cache frees them)
 struct FanWork : MsHalfEdgeBufs {
-    Scoped verts, tris, flag, small, parent, label, rflag, pos, rkey, rkey2, rval, rval2, fan_at, further, extra, index_of, foc, fov, counts,
+    DevBuf verts, tris, flag, small, parent, label, rflag, pos, rkey, rkey2, rval, rval2, fan_at, further, extra, index_of, foc, fov, counts,
         tris_out, verts_out, vert_of;
 };
 PerDevice<FanWork> g_fans_work;

@@ -210,7 +210,7 @@ inline unsigned ms_key_bits(int64_t n_verts) { return std::min(33u + ms_bits((ui
 // the buffers of the half-edge table: keys / vals as written, keys2 / vals2 sorted, temp for rocPRIM (a tool's work struct
 // derives from this and uses temp for its other sorts and scans too)
 struct MsHalfEdgeBufs {
-    Scoped keys, keys2, vals, vals2, temp;
+    DevBuf keys, keys2, vals, vals2, temp;
 };
 
 // The sorted half-edge table of n > 0 device triangles on `st`: sizes the buffers, launches ms_key_kernel<NPARENT, VFLAG>

@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(256) mh_apply_cap_kernel(const int32_t* __rest
 
 // work buffers of the hole calls, kept per device between calls (r2s_release_cache frees them)
 struct HoleWork : MsHalfEdgeBufs {
-    Scoped verts, tris, flag, small, bflag, bpos, bh, ekey, ekey2, eval, eval2, parent, succ, rflag, num, skey, skey2, sval, sval2, counts,
+    DevBuf verts, tris, flag, small, bflag, bpos, bh, ekey, ekey2, eval, eval2, parent, succ, rflag, num, skey, skey2, sval, sval2, counts,
         closed, addv, voff, addt, toff, pp0, pp1, start, rim_edge, partial, sums, tris_out, verts_out;
 };
 PerDevice<HoleWork> g_holes_work;

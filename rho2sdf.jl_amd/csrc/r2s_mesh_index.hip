@@ -532,7 +532,7 @@ int mi_build_tree(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
         return 0;
     }
     const unsigned blocks = (unsigned)((n_tris + 255) / 256);
-    Scoped small, keys, sorted, temp, parent, flags;
+    DevBuf small, keys, sorted, temp, parent, flags;
     // small: [0..5] the bounds, [6] the depth
     uint32_t h_small[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
     ENSURE(small, sizeof h_small);
@@ -628,7 +628,7 @@ int r2s_mesh_index_build_dev(const float* d_verts, int64_t n_verts, const int32_
     if (!out) return fail(R2S_ERR_ARG, "mesh_index_build: null output");
     if ((rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    Scoped flag;
+    DevBuf flag;
     if ((rc = check_mesh_dev("mesh_index_build", d_verts, n_verts, d_tris, n_tris, flag, st))) return rc;
     return new_index(out, [&](r2s_mesh_index* ix) {
         const int rc = upload_mesh(ix->verts, ix->tris, d_verts, n_verts, d_tris, n_tris, true, st);
@@ -665,7 +665,7 @@ int r2s_mesh_index_query(const r2s_mesh_index* ix, const void* points, int32_t p
     if (rc || n == 0) return rc;
     const size_t np = (size_t)n, psz = 3 * real_bytes(points_are_float32) * np, osz = real_bytes(out_is_float32) * np;
     const HostIo pts{points, nullptr, psz}, out{nullptr, dist_out, osz}, idx{nullptr, closest_tri_out, sizeof(int32_t) * np};
-    return staged_call(ix, {pts, out, idx}, [&](Scoped* b) {
+    return staged_call(ix, {pts, out, idx}, [&](DevBuf* b) {
         return mi_query(ix->tree, b[0].p, points_are_float32 != 0, n, nullptr, nullptr, 0.0, nullptr, false, 0.0, b[1].p, out_is_float32 != 0,
                         b[2].as<int32_t>(), nullptr);
     });
@@ -689,7 +689,7 @@ int r2s_mesh_index_raycast(const r2s_mesh_index* ix, const void* origins, const 
     const size_t nr = (size_t)n, psz = 3 * real_bytes(rays_are_float32) * nr, osz = real_bytes(out_is_float32) * nr;
     const HostIo org{origins, nullptr, psz}, dir{dirs, nullptr, psz}, out{nullptr, t_out, osz}, idx{nullptr, tri_out, sizeof(int32_t) * nr},
         side{nullptr, side_out, nr};
-    return staged_call(ix, {org, dir, out, idx, side}, [&](Scoped* b) {
+    return staged_call(ix, {org, dir, out, idx, side}, [&](DevBuf* b) {
         return mi_raycast(ix->tree, b[0].p, b[1].p, rays_are_float32 != 0, n, t_min, t_max, b[2].p, out_is_float32 != 0, b[3].as<int32_t>(),
                           b[4].as<int8_t>(), nullptr);
     });
@@ -714,7 +714,7 @@ int r2s_mesh_index_lattice(const r2s_mesh_index* ix, const int64_t dims[3], cons
     if (!ix || !dist_out) return fail(R2S_ERR_ARG, "mesh_index_lattice: null index / output");
     const size_t nvox = (size_t)(dims[0] * dims[1] * dims[2]);
     const HostIo out{nullptr, dist_out, real_bytes(out_is_float32) * nvox}, idx{nullptr, closest_tri_out, sizeof(int32_t) * nvox};
-    return staged_call(ix, {out, idx}, [&](Scoped* b) {
+    return staged_call(ix, {out, idx}, [&](DevBuf* b) {
         return mi_query(ix->tree, nullptr, false, 0, dims, origin, spacing, nullptr, false, 0.0, b[0].p, out_is_float32 != 0,
                         b[1].as<int32_t>(), nullptr);
     });

@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(256) mx_unpack_kernel(const uint64_t* __restri
 
 // work buffers of the intersection calls, kept per device between calls (r2s_release_cache frees them)
 struct IsectWork {
-    Scoped verts, tris, flag, small, hits, keys, keys2, temp, pairs;
+    DevBuf verts, tris, flag, small, hits, keys, keys2, temp, pairs;
 };
 PerDevice<IsectWork> g_mx_work;
 

@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(256) mo_remain_kernel(const uint64_t* __restri
 
 // work buffers of the orient calls, kept per device between calls (r2s_release_cache frees them)
 struct OrientWork : MsHalfEdgeBufs {
-    Scoped verts, tris, tris_out, flag, small, parent, info, rflag, num, patch, flip, skey, skey2, sval, sval2, seg, partial, counts, vol, gflag;
+    DevBuf verts, tris, tris_out, flag, small, parent, info, rflag, num, patch, flip, skey, skey2, sval, sval2, seg, partial, counts, vol, gflag;
 };
 PerDevice<OrientWork> g_orient_work;
 

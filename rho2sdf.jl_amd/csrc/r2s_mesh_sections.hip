@@ -419,7 +419,7 @@ __global__ void __launch_bounds__(MS_BLOCK) sx_sum_kernel(const float* __restric
 
 // work buffers of the section calls, kept per device between calls (r2s_release_cache frees them)
 struct SectionWork : MsHalfEdgeBufs {
-    Scoped verts, tris, flag, small, levels, h, first, cnt, offset, tri_of, level_of, parent, succ, rflag, num, rkeys, rkeys2, skey, skey2,
+    DevBuf verts, tris, flag, small, levels, h, first, cnt, offset, tri_of, level_of, parent, succ, rflag, num, rkeys, rkeys2, skey, skey2,
         sval, sval2, pp0, pp1, closed, start, order, partial, counts, sums, seg_tri, points;
 };
 PerDevice<SectionWork> g_section_work;

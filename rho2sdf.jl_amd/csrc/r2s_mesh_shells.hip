@@ -199,7 +199,7 @@ __global__ void __launch_bounds__(256) ms_totals_kernel(const int64_t* __restric
 
 // work buffers of the shell calls, kept per device between calls (r2s_release_cache frees them)
 struct ShellWork : MsHalfEdgeBufs {
-    Scoped verts, tris, flag, small, parent, rflag, num, shell, skey, skey2, sval, sval2, seg, partial, counts, sums, vflag;
+    DevBuf verts, tris, flag, small, parent, rflag, num, shell, skey, skey2, sval, sval2, seg, partial, counts, sums, vflag;
 };
 PerDevice<ShellWork> g_shell_work;
 

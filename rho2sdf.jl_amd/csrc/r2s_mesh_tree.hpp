@@ -11,10 +11,10 @@
 #include "r2s_common.hpp"
 #include "r2s_internal.hpp"
 
-// (the Scoped members free themselves: r2s_mesh_index_destroy deletes the index with its device current)
+// (the DevBuf members free themselves: r2s_mesh_index_destroy deletes the index with its device current)
 struct r2s_mesh_index {
     int device = 0;
-    Scoped verts, tris;
+    DevBuf verts, tris;
     r2s_int::MiTree tree;
 };
 
@@ -83,7 +83,7 @@ int staged_call(const r2s_mesh_index* ix, const std::vector<HostIo>& io, F enque
     if (rc) return rc;
     DeviceScope scope;
     if ((rc = scope.enter(ix->device))) return rc;
-    std::vector<Scoped> buf(io.size());   // (freed before the caller's device is current again)
+    std::vector<DevBuf> buf(io.size());   // (freed before the caller's device is current again)
     for (size_t k = 0; k < io.size(); ++k) {
         if (io[k].in || io[k].out) ENSURE(buf[k], io[k].bytes);
         if (io[k].in) HIP_TRY(hipMemcpy(buf[k].p, io[k].in, io[k].bytes, hipMemcpyHostToDevice));

@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(256) mw_tout_kernel(const int32_t* __restrict_
 
 // work buffers of the weld calls, kept per device between calls (r2s_release_cache frees them)
 struct WeldWork {
-    Scoped verts, tris, verts_out, tris_out, flag, small, k32, k32b, k64, g64, s64, idx, idx2, temp, hp, hp2, rep, is_rep, num, class_of, is_dup,
+    DevBuf verts, tris, verts_out, tris_out, flag, small, k32, k32b, k64, g64, s64, idx, idx2, temp, hp, hp2, rep, is_rep, num, class_of, is_dup,
         keep, tnum, used, unum, final_of, vert_map, tri_map;
 };
 PerDevice<WeldWork> g_weld_work;

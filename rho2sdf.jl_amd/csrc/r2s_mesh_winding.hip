@@ -408,7 +408,7 @@ int r2s_mesh_index_winding(const r2s_mesh_index* ix, const void* points, int32_t
     const size_t np = (size_t)n;
     const HostIo pts{points, nullptr, 3 * real_bytes(points_are_float32) * np}, w{nullptr, winding_out, sizeof(int32_t) * np},
         c{nullptr, crossings_out, sizeof(int32_t) * np};
-    return staged_call(ix, {pts, w, c}, [&](Scoped* b) {
+    return staged_call(ix, {pts, w, c}, [&](DevBuf* b) {
         return mwn_run(ix->tree, b[0].p, points_are_float32 != 0, n, nullptr, nullptr, 0.0, ray, b[1].as<int32_t>(), b[2].as<int32_t>(), nullptr,
                        false, 0, nullptr);
     });
@@ -431,7 +431,7 @@ int r2s_mesh_index_winding_lattice(const r2s_mesh_index* ix, const int64_t dims[
     if (rc) return rc;
     const size_t bytes = sizeof(int32_t) * lattice_size(dims);
     const HostIo w{nullptr, winding_out, bytes}, c{nullptr, crossings_out, bytes};
-    return staged_call(ix, {w, c}, [&](Scoped* b) {
+    return staged_call(ix, {w, c}, [&](DevBuf* b) {
         return mwn_run(ix->tree, nullptr, false, 0, dims, origin, spacing, ray, b[0].as<int32_t>(), b[1].as<int32_t>(), nullptr, false, 0, nullptr);
     });
 }
@@ -453,7 +453,7 @@ int r2s_mesh_index_signed(const r2s_mesh_index* ix, const void* points, int32_t 
     const size_t np = (size_t)n;
     const HostIo pts{points, nullptr, 3 * real_bytes(points_are_float32) * np}, out{nullptr, dist_out, real_bytes(out_is_float32) * np},
         idx{nullptr, closest_tri_out, sizeof(int32_t) * np};
-    return staged_call(ix, {pts, out, idx}, [&](Scoped* b) {
+    return staged_call(ix, {pts, out, idx}, [&](DevBuf* b) {
         return mwn_signed(ix->tree, b[0].p, points_are_float32 != 0, n, nullptr, nullptr, 0.0, rule, ray, b[1].p, out_is_float32 != 0,
                           b[2].as<int32_t>(), nullptr);
     });
@@ -476,7 +476,7 @@ int r2s_mesh_index_signed_lattice(const r2s_mesh_index* ix, const int64_t dims[3
     if (rc) return rc;
     const size_t nvox = lattice_size(dims);
     const HostIo out{nullptr, dist_out, real_bytes(out_is_float32) * nvox}, idx{nullptr, closest_tri_out, sizeof(int32_t) * nvox};
-    return staged_call(ix, {out, idx}, [&](Scoped* b) {
+    return staged_call(ix, {out, idx}, [&](DevBuf* b) {
         return mwn_signed(ix->tree, nullptr, false, 0, dims, origin, spacing, rule, ray, b[0].p, out_is_float32 != 0, b[1].as<int32_t>(), nullptr);
     });
 }
@@ -501,7 +501,7 @@ int r2s_mesh_signed_distance(const float* verts, int64_t n_verts, const int32_t*
     DeviceScope scope;   // (device < 0: the current device)
     if (device >= 0 && (rc = scope.enter(device))) return rc;
     const size_t bytes = real_bytes(out_is_float32) * lattice_size(dims);
-    Scoped dv, dt, dd;
+    DevBuf dv, dt, dd;
     if ((rc = upload_mesh(dv, dt, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
     ENSURE(dd, bytes);
     MiTree T;   // (built, used and dropped: the nodes free themselves)
@@ -521,7 +521,7 @@ int r2s_mesh_signed_distance_dev(const float* d_verts, int64_t n_verts, const in
     if (!d_out) return fail(R2S_ERR_ARG, "mesh_signed_distance: null output");
     if ((rc = ray_rule_args("mesh_signed_distance", ray, rule)) || (rc = check_device(0))) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    Scoped flag;
+    DevBuf flag;
     if ((rc = check_mesh_dev("mesh_signed_distance", d_verts, n_verts, d_tris, n_tris, flag, st))) return rc;
     MiTree T;
     if ((rc = mi_build_tree(d_verts, n_verts, d_tris, n_tris, st, T))) return rc;

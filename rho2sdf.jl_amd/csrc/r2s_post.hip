@@ -437,7 +437,7 @@ static int ccl_table(const uint32_t* L, const uint32_t* size, uint32_t n, DevBuf
 // the work arrays of remove_artifacts_dev / analyze_components_dev, kept between calls per device (r2s_release_cache
 // frees them): allocating and freeing 1.6 GB per call cost as much as a kernel of the stage
 struct CclWork {
-    Scoped L, size, roots, cnt, blk, tab;
+    DevBuf L, size, roots, cnt, blk, tab;
 };
 static r2s_int::PerDevice<CclWork> g_ccl_work;
 static void release_ccl_work() { g_ccl_work.release_all(); }
@@ -875,34 +875,17 @@ __global__ void __launch_bounds__(256) volume_narrow_kernel(const float* __restr
 // for the stream.  (A hipMemcpy of a few KB queues behind whatever bulk transfer the engine is busy with - in r2s_rho2sdf the
 // cleaned field, 1.07 GB in 32 MB pieces, travels while the CG runs, and each of its ~25 scalar read-backs waited up to
 // 0.6 ms for a piece to finish: the RBF stage took 38 or 46 ms depending on which engine the runtime had picked.)
-struct HostMailbox {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool ensure(size_t bytes)
-    {
-        if (bytes <= cap) return true;
-        release();
-        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-        cap = bytes;
-        return true;
-    }
-    void release()
-    {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 __global__ void __launch_bounds__(256) mailbox_copy_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t nwords)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nwords) dst[i] = src[i];
 }
 // host <- device, `bytes` a multiple of 4 and small; orders like a hipMemcpy on `st` followed by a stream synchronisation
-static int d2h_small(void* host, const void* dev, size_t bytes, hipStream_t st, HostMailbox& mb)
+static int d2h_small(void* host, const void* dev, size_t bytes, hipStream_t st, PinnedBuf& mb)
 {
     static const bool off = getenv("R2S_MAILBOX") && atoi(getenv("R2S_MAILBOX")) == 0;   // (A/B switch)
-    if (off || bytes == 0 || (bytes & 3u) || bytes > ((size_t)1 << 20) || !mb.ensure(std::max<size_t>(bytes, (size_t)64 << 10))) {
+    if (off || bytes == 0 || (bytes & 3u) || bytes > ((size_t)1 << 20) ||
+        mb.ensure(std::max<size_t>(bytes, (size_t)64 << 10)) != hipSuccess) {
         HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return 0;
@@ -921,7 +904,7 @@ static int vol_grid()
 }
 struct VolumeWork {
     DevBuf partial, result, segmn, segmx, qpts, live[2], cnt, cfull;
-    HostMailbox mb;
+    PinnedBuf mb;
     float qpts_jac = -1.0f;             // the Jacobian the point table was built with
     const float* seg_field = nullptr;   // the field the segment extrema were computed for (prepare)
     int cur = -1;                       // live[cur]: the rows the levels still work on (-1: all rows)
@@ -1004,13 +987,6 @@ struct VolumeWork {
             listed ? cnt.as<uint32_t>() + cur : nullptr);
         sum_f32_kernel<<<1, 1024, 0, st>>>(partial.as<float>(), nrows, result.as<float>());
         return d2h_small(out, result.p, sizeof(float), st, mb);
-    }
-    void release()
-    {
-        mb.release();
-        partial.release(); result.release(); segmn.release(); segmx.release(); qpts.release(); live[0].release(); live[1].release();
-        cnt.release(); cfull.release();
-        seg_field = nullptr; qpts_jac = -1.0f; cur = -1;
     }
 };
 
@@ -1174,7 +1150,8 @@ __global__ void __launch_bounds__(256) rbf_matvec_kernel(RbfGeom G, const float*
 // in the same order from the same values (bit-identical results).
 // The buffer is kept for the life of the process (r2s_release_cache frees it): giving tens of GB back to the
 // driver and asking for them again costs seconds per call (freed VRAM is scrubbed), far more than it saves.
-static DevBuf g_rbf_kv;
+// Never destroyed (the `*new` of PerDevice): at process exit the HIP runtime may be gone before a static destructor runs.
+static DevBuf& g_rbf_kv = *new DevBuf;
 static std::mutex g_rbf_kv_mutex;   // one smoothing call at a time may use (or regrow) the shared buffer
 #define RBF_MAX_TAPS 160
 struct RbfTaps {
@@ -2166,11 +2143,6 @@ struct RbfTables {
     RbfGeom G;
     RbfLutGeom LG, LGF;
     int build(const RbfPlan& P, hipStream_t s);
-    void release()
-    {
-        for (DevBuf* b : {&cx, &cy, &cz, &tx, &ty, &tz, &st, &vx, &vy, &vz, &lv, &wt, &t, &wa, &ta, &fvx, &fvy, &fvz, &lvf, &waf, &taf})
-            b->release();
-    }
 };
 #define RBF_TRY(expr)                                                                 \
     do {                                                                              \
@@ -2284,10 +2256,6 @@ struct RbfFineTables {
     DevBuf ids, vals, T, taps, meta;
     FineLut F;
     int build(const RbfPlan& P, hipStream_t s);
-    void release()
-    {
-        for (DevBuf* b : {&ids, &vals, &T, &taps, &meta}) b->release();
-    }
 };
 int RbfFineTables::build(const RbfPlan& P, hipStream_t s)
 {
@@ -2375,15 +2343,7 @@ struct RbfWork {   // the device buffers of one rbf_smooth_host call
     RbfTables tab;
     RbfFineTables fine_tab;
     VolumeWork vw;
-    HostMailbox mb;
-    void release()
-    {
-        mb.release();
-        for (DevBuf* b : {&sdf, &f, &w, &lsf, &fine, &cnt, &r, &u, &q, &part, &part2}) b->release();
-        tab.release();
-        fine_tab.release();
-        vw.release();
-    }
+    PinnedBuf mb;
 };
 // sdf_dev / out_dev: `sdf` / `fine_out` are device pointers (device-resident chaining of the stages)
 // d_weights_keep (optional): a device array of the lattice's size that receives the weights; with it fine_out may be null:
@@ -2410,55 +2370,39 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     RbfTables& T = W.tab;
     const FineLut& FL = W.fine_tab.F;
     VolumeWork& vw = W.vw;
-    auto cleanup = [&]() {
-        if (!ws) W.release();
-    };
-#define TRY_C(expr)                                                                   \
-    do {                                                                              \
-        int rc_ = (expr);                                                             \
-        if (rc_) { cleanup(); return rc_; }                                           \
-    } while (0)
-#define HIP_C(expr)                                                                   \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess) { cleanup(); return fail(R2S_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } \
-    } while (0)
-#define ENSURE_C(buf, bytes)                                                          \
-    do {                                                                              \
-        if ((buf).ensure(bytes)) { cleanup(); return fail(R2S_ERR_NOMEM, "hipMalloc of %zu bytes failed", (size_t)(bytes)); } \
-    } while (0)
-    if (!sdf_dev) ENSURE_C(W.sdf, sizeof(double) * (size_t)n);
-    ENSURE_C(W.f, sizeof(float) * (size_t)n);
-    ENSURE_C(W.w, sizeof(float) * (size_t)n);
-    ENSURE_C(W.lsf, sizeof(float) * (size_t)n);
-    if (!out_dev && fine_out) ENSURE_C(W.fine, sizeof(float) * (size_t)nf);
-    ENSURE_C(W.cnt, 64);
-    if (!sdf_dev) HIP_C(hipMemcpy(W.sdf.p, sdf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    int rc = 0;
+    if (!sdf_dev) ENSURE(W.sdf, sizeof(double) * (size_t)n);
+    ENSURE(W.f, sizeof(float) * (size_t)n);
+    ENSURE(W.w, sizeof(float) * (size_t)n);
+    ENSURE(W.lsf, sizeof(float) * (size_t)n);
+    if (!out_dev && fine_out) ENSURE(W.fine, sizeof(float) * (size_t)nf);
+    ENSURE(W.cnt, 64);
+    if (!sdf_dev) HIP_TRY(hipMemcpy(W.sdf.p, sdf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     const double* dsdf = sdf_dev ? sdf : W.sdf.as<double>();
     float* dfine = out_dev ? fine_out : W.fine.as<float>();
     float* const d_f = W.f.as<float>();
     float* const d_w = W.w.as<float>();
     float* const d_lsf = W.lsf.as<float>();
     // ---- process_vector ----
-    HIP_C(hipMemset(W.cnt.p, 0, 64));
+    HIP_TRY(hipMemset(W.cnt.p, 0, 64));
     const unsigned nb = (unsigned)((n + 255) / 256);
     pv_max_kernel<<<(nb < 2048u ? nb : 2048u), 256, 0, st>>>(dsdf, n, d_f, W.cnt.as<uint32_t>(), W.cnt.as<uint32_t>() + 1);
     uint32_t hc[2];
-    TRY_C(d2h_small(hc, W.cnt.p, 8, st, W.mb));
-    if (!hc[1]) { cleanup(); return fail(R2S_ERR_ARG, "every SDF value is a sentinel: nothing to smooth"); }   // A15
+    if ((rc = d2h_small(hc, W.cnt.p, 8, st, W.mb))) return rc;
+    if (!hc[1]) return fail(R2S_ERR_ARG, "every SDF value is a sentinel: nothing to smooth");   // A15
     pv_replace_kernel<<<nb, 256, 0, st>>>(d_f, n, W.cnt.as<uint32_t>());
     // ---- geometry and tables; the refined output grid's tables (R2S_RBF_APPLY=fly: on the fly, the tests compare) ----
-    TRY_C(T.build(P, st));
+    if ((rc = T.build(P, st))) return rc;
     rbf_record_plan(P, is_interp, T);
-    TRY_C(W.fine_tab.build(P, st));
+    if ((rc = W.fine_tab.build(P, st))) return rc;
     const RbfGeom& G = T.G;
     // ---- weights ----
     int its = 0;
     if (is_interp) {   // compute_rbf_weights (:191-202): cg(K, b), IterativeSolvers 0.9.4 defaults
-        ENSURE_C(W.r, sizeof(float) * (size_t)n);
-        ENSURE_C(W.u, sizeof(float) * (size_t)n);
-        ENSURE_C(W.q, sizeof(float) * (size_t)n);
-        ENSURE_C(W.part, sizeof(double) * (size_t)std::max(nz * DOT_PARTS, 1024));
+        ENSURE(W.r, sizeof(float) * (size_t)n);
+        ENSURE(W.u, sizeof(float) * (size_t)n);
+        ENSURE(W.q, sizeof(float) * (size_t)n);
+        ENSURE(W.part, sizeof(double) * (size_t)std::max(nz * DOT_PARTS, 1024));
         float* const d_r = W.r.as<float>();
         float* const d_u = W.u.as<float>();
         float* const d_q = W.q.as<float>();
@@ -2498,16 +2442,16 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
                 use_k = true;
             }
         }
-        HIP_C(hipMemcpy(d_r, d_f, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));
-        HIP_C(hipMemset(d_u, 0, sizeof(float) * (size_t)n));
-        HIP_C(hipMemset(d_w, 0, sizeof(float) * (size_t)n));
+        HIP_TRY(hipMemcpy(d_r, d_f, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemset(d_u, 0, sizeof(float) * (size_t)n));
+        HIP_TRY(hipMemset(d_w, 0, sizeof(float) * (size_t)n));
         // dot(u, q): the partial sums of the row-walk product's workgroups (formed by that kernel, or by rbf_walk_dot_kernel
         // for the other forms of the product: every form of the CG follows the same numbers), in (k, walk, row piece) order
         const size_t nparts = rbf_walk_nparts(nx, ny, nz, 0, nz);
-        ENSURE_C(W.part2, sizeof(double) * std::max(nparts, (size_t)1));
+        ENSURE(W.part2, sizeof(double) * std::max(nparts, (size_t)1));
         float rr;
         dot_planes_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_r, d_r, (int64_t)nx * ny, W.part.as<double>());
-        TRY_C(sum_parts(W.part, nplane_parts, &rr));
+        if ((rc = sum_parts(W.part, nplane_parts, &rr))) return rc;
         float residual = std::sqrt(rr), prev = 1.0f;
         const float tol = 3.4526698e-4f * residual;   // reltol = sqrt(eps(Float32)), abstol = 0
         const int64_t its_cap = n;
@@ -2523,11 +2467,11 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
                 WAr.T = T.LG.WT; WAr.x = d_u; WAr.y = d_q; WAr.dot_partial = W.part2.as<double>();
                 rbf_walk_launch(0, RBF_NV, WAr, st);
                 float uq;
-                TRY_C(sum_parts(W.part2, nparts, &uq));
+                if ((rc = sum_parts(W.part2, nparts, &uq))) return rc;
                 const float alpha = (residual * residual) / uq;
                 prev = residual;
                 cg_update_r_dot_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_r, d_q, alpha, (int64_t)nx * ny, W.part.as<double>());
-                TRY_C(sum_parts(W.part, nplane_parts, &rr));
+                if ((rc = sum_parts(W.part, nplane_parts, &rr))) return rc;
                 residual = std::sqrt(rr);
                 its++;
                 alpha_prev = alpha;
@@ -2542,20 +2486,20 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
             else rbf_matvec_kernel<<<nb, 256, 0, st>>>(G, d_u, d_q);
             rbf_walk_dot_launch(d_u, d_q, nx, ny, nz, 0, nz, W.part2.as<double>(), st);
             float uq;
-            TRY_C(sum_parts(W.part2, nparts, &uq));
+            if ((rc = sum_parts(W.part2, nparts, &uq))) return rc;
             const float alpha = (residual * residual) / uq;
             prev = residual;
             // weights / residual update with dot(r, r)
             cg_update_xr_dot_kernel<<<nz * DOT_PARTS, 256, 0, st>>>(d_w, d_r, d_u, d_q, alpha, (int64_t)nx * ny, W.part.as<double>());
-            TRY_C(sum_parts(W.part, nplane_parts, &rr));
+            if ((rc = sum_parts(W.part, nplane_parts, &rr))) return rc;
             residual = std::sqrt(rr);
             its++;
         }
     } else {
-        HIP_C(hipMemcpy(d_w, d_f, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));   // :353
+        HIP_TRY(hipMemcpy(d_w, d_f, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice));   // :353
     }
     if (cg_iters) *cg_iters = its;
-    if (d_weights_keep) HIP_C(hipMemcpyAsync(d_weights_keep, d_w, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    if (d_weights_keep) HIP_TRY(hipMemcpyAsync(d_weights_keep, d_w, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st));
     // the output field (:363-366) + `add`
     // (smooth = 1: one target per lattice point - through the table of ITS coordinate differences)
     // In RBF_FINE_CHUNKS Z chunks when the caller wants to forward finished chunks (fine_chunk), else in one launch.
@@ -2584,18 +2528,18 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     // fine_early: the field WITHOUT the level shift first (it needs the weights only), so that its chunks travel to the host
     // while the level is found; the caller adds the shift to what it received (x + 0 + th = x + th: the same Float32 sum).
     // The device array stays WITHOUT it (the chunks may still be on their way when the level is known)
-    if (fine_early && fine_out) TRY_C(eval_fine(0.0f));
+    if (fine_early && fine_out && (rc = eval_fine(0.0f))) return rc;
     // ---- LSF on the coarse grid (:357) and the volume-preserving level (:359, :265-300) ----
     if (!launch_rbf_apply_lut(P.ev, G, T.LG, P.sts[0], nb, st, d_w, G.cx, G.cy, G.cz, T.st.as<Stencil>(), 0.0f, d_lsf))
         rbf_apply_kernel<<<nb, 256, 0, st>>>(G, d_w, 1, nx, ny, nz, G.cx, G.cy, G.cz, T.st.as<Stencil>(), 0.0f, d_lsf);
-    if (lsf_out) HIP_C(hipMemcpy(lsf_out, d_lsf, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    TRY_C(vw.init(9));
-    TRY_C(vw.prepare(d_lsf, nx, ny, nz, st));
+    if (lsf_out) HIP_TRY(hipMemcpy(lsf_out, d_lsf, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    if ((rc = vw.init(9))) return rc;
+    if ((rc = vw.prepare(d_lsf, nx, ny, nz, st))) return rc;
     // the range of the field = the start of the bisection: from the extrema of the 64-cell segments that `prepare` has just
     // formed (every lattice point is a corner of some cell: the same two numbers as a sweep over the field, which cost
     // 0.28 ms at 512^3); a lattice without cells: the sweep
     int mmh[4] = {0x7FFFFFFF, (int)0x80000000, 0x7FFFFFFF, (int)0x80000000};
-    HIP_C(hipMemcpyAsync(W.cnt.p, mmh, 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.cnt.p, mmh, 16, hipMemcpyHostToDevice, st));
     const int64_t nsegs = vw.seg_field ? (int64_t)(ny - 1) * (nz - 1) * ((nx - 1 + 63) / 64) : 0;
     if (nsegs > 0) {
         const unsigned nbs = (unsigned)std::min<int64_t>((nsegs + 255) / 256, 128);   // (two same-address atomics per wavefront at the end: few wavefronts)
@@ -2604,7 +2548,7 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     } else {
         minmax_kernel<<<(nb < 2048u ? nb : 2048u), 256, 0, st>>>(d_lsf, n, W.cnt.as<int>());
     }
-    TRY_C(d2h_small(mmh, W.cnt.p, 16, st, W.mb));
+    if ((rc = d2h_small(mmh, W.cnt.p, 16, st, W.mb))) return rc;
     auto dec = [](int b) { b = b >= 0 ? b : (b ^ 0x7FFFFFFF); float f; memcpy(&f, &b, 4); return f; };
     float lo = dec(mmh[0]), hi = dec(nsegs > 0 ? mmh[3] : mmh[1]);
     const float edge = std::sqrt((P.cx[1] - P.cx[0]) * (P.cx[1] - P.cx[0]));   // norm(fine_grid[2,1,1] - fine_grid[1,1,1])
@@ -2614,8 +2558,8 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     while (it < 40 && eps > 1.0e-4) {
         th = (lo + hi) / 2;
         float vol;
-        if (it > 0) TRY_C(vw.narrow(nx, ny, nz, edge, lo, hi, st));   // (level 0: [lo, hi] = the range of the field, every row is live)
-        TRY_C(vw.run(d_lsf, nx, ny, nz, edge, th, 0.0f, st, &vol));
+        if (it > 0 && (rc = vw.narrow(nx, ny, nz, edge, lo, hi, st))) return rc;   // (level 0: [lo, hi] = the range of the field, every row is live)
+        if ((rc = vw.run(d_lsf, nx, ny, nz, edge, th, 0.0f, st, &vol))) return rc;
         eps = std::fabs(target_volume - (double)vol);
         if ((double)vol > target_volume) lo = th; else hi = th;
         it++;
@@ -2623,11 +2567,10 @@ static int rbf_smooth_host(const double* sdf, const r2s_grid* g, int is_interp, 
     th = -th;
     if (th_out) *th_out = th;
     // ---- fine grid (:363-366) ----
-    if (!fine_early && fine_out) TRY_C(eval_fine(th));   // (fine_early: done above, the shift is the caller's)
-    HIP_C(hipGetLastError());
-    if (out_dev || !fine_out) HIP_C(hipDeviceSynchronize());
-    else HIP_C(hipMemcpy(fine_out, W.fine.p, sizeof(float) * (size_t)nf, hipMemcpyDeviceToHost));
-    cleanup();
+    if (!fine_early && fine_out && (rc = eval_fine(th))) return rc;   // (fine_early: done above, the shift is the caller's)
+    HIP_TRY(hipGetLastError());
+    if (out_dev || !fine_out) HIP_TRY(hipDeviceSynchronize());
+    else HIP_TRY(hipMemcpy(fine_out, W.fine.p, sizeof(float) * (size_t)nf, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2646,17 +2589,6 @@ __global__ void scatter_u32_kernel(uint32_t* __restrict__ dst, const uint32_t* _
 }
 
 namespace {
-#define SLAB_HIP(expr)                                                                                       \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) { rc = fail(R2S_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
-    } while (0)
-#define SLAB_TRY(expr)                                                                                       \
-    do {                                                                                                     \
-        rc = (expr);                                                                                         \
-        if (rc) goto done;                                                                                   \
-    } while (0)
-
 struct SlabBufs {   // per-slab device buffers, allocated / freed on their device
     std::vector<DevBuf> b;
     const std::vector<r2s_int::Slab>* S;
@@ -2750,32 +2682,32 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
         const int64_t n64 = (int64_t)(d.k1 - d.k0) * plane;
         if (n64 >= 0xFFFFFFFFll) return fail(R2S_ERR_ARG, "slab too large for 32-bit labels");
         nvox[q] = (uint32_t)n64;
-        SLAB_TRY(L.ensure(q, 4 * (size_t)n64)); SLAB_TRY(root.ensure(q, 4 * (size_t)n64)); SLAB_TRY(size.ensure(q, 4 * (size_t)n64));
-        SLAB_TRY(cnt.ensure(q, 64));
+        if ((rc = L.ensure(q, 4 * (size_t)n64)) || (rc = root.ensure(q, 4 * (size_t)n64)) || (rc = size.ensure(q, 4 * (size_t)n64)) || (rc = cnt.ensure(q, 64)))
+            return rc;
         const unsigned nb = (unsigned)((n64 + 255) / 256);
         double* sdf = d.d_sdf + (int64_t)(d.k0 - d.h0) * plane;
         uint32_t h[4] = {0, NOLABEL, 0, 0};
-        SLAB_HIP(hipMemcpyAsync(cnt.at<uint32_t>(q), h, sizeof h, hipMemcpyHostToDevice, d.stream));
-        SLAB_HIP(hipMemsetAsync(size.at<uint32_t>(q), 0, 4 * (size_t)n64, d.stream));
+        HIP_TRY(hipMemcpyAsync(cnt.at<uint32_t>(q), h, sizeof h, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemsetAsync(size.at<uint32_t>(q), 0, 4 * (size_t)n64, d.stream));
         ccl_init_kernel<<<nb, 256, 0, d.stream>>>(sdf, nvox[q], nx, threshold, L.at<uint32_t>(q));
         ccl_union_kernel<<<nb, 256, 0, d.stream>>>(L.at<uint32_t>(q), nx, ny, d.k1 - d.k0);
         ccl_compress_heads_kernel<<<nb, 256, 0, d.stream>>>(L.at<uint32_t>(q), nvox[q], nx);
         ccl_flatten_count_kernel<<<(nb < 4096u ? nb : 4096u), 256, 0, d.stream>>>(L.at<uint32_t>(q), nvox[q], root.at<uint32_t>(q), size.at<uint32_t>(q));
         ccl_max_kernel<<<nb, 256, 0, d.stream>>>(size.at<uint32_t>(q), nvox[q], cnt.at<uint32_t>(q));   // [3]: interior voxels
     }
-    SLAB_TRY(sync_slabs(S));
+    if ((rc = sync_slabs(S))) return rc;
     for (size_t q : order) {
         const Slab& d = S[q];
         uint32_t h[4];
-        SLAB_HIP(hipSetDevice(d.device));
-        SLAB_HIP(hipMemcpy(h, cnt.at<uint32_t>(q), sizeof h, hipMemcpyDeviceToHost));
+        HIP_TRY(hipSetDevice(d.device));
+        HIP_TRY(hipMemcpy(h, cnt.at<uint32_t>(q), sizeof h, hipMemcpyDeviceToHost));
         interior += h[3];
         top[q].resize((size_t)plane); bot[q].resize((size_t)plane);
-        SLAB_HIP(hipMemcpy(bot[q].data(), root.at<uint32_t>(q), 4 * (size_t)plane, hipMemcpyDeviceToHost));
-        SLAB_HIP(hipMemcpy(top[q].data(), root.at<uint32_t>(q) + (size_t)(nvox[q] - plane), 4 * (size_t)plane, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bot[q].data(), root.at<uint32_t>(q), 4 * (size_t)plane, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(top[q].data(), root.at<uint32_t>(q) + (size_t)(nvox[q] - plane), 4 * (size_t)plane, hipMemcpyDeviceToHost));
         // the slab's component table: before the merge below rewrites size[] of the interface roots
-        if (table) SLAB_TRY(ccl_table(L.at<uint32_t>(q), size.at<uint32_t>(q), nvox[q], tblk.b[q], ttab.b[q], cnt.at<uint32_t>(q) + 8,
-                                      d.stream, local[q]));
+        if (table && (rc = ccl_table(L.at<uint32_t>(q), size.at<uint32_t>(q), nvox[q], tblk.b[q], ttab.b[q], cnt.at<uint32_t>(q) + 8,
+                                      d.stream, local[q]))) return rc;
     }
     if (interior == 0) {   // SdfArtifactRemoval.jl:150-153
         if (n_flipped) *n_flipped = 0;
@@ -2813,12 +2745,12 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
             bsz[q].resize(nbq);
             if (!nbq) continue;
             const Slab& d = S[q];
-            SLAB_TRY(idx.ensure(q, 4 * (size_t)nbq)); SLAB_TRY(val.ensure(q, 4 * (size_t)nbq));
-            SLAB_HIP(hipMemcpy(idx.at<uint32_t>(q), broots[q].data(), 4 * (size_t)nbq, hipMemcpyHostToDevice));
+            if ((rc = idx.ensure(q, 4 * (size_t)nbq)) || (rc = val.ensure(q, 4 * (size_t)nbq))) return rc;
+            HIP_TRY(hipMemcpy(idx.at<uint32_t>(q), broots[q].data(), 4 * (size_t)nbq, hipMemcpyHostToDevice));
             gather_u32_kernel<<<(nbq + 255) / 256, 256, 0, d.stream>>>(size.at<uint32_t>(q), idx.at<uint32_t>(q), nbq, val.at<uint32_t>(q));
-            SLAB_HIP(hipMemcpyAsync(bsz[q].data(), val.at<uint32_t>(q), 4 * (size_t)nbq, hipMemcpyDeviceToHost, d.stream));
+            HIP_TRY(hipMemcpyAsync(bsz[q].data(), val.at<uint32_t>(q), 4 * (size_t)nbq, hipMemcpyDeviceToHost, d.stream));
         }
-        SLAB_TRY(sync_slabs(S));
+        if ((rc = sync_slabs(S))) return rc;
         {
             std::vector<size_t> pos(G, 0);
             for (size_t i = 0; i < keys.size(); ++i) {
@@ -2870,8 +2802,8 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
                 const uint64_t sz = cls[find(key_of(q, broots[q][i]))].size;
                 v[i] = sz > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)sz;
             }
-            SLAB_HIP(hipSetDevice(d.device));
-            SLAB_HIP(hipMemcpy(val.at<uint32_t>(q), v.data(), 4 * (size_t)nbq, hipMemcpyHostToDevice));
+            HIP_TRY(hipSetDevice(d.device));
+            HIP_TRY(hipMemcpy(val.at<uint32_t>(q), v.data(), 4 * (size_t)nbq, hipMemcpyHostToDevice));
             scatter_u32_kernel<<<(nbq + 255) / 256, 256, 0, d.stream>>>(size.at<uint32_t>(q), idx.at<uint32_t>(q), val.at<uint32_t>(q), nbq);
         }
         // ---- the largest component: per slab (max size, smallest root having it), then the smallest grid index among ties ----
@@ -2879,16 +2811,16 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
             const Slab& d = S[q];
             const unsigned nb = (unsigned)((nvox[q] + 255u) / 256u);
             uint32_t h[4] = {0, NOLABEL, 0, 0};
-            SLAB_HIP(hipSetDevice(d.device));
-            SLAB_HIP(hipMemcpyAsync(cnt.at<uint32_t>(q), h, sizeof h, hipMemcpyHostToDevice, d.stream));
+            HIP_TRY(hipSetDevice(d.device));
+            HIP_TRY(hipMemcpyAsync(cnt.at<uint32_t>(q), h, sizeof h, hipMemcpyHostToDevice, d.stream));
             ccl_max_kernel<<<nb, 256, 0, d.stream>>>(size.at<uint32_t>(q), nvox[q], cnt.at<uint32_t>(q));
             ccl_argmax_kernel<<<nb, 256, 0, d.stream>>>(size.at<uint32_t>(q), nvox[q], cnt.at<uint32_t>(q));
         }
-        SLAB_TRY(sync_slabs(S));
+        if ((rc = sync_slabs(S))) return rc;
         for (size_t q : order) {
             uint32_t h[4];
-            SLAB_HIP(hipSetDevice(S[q].device));
-            SLAB_HIP(hipMemcpy(h, cnt.at<uint32_t>(q), sizeof h, hipMemcpyDeviceToHost));
+            HIP_TRY(hipSetDevice(S[q].device));
+            HIP_TRY(hipMemcpy(h, cnt.at<uint32_t>(q), sizeof h, hipMemcpyDeviceToHost));
             if (h[1] == NOLABEL) continue;
             uint64_t sz = h[0], gid = (uint64_t)S[q].k0 * (uint64_t)plane + h[1];
             size_t c = (size_t)-1;
@@ -2925,9 +2857,9 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
                 if (ids.empty()) continue;
                 const Slab& d = S[q];
                 std::vector<uint32_t> v(ids.size(), 0xFFFFFFFFu);
-                SLAB_HIP(hipSetDevice(d.device));
-                SLAB_HIP(hipMemcpy(idx.at<uint32_t>(q), ids.data(), 4 * ids.size(), hipMemcpyHostToDevice));
-                SLAB_HIP(hipMemcpy(val.at<uint32_t>(q), v.data(), 4 * v.size(), hipMemcpyHostToDevice));
+                HIP_TRY(hipSetDevice(d.device));
+                HIP_TRY(hipMemcpy(idx.at<uint32_t>(q), ids.data(), 4 * ids.size(), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(val.at<uint32_t>(q), v.data(), 4 * v.size(), hipMemcpyHostToDevice));
                 scatter_u32_kernel<<<(unsigned)((ids.size() + 255) / 256), 256, 0, d.stream>>>(size.at<uint32_t>(q), idx.at<uint32_t>(q),
                                                                                              val.at<uint32_t>(q), (uint32_t)ids.size());
             }
@@ -2939,24 +2871,32 @@ int remove_artifacts_slabs(const std::vector<Slab>& S, const r2s_grid* g, double
         const unsigned nb = (unsigned)((nvox[q] + 255u) / 256u);
         const uint32_t min_size = min_size64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)min_size64;
         uint32_t h[4] = {0, NOLABEL, 0, 0};
-        SLAB_HIP(hipSetDevice(d.device));
-        SLAB_HIP(hipMemcpyAsync(cnt.at<uint32_t>(q), h, sizeof h, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipSetDevice(d.device));
+        HIP_TRY(hipMemcpyAsync(cnt.at<uint32_t>(q), h, sizeof h, hipMemcpyHostToDevice, d.stream));
         ccl_flip_kernel<<<nb, 256, 0, d.stream>>>(d.d_sdf + (int64_t)(d.k0 - d.h0) * plane, root.at<uint32_t>(q), size.at<uint32_t>(q), nvox[q],
                                                 largest_local[q], min_size, cnt.at<uint32_t>(q));
     }
-    SLAB_TRY(sync_slabs(S));
+    if ((rc = sync_slabs(S))) return rc;
     for (size_t q : order) {
         uint32_t h[4];
-        SLAB_HIP(hipSetDevice(S[q].device));
-        SLAB_HIP(hipMemcpy(h, cnt.at<uint32_t>(q), sizeof h, hipMemcpyDeviceToHost));
+        HIP_TRY(hipSetDevice(S[q].device));
+        HIP_TRY(hipMemcpy(h, cnt.at<uint32_t>(q), sizeof h, hipMemcpyDeviceToHost));
         flipped += h[2];
     }
     if (n_flipped) *n_flipped = flipped;
-done:
-    return rc;
+    return 0;
 }
 
 }  // namespace r2s_int
+
+namespace {
+struct SlabWork {   // the smoothing tables and the volume work of one slab, freed with the slab's device current
+    int device = 0;
+    RbfTables tab;
+    VolumeWork vw;
+    ~SlabWork() { (void)hipSetDevice(device); }
+};
+}  // namespace
 
 namespace r2s_int {
 // RBFs_smoothing over Z-slabs (see r2s_internal.hpp).  Every step is the single-device step restricted to the
@@ -2986,8 +2926,8 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
     const bool mv_lut = P.mv == RbfMatvec::walk || P.mv == RbfMatvec::lut;
     SlabBufs bsegmn(S), bsegmx(S), bpart2(S);
     SlabBufs bf(S), bw(S), br(S), bu(S), bq(S), blsf(S), bfine(S), bcnt(S), bpart(S), brows(S);
-    std::vector<RbfTables> tab(G);
-    std::vector<VolumeWork> vw(G);
+    std::vector<SlabWork> sw(G);
+    for (size_t q = 0; q < G; ++q) sw[q].device = S[q].device;
     std::vector<void*> base(G, nullptr);
     auto nheld = [&](size_t q) { return (size_t)(S[q].h1 - S[q].h0) * (size_t)plane; };
     auto vptr = [&](float* p, size_t q) { return p - (int64_t)S[q].h0 * plane; };   // whole-grid addressing of a held array
@@ -3023,46 +2963,46 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
     for (size_t q : order) {
         const Slab& d = S[q];
         const size_t nh = nheld(q);
-        SLAB_TRY(bf.ensure(q, 4 * nh)); SLAB_TRY(bw.ensure(q, 4 * nh)); SLAB_TRY(blsf.ensure(q, 4 * nh));
-        SLAB_TRY(bcnt.ensure(q, 64)); SLAB_TRY(bpart.ensure(q, sizeof(double) * (size_t)std::max(nz * DOT_PARTS, 1024)));
-        if (is_interp) { SLAB_TRY(br.ensure(q, 4 * nh)); SLAB_TRY(bu.ensure(q, 4 * nh)); SLAB_TRY(bq.ensure(q, 4 * nh)); }
-        SLAB_HIP(hipSetDevice(d.device));
-        SLAB_TRY(tab[q].build(P, d.stream));
-        if (q == order[0]) rbf_record_plan(P, is_interp, tab[q]);   // (every slab builds the same forms)
+        if ((rc = bf.ensure(q, 4 * nh)) || (rc = bw.ensure(q, 4 * nh)) || (rc = blsf.ensure(q, 4 * nh))) return rc;
+        if ((rc = bcnt.ensure(q, 64)) || (rc = bpart.ensure(q, sizeof(double) * (size_t)std::max(nz * DOT_PARTS, 1024)))) return rc;
+        if (is_interp && ((rc = br.ensure(q, 4 * nh)) || (rc = bu.ensure(q, 4 * nh)) || (rc = bq.ensure(q, 4 * nh)))) return rc;
+        HIP_TRY(hipSetDevice(d.device));
+        if ((rc = sw[q].tab.build(P, d.stream))) return rc;
+        if (q == order[0]) rbf_record_plan(P, is_interp, sw[q].tab);   // (every slab builds the same forms)
         // process_vector pass 1 on the OWNED planes (every plane counts once for the maximum)
-        SLAB_HIP(hipMemsetAsync(bcnt.b[q].p, 0, 64, d.stream));
+        HIP_TRY(hipMemsetAsync(bcnt.b[q].p, 0, 64, d.stream));
         const int64_t no = nowned(q);
         const unsigned nbo = (unsigned)((no + 255) / 256);
         pv_max_kernel<<<(nbo < 2048u ? nbo : 2048u), 256, 0, d.stream>>>(d.d_sdf + (int64_t)(d.k0 - d.h0) * plane, no, owned(bf.at<float>(q), q),
                                                                          bcnt.at<uint32_t>(q), bcnt.at<uint32_t>(q) + 1);
     }
-    SLAB_TRY(sync_slabs(S));
+    if ((rc = sync_slabs(S))) return rc;
     for (size_t q : order) {
         uint32_t hc[2];
-        SLAB_HIP(hipSetDevice(S[q].device));
-        SLAB_HIP(hipMemcpy(hc, bcnt.b[q].p, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipSetDevice(S[q].device));
+        HIP_TRY(hipMemcpy(hc, bcnt.b[q].p, 8, hipMemcpyDeviceToHost));
         if (hc[1]) { any_real = true; gmax_bits = std::max(gmax_bits, hc[0]); }   // non-negative floats order like their bits
     }
-    if (!any_real) { rc = fail(R2S_ERR_ARG, "every SDF value is a sentinel: nothing to smooth"); goto done; }
+    if (!any_real) return fail(R2S_ERR_ARG, "every SDF value is a sentinel: nothing to smooth");
     for (size_t q : order) {
         const Slab& d = S[q];
         const int64_t no = nowned(q);
-        SLAB_HIP(hipSetDevice(d.device));
-        SLAB_HIP(hipMemcpyAsync(bcnt.b[q].p, &gmax_bits, 4, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipSetDevice(d.device));
+        HIP_TRY(hipMemcpyAsync(bcnt.b[q].p, &gmax_bits, 4, hipMemcpyHostToDevice, d.stream));
         pv_replace_kernel<<<(unsigned)((no + 255) / 256), 256, 0, d.stream>>>(owned(bf.at<float>(q), q), no, bcnt.at<uint32_t>(q));
     }
-    SLAB_TRY(sync_slabs(S));
+    if ((rc = sync_slabs(S))) return rc;
     // ---- weights ----
     if (is_interp) {   // compute_rbf_weights (:191-202), the CG of rbf_smooth_host slab by slab
         for (size_t q : order) {
             const Slab& d = S[q];
-            SLAB_HIP(hipSetDevice(d.device));
-            SLAB_HIP(hipMemcpyAsync(owned(br.at<float>(q), q), owned(bf.at<float>(q), q), 4 * (size_t)nowned(q), hipMemcpyDeviceToDevice, d.stream));
-            SLAB_HIP(hipMemsetAsync(bu.b[q].p, 0, 4 * nheld(q), d.stream));
-            SLAB_HIP(hipMemsetAsync(bw.b[q].p, 0, 4 * nheld(q), d.stream));
+            HIP_TRY(hipSetDevice(d.device));
+            HIP_TRY(hipMemcpyAsync(owned(br.at<float>(q), q), owned(bf.at<float>(q), q), 4 * (size_t)nowned(q), hipMemcpyDeviceToDevice, d.stream));
+            HIP_TRY(hipMemsetAsync(bu.b[q].p, 0, 4 * nheld(q), d.stream));
+            HIP_TRY(hipMemsetAsync(bw.b[q].p, 0, 4 * nheld(q), d.stream));
         }
         float rr;
-        SLAB_TRY(dot(br, br, &rr));
+        if ((rc = dot(br, br, &rr))) return rc;
         float residual = std::sqrt(rr), prev = 1.0f;
         const float tol = 3.4526698e-4f * residual;
         const int64_t ntot = (int64_t)nz * plane;
@@ -3071,31 +3011,31 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
             for (size_t q : order) {
                 const Slab& d = S[q];
                 const int64_t no = nowned(q);
-                SLAB_HIP(hipSetDevice(d.device));
+                HIP_TRY(hipSetDevice(d.device));
                 cg_update_u_kernel<<<(unsigned)((no + 255) / 256), 256, 0, d.stream>>>(owned(bu.at<float>(q), q), owned(br.at<float>(q), q), beta, no);
             }
-            SLAB_TRY(sync_slabs(S));
-            SLAB_TRY(halo_xchg(bu, P.G.tap_r));
+            if ((rc = sync_slabs(S))) return rc;
+            if ((rc = halo_xchg(bu, P.G.tap_r))) return rc;
             for (size_t q : order) {
                 const Slab& d = S[q];
                 const int64_t t0 = (int64_t)d.k0 * plane, t1 = (int64_t)d.k1 * plane;
                 const unsigned nb = (unsigned)((t1 - t0 + 255) / 256);
-                SLAB_HIP(hipSetDevice(d.device));
+                HIP_TRY(hipSetDevice(d.device));
                 float* xv = vptr(bu.at<float>(q), q);
                 float* yv = vptr(bq.at<float>(q), q);
                 const int64_t xlo = (int64_t)d.h0 * plane, xhi = (int64_t)d.h1 * plane - 1;
                 // dot(u, q): the partial sums of the row-walk product's workgroups, as on one device (rbf_smooth_host)
                 const size_t np = rbf_walk_nparts(nx, ny, nz, d.k0, d.k1);
-                SLAB_TRY(bpart2.ensure(q, sizeof(double) * std::max(np, (size_t)1)));
+                if ((rc = bpart2.ensure(q, sizeof(double) * std::max(np, (size_t)1)))) return rc;
                 hp2[q].resize(np);
                 const bool walk_mv = P.mv == RbfMatvec::walk;
-                if (mv_lut) launch_rbf_matvec_lut(P.mv, tab[q].LG, nb, d.stream, xv, yv, t0, t1, xlo, xhi, walk_mv ? bpart2.at<double>(q) : nullptr);
-                else rbf_matvec_kernel<<<nb, 256, 0, d.stream>>>(tab[q].G, xv, yv, t0, t1);
+                if (mv_lut) launch_rbf_matvec_lut(P.mv, sw[q].tab.LG, nb, d.stream, xv, yv, t0, t1, xlo, xhi, walk_mv ? bpart2.at<double>(q) : nullptr);
+                else rbf_matvec_kernel<<<nb, 256, 0, d.stream>>>(sw[q].tab.G, xv, yv, t0, t1);
                 if (!walk_mv) rbf_walk_dot_launch(xv, yv, nx, ny, nz, d.k0, d.k1, bpart2.at<double>(q), d.stream);
-                SLAB_HIP(hipMemcpyAsync(hp2[q].data(), bpart2.at<double>(q), sizeof(double) * np, hipMemcpyDeviceToHost, d.stream));
+                HIP_TRY(hipMemcpyAsync(hp2[q].data(), bpart2.at<double>(q), sizeof(double) * np, hipMemcpyDeviceToHost, d.stream));
             }
             float uq;
-            SLAB_TRY(sync_slabs(S));
+            if ((rc = sync_slabs(S))) return rc;
             {
                 double h = 0.0;
                 for (size_t q : order)   // (slabs in k order: the order of the single-device run)
@@ -3105,15 +3045,15 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
             const float alpha = (residual * residual) / uq;
             for (size_t q : order) {   // weights / residual update with the parts of dot(r, r)
                 const Slab& d = S[q];
-                SLAB_HIP(hipSetDevice(d.device));
+                HIP_TRY(hipSetDevice(d.device));
                 hp[q].resize((size_t)(d.k1 - d.k0) * DOT_PARTS);
                 cg_update_xr_dot_kernel<<<(d.k1 - d.k0) * DOT_PARTS, 256, 0, d.stream>>>(owned(bw.at<float>(q), q), owned(br.at<float>(q), q),
                                                                                          owned(bu.at<float>(q), q), owned(bq.at<float>(q), q), alpha,
                                                                                          plane, bpart.at<double>(q));
-                SLAB_HIP(hipMemcpyAsync(hp[q].data(), bpart.at<double>(q), sizeof(double) * hp[q].size(), hipMemcpyDeviceToHost, d.stream));
+                HIP_TRY(hipMemcpyAsync(hp[q].data(), bpart.at<double>(q), sizeof(double) * hp[q].size(), hipMemcpyDeviceToHost, d.stream));
             }
             prev = residual;
-            SLAB_TRY(sync_slabs(S));
+            if ((rc = sync_slabs(S))) return rc;
             {
                 double h = 0.0;
                 for (size_t q : order)
@@ -3125,28 +3065,28 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         }
     } else {
         for (size_t q : order) {
-            SLAB_HIP(hipSetDevice(S[q].device));
-            SLAB_HIP(hipMemcpyAsync(owned(bw.at<float>(q), q), owned(bf.at<float>(q), q), 4 * (size_t)nowned(q), hipMemcpyDeviceToDevice, S[q].stream));
+            HIP_TRY(hipSetDevice(S[q].device));
+            HIP_TRY(hipMemcpyAsync(owned(bw.at<float>(q), q), owned(bf.at<float>(q), q), 4 * (size_t)nowned(q), hipMemcpyDeviceToDevice, S[q].stream));
         }
-        SLAB_TRY(sync_slabs(S));
+        if ((rc = sync_slabs(S))) return rc;
     }
     if (cg_iters) *cg_iters = its;
     // ---- LSF on the coarse grid (:357) ----
-    SLAB_TRY(halo_xchg(bw, halo));
+    if ((rc = halo_xchg(bw, halo))) return rc;
     for (size_t q : order) {
         const Slab& d = S[q];
         const int64_t t0 = (int64_t)d.k0 * plane, t1 = (int64_t)d.k1 * plane;
-        SLAB_HIP(hipSetDevice(d.device));
-        const RbfGeom& Gq = tab[q].G;
-        if (!launch_rbf_apply_lut(P.ev, Gq, tab[q].LG, P.sts[0], (unsigned)((t1 - t0 + 255) / 256), d.stream, vptr(bw.at<float>(q), q), Gq.cx,
-                                  Gq.cy, Gq.cz, tab[q].st.as<Stencil>(), 0.0f, vptr(blsf.at<float>(q), q), t0, t1,
+        HIP_TRY(hipSetDevice(d.device));
+        const RbfGeom& Gq = sw[q].tab.G;
+        if (!launch_rbf_apply_lut(P.ev, Gq, sw[q].tab.LG, P.sts[0], (unsigned)((t1 - t0 + 255) / 256), d.stream, vptr(bw.at<float>(q), q), Gq.cx,
+                                  Gq.cy, Gq.cz, sw[q].tab.st.as<Stencil>(), 0.0f, vptr(blsf.at<float>(q), q), t0, t1,
                                   (int64_t)d.h0 * plane, (int64_t)d.h1 * plane - 1))
             rbf_apply_kernel<<<(unsigned)((t1 - t0 + 255) / 256), 256, 0, d.stream>>>(Gq, vptr(bw.at<float>(q), q), 1, nx, ny, nz, Gq.cx,
-                                                                                    Gq.cy, Gq.cz, tab[q].st.as<Stencil>(), 0.0f,
+                                                                                    Gq.cy, Gq.cz, sw[q].tab.st.as<Stencil>(), 0.0f,
                                                                                     vptr(blsf.at<float>(q), q), t0, t1);
     }
-    SLAB_TRY(sync_slabs(S));
-    SLAB_TRY(halo_xchg(blsf, 1));   // the cells of the last owned plane reach into the next one
+    if ((rc = sync_slabs(S))) return rc;
+    if ((rc = halo_xchg(blsf, 1))) return rc;   // the cells of the last owned plane reach into the next one
     // ---- volume-preserving level (:359, :265-300): bisection on the summed row volumes ----
     {
         int lo_i = 0x7FFFFFFF, hi_i = (int)0x80000000;
@@ -3155,15 +3095,15 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
             const int64_t no = nowned(q);
             const unsigned nbo = (unsigned)((no + 255) / 256);
             int mmh[2] = {0x7FFFFFFF, (int)0x80000000};
-            SLAB_HIP(hipSetDevice(d.device));
-            SLAB_HIP(hipMemcpyAsync(bcnt.b[q].p, mmh, 8, hipMemcpyHostToDevice, d.stream));
+            HIP_TRY(hipSetDevice(d.device));
+            HIP_TRY(hipMemcpyAsync(bcnt.b[q].p, mmh, 8, hipMemcpyHostToDevice, d.stream));
             minmax_kernel<<<(nbo < 2048u ? nbo : 2048u), 256, 0, d.stream>>>(owned(blsf.at<float>(q), q), no, bcnt.at<int>(q));
         }
-        SLAB_TRY(sync_slabs(S));
+        if ((rc = sync_slabs(S))) return rc;
         for (size_t q : order) {
             int mmh[2];
-            SLAB_HIP(hipSetDevice(S[q].device));
-            SLAB_HIP(hipMemcpy(mmh, bcnt.b[q].p, 8, hipMemcpyDeviceToHost));
+            HIP_TRY(hipSetDevice(S[q].device));
+            HIP_TRY(hipMemcpy(mmh, bcnt.b[q].p, 8, hipMemcpyDeviceToHost));
             lo_i = std::min(lo_i, mmh[0]);
             hi_i = std::max(hi_i, mmh[1]);
         }
@@ -3172,13 +3112,13 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         const size_t q0 = order[0];
         const int nrows = (ny - 1) * (nz - 1);
         for (size_t q : order) {
-            SLAB_HIP(hipSetDevice(S[q].device));
-            SLAB_TRY(vw[q].init(9));
-            SLAB_TRY(brows.ensure(q, sizeof(float) * (size_t)std::max(nrows, 1)));
+            HIP_TRY(hipSetDevice(S[q].device));
+            if ((rc = sw[q].vw.init(9))) return rc;
+            if ((rc = brows.ensure(q, sizeof(float) * (size_t)std::max(nrows, 1)))) return rc;
             // segment extrema of the slab's rows (arrays addressed by the row numbers of the whole grid)
             const int nseg = (nx - 1 + 63) / 64, kc1 = std::min(S[q].k1, nz - 1);
-            SLAB_TRY(bsegmn.ensure(q, sizeof(float) * (size_t)std::max(nrows, 1) * nseg));
-            SLAB_TRY(bsegmx.ensure(q, sizeof(float) * (size_t)std::max(nrows, 1) * nseg));
+            if ((rc = bsegmn.ensure(q, sizeof(float) * (size_t)std::max(nrows, 1) * nseg))) return rc;
+            if ((rc = bsegmx.ensure(q, sizeof(float) * (size_t)std::max(nrows, 1) * nseg))) return rc;
             if (kc1 > S[q].k0)
                 volume_seg_minmax_kernel<<<(kc1 - S[q].k0) * (ny - 1), 256, 0, S[q].stream>>>(vptr(blsf.at<float>(q), q), nx, ny, nz, bsegmn.at<float>(q),
                                                                                              bsegmx.at<float>(q), S[q].k0 * (ny - 1));
@@ -3186,8 +3126,8 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         const float edge = std::sqrt((P.cx[1] - P.cx[0]) * (P.cx[1] - P.cx[0]));
         const float elvol = edge * edge * edge, jac = elvol / 8.0f;
         for (size_t q : order) {
-            SLAB_HIP(hipSetDevice(S[q].device));
-            SLAB_TRY(vw[q].points(jac, S[q].stream));
+            HIP_TRY(hipSetDevice(S[q].device));
+            if ((rc = sw[q].vw.points(jac, S[q].stream))) return rc;
         }
         double eps = 1.0;
         int it = 0;
@@ -3198,20 +3138,20 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
                 const int kc1 = std::min(d.k1, nz - 1);
                 if (kc1 <= d.k0) continue;
                 const int row0 = d.k0 * (ny - 1), nr = (kc1 - d.k0) * (ny - 1);
-                SLAB_HIP(hipSetDevice(d.device));
+                HIP_TRY(hipSetDevice(d.device));
                 volume_rowwave_kernel<<<std::min((nr + 3) / 4, vol_grid()), 256, 0, d.stream>>>(vptr(blsf.at<float>(q), q), nx, ny, nz, th, 0.0f, elvol, jac,
-                                                                                          vw[q].q, brows.at<float>(q), row0, nr, bsegmn.at<float>(q),
-                                                                                          bsegmx.at<float>(q), vw[q].qpts.as<float4>(), nullptr, nullptr);
+                                                                                          sw[q].vw.q, brows.at<float>(q), row0, nr, bsegmn.at<float>(q),
+                                                                                          bsegmx.at<float>(q), sw[q].vw.qpts.as<float4>(), nullptr, nullptr);
                 if (q != q0)
-                    SLAB_HIP(hipMemcpyPeerAsync(brows.at<float>(q0) + row0, S[q0].device, brows.at<float>(q) + row0, d.device,
+                    HIP_TRY(hipMemcpyPeerAsync(brows.at<float>(q0) + row0, S[q0].device, brows.at<float>(q) + row0, d.device,
                                                 sizeof(float) * (size_t)nr, d.stream));
             }
-            SLAB_TRY(sync_slabs(S));
+            if ((rc = sync_slabs(S))) return rc;
             float vol;
-            SLAB_HIP(hipSetDevice(S[q0].device));
-            sum_f32_kernel<<<1, 1024, 0, S[q0].stream>>>(brows.at<float>(q0), nrows, vw[q0].result.as<float>());
-            SLAB_HIP(hipMemcpyAsync(&vol, vw[q0].result.p, sizeof(float), hipMemcpyDeviceToHost, S[q0].stream));
-            SLAB_HIP(hipStreamSynchronize(S[q0].stream));
+            HIP_TRY(hipSetDevice(S[q0].device));
+            sum_f32_kernel<<<1, 1024, 0, S[q0].stream>>>(brows.at<float>(q0), nrows, sw[q0].vw.result.as<float>());
+            HIP_TRY(hipMemcpyAsync(&vol, sw[q0].vw.result.p, sizeof(float), hipMemcpyDeviceToHost, S[q0].stream));
+            HIP_TRY(hipStreamSynchronize(S[q0].stream));
             eps = std::fabs(target_volume - (double)vol);
             if ((double)vol > target_volume) lo = th; else hi = th;
             it++;
@@ -3225,25 +3165,19 @@ int rbf_smooth_slabs(const std::vector<Slab>& S, const r2s_grid* g, int is_inter
         const int f0 = d.k0 * smooth, f1 = std::min(fz, (d.k1 == nz) ? fz : d.k1 * smooth);
         if (f1 <= f0) continue;
         const int64_t t0 = (int64_t)f0 * fplane, t1 = (int64_t)f1 * fplane;
-        SLAB_HIP(hipSetDevice(d.device));
-        SLAB_TRY(bfine.ensure(q, 4 * (size_t)(t1 - t0)));
-        RbfTables& T = tab[q];
+        HIP_TRY(hipSetDevice(d.device));
+        if ((rc = bfine.ensure(q, 4 * (size_t)(t1 - t0)))) return rc;
+        RbfTables& T = sw[q].tab;
         if (!(P.one_to_one && launch_rbf_apply_lut(P.ev, T.G, T.LGF, P.sts[1], (unsigned)((t1 - t0 + 255) / 256), d.stream, vptr(bw.at<float>(q), q),
                                                    T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), T.st.as<Stencil>() + 1, th,
                                                    bfine.at<float>(q) - t0, t0, t1, (int64_t)d.h0 * plane, (int64_t)d.h1 * plane - 1)))
             rbf_apply_kernel<<<(unsigned)((t1 - t0 + 255) / 256), 256, 0, d.stream>>>(T.G, vptr(bw.at<float>(q), q), smooth, fx, fy, fz, T.tx.as<float>(),
                                                                                     T.ty.as<float>(), T.tz.as<float>(), T.st.as<Stencil>() + 1, th,
                                                                                     bfine.at<float>(q) - t0, t0, t1);
-        SLAB_HIP(hipMemcpyAsync(fine_out_host + t0, bfine.at<float>(q), 4 * (size_t)(t1 - t0), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(fine_out_host + t0, bfine.at<float>(q), 4 * (size_t)(t1 - t0), hipMemcpyDeviceToHost, d.stream));
     }
-    SLAB_TRY(sync_slabs(S));
-done:
-    for (size_t q = 0; q < G; ++q) {
-        (void)hipSetDevice(S[q].device);
-        vw[q].release();
-        tab[q].release();
-    }
-    return rc;
+    if ((rc = sync_slabs(S))) return rc;
+    return 0;
 }
 
 int remove_artifacts_dev(double* d_sdf, const r2s_grid* g, double threshold, double min_ratio, hipStream_t st,
@@ -3270,12 +3204,7 @@ int rbf_fit_weights(const double* sdf, const r2s_grid* g, int is_interp, double 
 }
 void rbf_coarse_axis(double mn, double mx, int n, std::vector<float>& c) { coarse_coords(mn, mx, n, c); }
 void* rbf_workspace_create() { return new RbfWork(); }
-void rbf_workspace_release(void* w)
-{
-    if (!w) return;
-    ((RbfWork*)w)->release();
-    delete (RbfWork*)w;
-}
+void rbf_workspace_release(void* w) { delete (RbfWork*)w; }
 }  // namespace r2s_int
 
 extern "C" {
@@ -3288,15 +3217,10 @@ int r2s_remove_artifacts(double* sdf_inout, const r2s_grid* grid, double thresho
     if (rc) return rc;
     DevBuf d;
     ENSURE(d, sizeof(double) * (size_t)grid->ngp);
-    hipError_t e = hipMemcpy(d.p, sdf_inout, sizeof(double) * (size_t)grid->ngp, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { d.release(); return fail(R2S_ERR_HIP, "%s", hipGetErrorString(e)); }
-    rc = remove_artifacts_dev(d.as<double>(), grid, threshold, min_ratio, nullptr, n_flipped);
-    if (!rc) {
-        e = hipMemcpy(sdf_inout, d.p, sizeof(double) * (size_t)grid->ngp, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(R2S_ERR_HIP, "%s", hipGetErrorString(e));
-    }
-    d.release();
-    return rc;
+    HIP_TRY(hipMemcpy(d.p, sdf_inout, sizeof(double) * (size_t)grid->ngp, hipMemcpyHostToDevice));
+    if ((rc = remove_artifacts_dev(d.as<double>(), grid, threshold, min_ratio, nullptr, n_flipped))) return rc;
+    HIP_TRY(hipMemcpy(sdf_inout, d.p, sizeof(double) * (size_t)grid->ngp, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int r2s_remove_artifacts_dev(double* d_sdf, const r2s_grid* grid, double threshold, double min_ratio, void* stream,
@@ -3336,11 +3260,8 @@ int r2s_analyze_components(const double* sdf, const r2s_grid* grid, double thres
     DevBuf d;
     ENSURE(d, sizeof(double) * (size_t)grid->ngp);
     r2s_int::ComponentTable t;
-    hipError_t e = hipMemcpy(d.p, sdf, sizeof(double) * (size_t)grid->ngp, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(R2S_ERR_HIP, "%s", hipGetErrorString(e));
-    if (!rc) rc = analyze_components_dev(d.as<double>(), grid, threshold, nullptr, t);
-    d.release();
-    if (rc) return rc;
+    HIP_TRY(hipMemcpy(d.p, sdf, sizeof(double) * (size_t)grid->ngp, hipMemcpyHostToDevice));
+    if ((rc = analyze_components_dev(d.as<double>(), grid, threshold, nullptr, t))) return rc;
     r2s_int::set_last_components(std::move(t));
     return copy_components(roots_out, sizes_out, capacity, n_components);
 }
@@ -3372,16 +3293,11 @@ int r2s_volume_from_sdf(const float* sdf, int64_t nx, int64_t ny, int64_t nz, fl
     if (rc) return rc;
     VolumeWork vw;
     DevBuf d;
-    rc = vw.init(quad_order);
-    if (rc) return rc;
+    if ((rc = vw.init(quad_order))) return rc;
     const size_t bytes = sizeof(float) * (size_t)(nx * ny * nz);
-    if (d.ensure(bytes)) { vw.release(); return fail(R2S_ERR_NOMEM, "hipMalloc failed"); }
-    hipError_t e = hipMemcpy(d.p, sdf, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(R2S_ERR_HIP, "%s", hipGetErrorString(e));
-    if (!rc) rc = vw.run(d.as<float>(), (int)nx, (int)ny, (int)nz, edge, 0.0f, iso, nullptr, vol_out);
-    d.release();
-    vw.release();
-    return rc;
+    if (d.ensure(bytes)) return fail(R2S_ERR_NOMEM, "hipMalloc failed");
+    HIP_TRY(hipMemcpy(d.p, sdf, bytes, hipMemcpyHostToDevice));
+    return vw.run(d.as<float>(), (int)nx, (int)ny, (int)nz, edge, 0.0f, iso, nullptr, vol_out);
 }
 
 int r2s_rbf_smooth(const double* sdf, const r2s_grid* grid, int32_t is_interp, int32_t smooth, double kernel_threshold,
@@ -3435,5 +3351,7 @@ void r2s_release_cache(void)
     r2s_int::release_intersect_work();
     r2s_int::release_host_sessions();
 }
+
+int64_t r2s_live_device_bytes(void) { return g_live_device_bytes.load(); }
 
 }  // extern "C"

@@ -515,20 +515,18 @@ __global__ void __launch_bounds__(256) ien_check_kernel(const int64_t* __restric
 static int check_ien_dev(const int64_t* dIEN, int64_t total, int64_t nnp)
 {
     DevBuf flag;
-    auto done = [&](int r) { flag.release(); return r; };
-    if (flag.ensure(4)) return done(fail(R2S_ERR_NOMEM, "hipMalloc failed"));
+    if (flag.ensure(4)) return fail(R2S_ERR_NOMEM, "hipMalloc failed");
     uint32_t h_bad = 0;
-    if (hipMemsetAsync(flag.p, 0, 4, nullptr) != hipSuccess) return done(fail(R2S_ERR_HIP, "hipMemset failed"));
+    if (hipMemsetAsync(flag.p, 0, 4, nullptr) != hipSuccess) return fail(R2S_ERR_HIP, "hipMemset failed");
     ien_check_kernel<<<(unsigned)((total + 255) / 256), 256>>>(dIEN, total, nnp, flag.as<uint32_t>());
     if (hipMemcpy(&h_bad, flag.p, 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(R2S_ERR_HIP, "connectivity check failed: %s", hipGetErrorString(hipGetLastError())));
-    if (h_bad) return done(fail(R2S_ERR_ARG, "IEN contains node ids outside 1..nnp"));
-    return done(0);
+        return fail(R2S_ERR_HIP, "connectivity check failed: %s", hipGetErrorString(hipGetLastError()));
+    if (h_bad) return fail(R2S_ERR_ARG, "IEN contains node ids outside 1..nnp");
+    return 0;
 }
 
 struct MeshDev {
     DevBuf X, IEN, a, b;
-    void release() { X.release(); IEN.release(); a.release(); b.release(); }
 };
 
 static int upload_mesh(MeshDev& m, const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, int nen)
@@ -559,18 +557,17 @@ int mesh_volume_dev(const double* dX, const int64_t* dIEN, int64_t nel, int elem
     DevBuf& part = ws ? ws[1] : own[1];
     GaussTab g3, g15;
     tables(g3, g15);
-    auto done = [&](int r) { own[0].release(); own[1].release(); return r; };
-    if (vol.ensure(sizeof(double) * (size_t)nel)) return done(fail(R2S_ERR_NOMEM, "hipMalloc failed"));
+    if (vol.ensure(sizeof(double) * (size_t)nel)) return fail(R2S_ERR_NOMEM, "hipMalloc failed");
     if (elem_type == R2S_HEX8)
         elem_volume_kernel<<<(unsigned)((nel + 3) / 4), 256>>>(dX, dIEN, nullptr, nel, 0, 0.0, g3, g15, vol.as<double>());
     else
         tet_volume_kernel<<<(unsigned)((nel + 255) / 256), 256>>>(dX, dIEN, nel, g3, vol.as<double>());
     double s[2];
     int rc = sum2(vol.as<double>(), d_rho_e, nel, part, s);
-    if (rc) return done(rc);
+    if (rc) return rc;
     *V_domain = s[0];
     *V_frac = s[1] / s[0];   // MeshVolume.jl:41
-    return done(0);
+    return 0;
 }
 
 int dense_in_nodes_dev(const double* dX, int64_t nnp, const int64_t* dIEN, int64_t nel, int elem_type, const double* d_rho_e,
@@ -579,17 +576,16 @@ int dense_in_nodes_dev(const double* dX, int64_t nnp, const int64_t* dIEN, int64
     const int nen = elem_type == R2S_HEX8 ? 8 : 4;
     DevBuf own[5];   // (ws: five buffers the caller keeps between calls)
     DevBuf* b = ws ? ws : own;
-    auto done = [&](int r) { for (DevBuf& x : own) x.release(); return r; };
     int rc = build_ine_dev(dIEN, nel, nen, nnp, b);
-    if (rc) return done(rc);
-    if (b[4].ensure(sizeof(double) * 3 * (size_t)nel)) return done(fail(R2S_ERR_NOMEM, "hipMalloc failed"));
+    if (rc) return rc;
+    if (b[4].ensure(sizeof(double) * 3 * (size_t)nel)) return fail(R2S_ERR_NOMEM, "hipMalloc failed");
     centroid_kernel<<<(unsigned)((nel + 255) / 256), 256>>>(dX, dIEN, nel, nen, b[4].as<double>());
     dense_in_nodes_kernel<<<(unsigned)((nnp + 127) / 128), 128>>>(dX, nnp, b[0].as<uint32_t>(), b[2].as<uint32_t>(), b[4].as<double>(), d_rho_e,
                                                                  d_rho_n_out);
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return done(fail(R2S_ERR_HIP, "dense_in_nodes kernels failed: %s", hipGetErrorString(e)));
-    return done(0);
+    if (e != hipSuccess) return fail(R2S_ERR_HIP, "dense_in_nodes kernels failed: %s", hipGetErrorString(e));
+    return 0;
 }
 
 struct IsoVolume {   // calculate_isocontour_volume (:1-75) for a sequence of thresholds
@@ -617,7 +613,6 @@ struct IsoVolume {   // calculate_isocontour_volume (:1-75) for a sequence of th
         *out = s[0];
         return rc;
     }
-    void release() { vol.release(); part.release(); }
 };
 
 int isocontour_volume_dev(const double* dX, const int64_t* dIEN, int64_t nel, int elem_type, const double* d_rho_n,
@@ -626,7 +621,6 @@ int isocontour_volume_dev(const double* dX, const int64_t* dIEN, int64_t nel, in
     IsoVolume iv{dX, dIEN, nel, elem_type, d_rho_n};
     int rc = iv.init();
     if (!rc) rc = iv.run(thr, volume_out);
-    iv.release();
     return rc;
 }
 
@@ -635,19 +629,18 @@ int find_threshold_dev(const double* dX, const int64_t* dIEN, int64_t nel, int e
 {
     IsoVolume iv{dX, dIEN, nel, elem_type, d_rho_n};
     int rc = iv.init();
-    auto done = [&](int r) { iv.release(); return r; };
-    if (rc) return done(rc);
+    if (rc) return rc;
     double lo = 0.0, hi = 1.0, vmin = 0.0, vmax = 0.0;
-    if ((rc = iv.run(hi, &vmin)) || (rc = iv.run(lo, &vmax))) return done(rc);
+    if ((rc = iv.run(hi, &vmin)) || (rc = iv.run(lo, &vmax))) return rc;
     if (target_volume > vmax || target_volume < vmin)   // Isocontour_volume.jl:93-95
-        return done(fail(R2S_ERR_ARG, "Requested volume %.17g is outside the possible range [%.17g, %.17g]",
-                         target_volume, vmin, vmax));
+        return fail(R2S_ERR_ARG, "Requested volume %.17g is outside the possible range [%.17g, %.17g]",
+                         target_volume, vmin, vmax);
     int it = 0;
     double best = 0.0, best_err = INFINITY;
     while (it < maxit) {
         const double thr = (lo + hi) / 2;
         double v = 0.0;
-        if ((rc = iv.run(thr, &v))) return done(rc);
+        if ((rc = iv.run(thr, &v))) return rc;
         const double e = std::fabs(v - target_volume) / target_volume;
         if (e < best_err) { best = thr; best_err = e; }
         if (e < tol) break;
@@ -656,7 +649,7 @@ int find_threshold_dev(const double* dX, const int64_t* dIEN, int64_t nel, int e
     }
     *rho_t_out = best;
     if (iters_out) *iters_out = it;
-    return done(0);
+    return 0;
 }
 
 }  // namespace r2s_int
@@ -673,13 +666,12 @@ int r2s_mesh_volume(const double* X, int64_t nnp, const int64_t* IEN, int64_t ne
     if (rc) return rc;
     MeshDev m;
     DevBuf rho;
-    auto done = [&](int r) { m.release(); rho.release(); return r; };
-    if ((rc = upload_mesh(m, X, nnp, IEN, nel, nen))) return done(rc);
-    if ((rc = check_ien_dev(m.IEN.as<int64_t>(), nel * nen, nnp))) return done(rc);
-    if (rho.ensure(sizeof(double) * (size_t)nel)) return done(fail(R2S_ERR_NOMEM, "hipMalloc failed"));
+    if ((rc = upload_mesh(m, X, nnp, IEN, nel, nen))) return rc;
+    if ((rc = check_ien_dev(m.IEN.as<int64_t>(), nel * nen, nnp))) return rc;
+    if (rho.ensure(sizeof(double) * (size_t)nel)) return fail(R2S_ERR_NOMEM, "hipMalloc failed");
     if (hipMemcpy(rho.p, rho_e, sizeof(double) * (size_t)nel, hipMemcpyHostToDevice) != hipSuccess)
-        return done(fail(R2S_ERR_HIP, "hipMemcpy failed"));
-    return done(r2s_int::mesh_volume_dev(m.X.as<double>(), m.IEN.as<int64_t>(), nel, elem_type, rho.as<double>(), V_domain, V_frac));
+        return fail(R2S_ERR_HIP, "hipMemcpy failed");
+    return r2s_int::mesh_volume_dev(m.X.as<double>(), m.IEN.as<int64_t>(), nel, elem_type, rho.as<double>(), V_domain, V_frac);
 }
 
 int r2s_dense_in_nodes(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, int32_t elem_type,
@@ -692,18 +684,17 @@ int r2s_dense_in_nodes(const double* X, int64_t nnp, const int64_t* IEN, int64_t
     if (rc) return rc;
     MeshDev m;
     DevBuf rho, out;
-    auto done = [&](int r) { m.release(); rho.release(); out.release(); return r; };
-    if ((rc = upload_mesh(m, X, nnp, IEN, nel, nen))) return done(rc);
+    if ((rc = upload_mesh(m, X, nnp, IEN, nel, nen))) return rc;
     if (rho.ensure(sizeof(double) * (size_t)nel) || out.ensure(sizeof(double) * (size_t)nnp))
-        return done(fail(R2S_ERR_NOMEM, "hipMalloc failed"));
+        return fail(R2S_ERR_NOMEM, "hipMalloc failed");
     if (hipMemcpy(rho.p, rho_e, sizeof(double) * (size_t)nel, hipMemcpyHostToDevice) != hipSuccess)
-        return done(fail(R2S_ERR_HIP, "hipMemcpy failed"));
+        return fail(R2S_ERR_HIP, "hipMemcpy failed");
     if ((rc = r2s_int::dense_in_nodes_dev(m.X.as<double>(), nnp, m.IEN.as<int64_t>(), nel, elem_type, rho.as<double>(),
                                           out.as<double>())))
-        return done(rc);
+        return rc;
     if (hipMemcpy(rho_n_out, out.p, sizeof(double) * (size_t)nnp, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(R2S_ERR_HIP, "copy failed: %s", hipGetErrorString(hipGetLastError())));
-    return done(0);
+        return fail(R2S_ERR_HIP, "copy failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 static int upload_nodal(MeshDev& m, DevBuf& rho, const double* X, int64_t nnp, const int64_t* IEN, int64_t nel,
@@ -735,13 +726,12 @@ int r2s_find_threshold_et(const double* X, int64_t nnp, const int64_t* IEN, int6
     if (rc) return rc;
     MeshDev m;
     DevBuf rho;
-    auto done = [&](int r) { m.release(); rho.release(); return r; };
-    if ((rc = upload_nodal(m, rho, X, nnp, IEN, nel, elem_type, rho_n))) return done(rc);
+    if ((rc = upload_nodal(m, rho, X, nnp, IEN, nel, elem_type, rho_n))) return rc;
     int it = 0;
     rc = r2s_int::find_threshold_dev(m.X.as<double>(), m.IEN.as<int64_t>(), nel, elem_type, rho.as<double>(), target_volume,
                                      tol, maxit, rho_t_out, &it);
     if (iters_out) *iters_out = it;
-    return done(rc);
+    return rc;
 }
 
 int r2s_isocontour_volume(const double* X, int64_t nnp, const int64_t* IEN, int64_t nel, int32_t elem_type,
@@ -753,10 +743,9 @@ int r2s_isocontour_volume(const double* X, int64_t nnp, const int64_t* IEN, int6
     if (rc) return rc;
     MeshDev m;
     DevBuf rho;
-    auto done = [&](int r) { m.release(); rho.release(); return r; };
-    if ((rc = upload_nodal(m, rho, X, nnp, IEN, nel, elem_type, rho_n))) return done(rc);
-    return done(r2s_int::isocontour_volume_dev(m.X.as<double>(), m.IEN.as<int64_t>(), nel, elem_type, rho.as<double>(),
-                                               threshold, volume_out));
+    if ((rc = upload_nodal(m, rho, X, nnp, IEN, nel, elem_type, rho_n))) return rc;
+    return r2s_int::isocontour_volume_dev(m.X.as<double>(), m.IEN.as<int64_t>(), nel, elem_type, rho.as<double>(),
+                                               threshold, volume_out);
 }
 
 }  // extern "C"

@@ -230,8 +230,8 @@ __global__ void __launch_bounds__(256) md_tile_kernel(const float* __restrict__ 
 
 // work buffers of the distance calls, kept per device between calls (r2s_release_cache frees them)
 struct DistWork {
-    Scoped cnt, off, list, flag;            // binning
-    Scoped verts, tris, out, idx, field;   // host-pointer variants / the extracted surface
+    DevBuf cnt, off, list, flag;            // binning
+    DevBuf verts, tris, out, idx, field;   // host-pointer variants / the extracted surface
 };
 PerDevice<DistWork> g_dist_work;
 
@@ -325,22 +325,17 @@ size_t workspace_budget()
 }
 
 struct Timer {
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     hipStream_t st;
     float total = 0.0f;
     bool open = false;
     explicit Timer(hipStream_t s) : st(s)
     {
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) a = b = nullptr;
-    }
-    ~Timer()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
+        if (hipEventCreate(&a.h) != hipSuccess || hipEventCreate(&b.h) != hipSuccess) (void)hipGetLastError();
     }
     void start()
     {
-        if (a) (void)hipEventRecord(a, st), open = true;
+        if (a.h && b.h) (void)hipEventRecord(a, st), open = true;
     }
     void stop()   // waits for the stream
     {

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
+#include <memory>
 #include <utility>
 #include <string>
 #include <vector>
@@ -2275,7 +2276,8 @@ struct r2s_plan {
     GridDev last_g;
     uint32_t last_n_any = 0, last_n_band = 0, last_n_sonly = 0;
     bool has_last = false;
-    uint32_t* h_pinned = nullptr;  // 32 words
+    PinnedBuf pinned;              // 32 words, mapped
+    uint32_t* h_pinned() const { return (uint32_t*)pinned.p; }
     uint32_t* d_pinned = nullptr;  // the same block as the device sees it
     // sizes read back by the last completed call, and the shapes they belong to (speculation, see read_back_kernel)
     struct Spec {
@@ -2283,13 +2285,14 @@ struct r2s_plan {
         int64_t key[12] = {0};
         uint32_t v[16] = {0};
     } spec;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Event ev[8];
     // second stream: sentinel sweep + sign pass run beside the iso-surface projection (fused SDF output)
-    hipStream_t st2 = nullptr;
-    hipStream_t st3 = nullptr;   // bounding half-spaces (hex_planes_kernel), beside the chains of the other two during preparation
-    hipEvent_t ev2[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fast[2] = {nullptr, nullptr};   // around iso_project_hex_pl_kernel alone (r2s_stats.ms_iso_fast)
-    bool fast_timed = false;                      // ... recorded by the current call
+    Stream st2;
+    Stream st3;   // bounding half-spaces (hex_planes_kernel), beside the chains of the other two during preparation
+    Event ev2[8];
+    Event ev_fast[2];   // around iso_project_hex_pl_kernel alone (r2s_stats.ms_iso_fast)
+    bool fast_timed = false;   // ... recorded by the current call
+    ~r2s_plan() { (void)hipSetDevice(device); }   // (runs before the members free themselves)
 };
 
 // exclusive scans of one or two (in1 != nullptr) arrays of n entries each
@@ -2418,17 +2421,17 @@ int r2s_plan_create(int32_t device, r2s_plan** out)
     int rc = check_device(device);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
-    r2s_plan* P = new r2s_plan();
+    std::unique_ptr<r2s_plan> P(new r2s_plan());   // (a failure below frees the half-built plan)
     P->device = device;
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) P->n_cu = prop.multiProcessorCount;
     }
-    HIP_TRY(hipHostMalloc((void**)&P->h_pinned, 128, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void**)&P->d_pinned, P->h_pinned, 0));
-    for (int i = 0; i < 8; ++i) HIP_TRY(hipEventCreate(&P->ev[i]));
-    for (int i = 0; i < 8; ++i) HIP_TRY(hipEventCreate(&P->ev2[i]));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&P->ev_fast[i]));
+    HIP_TRY(P->pinned.ensure(128, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void**)&P->d_pinned, P->h_pinned(), 0));
+    for (int i = 0; i < 8; ++i) HIP_TRY(hipEventCreate(&P->ev[i].h));
+    for (int i = 0; i < 8; ++i) HIP_TRY(hipEventCreate(&P->ev2[i].h));
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&P->ev_fast[i].h));
     {
         // high priority: the short stages of the second stream (sentinel sweep, inverse maps of the sign pass,
         // sign-only gather) get wave slots ahead of the long persistent projection kernel.  Measured on the
@@ -2436,33 +2439,16 @@ int r2s_plan_create(int32_t device, r2s_plan** out)
         int prio_lo = 0, prio_hi = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
         (void)prio_lo;
-        HIP_TRY(hipStreamCreateWithPriority(&P->st2, hipStreamNonBlocking, prio_hi));
-        HIP_TRY(hipStreamCreateWithFlags(&P->st3, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithPriority(&P->st2.h, hipStreamNonBlocking, prio_hi));
+        HIP_TRY(hipStreamCreateWithFlags(&P->st3.h, hipStreamNonBlocking));
     }
-    *out = P;
+    *out = P.release();
     return 0;
 }
 
 void r2s_plan_destroy(r2s_plan* P)
 {
     if (!P) return;
-    (void)hipSetDevice(P->device);
-    DevBuf* all[] = {&P->deg, &P->ine_ptr, &P->ine, &P->cursor, &P->erec, &P->cls, &P->fmask, &P->nitems,
-                     &P->item_off, &P->items, &P->band_cnt, &P->band_off, &P->band_raw, &P->band_ent,
-                     &P->sign_cnt, &P->sign_off, &P->sign_raw, &P->sign_ent, &P->band_aux, &P->sign_aux, &P->active, &P->active_sign, &P->active_any, &P->active_sonly, &P->active_lean, &P->active_tri, &P->tri,
-                     &P->hot, &P->counters, &P->nchunks, &P->chunk_off, &P->iso_res, &P->iso_res_xp, &P->strag,
-                     &P->perm, &P->wchunks, &P->hardflag, &P->sbox, &P->s_nchunks, &P->s_chunk_off, &P->sres, &P->nstore, &P->store_off, &P->s_nstore, &P->s_store_off,
-                     &P->scan_tmp[0], &P->scan_tmp[1], &P->scan_tmp[2], &P->scan_tmp2[0], &P->scan_tmp2[1], &P->scan_tmp2[2]};
-    for (DevBuf* b : all) b->release();
-    if (P->h_pinned) (void)hipHostFree(P->h_pinned);
-    for (int i = 0; i < 8; ++i)
-        if (P->ev[i]) (void)hipEventDestroy(P->ev[i]);
-    for (int i = 0; i < 8; ++i)
-        if (P->ev2[i]) (void)hipEventDestroy(P->ev2[i]);
-    for (int i = 0; i < 2; ++i)
-        if (P->ev_fast[i]) (void)hipEventDestroy(P->ev_fast[i]);
-    if (P->st2) (void)hipStreamDestroy(P->st2);
-    if (P->st3) (void)hipStreamDestroy(P->st3);
     delete P;
 }
 
@@ -2620,7 +2606,7 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
     uint32_t cnt[16] = {0};   // the 16 words of the read-back block: speculated, or read after a wait
     SpecExpect ex;
     memset(&ex, 0, sizeof ex);
-    for (int q = 0; q < 32; ++q) P->h_pinned[q] = 0u;   // (words this call does not report read as 0, now and when compared)
+    for (int q = 0; q < 32; ++q) P->h_pinned()[q] = 0u;   // (words this call does not report read as 0, now and when compared)
     if (spec) {
         memcpy(cnt, P->spec.v, sizeof cnt);
         memcpy(ex.v, P->spec.v, sizeof cnt);
@@ -2706,8 +2692,8 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
     }
     if (!spec) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (P->h_pinned[1]) return fail(R2S_ERR_ARG, "IEN contains node ids outside 1..nnp");
-        cnt[0] = P->h_pinned[0];
+        if (P->h_pinned()[1]) return fail(R2S_ERR_ARG, "IEN contains node ids outside 1..nnp");
+        cnt[0] = P->h_pinned()[0];
         cnt[1] = 0;
     }
     const uint32_t n_items = want_dist ? cnt[0] : 0;
@@ -2828,7 +2814,7 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
     read_back_kernel<<<1, 64, 0, bs>>>(rb2, P->d_pinned, ex, counters + 15);
     if (!spec) {
         HIP_TRY(hipStreamSynchronize(bs));
-        for (int q = 2; q < 16; ++q) cnt[q] = P->h_pinned[q];
+        for (int q = 2; q < 16; ++q) cnt[q] = P->h_pinned()[q];
     }
     const uint32_t n_band = cnt[2], n_sign = cnt[3], n_active = cnt[4], n_active_sign = cnt[5];
     P->last_s = s; P->last_g = g; P->last_n_any = cnt[8]; P->last_n_band = cnt[4]; P->last_n_sonly = cnt[9]; P->has_last = true;
@@ -3048,13 +3034,13 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     if (spec) {
-        if (P->h_pinned[1]) {
+        if (P->h_pinned()[1]) {
             P->spec.valid = false;
             return fail(R2S_ERR_ARG, "IEN contains node ids outside 1..nnp");
         }
-        bool same = P->h_pinned[16] == 0u;
+        bool same = P->h_pinned()[16] == 0u;
         for (int q = 0; q < 16 && same; ++q)
-            if (q != 1 && P->h_pinned[q] != cnt[q]) same = false;
+            if (q != 1 && P->h_pinned()[q] != cnt[q]) same = false;
         if (!same) {
             // the sizes of this call differ from the remembered ones (another mesh / density / threshold behind the
             // same shapes): nothing was written outside the buffers, the outputs are not valid - once more, waiting
@@ -3064,7 +3050,7 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
         }
     } else {
         memcpy(P->spec.key, key, sizeof key);
-        for (int q = 0; q < 16; ++q) P->spec.v[q] = P->h_pinned[q];
+        for (int q = 0; q < 16; ++q) P->spec.v[q] = P->h_pinned()[q];
         P->spec.v[1] = 0;
         P->spec.valid = true;
     }
@@ -3079,8 +3065,8 @@ static int run_impl(r2s_plan* P, const double* dX, int64_t nnp, const int64_t* d
         stats->n_active_sign_tiles = n_active_sign;
         stats->n_any_tiles = P->last_n_any;
         stats->n_sign_only_tiles = P->last_n_sonly;
-        stats->n_iso_fail = P->h_pinned[17];
-        stats->n_iso_straggler = P->h_pinned[18];
+        stats->n_iso_fail = P->h_pinned()[17];
+        stats->n_iso_straggler = P->h_pinned()[18];
         float ms = 0;
         if (hipEventElapsedTime(&ms, P->ev[0], P->ev[1]) == hipSuccess) stats->ms_prep = ms;
         if (hipEventElapsedTime(&ms, P->ev[1], P->ev[2]) == hipSuccess) stats->ms_bins = ms;
