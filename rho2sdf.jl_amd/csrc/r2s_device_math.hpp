@@ -595,7 +595,7 @@ R2S_DEV void iso_eval_fc(const ER& E, const double x[3], double rt, const double
 // minus the ones whose operands the mask makes 0 or 1 (x * 1, x + 0 and 0 * finite are exact), so d, lam and q come out
 // bit for bit as from qp_pattern (checked against the oracle's qp_pattern on 7.2 M random pattern solves incl.
 // indefinite matrices, vanishing gradient components and degenerate bounds).  The non-convex search of
-// iso_project_full evaluates all 19 patterns in every such iteration; these cost a fifth of the generic form.
+// the complete solver (iso_full_enum) evaluates all 19 patterns in every such iteration; these cost a fifth of the generic form.
 // Return value as qp_pattern; kkt / next are not produced (the search takes the feasible pattern of least value).
 template <int k /* free */>
 R2S_DEV int qp_fixed2_t(int si, int sj, const Sym3& H, const double g[3], const double a[3], double e,
@@ -727,9 +727,9 @@ R2S_DEV int iso_clean_pattern(int pat, const double xi[3])
 // ---- the complete solver, one lane = one (element, voxel) pair ------------------------------------------
 // Operation for operation the oracle's iso_project_hex8 (oracle/r2s_oracle.c): exact Lagrangian Hessian, convex
 // active-set QP or the global minimiser of the non-convex QP over the trust region, L1 merit with second-order
-// correction, restoration along nodal segments from stalls.  This straight-line form is the REFERENCE for the two lane
-// machines below (the complete one of iso_straggler_kernel, phase by phase the same operations; the fast path of
-// iso_project_hex_pl_kernel, its common case) and what iso_sweep_kernel runs when the straggler list overflowed.
+// correction, restoration along nodal segments from stalls.  The oracle is the REFERENCE; the iso_full_* phases below
+// are the one definition of that solver on the device (iso_straggler_kernel runs them with lane refill, iso_sweep_kernel
+// through iso_full_run), and the fast path of iso_project_hex_pl_kernel is their common case.
 template <class ER>
 R2S_DEV bool iso_restore(const ER& E, const double x[3], double rt, const double xi[3], double c, double out[3])
 {
@@ -767,310 +767,12 @@ R2S_DEV bool iso_restore(const ER& E, const double x[3], double rt, const double
     return found;
 }
 
-// Returns the number of the last iteration (R2S_ISO_MAXIT + 1: cap).  Start state (xi, mu0, Delta0, pat0, it0): (0, 0, 2, 0, 0) for a run from the start, or the state at the beginning of
-// the iteration in which the fast lane machine gave up - the same thing, provided no earlier iterate was exactly
-// feasible (the run remembers the nearest feasible iterate for the case that it fails: IsoLane::seen).
-template <class ER>
-R2S_DEV int iso_project_full(const ER& E, double rmax_abs, const double x[3], double rt, double xi[3], double mu0 = 0.0,
-                              double Delta0 = 2.0, int pat0 = 0, int it0 = 0)
-{
-    double mu = mu0, lam = 0.0, Delta = Delta0;
-    int pat = pat0, nrest = 0;
-    const double rtol = fmax(fabs(rt), rmax_abs) * 1e-14;
-    double fbest = INFINITY, xbest[3] = {0.0, 0.0, 0.0};
-    double sx[3] = {0.0, 0.0, 0.0}, smu = -1.0, sDelta = -1.0;   // cycle detection (see the oracle): the state at 16, 32, 64, 128
-    int spat = -1, n_nonconvex = 0;   // (a hand-over has seen no non-convex model: the fast path gives up at the first)
-    for (int it = it0; it < R2S_ISO_MAXIT; ++it) {
-        double r[3], J[3][3], a[3], g[3], G[3][3], M2[3][3];
-        if (it > 16 && xi[0] == sx[0] && xi[1] == sx[1] && xi[2] == sx[2] && mu == smu && Delta == sDelta && pat == spat) {
-            if (fbest < INFINITY) { xi[0] = xbest[0]; xi[1] = xbest[1]; xi[2] = xbest[2]; }
-            return R2S_ISO_MAXIT + 1;
-        }
-        if (it == 16 || it == 32 || it == 64 || it == 128) {   // (a hand-over starts at it0 <= R2S_ISO_FAST_IT = 16: no snapshot is missed)
-            sx[0] = xi[0]; sx[1] = xi[1]; sx[2] = xi[2]; smu = mu; sDelta = Delta; spat = pat;
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const TriEval t = tri_eval_full(R2S_CX(E, i), xi);
-            r[i] = x[i] - t.v;
-            J[i][0] = t.d1; J[i][1] = t.d2; J[i][2] = t.d3;
-            M2[i][0] = t.m12; M2[i][1] = t.m13; M2[i][2] = t.m23;
-        }
-        const double f = dot3(r[0], r[1], r[2], r[0], r[1], r[2]);
-        const TriEval tr = tri_eval_full(R2S_CR(E), xi);
-        double c = tr.v - rt;
-        a[0] = tr.d1; a[1] = tr.d2; a[2] = tr.d3;
-        if (fabs(c) <= rtol) c = 0.0;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (fabs(a[j]) <= rtol) a[j] = 0.0;
-        if (c == 0.0 && f < fbest) { fbest = f; xbest[0] = xi[0]; xbest[1] = xi[1]; xbest[2] = xi[2]; }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) g[j] = -2.0 * dot3(r[0], r[1], r[2], J[0][j], J[1][j], J[2][j]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = i; j < 3; ++j)
-                G[i][j] = G[j][i] = 2.0 * dot3(J[0][i], J[1][i], J[2][i], J[0][j], J[1][j], J[2][j]);
-        pat = iso_clean_pattern(pat, xi);
-        {
-            double num = 0.0, den = 0.0;
-            const int sp[3] = {pat & 3, (pat >> 2) & 3, pat >> 4};
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                if (!sp[i]) { num = fma(a[i], g[i], num); den = fma(a[i], a[i], den); }
-            lam = (den > 0.0) ? -num / den : 0.0;
-        }
-        double S[3];
-        {
-            const double mr[3] = {tr.m12, tr.m13, tr.m23};
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                S[q] = fma(lam, mr[q], -2.0 * dot3(r[0], r[1], r[2], M2[0][q], M2[1][q], M2[2][q]));
-        }
-        double lo[3], hi[3], d[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            lo[i] = fmax(-1.0 - xi[i], -Delta);
-            hi[i] = fmin(1.0 - xi[i], Delta);
-        }
-        const double e = -c;
-        double mplus = 0.0, mminus = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double p = a[i] * lo[i], q = a[i] * hi[i];
-            mplus += fmax(p, q);
-            mminus += fmin(p, q);
-        }
-        const double trG = G[0][0] + G[1][1] + G[2][2];
-        const double aa2 = dot3(a[0], a[1], a[2], a[0], a[1], a[2]);
-        const double sigma = 100.0 * trG / aa2;
-        bool convex = true, corner = false, stall = false;
-        int stop = 0;
-        const bool near_feas = (fabs(c) <= 1e4 * rtol);
-        const double mu_keep = (fabs(c) <= 1e10 * rtol) ? 0.5 : 1.0;
-        double lam_new = lam, alpha = 1.0, qstep = 0.0, dGd = 0.0;
-        if (e > mplus) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) d[i] = (a[i] > 0.0) ? hi[i] : ((a[i] < 0.0) ? lo[i] : 0.0);
-            corner = true;
-        } else if (e < mminus) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) d[i] = (a[i] > 0.0) ? lo[i] : ((a[i] < 0.0) ? hi[i] : 0.0);
-            corner = true;
-        }
-        if (corner) {
-            double bp = 0.0, bm = 0.0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const double p = a[i] * (-1.0 - xi[i]), q = a[i] * (1.0 - xi[i]);
-                bp += fmax(p, q);
-                bm += fmin(p, q);
-            }
-            if ((e > 0.0) ? !(bp > 0.05 * e) : !(bm < 0.05 * e)) stall = true;
-            double Gd[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) Gd[i] = dot3(G[i][0], G[i][1], G[i][2], d[0], d[1], d[2]);
-            dGd = dot3(d[0], d[1], d[2], Gd[0], Gd[1], Gd[2]);
-        } else {
-            Sym3 H;
-            double gp[3];
-            int stage = 0;
-            double sg = sigma;
-            for (;;) {
-                iso_qp_data(G, S, a, g, sg, e, H, gp);
-                convex = iso_face_spd(H, pat);
-                if (convex || stage) break;
-                stage = 1;
-                sg = 100.0 * sigma;
-            }
-            QpOut o;
-            bool found = false;
-            if (convex) {
-                int p = pat;
-                for (int step = 0; step < R2S_QP_WALK && p >= 0; ++step) {
-                    const int rc = qp_pattern(p, H, gp, a, e, lo, hi, o);
-                    if (rc == 0 && !stage) {
-                        stage = 1;
-                        sg = 100.0 * sigma;
-                        iso_qp_data(G, S, a, g, sg, e, H, gp);
-                        p = pat;
-                        step = -1;
-                        continue;
-                    }
-                    if (rc == 0) { convex = false; break; }
-                    if (rc == 1 && o.kkt) {
-                        found = true;
-                        pat = p;
-                        d[0] = o.d[0]; d[1] = o.d[1]; d[2] = o.d[2];
-                        lam_new = o.lam;
-                        qstep = o.q;
-                        break;
-                    }
-                    p = o.next;
-                }
-            }
-            if (!found) {
-                double bestq = INFINITY;
-                for (int ip = 0; ip < 19; ++ip) {
-                    const int p = c_pat_order[ip];
-                    int rc;
-                    if (convex || ip == 0) {
-                        rc = qp_pattern(p, H, gp, a, e, lo, hi, o);
-                    } else if (ip < 7) {   // one variable fixed
-                        const int s0 = p & 3, s1 = (p >> 2) & 3, s2 = p >> 4;
-                        const int i = s0 ? 0 : (s1 ? 1 : 2);
-                        rc = qp_fixed1(i, s0 + s1 + s2, H, gp, a, e, lo, hi, o);
-                    } else {               // two fixed
-                        const int s0 = p & 3, s1 = (p >> 2) & 3, s2 = p >> 4;
-                        const int k = !s0 ? 0 : (!s1 ? 1 : 2);
-                        rc = qp_fixed2(k, (k == 0) ? s1 : s0, (k == 2) ? s1 : s2, H, gp, a, e, lo, hi, o);
-                    }
-                    if (rc == 1) {
-                        if ((convex && o.kkt) || o.q < bestq) {
-                            bestq = o.q;
-                            found = true;
-                            pat = p;
-                            d[0] = o.d[0]; d[1] = o.d[1]; d[2] = o.d[2];
-                            lam_new = o.lam;
-                            qstep = o.q;
-                        }
-                        if (convex && o.kkt) break;
-                    }
-                }
-            }
-            if (!found) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    d[i] = (e > 0.0) ? ((a[i] > 0.0) ? hi[i] : ((a[i] < 0.0) ? lo[i] : 0.0))
-                                     : ((a[i] > 0.0) ? lo[i] : ((a[i] < 0.0) ? hi[i] : 0.0));
-                corner = true;
-                convex = true;
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) d[i] = fmin(fmax(d[i], lo[i]), hi[i]);
-        }
-        if (!convex && ++n_nonconvex > R2S_ISO_MAX_NONCONVEX) {
-            if (fbest < INFINITY) { xi[0] = xbest[0]; xi[1] = xbest[1]; xi[2] = xbest[2]; }
-            return R2S_ISO_MAXIT + 1;
-        }
-        const double dmax = fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2])));
-        const double ad = dot3(a[0], a[1], a[2], d[0], d[1], d[2]);
-        const double pred_c = fabs(c) - fabs(c + ad);
-        if (stall) {
-            stop = 2;
-        } else if (!convex) {
-            double mu_t = fmax(mu_keep * mu, 2.0 * fabs(lam_new));
-            double pred = fma(mu_t, pred_c, -qstep);
-            if (!(pred > 0.0)) {
-                if (pred_c > 0.0) { mu_t = 2.0 * qstep / pred_c; pred = qstep; }
-                else stop = near_feas ? 3 : 2;
-            }
-            if (!stop && !(pred > 1e-14 * f)) stop = 3;
-            if (!stop) {
-                mu = mu_t;
-                double xt[3], ft, ct;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) xt[i] = fmin(fmax(xi[i] + d[i], -1.0), 1.0);
-                iso_eval_fc(E, x, rt, xt, ft, ct);
-                const double phi0 = fma(mu, fabs(c), f);
-                if (!(phi0 - fma(mu, fabs(ct), ft) >= 1e-4 * pred)) {
-                    const int sp[3] = {pat & 3, (pat >> 2) & 3, pat >> 4};
-                    double den = 0.0, d2[3] = {d[0], d[1], d[2]};
-                    bool ok = false;
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        if (!sp[i]) den = fma(a[i], a[i], den);
-                    if (den > 0.0) {
-                        const double sc = -ct / den;
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            if (!sp[i]) d2[i] = fma(sc, a[i], d[i]);
-                            xt[i] = fmin(fmax(xi[i] + d2[i], -1.0), 1.0);
-                        }
-                        double f2, c2;
-                        iso_eval_fc(E, x, rt, xt, f2, c2);
-                        ok = (phi0 - fma(mu, fabs(c2), f2) >= 1e-4 * pred);
-                    }
-                    if (ok) { d[0] = d2[0]; d[1] = d2[1]; d[2] = d2[2]; }
-                    else alpha = 0.0;
-                }
-            }
-        } else if (!(dmax > R2S_ISO_TOL)) {
-            stop = (corner && !near_feas) ? 2 : 1;
-        } else {
-            const double gd = dot3(g[0], g[1], g[2], d[0], d[1], d[2]);
-            double mu_t = corner ? mu : fmax(mu_keep * mu, 2.0 * fabs(lam_new));
-            if (corner && pred_c > 0.0) {
-                const double need = 2.0 * fma(0.5, dGd, gd) / pred_c;
-                if (need > mu_t) mu_t = need;
-            }
-            if (!(fma(-mu_t, pred_c, gd) < 0.0)) {
-                if (pred_c > 0.0) mu_t = 2.0 * gd / pred_c;
-                else stop = (near_feas && !corner) ? 4 : 2;
-            }
-            if (!stop) {
-                mu = mu_t;
-                const double D = fma(-mu, pred_c, gd);
-                const double phi0 = fma(mu, fabs(c), f);
-                for (int ls = 0; ls < 30; ++ls) {
-                    double xt[3], ft, ct;
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) xt[i] = fmin(fmax(fma(alpha, d[i], xi[i]), -1.0), 1.0);
-                    iso_eval_fc(E, x, rt, xt, ft, ct);
-                    if (fma(mu, fabs(ct), ft) <= fma(1e-4 * alpha, D, phi0)) break;
-                    if (ls == 0 && !corner) {
-                        const int sp[3] = {pat & 3, (pat >> 2) & 3, pat >> 4};
-                        double den = 0.0;
-#pragma unroll
-                        for (int i = 0; i < 3; ++i)
-                            if (!sp[i]) den = fma(a[i], a[i], den);
-                        if (den > 0.0) {
-                            const double sc = -ct / den;
-                            double d2[3];
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) {
-                                d2[i] = sp[i] ? d[i] : fma(sc, a[i], d[i]);
-                                xt[i] = fmin(fmax(xi[i] + d2[i], -1.0), 1.0);
-                            }
-                            double f2, c2;
-                            iso_eval_fc(E, x, rt, xt, f2, c2);
-                            if (fma(mu, fabs(c2), f2) <= fma(1e-4, D, phi0)) {
-                                d[0] = d2[0]; d[1] = d2[1]; d[2] = d2[2];
-                                break;
-                            }
-                        }
-                    }
-                    alpha *= 0.5;
-                }
-            }
-        }
-        Delta = (alpha < 1.0) ? ((alpha > 0.0) ? alpha * dmax : 0.25 * dmax) : fmin(2.0, fmax(Delta, 2.0 * dmax));
-        if (stop == 2) {
-            double xr[3];
-            if (!near_feas && nrest < R2S_ISO_MAX_RESTORE && iso_restore(E, x, rt, xi, c, xr)) {
-                xi[0] = xr[0]; xi[1] = xr[1]; xi[2] = xr[2];
-                mu = 0.0; Delta = 2.0; pat = 0; nrest++;
-                continue;
-            }
-            if (fbest < INFINITY) { xi[0] = xbest[0]; xi[1] = xbest[1]; xi[2] = xbest[2]; }
-            return R2S_ISO_MAXIT + 1;   // (a stall no restoration repairs: no KKT point - the oracle's return value, counted by the callers)
-        }
-        if (stop == 3 || stop == 4) return it + 1;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) xi[i] = fmin(fmax(fma(alpha, d[i], xi[i]), -1.0), 1.0);
-        if (stop == 1) return it + 1;
-    }
-    if (fbest < INFINITY) { xi[0] = xbest[0]; xi[1] = xbest[1]; xi[2] = xbest[2]; }
-    return R2S_ISO_MAXIT + 1;
-}
-
 // ---- the complete solver as a per-lane state machine -----------------------------------------------------
-// iso_straggler_kernel: the handed-over pairs are worked off by persistent wavefronts with lane refill, like the fast
-// path, but every rule of iso_project_full is there - as phases, so that a trip costs what its lanes' phases cost (a
-// plain iteration: one trip of ~900 instructions) instead of the union of all branches of the straight-line solver
-// (~2 800 per wavefront-iteration).  Each phase performs exactly the IEEE operations of the corresponding part of
-// iso_project_full, in the same order.
+// The device's complete solver: each phase performs exactly the IEEE operations of the corresponding part of the oracle's
+// iso_project_hex8, in the same order.  It is cut into phases so that lanes of a wavefront in different parts of
+// different iterations share a trip that costs what its lanes' phases cost (a plain iteration: ~900 instructions)
+// instead of the union of all branches of the iteration (~2 800).  iso_straggler_kernel works the handed-over pairs off
+// with persistent wavefronts and lane refill, like the fast path; iso_full_run is the phases run to completion by one lane.
 //   EVAL  cycle test, fields, QP data (first sigma, then the second), corner / stall test   -> QP | ENUM | POST
 //   QP    ONE active-set pattern of the walk per visit                                       -> QP | EVAL (second sigma) | ENUM | POST
 //   ENUM  the whole 19-pattern search (convex: first KKT pattern; non-convex: least value)  -> POST
@@ -1094,6 +796,10 @@ struct IsoFullLane {
     bool corner, convex, stall, stage2, force2;
 };
 
+// Start state (xi, mu, Delta, pat, it): (0, 0, 2, 0, 0) for a run from the start, or the state at the beginning of the
+// iteration in which the fast lane machine gave up - the same thing, provided no earlier iterate was exactly feasible (the
+// run remembers the nearest feasible iterate for the case that it fails: IsoLane::seen).  A hand-over has seen no
+// non-convex model (the fast path gives up at the first) and starts at it <= R2S_ISO_FAST_IT = 16: no cycle snapshot is missed.
 R2S_DEV void iso_full_start(IsoFullLane& s, const double x[3], const double xi[3], double mu, double Delta, int pat, int it)
 {
     s.x[0] = x[0]; s.x[1] = x[1]; s.x[2] = x[2];
@@ -1109,7 +815,7 @@ R2S_DEV void iso_full_start(IsoFullLane& s, const double x[3], const double xi[3
 R2S_DEV void iso_full_fail(IsoFullLane& s)
 {
     if (s.fbest < INFINITY) { s.xi[0] = s.xbest[0]; s.xi[1] = s.xbest[1]; s.xi[2] = s.xbest[2]; }
-    s.it = R2S_ISO_MAXIT + 1;   // (what iso_project_full returns for a run that ends without a KKT point: counted, r2s_stats::n_iso_fail)
+    s.it = R2S_ISO_MAXIT + 1;   // (the oracle's return value for a run that ends without a KKT point: counted, r2s_stats::n_iso_fail)
     s.phase = FS_DONE;
 }
 
@@ -1526,12 +1232,32 @@ R2S_DEV void iso_full_upd(const ER& E, double rt, double rtol, IsoFullLane& s)
     if (s.it == R2S_ISO_MAXIT) iso_full_fail(s); else s.phase = FS_EVAL;
 }
 
+// The phases run to completion by one lane, from the start (iso_sweep_kernel).  Returns the iteration the run ended
+// in; > R2S_ISO_MAXIT: it ended without a KKT point.  (iso_full_enum, not the cooperative form: lanes come alone.)
+template <class ER>
+R2S_DEV int iso_full_run(const ER& E, double rmax_abs, const double x[3], double rt, double xi[3])
+{
+    const double rtol = fmax(fabs(rt), rmax_abs) * 1e-14;
+    IsoFullLane s;
+    iso_full_start(s, x, xi, 0.0, 2.0, 0, 0);
+    while (s.phase != FS_DONE) {
+        if (s.phase == FS_EVAL) iso_full_eval(E, rt, rtol, s);
+        if (s.phase == FS_QP) iso_full_qp(s);
+        if (s.phase == FS_ENUM) iso_full_enum(s);
+        if (s.phase == FS_POST) iso_full_post(E, rt, rtol, s);
+        if (s.phase == FS_LS) iso_full_ls(E, rt, s);
+        if (s.phase == FS_UPD) iso_full_upd(E, rt, rtol, s);
+    }
+    xi[0] = s.xi[0]; xi[1] = s.xi[1]; xi[2] = s.xi[2];
+    return s.it;
+}
+
 // ---- the fast path of the same solver as a per-lane state machine ---------------------------------------
 // iso_project_hex_pl_kernel runs the COMMON case of the iteration above with the lanes of a wavefront in
 // different phases / iterations / voxels: plain SQP steps - the QP convex on the faces the active-set walk visits
 // (first sigma), found within R2S_QP_WALK patterns, the full step accepted by the merit function at the first trial -
 // and feasibility steps into a corner of the trust region.  Every phase performs exactly the IEEE operations of the
-// corresponding part of iso_project_full, in the same order.  Anything else (non-convex model, second sigma, exhaustive
+// corresponding part of the complete solver (iso_full_*), in the same order.  Anything else (non-convex model, second sigma, exhaustive
 // pattern search, rejected step, stall, more than R2S_ISO_FAST_IT iterations) ends in ISO_BAIL: the pair goes to the
 // straggler list with its state at the start of the iteration (xi, mu, Delta, pattern, iteration count) and the complete
 // lane machine continues from there (from xi = 0 when an earlier iterate was exactly feasible: IsoLane::seen).  The fast

@@ -1372,10 +1372,45 @@ extern "C" int r2s_debug_strag_hist(unsigned long long* out)
     return hipMemcpyToSymbol(HIP_SYMBOL(g_strag_hist), z, sizeof z) != hipSuccess;
 }
 #endif
+// |x - xp| and, when requested, xp = X(xi) of a solved pair into its result slot; E: any record with X[8][3].  For the
+// two kernels of the complete solver (iso_project_hex_pl_kernel has these lines in place: through a helper the compiler
+// orders its instructions differently, and that kernel is the step's critical path)
+template <class XR>
+__device__ __forceinline__ void iso_store_result(const XR& E, const double x[3], const double xi[3], size_t slot,
+                                                 double* __restrict__ res, double* __restrict__ res_xp)
+{
+    double N[8], xp[3];
+    hex8_shape(xi, N);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t = fma(E.X[k][i], N[k], t);
+        xp[i] = t;
+    }
+    res[slot] = norm3(x[0] - xp[0], x[1] - xp[1], x[2] - xp[2]);
+    if (res_xp) {
+        res_xp[3 * slot] = xp[0];
+        res_xp[3 * slot + 1] = xp[1];
+        res_xp[3 * slot + 2] = xp[2];
+    }
+}
+
+// the 32 solver coefficients of an element into any record with C[8][3], Cr[8]
+template <class KR>
+__device__ __forceinline__ void iso_coef_copy(const ElemRec& E, KR& K)
+{
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        K.C[k][0] = E.C[k][0]; K.C[k][1] = E.C[k][1]; K.C[k][2] = E.C[k][2];
+        K.Cr[k] = E.Cr[k];
+    }
+}
+
 // The pairs the fast path handed over, compacted.  Persistent one-wave workgroups with lane refill run the COMPLETE
-// solver as a lane machine (iso_full_* in r2s_device_math.hpp = iso_project_full = the oracle's iteration, operation for
-// operation): a lane takes the next list entry when its pair is done, and a trip costs what the phases of its lanes cost.
-// (Round 3 started with one lane per pair running iso_project_full straight through: a wavefront then lasts as long as
+// solver as a lane machine (iso_full_* in r2s_device_math.hpp = the oracle's iteration, operation for operation): a lane
+// takes the next list entry when its pair is done, and a trip costs what the phases of its lanes cost.
+// (Round 3 started with one lane per pair running the whole iteration straight through: a wavefront then lasts as long as
 // its slowest lane and executes the union of its lanes' branches in every iteration - 14 us per wavefront-iteration,
 // 0.45-0.6 ms for 3 % of the fast kernel's instructions.)  Every lane has its own element: the 32 coefficients of the
 // solver live in a padded LDS column per lane (33 doubles: two-way bank conflicts at most).
@@ -1428,22 +1463,7 @@ __global__ void __launch_bounds__(64, 2) iso_straggler_kernel(const IsoStraggler
                 if (mf && lane == (uint32_t)__builtin_ctzll(mf)) atomicAdd(n_fail, (uint32_t)__popcll(mf));
             }
             if (s.phase == FS_DONE) {
-                const ElemRec& E = erec[my_el];
-                double N[8], xp[3];
-                hex8_shape(s.xi, N);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) t = fma(E.X[k][q], N[k], t);
-                    xp[q] = t;
-                }
-                res[my_slot] = norm3(s.x[0] - xp[0], s.x[1] - xp[1], s.x[2] - xp[2]);
-                if (res_xp) {
-                    res_xp[3 * my_slot] = xp[0];
-                    res_xp[3 * my_slot + 1] = xp[1];
-                    res_xp[3 * my_slot + 2] = xp[2];
-                }
+                iso_store_result(erec[my_el], s.x, s.xi, my_slot, res, res_xp);
 #ifdef R2S_STRAG_DIAG
                 if (R2S_STRAG_DIAG >= 2) {   // (same-address atomics: the wavefront times of such a build mean nothing)
                     atomicAdd(&g_strag_hist[min(max(s.it, 0), 127)], 1ull);
@@ -1471,12 +1491,7 @@ __global__ void __launch_bounds__(64, 2) iso_straggler_kernel(const IsoStraggler
                 if (s.phase == FS_IDLE && ((m_idle >> lane) & 1ull) && i < n) {
                     const IsoStraggler e = strag[i];
                     const ElemRec& E = erec[e.el];
-                    IsoCoefPad& K = coef[lane];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        K.C[k][0] = E.C[k][0]; K.C[k][1] = E.C[k][1]; K.C[k][2] = E.C[k][2];
-                        K.Cr[k] = E.Cr[k];
-                    }
+                    iso_coef_copy(E, coef[lane]);
                     rtol = fmax(fabs(rho_t), fmax(fabs(E.rmax), fabs(E.rmin))) * 1e-14;
                     my_el = e.el;
                     my_slot = e.slot;
@@ -1533,7 +1548,8 @@ __global__ void __launch_bounds__(64, 2) iso_straggler_kernel(const IsoStraggler
 
 // Only when the straggler list overflowed (a mesh on which more than ~6 % of the pairs leave the fast path - tiny grids
 // are sized so that it cannot happen): every pair of every item is visited item-major and the slots still marked
-// unsolved are worked off in place.  Slow (a wavefront waits for its few unsolved lanes), rare, correct.
+// unsolved are worked off in place, each by its own lane running the phases of the complete solver from the start
+// (iso_full_run).  Slow (a wavefront waits for its few unsolved lanes), rare, correct.
 __global__ void __launch_bounds__(256) iso_sweep_kernel(const BandItem* __restrict__ items, uint32_t nitems,
                                                         const uint32_t* __restrict__ chunk_off, uint32_t nchunks,
                                                         const uint32_t* __restrict__ perm, const ElemRec* __restrict__ erec,
@@ -1564,27 +1580,9 @@ __global__ void __launch_bounds__(256) iso_sweep_kernel(const BandItem* __restri
         x[2] = grid_coord(g, 2, slab_global_k(sl, T.lo[2] + lk));
         const ElemRec& E = erec[T.el];
         IsoElemCoef K;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            K.C[k][0] = E.C[k][0]; K.C[k][1] = E.C[k][1]; K.C[k][2] = E.C[k][2];
-            K.Cr[k] = E.Cr[k];
-        }
-        if (iso_project_full(K, fmax(fabs(E.rmax), fabs(E.rmin)), x, rho_t, xi) > R2S_ISO_MAXIT) atomicAdd(n_fail, 1u);
-        double N[8], xp[3];
-        hex8_shape(xi, N);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            double t = 0.0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) t = fma(E.X[k][q], N[k], t);
-            xp[q] = t;
-        }
-        res[slot] = norm3(x[0] - xp[0], x[1] - xp[1], x[2] - xp[2]);
-        if (res_xp) {
-            res_xp[3 * slot] = xp[0];
-            res_xp[3 * slot + 1] = xp[1];
-            res_xp[3 * slot + 2] = xp[2];
-        }
+        iso_coef_copy(E, K);
+        if (iso_full_run(K, fmax(fabs(E.rmax), fabs(E.rmin)), x, rho_t, xi) > R2S_ISO_MAXIT) atomicAdd(n_fail, 1u);
+        iso_store_result(E, x, xi, slot, res, res_xp);
     }
 }
 
