@@ -44,8 +44,11 @@
  *     on that run's stream before the plan's next run; different plans are independent and may be driven on different
  *     streams.  A field (r2s_rbf_field) and a mesh index are only read by their _dev entry points: one object may be used
  *     from several streams and threads at once.  The entry points that keep work buffers per device (removal and component
- *     analysis, smoothing, extraction, redistancing, shells, sections, weld) take a lock for the length of the call: concurrent calls are
- *     safe and run one after the other.
+ *     analysis, smoothing, extraction, redistancing, shells, sections, weld, orient, fans, holes, intersections) take a lock
+ *     for the length of the call: concurrent calls are safe and run one after the other.  The host-pointer SDF entry points
+ *     (r2s_eval_distances, r2s_sign_detection, r2s_sdf, r2s_rho2sdf) lock their device's session in the same way.  Results a
+ *     call leaves behind for r2s_last_* and r2s_last_error belong to the calling thread.  tests/test_threads_gpu.py is the
+ *     executable form of this item for host threads; r2s_release_cache is the exception (see there).
  *   - devices.  Device pointers and `stream` belong to one device.  r2s_plan_run_dev and r2s_plan_pack_tiles*_dev make the
  *     plan's device current (and leave it current); the _dev entry points of a field or an index refuse a call while
  *     another device than the object's is current (R2S_ERR_ARG, outputs untouched); for every other _dev entry point the
