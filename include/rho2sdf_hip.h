@@ -37,14 +37,14 @@
  *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
  *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
  *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev,
- *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev, r2s_mesh_fans_dev, r2s_mesh_holes_dev.
- *     A caller should still order its consumers on `stream`, not on that wait.
+ *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev, r2s_mesh_fans_dev, r2s_mesh_holes_dev,
+ *     r2s_mesh_nesting_dev.  A caller should still order its consumers on `stream`, not on that wait.
  *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
  *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
  *     on that run's stream before the plan's next run; different plans are independent and may be driven on different
  *     streams.  A field (r2s_rbf_field) and a mesh index are only read by their _dev entry points: one object may be used
  *     from several streams and threads at once.  The entry points that keep work buffers per device (removal and component
- *     analysis, smoothing, extraction, redistancing, shells, sections, weld, orient, fans, holes, intersections) take a lock
+ *     analysis, smoothing, extraction, redistancing, shells, sections, weld, orient, fans, holes, intersections, nesting) take a lock
  *     for the length of the call: concurrent calls are safe and run one after the other.  The host-pointer SDF entry points
  *     (r2s_eval_distances, r2s_sign_detection, r2s_sdf, r2s_rho2sdf) lock their device's session in the same way.  Results a
  *     call leaves behind for r2s_last_* and r2s_last_error belong to the calling thread.  tests/test_threads_gpu.py is the
@@ -797,8 +797,8 @@ int r2s_mesh_signed_distance_dev(const float *d_verts, int64_t n_verts, const in
  * R2S_ERR_ARG before anything else runs, outputs untouched: NULL arrays with a count, a negative count, NULL n_shells /
  * ref_point / totals, a triangle index outside [0, n_verts) or a non-finite vertex (host variant: on the host; _dev: the
  * check kernel of r2s_mesh_distance_dev).  n_tris > 2^30 or n_verts beyond 32 bits: R2S_ERR_UNSUPPORTED.  No GPU:
- * R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 shells.  Not here: which shell encloses which, hole filling; for welding
- * see r2s_mesh_weld below, for the repair of flipped triangles r2s_mesh_orient. */
+ * R2S_ERR_NO_DEVICE.  n_tris == 0 succeeds with 0 shells.  Not here: which shell encloses which
+ * (r2s_mesh_nesting), hole filling; for welding see r2s_mesh_weld below, for the repair of flipped triangles r2s_mesh_orient. */
 int r2s_mesh_shells(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t device,
                     int32_t *shell_of_tri_out, int64_t *n_shells, double ref_point[3], int64_t totals[8]);
 int r2s_last_mesh_shells(int64_t *counts_out, double *sums_out, int64_t capacity, int64_t *n_shells);
@@ -968,7 +968,7 @@ int r2s_mesh_weld_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tr
  *     [5] closed patches, [6] patches decided by volume, [7] flipped edges remaining IN THE OUTPUT: 0 unless a patch is
  *     non-orientable; equal to totals[5] of r2s_mesh_shells on the output mesh.
  *   - NOT HERE.  Nesting is ignored: R2S_ORIENT_OUTWARD makes EVERY closed patch a positive body, so an enclosed void becomes a
- *     body (reverse it again with the patch labels if you know it is a void); the majority rule leaves a void as most of its
+ *     body (r2s_mesh_nesting with R2S_NESTING_REWIND on the output reverses the enclosed voids again); the majority rule leaves a void as most of its
  *     triangles say.  That is why OUTWARD is opt-in.  No orientation is carried across non-manifold edges.  No hole filling.
  *   - determinism: no result depends on an atomic's arrival order (the union-find hooks the larger root under the smaller, the
  *     counts are integer sums); no floating-point atomic and no library reduction touches V.  V is summed by the shells' scheme:
@@ -1220,6 +1220,77 @@ int r2s_mesh_intersections(const float *verts, int64_t n_verts, const int32_t *t
 int r2s_mesh_intersections_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris,
                                int32_t *d_hits_of_tri, int32_t *d_pairs, int64_t pair_capacity, int64_t totals[8],
                                void *stream);
+
+/* ---- mesh nesting: which closed patch encloses which, voids by depth ------------------------------
+ * Is this void enclosed, and in which body?  r2s_mesh_shells calls a closed shell of negative volume a void without asking what
+ * encloses it, and r2s_mesh_orient(OUTWARD) makes every closed patch a positive body.  The nesting is the containment forest of
+ * the orient's patches, found with the exact axis-ray pair test of r2s_mesh_index_winding through the tree of the mesh index.
+ * All outputs are integers, defined so that a loop over all (patch, triangle) pairs gives them bit for bit.  verts float32
+ * [n_verts][3], tris int32 [n_tris][3], 0-based.
+ *   - patches: collapsed triangles, half-edges, edge groups, patches, patch_of_tri and "closed patch" are exactly those of
+ *     r2s_mesh_orient, with the same numbering (ascending smallest triangle index; -1 for a collapsed triangle).  No orientation
+ *     is needed and none is read: the tool works on inconsistently wound input.
+ *   - sample of a patch P: the float32 vertex at corner 0 of P's first (smallest-index) triangle, widened to double.
+ *   - cross(P, Q), for a patch P and a CLOSED patch Q != P: the number of triangles of Q that are a crossing of the axis ray
+ *     `ray` (0..5 as in r2s_mesh_index_winding) from P's sample, by steps 1 to 6 of that section: the effective signs with the
+ *     tie rule, the own-box condition, det != 0, t > 0, every operation rounded on its own (no fma).  `side` is not used, only
+ *     the parity counts.  Triangles of P itself, of open patches, and collapsed triangles take part in nothing.
+ *   - containment: Q contains P iff cross(P, Q) is odd.  Every patch, open or closed, is a query; only closed patches are
+ *     containers.
+ *   - depth(P) = the number of containers of P.  parent(P) = the container of the largest depth, among equals the smallest patch
+ *     number, -1 without a container.
+ *   - P is IRREGULAR iff depth(P) > 0 and depth(parent(P)) != depth(P) - 1: its containers are not a chain, so patches pass
+ *     through each other (r2s_mesh_index_intersections says where).
+ *   - integer record of a patch, int64[8]: [0] first_tri, [1] n_tris, [2] status bits: 1 closed, 2 reversed in the output, 4
+ *     irregular, [3] parent, [4] depth, [5] n_children, the number of patches whose parent it is, [6] the sum of cross(P, Q) over
+ *     all closed Q != P, [7] 0.
+ *   - totals, int64[8]: [0] patches, [1] triangles (n_tris), [2] collapsed, [3] closed patches, [4] containment pairs, equal to
+ *     the sum of the depths, [5] the largest depth, [6] irregular patches, [7] triangles reversed in the output.
+ *   - pair list: all (query, container) pairs as int64 (P << 32) | Q, sorted ascending.
+ *   - flag R2S_NESTING_REWIND: tris_out receives the input triangles in their order, every triangle of a closed patch at ODD
+ *     depth written (i0, i2, i1), everything else copied.  This is relative to the input: applied to the output of
+ *     r2s_mesh_orient(OUTWARD) it yields positive bodies and negative voids, alternating with depth.  Without the flag tris_out
+ *     may be NULL and is not written, no status has bit 2 and totals[7] is 0.  Any other flag bit: R2S_ERR_ARG.
+ *   - why the tree is exact: the argument of r2s_mesh_index_winding carries over.  The own-box condition is part of the pair
+ *     test, float32 min / max do not round, so every ancestor's box contains the leaf's; entering a child iff the same three
+ *     comparisons hold on the child's box reaches every crossing of the definition.  The tree holds all triangles; whose they are
+ *     is decided at the leaf.
+ *   - limits: a sample that lies on another patch gets a ray-dependent answer (t > 0 is strict); the known rounding limit of the
+ *     tie rule applies as stated there; a patch with a non-manifold or boundary edge is never a container: weld, split and fill
+ *     first; one ray per call.  Not here: voting over rays, nesting of open surfaces, repair of irregular patches.
+ *   - determinism: integer work only; the only atomics are integer adds and the cursor of the crossing list, which is sorted
+ *     afterwards; nothing depends on an arrival order.  Under a permutation of the triangles every output follows the
+ *     permutation, through the renumbering of the patches.  No claim is made under a rotation of a triangle's corners: the sample
+ *     changes.
+ * r2s_mesh_nesting: host arrays, `device` (-1 = current); a tree is built, used and dropped.  tris_out [n_tris][3] is required
+ * with R2S_NESTING_REWIND when n_tris > 0 and must not overlap tris; patch_of_tri_out [n_tris] may be NULL.  *n_patches and
+ * totals are always written on success; the records and the pair list become the calling thread's last result, read with
+ * r2s_last_mesh_nesting: counts_out [capacity][8], pairs_out [pair_capacity]; *n_patches and *n_pairs are always the full counts,
+ * the first min(capacity, n) records and min(pair_capacity, m) pairs are written; a pointer may be NULL only with its capacity 0.
+ * r2s_mesh_nesting_dev: device arrays on the current device, read after the work queued on `stream`, which is the only stream the
+ * call queues on.  index: an r2s_mesh_index of the SAME mesh on the current device, used and left unchanged (its triangle count
+ * must be n_tris, else R2S_ERR_ARG), or NULL: a tree is built and dropped.  d_tris_out (with the flag), d_patch_of_tri (may be
+ * NULL), d_counts [patch_capacity][8] and d_pairs [pair_capacity] are device pointers; n_patches, n_pairs and totals host
+ * pointers, always written on success.  The triangles and the patch labels are always written; the records only when
+ * patch_capacity >= *n_patches and the pairs only when pair_capacity >= *n_pairs (else that table is left untouched: ask with
+ * capacity 0, then call again).  Synchronous on return; it does not touch the thread's last result.  Work buffers are kept per
+ * device and freed by r2s_release_cache.
+ * R2S_ERR_ARG before any output is touched, as by r2s_mesh_orient: NULL arrays with a count, a negative count or capacity, ray
+ * outside 0..5, a bad flag, NULL tris_out with the flag and a count, tris_out overlapping tris, NULL n_patches / n_pairs /
+ * totals, NULL tables with a capacity, an index of another triangle count or on another device, a triangle index outside
+ * [0, n_verts) or a non-finite vertex (host variant: on the host; _dev: the check kernel of r2s_mesh_distance_dev).
+ * R2S_ERR_UNSUPPORTED, outputs untouched: n_tris > 2^30 or n_verts beyond 32 bits (before anything is read), more than 2^31 - 1
+ * crossings, a tree deeper than the traversal stack (64 levels).  No GPU: R2S_ERR_NO_DEVICE; there is no CPU fallback.
+ * n_tris == 0 succeeds with 0 patches. */
+#define R2S_NESTING_REWIND 1
+int r2s_mesh_nesting(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, int32_t ray, int32_t flags,
+                     int32_t device, int32_t *tris_out, int32_t *patch_of_tri_out, int64_t *n_patches, int64_t totals[8]);
+int r2s_last_mesh_nesting(int64_t *counts_out, int64_t capacity, int64_t *pairs_out, int64_t pair_capacity, int64_t *n_patches,
+                          int64_t *n_pairs);
+int r2s_mesh_nesting_dev(const r2s_mesh_index *index, const float *d_verts, int64_t n_verts, const int32_t *d_tris,
+                         int64_t n_tris, int32_t ray, int32_t flags, int32_t *d_tris_out, int32_t *d_patch_of_tri,
+                         int64_t *d_counts, int64_t patch_capacity, int64_t *d_pairs, int64_t pair_capacity, int64_t *n_patches,
+                         int64_t *n_pairs, int64_t totals[8], void *stream);
 
 /* ---- on-disk output ------------------------------------------------------------------ */
 

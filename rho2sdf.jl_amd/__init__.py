@@ -21,6 +21,7 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   MeshFans, mesh_fans, mesh_fans_dev,
                   MeshHoles, mesh_holes, mesh_holes_dev,
                   MeshIntersections, mesh_intersections, mesh_intersections_dev,
+                  MeshNesting, mesh_nesting, mesh_nesting_dev,
                   mesh_signed_distance, mesh_signed_distance_dev)
 
 __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh", "RBFs_smoothing", "Rho2sdfOptions", "Sign_Detection",
@@ -39,5 +40,6 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "MeshFans", "mesh_fans", "mesh_fans_dev",
            "MeshHoles", "mesh_holes", "mesh_holes_dev",
            "MeshIntersections", "mesh_intersections", "mesh_intersections_dev",
+           "MeshNesting", "mesh_nesting", "mesh_nesting_dev",
            "mesh_signed_distance", "mesh_signed_distance_dev",
            "_lib"]

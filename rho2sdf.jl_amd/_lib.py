@@ -255,6 +255,11 @@ SYMBOLS = [
     ("r2s_mesh_intersections", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_int32, c_int32_p, c_int32_p,
                                               ctypes.c_int64, c_int64_p]),
     ("r2s_mesh_intersections_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, c_int64_p, _P]),
+    ("r2s_mesh_nesting", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        c_int32_p, c_int32_p, c_int64_p, c_int64_p]),
+    ("r2s_last_mesh_nesting", ctypes.c_int, [c_int64_p, ctypes.c_int64, c_int64_p, ctypes.c_int64, c_int64_p, c_int64_p]),
+    ("r2s_mesh_nesting_dev", ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                            ctypes.c_int64, _P, ctypes.c_int64, c_int64_p, c_int64_p, c_int64_p, _P]),
     ("r2s_import_stl", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(R2SStlMesh)]),
     ("r2s_free_stl_mesh", None, [ctypes.POINTER(R2SStlMesh)]),
 ]
@@ -263,6 +268,7 @@ OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8
 HEX8, TET4 = 0, 1
 WELD_DROP_COLLAPSED, WELD_DROP_DUPLICATES, WELD_DROP_UNUSED = 1, 2, 4
 ORIENT_OUTWARD = 1
+NESTING_REWIND = 1
 
 _lib = None
 

@@ -1202,7 +1202,7 @@ def mesh_orient(verts, tris, *, outward=False, device=-1):
     into patches over the edges that exactly two triangles share; inside an orientable patch every triangle gets the winding of
     its neighbours, and the patch as a whole keeps the winding of the MAJORITY of its triangles (a tie: of its first triangle).
     outward=True: a closed patch with a non-zero volume is wound so that its volume is positive instead.  Nesting is ignored:
-    outward=True turns an enclosed void into a body (reverse it again with flip_patches if you know it is one), the majority
+    outward=True turns an enclosed void into a body (mesh_nesting(rewind=True) on the result reverses the voids again), the majority
     rule leaves a void as most of its triangles say.  Non-orientable patches are copied unchanged and counted; no orientation is
     carried across non-manifold edges; no holes are filled.  One library call and a copy of the thread's last tables."""
     v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
@@ -1273,6 +1273,110 @@ def flip_patches(tris, patch_of_tri, which):
     rev = (pot >= 0) & np.concatenate([sel, [False]])[pot]
     t[rev] = t[rev][:, [0, 2, 1]]
     return t
+
+
+class MeshNesting:
+    """The result of mesh_nesting (include/rho2sdf_hip.h, r2s_mesh_nesting): `tris` (nt, 3) int32, with rewind=True the input
+    triangles in their order with those of the closed patches at odd depth written (i0, i2, i1), else None; `patch_of_tri` (nt,)
+    int32, the patches of mesh_orient (-1 for a collapsed triangle); `counts` (n, 8) int64 (first_tri, n_tris, status bits 1
+    closed / 2 reversed in the output / 4 irregular, parent, depth, n_children, the sum of the crossings, 0); `pairs` (m,) int64,
+    the (query, container) pairs as (P << 32) | Q, ascending; `totals` (8,) int64 (patches, triangles, collapsed, closed patches,
+    containment pairs, largest depth, irregular patches, triangles reversed).  Derived on the host: parent, depth, closed,
+    irregular (one entry per patch), roots (the patches without a container), children(p), voids (closed, odd depth) and bodies
+    (closed, even depth) as ascending patch numbers.  numpy arrays from mesh_nesting; mesh_nesting_dev keeps tris, patch_of_tri
+    and pairs on the device."""
+
+    def __init__(self, tris, patch_of_tri, counts, pairs, totals):
+        self.tris, self.patch_of_tri, self.counts, self.pairs, self.totals = tris, patch_of_tri, counts, pairs, totals
+
+    n_patches = property(lambda s: len(s.counts))
+    first_tri = property(lambda s: s.counts[:, 0])
+    n_tris = property(lambda s: s.counts[:, 1])
+    closed = property(lambda s: (s.counts[:, 2] & 1) != 0)
+    reversed = property(lambda s: (s.counts[:, 2] & 2) != 0)
+    irregular = property(lambda s: (s.counts[:, 2] & 4) != 0)
+    parent = property(lambda s: s.counts[:, 3])
+    depth = property(lambda s: s.counts[:, 4])
+    n_children = property(lambda s: s.counts[:, 5])
+    roots = property(lambda s: np.nonzero(s.counts[:, 3] < 0)[0])
+    voids = property(lambda s: np.nonzero(s.closed & (s.depth % 2 == 1))[0])
+    bodies = property(lambda s: np.nonzero(s.closed & (s.depth % 2 == 0))[0])
+
+    def children(self, p):
+        """the patches whose parent is patch p, ascending"""
+        return np.nonzero(self.counts[:, 3] == int(p))[0]
+
+    def __len__(self):
+        return len(self.counts)
+
+
+def _nesting_ray(ray):
+    if isinstance(ray, bool) or not isinstance(ray, (int, np.integer)) or not 0 <= ray <= 5:
+        raise L.R2SError("ray must be 0..5 (+x +y +z -x -y -z)")
+    return int(ray)
+
+
+def mesh_nesting(verts, tris, *, ray=2, rewind=False, index=None, device=-1):
+    """Which closed patch of a triangle mesh encloses which patch (verts (nv, 3) float32, tris (nt, 3) int32, 0-based) ->
+    MeshNesting.  The patches are those of mesh_orient; no winding is read.  A closed patch Q contains a patch P when the axis ray
+    `ray` (0..5: +x +y +z -x -y -z) from P's sample vertex crosses Q an odd number of times, by the exact pair test of
+    MeshIndex.winding; the depth of a patch is the number of its containers, its parent the deepest of them.  Closed patches at
+    even depth are bodies, at odd depth voids.  rewind=True: `tris` of the result has the voids reversed relative to the input,
+    so after mesh_orient(outward=True) bodies are positive and voids negative.  Patches with a boundary or a non-manifold edge
+    contain nothing (weld, split and fill first); an irregular patch says that surfaces pass through each other.  index: a
+    MeshIndex of the same mesh on the current device, used and left unchanged (the arrays then travel as torch tensors and
+    `device` is ignored); None: the library builds a tree, uses it and drops it."""
+    ray = _nesting_ray(ray)
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    if index is not None:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        r = mesh_nesting_dev(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), ray=ray, rewind=rewind, index=index)
+        return MeshNesting(r.tris.cpu().numpy() if rewind else None, r.patch_of_tri.cpu().numpy(), r.counts, r.pairs.cpu().numpy(), r.totals)
+    out, pot = np.empty((len(t), 3), np.int32) if rewind else None, np.empty(len(t), np.int32)
+    n, m = ctypes.c_int64(), ctypes.c_int64()
+    tot = np.zeros(8, np.int64)
+    ip = lambda a: a.ctypes.data_as(L.c_int32_p)   # noqa: E731
+    L.check(L.lib().r2s_mesh_nesting(_f(v) if len(v) else None, len(v), ip(t) if len(t) else None, len(t), ray,
+                                     L.NESTING_REWIND if rewind else 0, int(device), ip(out) if rewind else None, ip(pot),
+                                     ctypes.byref(n), _i(tot)))
+    L.check(L.lib().r2s_last_mesh_nesting(None, 0, None, 0, ctypes.byref(n), ctypes.byref(m)))
+    counts, pairs = np.empty((n.value, 8), np.int64), np.empty(m.value, np.int64)
+    if n.value:
+        L.check(L.lib().r2s_last_mesh_nesting(_i(counts), n.value, _i(pairs) if m.value else None, m.value, ctypes.byref(n), ctypes.byref(m)))
+    return MeshNesting(out, pot, counts, pairs, tot)
+
+
+def mesh_nesting_dev(verts, tris, stream=None, *, ray=2, rewind=False, index=None, capacity=0, pair_capacity=0):
+    """mesh_nesting on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous).  The records
+    and totals come back as numpy arrays; tris (with rewind), patch_of_tri and pairs stay device tensors.  index: a MeshIndex of
+    the same mesh on the current device.  The library writes a table only into room for all of it: with more patches than
+    `capacity` or more pairs than `pair_capacity` the call is made a second time."""
+    import torch
+    ray = _nesting_ray(ray)
+    _mesh_tensors(verts, tris)
+    st = _stream(stream)
+    dev = verts.device
+    nt = tris.numel() // 3
+    out = torch.empty((nt, 3), dtype=torch.int32, device=dev) if rewind else None
+    pot = torch.empty(nt, dtype=torch.int32, device=dev)
+    n, m = ctypes.c_int64(), ctypes.c_int64()
+    tot = np.zeros(8, np.int64)
+    cap, pcap = int(capacity), int(pair_capacity)
+    vp = ctypes.c_void_p
+    h = index._handle() if index is not None else None
+    while True:
+        counts = torch.empty((cap, 8), dtype=torch.int64, device=dev)
+        pairs = torch.empty(pcap, dtype=torch.int64, device=dev)
+        L.check(L.lib().r2s_mesh_nesting_dev(h, vp(verts.data_ptr()), verts.numel() // 3, vp(tris.data_ptr()), nt, ray,
+                                             L.NESTING_REWIND if rewind else 0, vp(out.data_ptr()) if rewind else None,
+                                             vp(pot.data_ptr()), vp(counts.data_ptr()) if cap else None, cap,
+                                             vp(pairs.data_ptr()) if pcap else None, pcap, ctypes.byref(n), ctypes.byref(m), _i(tot), st))
+        if n.value <= cap and m.value <= pcap:
+            break
+        cap, pcap = max(cap, n.value), max(pcap, m.value)
+    return MeshNesting(out, pot, counts[:n.value].cpu().numpy(), pairs[:m.value], tot)
 
 
 class MeshFans:
@@ -1979,7 +2083,9 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     vertices dropped), so the mesh tools see shared vertices; weld=False: the soup as the file holds it, 3 nt vertices and
     tris = arange.  Facet normals and attribute bytes are ignored.  orient=None: the windings as the file holds them;
     "majority" or "outward" (needs weld=True): the welded triangles go through mesh_orient(outward=(orient == "outward")), whose
-    docstring has the rules and the caveat about enclosed voids.  check_intersections=True (needs weld=True): the result is
+    docstring has the rules and the caveat about enclosed voids; "nested" (needs weld=True): mesh_orient(outward=True) and then
+    mesh_nesting(rewind=True), so that closed bodies are positive and the voids enclosed in them negative, alternating with the
+    depth of the nesting.  check_intersections=True (needs weld=True): the result is
     (verts, tris, MeshIntersections), the self-intersections of the mesh as returned (mesh_intersections): zero pairs are what
     the shells, the orientation, sections and thickness take for granted.  split_vertices=True (needs weld=True): after the weld,
     and after the orient if one is asked for, the vertices the weld left pinched (two bodies touching in a point) are split by
@@ -1993,12 +2099,13 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
         verts, tris, x = import_stl("part.stl", orient="majority", split_vertices=True, fill_holes=-1, check_intersections=True)
         assert len(x) == 0                                        # the surface, caps included, does not pass through itself
         assert mesh_holes(verts, tris).watertight                 # no rim was left open (a fin, a non-manifold edge)
-        tris = mesh_orient(verts, tris, outward=True).tris        # the sign of a closed shell: outward
+        tris = mesh_orient(verts, tris, outward=True).tris        # every closed shell outward ...
+        tris = mesh_nesting(verts, tris, rewind=True).tris        # ... and the enclosed voids inward again, by depth
         grid = Grid(verts.min(0), verts.max(0), 128)              # 128 cells along the longest side, 3 cells of margin
         sdf = mesh_signed_distance(verts, tris, grid)             # (nz, ny, nx), positive inside
         exportSdfToVTI("part_sdf", grid, sdf, "distance")"""
-    if orient not in (None, "majority", "outward"):
-        raise L.R2SError('orient must be None, "majority" or "outward"')
+    if orient not in (None, "majority", "outward", "nested"):
+        raise L.R2SError('orient must be None, "majority", "outward" or "nested"')
     if orient is not None and not weld:
         raise L.R2SError("orient needs weld=True: a soup has no shared edges to orient across")
     if split_vertices and not weld:
@@ -2018,7 +2125,9 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
         return soup, np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
     w = mesh_weld(soup, None, snap=snap, device=device)
     verts = w.verts
-    tris = w.tris if orient is None else mesh_orient(verts, w.tris, outward=orient == "outward", device=device).tris
+    tris = w.tris if orient is None else mesh_orient(verts, w.tris, outward=orient != "majority", device=device).tris
+    if orient == "nested":
+        tris = mesh_nesting(verts, tris, rewind=True, device=device).tris
     if split_vertices:
         f = mesh_fans(verts, tris, split=True, device=device)
         verts, tris = f.verts, f.tris

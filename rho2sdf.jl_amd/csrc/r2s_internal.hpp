@@ -215,4 +215,8 @@ void release_holes_work();
 // frees the work buffers the intersection calls keep per device; called by r2s_release_cache()
 void release_intersect_work();
 
+// ---- mesh nesting (r2s_mesh_nesting.hip) ------------------------------------------------------------------------------
+// frees the work buffers the nesting calls keep per device; called by r2s_release_cache()
+void release_nesting_work();
+
 }  // namespace r2s_int

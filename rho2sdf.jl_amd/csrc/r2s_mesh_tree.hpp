@@ -1,5 +1,6 @@
 // What the traversals of the mesh index share across files (r2s_mesh_index.hip: distance and ray queries; r2s_mesh_intersect.hip:
-// self-intersection pairs; r2s_mesh_winding.hip: winding number and signed distance): the index object, the node of its tree and how
+// self-intersection pairs; r2s_mesh_winding.hip: winding number and signed distance; r2s_mesh_nesting.hip: containment of
+// patches): the index object, the node of its tree and how
 // a wavefront reads it, the box of a triangle, the depth of the per-lane stack, the host checks every entry point on an index makes
 // and the staging of a host-pointer call.  One definition for all files.
 #pragma once
@@ -48,6 +49,16 @@ __device__ inline void tri_box(const float* a, const float* b, const float* c, f
         lo[k] = fminf(a[k], fminf(b[k], c[k]));
         hi[k] = fmaxf(a[k], fmaxf(b[k], c[k]));
     }
+}
+
+// may the axis ray from o along +e_KZ (neg: -e_KZ) meet something inside the float32 box b (lo xyz, hi xyz)?  The three exact
+// comparisons of the own-box condition of the pair test (axis_cross, r2s_tri_math.hpp): the cull of the winding and of the nesting
+template <int KZ>
+__device__ inline bool axis_enter(const float* __restrict__ b, double o1, double o2, double oz, bool neg)
+{
+    constexpr int K1 = (KZ + 1) % 3, K2 = (KZ + 2) % 3;
+    const bool ahead = neg ? (double)b[KZ] <= oz : (double)b[3 + KZ] >= oz;
+    return (double)b[K1] <= o1 && o1 <= (double)b[3 + K1] && (double)b[K2] <= o2 && o2 <= (double)b[3 + K2] && ahead;
 }
 
 // the traversal kernels keep one pending sibling per level on a per-lane stack of MI_STACK entries (r2s_mesh_index.hip)

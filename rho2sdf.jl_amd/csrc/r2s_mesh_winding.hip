@@ -1,7 +1,7 @@
 // Mesh winding: the signed count of crossings of an axis ray from every query point, the inside / outside verdict derived from
 // it and the signed distance s * d (include/rho2sdf_hip.h, r2s_mesh_index_winding / _signed; DESIGN.md "Mesh winding").
 // mwn_points_kernel: one lane per point, 64 points per workgroup, the per-lane LDS stack of mi_query_kernel.  The ray is one of
-// the six axis directions, so a box is culled by three exact comparisons and no ordering of the children is needed: every
+// the six axis directions, so a box is culled by three exact comparisons (axis_enter, r2s_mesh_tree.hpp) and no ordering of the children is needed: every
 // child whose box passes is entered, the second one through the stack.  A leaf runs axis_cross (r2s_tri_math.hpp), which holds
 // the own-box condition of the definition; two integer accumulators per lane, plain stores, no atomics.  With a distance
 // buffer the lane then applies the inside rule to the distance mi_query_kernel left there for the same point, in place.
@@ -40,15 +40,6 @@ struct MwnArgs {
     int dist_f32;
     int rule;
 };
-
-// may the ray from o meet something inside the float32 box b (lo xyz, hi xyz)?  The three comparisons of the own-box condition
-template <int KZ>
-__device__ inline bool mwn_enter(const float* __restrict__ b, double o1, double o2, double oz, bool neg)
-{
-    constexpr int K1 = (KZ + 1) % 3, K2 = (KZ + 2) % 3;
-    const bool ahead = neg ? (double)b[KZ] <= oz : (double)b[3 + KZ] >= oz;
-    return (double)b[K1] <= o1 && o1 <= (double)b[3 + K1] && (double)b[K2] <= o2 && o2 <= (double)b[3 + K2] && ahead;
-}
 
 // One lane per query point.  LATTICE: a workgroup (one wave) is a 4x4x4 block of lattice points; else 64 consecutive points.
 template <int KZ, bool LATTICE>
@@ -102,7 +93,7 @@ __global__ void __launch_bounds__(64) mwn_points_kernel(MwnArgs g)
                 }
             } else {
                 const MiNode nd = load_node(g.nodes + cur);
-                const bool e0 = mwn_enter<KZ>(nd.box[0], o1, o2, oz, neg), e1 = mwn_enter<KZ>(nd.box[1], o1, o2, oz, neg);
+                const bool e0 = axis_enter<KZ>(nd.box[0], o1, o2, oz, neg), e1 = axis_enter<KZ>(nd.box[1], o1, o2, oz, neg);
                 if (e0 && e1) {
                     stk[sp * 64 + lane] = nd.child[1];
                     ++sp;
@@ -219,7 +210,7 @@ __global__ void __launch_bounds__(64) mwn_rows_kernel(MwnRows g)
             }
         } else {
             const MiNode nd = load_node(g.nodes + cur);
-            const bool e0 = mwn_enter<KZ>(nd.box[0], o1, o2, zend, neg), e1 = mwn_enter<KZ>(nd.box[1], o1, o2, zend, neg);
+            const bool e0 = axis_enter<KZ>(nd.box[0], o1, o2, zend, neg), e1 = axis_enter<KZ>(nd.box[1], o1, o2, zend, neg);
             if (e0 && e1) {
                 stk[sp * 64 + lane] = nd.child[1];
                 ++sp;

@@ -3349,6 +3349,7 @@ void r2s_release_cache(void)
     r2s_int::release_fans_work();
     r2s_int::release_holes_work();
     r2s_int::release_intersect_work();
+    r2s_int::release_nesting_work();
     r2s_int::release_host_sessions();
 }
 

@@ -669,6 +669,67 @@ function mesh_orient_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{
     return n[], ref, totals
 end
 
+# Which closed patch encloses which (include/rho2sdf_hip.h, r2s_mesh_nesting): verts 3 x nv Float32, tris 3 x nt 1-based.  The
+# patches are those of mesh_orient_hip; a closed patch Q contains a patch P when the axis ray `ray` (0..5: +x +y +z -x -y -z) from
+# P's sample vertex crosses Q an odd number of times.  depth = the number of containers, parent = the deepest of them; closed
+# patches at even depth are bodies, at odd depth voids.  rewind = true: tris comes back with the voids reversed relative to the
+# input (after mesh_orient_hip(outward = true): bodies positive, voids negative); otherwise tris is nothing.
+# -> (tris 3 x nt 1-based or nothing, patch_of_tri (1-based, 0 = collapsed triangle), counts 8 x n Int64 (first_tri 1-based, n_tris,
+# status bits 1 closed / 2 reversed / 4 irregular, parent 1-based (0 = none), depth, n_children, sum of crossings, 0), pairs
+# (query, container) 2 x m 1-based, ascending, totals)
+const NESTING_REWIND = Int32(1)
+function mesh_nesting_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}; ray::Integer = 2, rewind::Bool = false,
+                          device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    t0 = Int32.(tris) .- Int32(1)
+    nt = size(t0, 2)
+    tout = Matrix{Int32}(undef, 3, rewind ? nt : 0)
+    patch = Vector{Int32}(undef, nt)
+    n = Ref{Int64}(0)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_nesting, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Int32, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}),
+                Matrix(verts), size(verts, 2), t0, nt, Int32(ray), rewind ? NESTING_REWIND : Int32(0), Int32(device),
+                rewind ? tout : Ptr{Int32}(C_NULL), patch, n, totals))
+    counts, pairs = last_mesh_nesting_hip()
+    return (tris = rewind ? tout .+ Int32(1) : nothing, patch_of_tri = patch .+ Int32(1), counts = counts, pairs = pairs, totals = totals)
+end
+
+# the calling thread's last nesting tables (r2s_last_mesh_nesting): counts 8 x n (first_tri and parent made 1-based), pairs 2 x m
+function last_mesh_nesting_hip()
+    n = Ref{Int64}(0); m = Ref{Int64}(0)
+    check(ccall((:r2s_last_mesh_nesting, LIB[]), Cint, (Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}),
+                Ptr{Int64}(C_NULL), Int64(0), Ptr{Int64}(C_NULL), Int64(0), n, m))
+    counts = Matrix{Int64}(undef, 8, n[])
+    keys = Vector{Int64}(undef, m[])
+    check(ccall((:r2s_last_mesh_nesting, LIB[]), Cint, (Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}),
+                n[] == 0 ? Ptr{Int64}(C_NULL) : pointer(counts), n[], m[] == 0 ? Ptr{Int64}(C_NULL) : pointer(keys), m[], n, m))
+    counts[1, :] .+= 1
+    counts[4, :] .+= 1
+    pairs = Matrix{Int64}(undef, 2, length(keys))
+    pairs[1, :] .= (keys .>> 32) .+ 1
+    pairs[2, :] .= (keys .& 0xffffffff) .+ 1
+    return counts, pairs
+end
+
+# the same on device arrays of the current device (raw pointers); index: the handle of a mesh index of the same mesh on that device
+# or C_NULL (a tree is built and dropped).  d_tris_out is needed with rewind only and must not overlap d_tris, d_patch_of_tri may be
+# C_NULL; the records and the pairs ((P << 32) | Q, 0-based) are written only when their capacity holds all of them
+# -> (n_patches, n_pairs, totals); indices stay 0-based on the device
+function mesh_nesting_dev_hip(index::Ptr{Cvoid}, d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer,
+                              d_tris_out::Ptr{Cvoid}, d_patch_of_tri::Ptr{Cvoid}, d_counts::Ptr{Cvoid}, patch_capacity::Integer,
+                              d_pairs::Ptr{Cvoid}, pair_capacity::Integer; ray::Integer = 2, rewind::Bool = false,
+                              stream::Ptr{Cvoid} = C_NULL)
+    n = Ref{Int64}(0); m = Ref{Int64}(0)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_nesting_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid},
+                 Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cvoid}),
+                index, d_verts, Int64(n_verts), d_tris, Int64(n_tris), Int32(ray), rewind ? NESTING_REWIND : Int32(0), d_tris_out,
+                d_patch_of_tri, d_counts, Int64(patch_capacity), d_pairs, Int64(pair_capacity), n, m, totals, stream))
+    return n[], m[], totals
+end
+
 # The fans of a triangle mesh (include/rho2sdf_hip.h, r2s_mesh_fans): verts 3 x nv Float32, tris 3 x nt 1-based.  The corners of
 # every vertex fall into fans, connected over the edges their triangles share at that vertex; a vertex with two or more fans is
 # pinched (non-manifold, although every edge may be regular), which mesh_shells_hip cannot see.  split = true also returns the
@@ -935,7 +996,8 @@ end
 # The triangles of a binary or ASCII STL file (r2s_import_stl) -> (verts 3 x nv Float32, tris 3 x nt 1-based).  weld = true: the
 # equal vertices are merged by mesh_weld_hip(soup; snap); weld = false: the soup as the file holds it, tris = 1:3nt.
 # orient = nothing: the windings as the file holds them; :majority or :outward (needs weld = true): the welded triangles go
-# through mesh_orient_hip (see there for the rules and the caveat about enclosed voids).  check_intersections = true (needs
+# through mesh_orient_hip (see there for the rules and the caveat about enclosed voids); :nested: outward, then the enclosed
+# voids reversed again by mesh_nesting_hip(rewind = true).  check_intersections = true (needs
 # weld = true): -> (verts, tris, mesh_intersections_hip of the mesh as returned).  split_vertices = true (needs weld = true): the
 # vertices the weld left pinched are split by mesh_fans_hip(split = true), after the orient if one is asked for.  fill_holes = k
 # (needs weld = true): after that the closed rims are capped by mesh_holes_hip(fill = k), -1 every hole, k > 0 those of at most
@@ -943,7 +1005,7 @@ end
 function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real = 0.0, device::Integer = -1,
                         orient::Union{Nothing,Symbol} = nothing, check_intersections::Bool = false, split_vertices::Bool = false,
                         fill_holes::Union{Nothing,Integer} = nothing)
-    orient === nothing || orient in (:majority, :outward) || error("orient must be nothing, :majority or :outward")
+    orient === nothing || orient in (:majority, :outward, :nested) || error("orient must be nothing, :majority, :outward or :nested")
     orient === nothing || weld || error("orient needs weld = true")
     !split_vertices || weld || error("split_vertices needs weld = true")
     !check_intersections || weld || error("check_intersections needs weld = true")
@@ -954,7 +1016,8 @@ function import_stl_hip(filename::AbstractString; weld::Bool = true, snap::Real 
     ccall((:r2s_free_stl_mesh, LIB[]), Cvoid, (Ref{R2SStlMesh},), m)
     weld || return soup, reshape(Int32.(1:size(soup, 2)), 3, :)
     w = mesh_weld_hip(soup; snap = snap, device = device)
-    tris = orient === nothing ? w.tris : mesh_orient_hip(w.verts, w.tris; outward = orient === :outward, device = device).tris
+    tris = orient === nothing ? w.tris : mesh_orient_hip(w.verts, w.tris; outward = orient !== :majority, device = device).tris
+    orient === :nested && (tris = mesh_nesting_hip(w.verts, tris; rewind = true, device = device).tris)
     verts = w.verts
     if split_vertices
         f = mesh_fans_hip(verts, tris; split = true, device = device)
