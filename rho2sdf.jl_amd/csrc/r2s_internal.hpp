@@ -13,12 +13,28 @@
 namespace r2s_int {
 
 // ---- per-device work caches ----------------------------------------------------------------------------------------------
+// Every PerDevice of the process, in the order they were constructed.  Each one puts itself here, so that r2s_release_cache()
+// frees a new family's cache without being told about it.  The list is never destroyed, like the maps of its members, and it
+// is created on first use: the order of static initialisation across files does not matter.  The members are objects of static
+// storage, constructed one after the other while the library is loaded: the list needs no lock of its own, and
+// r2s_release_cache(), which walks it, must not run concurrently with any other call anyway (include/rho2sdf_hip.h).
+class PerDeviceCache {
+public:
+    virtual void release_all() = 0;
+
+protected:
+    PerDeviceCache();
+    ~PerDeviceCache() = default;
+};
+std::vector<PerDeviceCache*>& per_device_caches();   // (r2s_post.hip)
+inline PerDeviceCache::PerDeviceCache() { per_device_caches().push_back(this); }
+
 // The work buffers a family of entry points keeps between calls, one W per device.  W holds its device buffers as DevBuf
 // members (which free themselves), so that destroying an entry frees every one of them: there is no second list of the members to keep in step.
 // A call locks `mu` for as long as it uses its entry.  The map is never destroyed: at process exit the HIP runtime may be
 // gone before a static destructor runs, and the driver reclaims the memory anyway.
 template <class W>
-class PerDevice {
+class PerDevice : public PerDeviceCache {
 public:
     std::mutex mu;
     // the entry of `device` (empty on first use); the caller holds mu
@@ -35,7 +51,7 @@ public:
         return &map_[dev];
     }
     // frees every entry with its own device current, then makes the caller's device current again
-    void release_all()
+    void release_all() override
     {
         std::lock_guard<std::mutex> lock(mu);
         int cur = -1;
@@ -147,12 +163,6 @@ int extract_isosurface_dev(const void* d_values, bool is_float32, const int64_t 
 // the same from a host array (uploaded to the current device)
 int extract_isosurface_host(const void* values, bool is_float32, const int64_t dims[3], const double origin[3], double spacing,
                             double iso, Surface& out);
-// frees the work buffers r2s_extract_isosurface_dev keeps per device; called by r2s_release_cache()
-void release_iso_work();
-
-// ---- redistancing (r2s_redistance.hip) --------------------------------------------------------------------------------
-// frees the work buffers the distance calls keep per device; called by r2s_release_cache()
-void release_dist_work();
 
 // ---- mesh index (r2s_mesh_index.hip) and what its entry points share with r2s_redistance.hip -------------------------------
 // the tree of a mesh index and the mesh it refers to (r2s_mesh_index owns all three; redistance_full borrows the mesh)
@@ -182,41 +192,16 @@ int check_mesh_dev(const char* who, const float* d_verts, int64_t n_verts, const
 inline size_t real_bytes(int32_t is_float32) { return is_float32 ? sizeof(float) : sizeof(double); }
 inline size_t vert_bytes(int64_t n_verts) { return 3 * sizeof(float) * (size_t)n_verts; }
 inline size_t tri_bytes(int64_t n_tris) { return 3 * sizeof(int32_t) * (size_t)n_tris; }
+// whether the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte (a null pointer or an empty range shares none)
+inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
+{
+    if (!a || !b || !abytes || !bbytes) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
 // sizes dv / dt for the mesh (at least one element each) and copies it in: from the host with hipMemcpy, or
 // (from_device) from the current device on `st`
 int upload_mesh(DevBuf& dv, DevBuf& dt, const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, bool from_device,
                 hipStream_t st);
-
-// ---- mesh shells (r2s_mesh_shells.hip) --------------------------------------------------------------------------------
-// frees the work buffers the shell calls keep per device; called by r2s_release_cache()
-void release_shell_work();
-
-// ---- mesh sections (r2s_mesh_sections.hip) ----------------------------------------------------------------------------
-// frees the work buffers the section calls keep per device; called by r2s_release_cache()
-void release_section_work();
-
-// ---- mesh weld (r2s_mesh_weld.hip) ------------------------------------------------------------------------------------
-// frees the work buffers the weld calls keep per device; called by r2s_release_cache()
-void release_weld_work();
-
-// ---- mesh orient (r2s_mesh_orient.hip) --------------------------------------------------------------------------------
-// frees the work buffers the orient calls keep per device; called by r2s_release_cache()
-void release_orient_work();
-
-// ---- mesh fans (r2s_mesh_fans.hip) ------------------------------------------------------------------------------------
-// frees the work buffers the fan calls keep per device; called by r2s_release_cache()
-void release_fans_work();
-
-// ---- mesh holes (r2s_mesh_holes.hip) ----------------------------------------------------------------------------------
-// frees the work buffers the hole calls keep per device; called by r2s_release_cache()
-void release_holes_work();
-
-// ---- mesh intersections (r2s_mesh_intersect.hip) ----------------------------------------------------------------------
-// frees the work buffers the intersection calls keep per device; called by r2s_release_cache()
-void release_intersect_work();
-
-// ---- mesh nesting (r2s_mesh_nesting.hip) ------------------------------------------------------------------------------
-// frees the work buffers the nesting calls keep per device; called by r2s_release_cache()
-void release_nesting_work();
 
 }  // namespace r2s_int

@@ -345,13 +345,6 @@ int fans_apply(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int
     return 0;
 }
 
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
-{
-    if (!a || !b || !abytes || !bbytes) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 // the checks that need no device; *split: the split was asked for
 int fans_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tris, const void* fan_of_corner, const void* fans_of_vert,
               const void* tris_out, const void* verts_out, const void* vert_of_out, int64_t vert_capacity, const int64_t* n_fans,
@@ -375,12 +368,6 @@ int fans_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tr
 }
 
 }  // namespace
-
-namespace r2s_int {
-
-void release_fans_work() { g_fans_work.release_all(); }
-
-}  // namespace r2s_int
 
 extern "C" {
 

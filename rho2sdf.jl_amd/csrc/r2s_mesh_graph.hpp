@@ -1,12 +1,19 @@
-// What r2s_mesh_shells.hip, r2s_mesh_sections.hip, r2s_mesh_orient.hip, r2s_mesh_fans.hip and r2s_mesh_holes.hip share:
+// What r2s_mesh_shells.hip, r2s_mesh_sections.hip, r2s_mesh_orient.hip, r2s_mesh_fans.hip, r2s_mesh_holes.hip and
+// r2s_mesh_nesting.hip share:
 //   the box of the vertices behind the reference point (ms_bounds_kernel, ms_ref_point) and the collapsed-triangle test;
 //   the half-edge table: ms_half_edge_keys writes the keys of one triangle, ms_key_kernel is the one key launch of shells,
-//     orient, fans and holes (sections writes its keys in sx_tri_kernel with the same function), ms_sort_half_edges sizes the
-//     buffers (MsHalfEdgeBufs), launches the keys and sorts the pairs; ms_run_size reads the sorted runs;
+//     orient, fans, holes and nesting (sections writes its keys in sx_tri_kernel with the same function), ms_sort_half_edges
+//     sizes the buffers (MsHalfEdgeBufs), launches the keys and sorts the pairs; ms_run_size reads the sorted runs from any
+//     member, ms_run_class names the class of a run at its head (the shells' edge classes, the sections' node classes);
 //   the integer union-find with min-root (ms_find, ms_union) and the per-group integer counting (ms_count);
+//   the component numbering behind the unions: ms_flatten_kernel<false> (sections, holes) and <true> (shells, nesting: triangles)
+//     leave parent = root and flag the roots, the caller scans the flags, ms_number_kernel writes the group of every triangle
+//     (shells, orient, nesting), with the sort pairs where asked;
+//   the loop ordering of sections and holes, ms_order_loops: pointer jumping (ms_rank_init_kernel, ms_jump_kernel), the stable
+//     sort by group, ms_start_kernel and ms_place_kernel;
 //   the segmented Float64 sum every Float64 table of these tools is defined by (include/rho2sdf_hip.h): ms_block_sum, the tree
 //     over 256 consecutive sorted items with one partial per (block, segment) at slot block + segment, and ms_combine_kernel,
-//     one wavefront per segment; ms_segment_kernel finds the segment starts of shells and orient.
+//     one wavefront per segment; ms_segment_kernel finds the segment starts of shells and orient, with the first item of each.
 // r2s_mesh_weld.hip takes the order-preserving bit pattern of a float32 and the launch / bit-count helpers from here.
 // Everything has internal linkage: each file gets its own copy of a kernel, and a template only where it is used.
 #pragma once
@@ -108,6 +115,52 @@ __device__ inline void ms_union(uint32_t* L, uint32_t a, uint32_t b)
     }
 }
 
+// After the unions: parent[x] = the root of x, the smallest node of its group, and flag[x] = x is that root.  The exclusive
+// scan of the flags numbers the groups by ascending root: the group of x is num[parent[x]].
+__device__ inline void ms_flatten(uint32_t* parent, uint32_t x, int32_t* __restrict__ flag)
+{
+    const uint32_t r = ms_find(parent, x);
+    if (r != x) atomicMin(&parent[x], r);
+    flag[x] = r == x ? 1 : 0;
+}
+
+// TRIS: the nodes are triangles, and a collapsed one is in no group (flag 0); else tris is not read
+template <bool TRIS>
+__global__ void __launch_bounds__(256) ms_flatten_kernel(const int32_t* __restrict__ tris, int64_t n, uint32_t* parent, int32_t* __restrict__ flag)
+{
+    const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    int32_t i0, i1, i2;
+    if (TRIS && ms_collapsed(tris, x, i0, i1, i2)) {
+        flag[x] = 0;
+        return;
+    }
+    ms_flatten(parent, (uint32_t)x, flag);
+}
+
+// num = the exclusive scan of the root flags of n triangles: group_of[t] (-1: collapsed) and the number of groups.  The root of
+// t is node[t], what ms_flatten_kernel<true> left in parent; DOUBLED: node[t] is the orient's info word, 2 root + parity with
+// MS_DOUBLED_FLAG on top.  PAIRS: also the sort pair of t, a collapsed triangle behind every group.
+constexpr uint32_t MS_DOUBLED_FLAG = 0x80000000u;   // bit 31 of a doubled-graph word is the caller's (orient: non-orientable)
+template <bool DOUBLED, bool PAIRS>
+__global__ void __launch_bounds__(256) ms_number_kernel(const int32_t* __restrict__ tris, int64_t n, const uint32_t* __restrict__ node,
+                                                         const int32_t* __restrict__ num, const int32_t* __restrict__ flag,
+                                                         int32_t* __restrict__ group_of, uint32_t* __restrict__ skey, uint32_t* __restrict__ sval,
+                                                         uint64_t* __restrict__ n_groups)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int32_t ng = num[n - 1] + flag[n - 1];
+    int32_t i0, i1, i2;
+    const int32_t g = ms_collapsed(tris, t, i0, i1, i2) ? -1 : num[DOUBLED ? (node[t] & ~MS_DOUBLED_FLAG) >> 1 : node[t]];
+    group_of[t] = g;
+    if (PAIRS) {
+        skey[t] = g < 0 ? (uint32_t)ng : (uint32_t)g;
+        sval[t] = (uint32_t)t;
+    }
+    if (t == n - 1) *n_groups = (uint64_t)ng;
+}
+
 // The sorted half-edge keys are (min << 33) | (max << 1) | direction, the collapsed triangles' keys behind them (below).
 // The number of members of the run of sorted half-edge i, capped at 3 (i is a real half-edge: keys[i] < ckey)
 __device__ inline int ms_run_size(const uint64_t* __restrict__ keys, int64_t i, int64_t nh, bool& head)
@@ -118,6 +171,18 @@ __device__ inline int ms_run_size(const uint64_t* __restrict__ keys, int64_t i, 
     head = !p1;
     if (!p1 && !n1) return 1;
     return (p2 || (p1 && n1) || n2) ? 3 : 2;
+}
+
+// The class of the run whose FIRST member is sorted half-edge i (a real one): alone (a boundary edge), a regular pair (opposite
+// directions), a pair in the same direction (a flipped edge), three or more (a non-manifold edge)
+enum { MS_RUN_SINGLE = 0, MS_RUN_PAIR = 1, MS_RUN_SAME = 2, MS_RUN_MANY = 3 };
+__device__ inline int ms_run_class(const uint64_t* __restrict__ keys, int64_t i, int64_t nh)
+{
+    const uint64_t k = keys[i], k1 = i + 1 < nh ? keys[i + 1] : ~0ull, k2 = i + 2 < nh ? keys[i + 2] : ~0ull;
+    const bool two = (k1 >> 1) == (k >> 1), three = two && (k2 >> 1) == (k >> 1);
+    if (!two) return MS_RUN_SINGLE;
+    if (three) return MS_RUN_MANY;
+    return ((k1 ^ k) & 1ull) == 0ull ? MS_RUN_SAME : MS_RUN_PAIR;
 }
 
 // adds 1 to counts[group][col0 + k] (rows of STRIDE) for every k < NC with add[k] set, over the workgroup's active threads: once
@@ -341,5 +406,93 @@ __global__ void __launch_bounds__(256) ms_combine_kernel(const int64_t* __restri
         for (int q = 0; q < NSUM; ++q) sums[s * NSUM + q] = v[q];
         if (n_items) n_items[s * item_stride] = end - first;
     }
+}
+
+// ---- the loop ordering ------------------------------------------------------------------------------------------------------
+// Lays the n items of a graph of chains out group by group (sections: segments by contour, holes: boundary half-edges by rim):
+// a closed group, a single cycle along succ, in walking order from its head, every other group in ascending item id.
+// (The three kernels without a parameter of their own are templates too, so that only a file that launches them compiles them.)
+// The head of a group is its root.  The caller's ms_flatten_kernel<false> left parent = root, and the root is the smallest item of
+// the group, so parent[i] == i names the head and nothing else has to say which item it is.
+
+// (distance << 32) | pointer: an item of a closed group points at its successor at distance 1, the head and every item of
+// another group at itself at distance 0
+template <class OnlyWhereLaunched = void>
+__global__ void __launch_bounds__(256) ms_rank_init_kernel(int64_t n, const uint32_t* __restrict__ group_of, const int32_t* __restrict__ closed,
+                                                            const uint32_t* __restrict__ parent, const uint32_t* __restrict__ succ,
+                                                            uint64_t* __restrict__ pp)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool walks = closed[group_of[i]] && parent[i] != (uint32_t)i;
+    pp[i] = walks ? ((1ull << 32) | (uint64_t)succ[i]) : (uint64_t)i;
+}
+
+// one round of pointer jumping from `in` to `out`
+template <class OnlyWhereLaunched = void>
+__global__ void __launch_bounds__(256) ms_jump_kernel(int64_t n, const uint64_t* __restrict__ in, uint64_t* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t v = in[i], w = in[(uint32_t)v];
+    out[i] = (((v >> 32) + (w >> 32)) << 32) | (uint64_t)(uint32_t)w;
+}
+
+// start[g] = the first sorted position of group g, start[n_groups] = n
+template <class OnlyWhereLaunched = void>
+__global__ void __launch_bounds__(256) ms_start_kernel(const uint32_t* __restrict__ skey, int64_t n, int64_t n_groups, int64_t* __restrict__ start)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t g = skey[i];
+    if (i == 0 || skey[i - 1] != g) start[g] = i;
+    if (i == 0) start[n_groups] = n;
+}
+
+// the output order: the stable sort left every group in ascending item id; a closed group is laid out by rank instead (rank 0 =
+// the head, rank r = length - distance to the head along the successors).  The length of group g is counts[g * STRIDE + COL];
+// MAP: what is placed is map[item], not the item.
+template <int STRIDE, int COL, bool MAP>
+__global__ void __launch_bounds__(256) ms_place_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval, int64_t n,
+                                                        const int32_t* __restrict__ closed, const int64_t* __restrict__ counts,
+                                                        const int64_t* __restrict__ start, const uint64_t* __restrict__ pp,
+                                                        const uint32_t* __restrict__ map, uint32_t* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t g = skey[i], item = sval[i];
+    int64_t pos = i;
+    if (closed[g]) {
+        const int64_t len = counts[(int64_t)g * STRIDE + COL], d = (int64_t)(pp[item] >> 32);
+        const int64_t rank = d ? len - d : 0;
+        if (rank < 0 || rank >= len) return;   // (cannot happen on a cycle; keeps the store inside the group's range)
+        pos = start[g] + rank;
+    }
+    out[pos] = MAP ? map[item] : item;
+}
+
+// The whole stage on `st`: ms_rank_init_kernel, the jump rounds for a longest closed group of `longest` items (2^rounds >=
+// longest) over pp0 / pp1, the stable radix sort of (skey = group, sval = item) into skey2 / sval2, out = 0, ms_start_kernel,
+// ms_place_kernel.  Every buffer is the caller's; temp holds temp_bytes, what rocprim::radix_sort_pairs of these n pairs over
+// ms_bits(n_groups) bits asked for.
+template <int STRIDE, int COL, bool MAP>
+int ms_order_loops(int64_t n, int64_t n_groups, uint64_t longest, const int32_t* closed, const uint32_t* parent, const uint32_t* succ,
+                   const int64_t* counts, uint32_t* skey, uint32_t* skey2, uint32_t* sval, uint32_t* sval2, uint64_t* pp0, uint64_t* pp1,
+                   void* temp, size_t temp_bytes, int64_t* start, const uint32_t* map, uint32_t* out, hipStream_t st)
+{
+    ms_rank_init_kernel<><<<ms_blocks(n), 256, 0, st>>>(n, skey, closed, parent, succ, pp0);
+    HIP_TRY(hipGetLastError());
+    for (uint64_t reach = 1; reach < longest; reach <<= 1) {
+        ms_jump_kernel<><<<ms_blocks(n), 256, 0, st>>>(n, pp0, pp1);
+        HIP_TRY(hipGetLastError());
+        std::swap(pp0, pp1);
+    }
+    HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, skey, skey2, sval, sval2, (size_t)n, 0u, ms_bits((uint64_t)n_groups), st));
+    HIP_TRY(hipMemsetAsync(out, 0, sizeof(uint32_t) * (size_t)n, st));
+    ms_start_kernel<><<<ms_blocks(n), 256, 0, st>>>(skey2, n, n_groups, start);
+    HIP_TRY(hipGetLastError());
+    ms_place_kernel<STRIDE, COL, MAP><<<ms_blocks(n), 256, 0, st>>>(skey2, sval2, n, closed, counts, start, pp0, map, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 }  // namespace

@@ -9,15 +9,15 @@
 //                      parent = successor = itself -> stable radix sort of the ends by vertex: a run is a node
 //   mh_link_kernel     every member of a run joins the member before it (the shells' union-find: the larger root under the smaller,
 //                      so a rim's root is its first half-edge); the head of a regular run writes the successor
-//   mh_flatten_kernel  parent = root, root flags -> scan: the roots in ascending half-edge id are the rim numbers
+//   ms_flatten_kernel<false> (r2s_mesh_graph.hpp) parent = root, root flags -> scan: the roots in ascending half-edge id are the rim numbers
 //   mh_number_kernel   rim of every half-edge, first half-edge and n_edges of every rim;  mh_node_kernel: the runs again, the class
 //                      of every node counted into its rim
 //   mh_closed_kernel   closed flags, the longest closed rim (integer atomicMax), the totals, what the fill adds per rim
 //   -> two exclusive scans (added vertices, added triangles) -> mh_fill_kernel: status and added vertex of every rim
-//   mh_rank_init_kernel / mh_jump_kernel   distance to the first half-edge by pointer jumping, ping-pong buffers,
-//                      ceil(log2(longest closed rim)) rounds
-//   -> stable radix sort of the half-edges by rim -> mh_start_kernel -> mh_place_kernel: closed rims are laid out by rank, the
-//      others keep ascending half-edge id
+//   ms_order_loops     (r2s_mesh_graph.hpp) ms_rank_init_kernel / ms_jump_kernel: distance to the first half-edge by pointer
+//                      jumping, ping-pong buffers, ceil(log2(longest closed rim)) rounds -> stable radix sort of the half-edges by
+//                      rim -> ms_start_kernel -> ms_place_kernel<8, 1, true>: closed rims are laid out by rank, the others keep
+//                      ascending half-edge id; what is placed is the half-edge id bh[b]
 //   mh_sum_kernel      blocks of 256 output positions, the 7 terms of every half-edge -> ms_block_sum<7> (r2s_mesh_graph.hpp): a
 //                      segmented fixed tree in LDS, one partial per (block, rim);  ms_combine_kernel<7> (r2s_mesh_graph.hpp): one
 //                      wavefront per rim
@@ -127,15 +127,6 @@ __global__ void __launch_bounds__(256) mh_link_kernel(const uint32_t* __restrict
     }
 }
 
-__global__ void __launch_bounds__(256) mh_flatten_kernel(int64_t nb, uint32_t* parent, int32_t* __restrict__ flag)
-{
-    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (b >= nb) return;
-    const uint32_t r = ms_find(parent, (uint32_t)b);
-    if (r != (uint32_t)b) atomicMin(&parent[b], r);
-    flag[b] = r == (uint32_t)b ? 1 : 0;
-}
-
 // num = the exclusive scan of flag: the rim of every half-edge, the sort pairs, first half-edge and n_edges of every rim; n_rims
 __global__ void __launch_bounds__(256) mh_number_kernel(int64_t nb, const uint32_t* __restrict__ parent, const int32_t* __restrict__ flag,
                                                          const int32_t* __restrict__ num, const uint32_t* __restrict__ bh,
@@ -146,7 +137,7 @@ __global__ void __launch_bounds__(256) mh_number_kernel(int64_t nb, const uint32
     const bool active = b < nb;
     int32_t rim = -1;
     if (active) {
-        rim = num[parent[b]];   // (mh_flatten_kernel left parent = root)
+        rim = num[parent[b]];   // (ms_flatten_kernel left parent = root)
         skey[b] = (uint32_t)rim;
         sval[b] = (uint32_t)b;
         if (flag[b]) counts[(int64_t)rim * MH_NCNT + MH_FIRST] = (int64_t)bh[b];
@@ -235,57 +226,6 @@ __global__ void __launch_bounds__(256) mh_fill_kernel(int64_t nb, int64_t n_vert
         small[MH_ADDV] = (uint64_t)((int64_t)voff[c] + addv[c]);
         small[MH_ADDT] = (uint64_t)(toff[c] + addt[c]);
     }
-}
-
-// (distance << 32) | pointer: a half-edge of a closed rim points at its successor at distance 1, the rim's first half-edge (its
-// root) and every half-edge of another rim at itself at distance 0
-__global__ void __launch_bounds__(256) mh_rank_init_kernel(int64_t nb, const uint32_t* __restrict__ skey, const int32_t* __restrict__ closed,
-                                                            const uint32_t* __restrict__ parent, const uint32_t* __restrict__ succ,
-                                                            uint64_t* __restrict__ pp)
-{
-    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (b >= nb) return;
-    const bool walks = closed[skey[b]] && parent[b] != (uint32_t)b;
-    pp[b] = walks ? ((1ull << 32) | (uint64_t)succ[b]) : (uint64_t)b;
-}
-
-// one round of pointer jumping from `in` to `out`
-__global__ void __launch_bounds__(256) mh_jump_kernel(int64_t nb, const uint64_t* __restrict__ in, uint64_t* __restrict__ out)
-{
-    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (b >= nb) return;
-    const uint64_t v = in[b], w = in[(uint32_t)v];
-    out[b] = (((v >> 32) + (w >> 32)) << 32) | (uint64_t)(uint32_t)w;
-}
-
-// start[c] = the first sorted position of rim c, start[n_rims] = n_b
-__global__ void __launch_bounds__(256) mh_start_kernel(const uint32_t* __restrict__ skey, int64_t nb, int64_t nr, int64_t* __restrict__ start)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nb) return;
-    const uint32_t c = skey[i];
-    if (i == 0 || skey[i - 1] != c) start[c] = i;
-    if (i == 0) start[nr] = nb;
-}
-
-// the output order: the stable sort left every rim in ascending half-edge id; a closed rim is laid out by rank instead
-// (rank 0 = its first half-edge, rank r = n - distance to it along the successors)
-__global__ void __launch_bounds__(256) mh_place_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval, int64_t nb,
-                                                        const int32_t* __restrict__ closed, const int64_t* __restrict__ counts,
-                                                        const int64_t* __restrict__ start, const uint64_t* __restrict__ pp,
-                                                        const uint32_t* __restrict__ bh, int32_t* __restrict__ rim_edge)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nb) return;
-    const uint32_t c = skey[i], b = sval[i];
-    int64_t pos = i;
-    if (closed[c]) {
-        const int64_t n = counts[(int64_t)c * MH_NCNT + MH_NEDGES], d = (int64_t)(pp[b] >> 32);
-        const int64_t rank = d ? n - d : 0;
-        if (rank < 0 || rank >= n) return;   // (cannot happen on a cycle; keeps the store inside the rim's range)
-        pos = start[c] + rank;
-    }
-    rim_edge[pos] = (int32_t)bh[b];
 }
 
 // one thread per output position: the 7 terms of its half-edge into the segmented sum of its block (ms_block_sum: slot block + rim)
@@ -453,7 +393,7 @@ int holes_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int
         HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, ekey, ekey2, eval, eval2, (size_t)n2, 0u, vbits, st));
         mh_link_kernel<<<ms_blocks(n2), 256, 0, st>>>(ekey2, eval2, n2, parent, succ);
         HIP_TRY(hipGetLastError());
-        mh_flatten_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, parent, rflag);
+        ms_flatten_kernel<false><<<ms_blocks(nb), 256, 0, st>>>(nullptr, nb, parent, rflag);
         HIP_TRY(hipGetLastError());
         HIP_TRY(rocprim::exclusive_scan(w.temp.p, sb, rflag, num, (int32_t)0, (size_t)nb, rocprim::plus<int32_t>(), st));
         HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * MH_NCNT * (size_t)nb, st));
@@ -471,24 +411,13 @@ int holes_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int
         HIP_TRY(hipStreamSynchronize(st));
         nr = (int64_t)h_small[MH_NRIMS];
 
-        // the round count comes from the longest closed rim the device found: 2^rounds >= that length
-        uint64_t *pin = w.pp0.as<uint64_t>(), *pout = w.pp1.as<uint64_t>();
-        mh_rank_init_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, skey, closed, parent, succ, pin);
-        HIP_TRY(hipGetLastError());
-        for (uint64_t reach = 1; reach < h_small[MH_MAXLOOP]; reach <<= 1) {
-            mh_jump_kernel<<<ms_blocks(nb), 256, 0, st>>>(nb, pin, pout);
-            HIP_TRY(hipGetLastError());
-            std::swap(pin, pout);
-        }
-        const unsigned rbits = ms_bits((uint64_t)nr);
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)nb, 0u, rbits, st));
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)nb, 0u, ms_bits((uint64_t)nr), st));
         ENSURE(w.temp, std::max<size_t>(tb, 16));
-        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)nb, 0u, rbits, st));
-        HIP_TRY(hipMemsetAsync(w.rim_edge.p, 0, sizeof(int32_t) * (size_t)nb, st));
-        mh_start_kernel<<<ms_blocks(nb), 256, 0, st>>>(skey2, nb, nr, w.start.as<int64_t>());
-        HIP_TRY(hipGetLastError());
-        mh_place_kernel<<<ms_blocks(nb), 256, 0, st>>>(skey2, sval2, nb, closed, counts, w.start.as<int64_t>(), pin, bh, w.rim_edge.as<int32_t>());
-        HIP_TRY(hipGetLastError());
+        // the round count comes from the longest closed rim the device found
+        if (const int rc = ms_order_loops<MH_NCNT, MH_NEDGES, true>(nb, nr, h_small[MH_MAXLOOP], closed, parent, succ, counts, skey, skey2, sval,
+                                                                    sval2, w.pp0.as<uint64_t>(), w.pp1.as<uint64_t>(), w.temp.p, tb,
+                                                                    w.start.as<int64_t>(), bh, w.rim_edge.as<uint32_t>(), st))
+            return rc;
         mh_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, skey2, w.rim_edge.as<int32_t>(), nb, out.r[0], out.r[1], out.r[2],
                                                           w.partial.as<double>());
         HIP_TRY(hipGetLastError());
@@ -530,13 +459,6 @@ int holes_apply(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         }
     }
     return 0;
-}
-
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
-{
-    if (!a || !b || !abytes || !bbytes) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
 }
 
 struct Span {
@@ -585,12 +507,6 @@ void holes_return(const HoleSizes& s, int64_t* n_rims, int64_t* n_edges, int64_t
 }
 
 }  // namespace
-
-namespace r2s_int {
-
-void release_holes_work() { g_holes_work.release_all(); }
-
-}  // namespace r2s_int
 
 extern "C" {
 

@@ -299,12 +299,6 @@ int isect_copy_dev(IsectWork& w, int64_t n_tris, int32_t* d_hits, hipStream_t st
 
 }  // namespace
 
-namespace r2s_int {
-
-void release_intersect_work() { g_mx_work.release_all(); }
-
-}  // namespace r2s_int
-
 extern "C" {
 
 int r2s_mesh_index_intersections(const r2s_mesh_index* ix, int32_t* hits_of_tri_out, int32_t* pairs_out, int64_t pair_capacity,

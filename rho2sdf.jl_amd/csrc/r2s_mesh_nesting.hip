@@ -4,8 +4,8 @@
 //                      sort of pairs
 //   mn_union_kernel    the second member of every run of EXACTLY two joins its two triangles (the shells' union-find: larger
 //                      root under the smaller, so a patch's root is its smallest triangle)
-//   mn_flatten_kernel  root of every triangle, the flag of the first triangle of a patch -> rocPRIM exclusive scan ->
-//   mn_number_kernel   patch_of_tri, the orient's numbering; n_patches
+//   ms_flatten_kernel<true> (r2s_mesh_graph.hpp) parent = root, the flag of the first triangle of a patch -> rocPRIM exclusive
+//                      scan -> ms_number_kernel<false, false> (r2s_mesh_graph.hpp): patch_of_tri, the orient's numbering; n_patches
 //   mn_first_kernel    first_tri and n_tris of every patch; mn_edge_kernel: the half-edges in runs of one or of three and more,
 //                      per patch; mn_record_kernel: closed[p], the record's start values
 //   mn_cross_kernel<KZ, false>  one lane per query patch P, the per-lane LDS stack and the three-comparison cull of
@@ -61,35 +61,6 @@ __global__ void __launch_bounds__(256) mn_union_kernel(const uint64_t* __restric
     bool head;
     if (ms_run_size(keys, i, nh, head) != 2 || head) return;
     ms_union(parent, vals[i - 1] / 3u, vals[i] / 3u);
-}
-
-// root[t] = the smallest triangle of t's patch; flag[t] = 1 for that triangle itself
-__global__ void __launch_bounds__(256) mn_flatten_kernel(const int32_t* __restrict__ tris, int64_t n, uint32_t* parent, uint32_t* __restrict__ root,
-                                                          int32_t* __restrict__ flag)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    int32_t i0, i1, i2;
-    if (ms_collapsed(tris, t, i0, i1, i2)) {
-        flag[t] = 0;
-        root[t] = 0u;
-        return;
-    }
-    const uint32_t r = ms_find(parent, (uint32_t)t);
-    root[t] = r;
-    flag[t] = r == (uint32_t)t ? 1 : 0;
-}
-
-// num = the exclusive scan of flag: patch_of[t] (-1: collapsed), n_patches
-__global__ void __launch_bounds__(256) mn_number_kernel(const int32_t* __restrict__ tris, int64_t n, const uint32_t* __restrict__ root,
-                                                         const int32_t* __restrict__ num, const int32_t* __restrict__ flag,
-                                                         int32_t* __restrict__ patch_of, uint64_t* __restrict__ small)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    int32_t i0, i1, i2;
-    patch_of[t] = ms_collapsed(tris, t, i0, i1, i2) ? -1 : num[root[t]];
-    if (t == n - 1) small[MN_NPATCHES] = (uint64_t)(num[n - 1] + flag[n - 1]);
 }
 
 // one thread per triangle: the first triangle of a patch writes first_tri; n_tris per patch
@@ -320,7 +291,7 @@ __global__ void __launch_bounds__(256) mn_rewind_kernel(const int32_t* __restric
 
 // work buffers of the nesting calls, kept per device between calls (r2s_release_cache frees them)
 struct NestWork : MsHalfEdgeBufs {
-    DevBuf verts, tris, tris_out, flag, small, parent, root, rflag, num, patch, counts, closed, depth, ckeys, ckeys2, odd, pos, pairs;
+    DevBuf verts, tris, tris_out, flag, small, parent, rflag, num, patch, counts, closed, depth, ckeys, ckeys2, odd, pos, pairs;
 };
 PerDevice<NestWork> g_nest_work;
 
@@ -361,7 +332,6 @@ int nesting_core(const MiTree* index, const float* d_verts, int64_t n_verts, con
     const int64_t nh = 3 * n;
     const uint64_t ckey = ms_collapsed_key(n_verts);
     ENSURE(w.parent, sizeof(uint32_t) * (size_t)n);
-    ENSURE(w.root, sizeof(uint32_t) * (size_t)n);
     ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
     ENSURE(w.num, sizeof(int32_t) * (size_t)n);
     ENSURE(w.patch, sizeof(int32_t) * (size_t)n);
@@ -375,10 +345,11 @@ int nesting_core(const MiTree* index, const float* d_verts, int64_t n_verts, con
     const uint32_t* hvals = w.vals2.as<uint32_t>();
     mn_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(hkeys, hvals, nh, ckey, parent);
     HIP_TRY(hipGetLastError());
-    mn_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.root.as<uint32_t>(), rflag);
+    ms_flatten_kernel<true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, rflag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(rocprim::exclusive_scan(w.temp.p, scan_bytes, rflag, num, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
-    mn_number_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, w.root.as<uint32_t>(), num, rflag, patch, (uint64_t*)small);
+    ms_number_kernel<false, false><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, num, rflag, patch, nullptr, nullptr,
+                                                               (uint64_t*)small + MN_NPATCHES);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -476,13 +447,6 @@ int nesting_core(const MiTree* index, const float* d_verts, int64_t n_verts, con
     return 0;
 }
 
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
-{
-    if (!a || !b || !abytes || !bbytes) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 // the checks that need no device
 int nesting_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tris, int32_t ray, int32_t flags, const void* tris_out,
                  const int64_t* n_patches, const int64_t* totals)
@@ -500,12 +464,6 @@ int nesting_args(const void* verts, int64_t n_verts, const void* tris, int64_t n
 }
 
 }  // namespace
-
-namespace r2s_int {
-
-void release_nesting_work() { g_nest_work.release_all(); }
-
-}  // namespace r2s_int
 
 extern "C" {
 

@@ -8,7 +8,7 @@
 //                      directions join (2a, 2b+1) and (2a+1, 2b) (the shells' union-find: larger root under the smaller)
 //   mo_flatten_kernel  root(2t) = 2f + rel[t] in an orientable patch with first triangle f, root(2t) = root(2t+1) = 2f in a
 //                      non-orientable one: first triangle, parity and orientability of every triangle; root flags
-//   -> rocPRIM exclusive scan (integers) -> mo_number_kernel: patch numbers, sort keys
+//   -> rocPRIM exclusive scan (integers) -> ms_number_kernel<true, true> (r2s_mesh_graph.hpp): patch numbers, sort pairs
 //   -> stable radix sort of the triangle ids by patch -> ms_segment_kernel (r2s_mesh_graph.hpp): where each patch starts, its
 //      first triangle
 //   mo_sum_kernel      blocks of 256 consecutive sorted triangles, the volume term negated where rel = 1 -> ms_block_sum<1>
@@ -42,7 +42,7 @@ namespace {
 constexpr int MO_NCNT = 8;
 constexpr int64_t MO_MAX_TRIS = (int64_t)1 << 30;
 constexpr int32_t MO_FLAGS = 1;   // R2S_ORIENT_OUTWARD
-constexpr uint32_t MO_NONORIENTABLE = 0x80000000u;   // bit 31 of info[t]; bits 0..30: root(2t) = 2 first_tri + rel
+constexpr uint32_t MO_NONORIENTABLE = MS_DOUBLED_FLAG;   // bit 31 of info[t]; bits 0..30: root(2t) = 2 first_tri + rel
 // slots of the small device array: [0..5] the bounds, then
 constexpr int MO_COLLAPSED = 6, MO_NPATCHES = 7, MO_TOT = 8;   // [MO_TOT .. MO_TOT + 4]: flipped triangles, non-orientable, closed, by volume, remaining flipped edges
 constexpr int MO_SMALL = 16;
@@ -80,23 +80,6 @@ __global__ void __launch_bounds__(256) mo_flatten_kernel(const int32_t* __restri
     const uint32_t r0 = ms_find(parent, (uint32_t)(2 * t)), r1 = ms_find(parent, (uint32_t)(2 * t + 1));
     info[t] = r0 | (r0 == r1 ? MO_NONORIENTABLE : 0u);
     flag[t] = r0 == (uint32_t)(2 * t) ? 1 : 0;
-}
-
-// num = the exclusive scan of flag: patch_of[t], the sort key of t (collapsed: n_patches, behind every patch), n_patches
-__global__ void __launch_bounds__(256) mo_number_kernel(const int32_t* __restrict__ tris, int64_t n, const uint32_t* __restrict__ info,
-                                                         const int32_t* __restrict__ num, const int32_t* __restrict__ flag,
-                                                         int32_t* __restrict__ patch_of, uint32_t* __restrict__ skey, uint32_t* __restrict__ sval,
-                                                         uint64_t* __restrict__ small)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    const int32_t np = num[n - 1] + flag[n - 1];
-    int32_t i0, i1, i2;
-    const int32_t s = ms_collapsed(tris, t, i0, i1, i2) ? -1 : num[(info[t] & ~MO_NONORIENTABLE) >> 1];
-    patch_of[t] = s;
-    skey[t] = s < 0 ? (uint32_t)np : (uint32_t)s;
-    sval[t] = (uint32_t)t;
-    if (t == n - 1) small[MO_NPATCHES] = (uint64_t)np;
 }
 
 // the shells' volume term of one triangle, in the header's operation order
@@ -288,8 +271,9 @@ int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         HIP_TRY(hipGetLastError());
         HIP_TRY(rocprim::exclusive_scan(w.temp.p, scan_bytes, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n,
                                         rocprim::plus<int32_t>(), st));
-        mo_number_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, w.info.as<uint32_t>(), w.num.as<int32_t>(), w.rflag.as<int32_t>(),
-                                                     w.patch.as<int32_t>(), w.skey.as<uint32_t>(), w.sval.as<uint32_t>(), small);
+        ms_number_kernel<true, true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, w.info.as<uint32_t>(), w.num.as<int32_t>(), w.rflag.as<int32_t>(),
+                                                                 w.patch.as<int32_t>(), w.skey.as<uint32_t>(), w.sval.as<uint32_t>(),
+                                                                 small + MO_NPATCHES);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
@@ -360,12 +344,6 @@ int orient_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_
 }
 
 }  // namespace
-
-namespace r2s_int {
-
-void release_orient_work() { g_orient_work.release_all(); }
-
-}  // namespace r2s_int
 
 extern "C" {
 

@@ -11,23 +11,25 @@
 //                      the EDGE, so for every level in it the segments of the two triangles are united (integer union-find,
 //                      min-root) and, in a run of exactly two ends of different kinds, the successor link is written - no
 //                      second sort and no key wider than 64 bits
-//   sx_flatten_kernel  parent = root, root flags -> scan -> sx_rootkey_kernel: (level << 32) | root of every root -> radix sort
-//                      of those keys -> sx_contour_kernel: contour numbers by ascending (level, smallest segment)
+//   ms_flatten_kernel<false> (r2s_mesh_graph.hpp) parent = root, root flags -> scan -> sx_rootkey_kernel: (level << 32) | root of every
+//                      root -> radix sort of those keys -> sx_contour_kernel: contour numbers by ascending (level, smallest segment)
 //   sx_number_kernel   contour of every segment, n_segs;  sx_node_kernel: the edge runs again, the class of every node
+//                      (ms_run_class, r2s_mesh_graph.hpp)
 //   sx_closed_kernel   closed flags, the longest closed loop (integer atomicMax), the totals
-//   sx_rank_init_kernel / sx_jump_kernel   distance to the head segment by pointer jumping, ping-pong buffers,
-//                      ceil(log2(longest closed loop)) rounds
-//   -> stable radix sort of the segment ids by contour -> sx_start_kernel -> sx_place_kernel: closed contours are laid out by
-//      rank, the others keep ascending segment id
+//   ms_order_loops     (r2s_mesh_graph.hpp) ms_rank_init_kernel / ms_jump_kernel: distance to the head segment by pointer jumping,
+//                      ping-pong buffers, ceil(log2(longest closed loop)) rounds -> stable radix sort of the segment ids by contour
+//                      -> ms_start_kernel -> ms_place_kernel<8, 2, false>: closed contours are laid out by rank, the others keep
+//                      ascending segment id
 //   sx_sum_kernel      blocks of 256 output positions: the two points and the 7 terms of every segment -> ms_block_sum<7>
 //                      (r2s_mesh_graph.hpp): a segmented fixed tree in LDS, one partial per (block, contour);
 //                      ms_combine_kernel<7> (r2s_mesh_graph.hpp): one wavefront per contour
 // Integer counts use integer atomics (one per wavefront and contour); no floating-point atomic and no library reduction
 // touches the Float64 sums.
 // Registers of the gfx950 build (hipcc -O3 -ffp-contract=off, -Rpass-analysis=kernel-resource-usage), VGPRs / scratch bytes:
-//   sx_height 8 / 0, sx_tri 28 / 0, sx_expand 13 / 0, sx_link 22 / 0, sx_flatten 12 / 0, sx_rootkey 8 / 0, sx_contour 10 / 0,
-//   sx_number 10 / 0, sx_node 22 / 0, sx_closed 23 / 0, sx_rank_init 6 / 0, sx_jump 8 / 0, sx_start 6 / 0, sx_place 12 / 0,
-//   sx_sum 63 / 0 (15 KiB of LDS), ms_combine<7> 42 / 0, ms_bounds 18 / 0: no kernel uses scratch, all run 8 waves per SIMD.
+//   sx_height 8 / 0, sx_tri 28 / 0, sx_expand 13 / 0, sx_link 22 / 0, ms_flatten 12 / 0, sx_rootkey 8 / 0, sx_contour 10 / 0,
+//   sx_number 10 / 0, sx_node 22 / 0, sx_closed 23 / 0, ms_rank_init 4 / 0, ms_jump 8 / 0, ms_start 6 / 0,
+//   ms_place<8, 2, false> 12 / 0, sx_sum 63 / 0 (15 KiB of LDS), ms_combine<7> 42 / 0, ms_bounds 18 / 0: no kernel uses scratch,
+//   all run 8 waves per SIMD.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -160,15 +162,6 @@ __global__ void __launch_bounds__(256) sx_link_kernel(const uint64_t* __restrict
     }
 }
 
-__global__ void __launch_bounds__(256) sx_flatten_kernel(int64_t nseg, uint32_t* parent, int32_t* __restrict__ flag)
-{
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= nseg) return;
-    const uint32_t r = ms_find(parent, (uint32_t)s);
-    if (r != (uint32_t)s) atomicMin(&parent[s], r);
-    flag[s] = r == (uint32_t)s ? 1 : 0;
-}
-
 // num = the exclusive scan of flag: the sort key of root number num[s]
 __global__ void __launch_bounds__(256) sx_rootkey_kernel(int64_t nseg, const int32_t* __restrict__ flag, const int32_t* __restrict__ num,
                                                           const int32_t* __restrict__ level_of, uint64_t* __restrict__ rkeys)
@@ -217,7 +210,7 @@ __global__ void __launch_bounds__(256) sx_number_kernel(int64_t nseg, const uint
     const bool active = s < nseg;
     uint32_t c = 0;
     if (active) {
-        c = (uint32_t)num[parent[s]];   // (sx_flatten_kernel left parent = root)
+        c = (uint32_t)num[parent[s]];   // (ms_flatten_kernel left parent = root)
         skey[s] = c;
         sval[s] = (uint32_t)s;
     }
@@ -242,11 +235,10 @@ __global__ void __launch_bounds__(256) sx_node_kernel(const uint64_t* __restrict
             bool a_above;
             sx_edge_range(k, h, levels, nl, e0, e1, a_above);
             if (e0 < e1) {
-                const uint64_t k1 = i + 1 < nh ? keys[i + 1] : ~0ull, k2 = i + 2 < nh ? keys[i + 2] : ~0ull;
-                const bool two = (k1 >> 1) == (k >> 1), three = two && (k2 >> 1) == (k >> 1);
-                add[1] = !two;
-                add[2] = two && !three && ((k1 ^ k) & 1ull) == 0ull;   // the same direction along one edge: two ends of one kind
-                add[3] = three;
+                const int cls = ms_run_class(keys, i, nh);
+                add[1] = cls == MS_RUN_SINGLE;
+                add[2] = cls == MS_RUN_SAME;   // the same direction along one edge: two ends of one kind
+                add[3] = cls == MS_RUN_MANY;
                 const uint32_t t = vals[i] / 3u;
                 len = (uint32_t)(e1 - e0);
                 s0 = (uint32_t)(offset[t] + (e0 - first[t]));
@@ -285,58 +277,6 @@ __global__ void __launch_bounds__(256) sx_closed_kernel(const int64_t* __restric
         for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d, 64);
         if ((threadIdx.x & 63) == 0 && v[k]) atomicAdd((unsigned long long*)&small[SX_TOT + k], (unsigned long long)v[k]);
     }
-}
-
-// (distance << 32) | pointer: a segment of a closed contour points at its successor at distance 1, the head segment (the
-// contour's smallest) and every segment of another contour at itself at distance 0
-__global__ void __launch_bounds__(256) sx_rank_init_kernel(int64_t nseg, const uint32_t* __restrict__ skey, const int32_t* __restrict__ closed,
-                                                            const int64_t* __restrict__ counts, const uint32_t* __restrict__ succ,
-                                                            uint64_t* __restrict__ pp)
-{
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= nseg) return;
-    const uint32_t c = skey[s];
-    const bool walks = closed[c] && counts[(int64_t)c * SX_NCNT + 1] != s;
-    pp[s] = walks ? ((1ull << 32) | (uint64_t)succ[s]) : (uint64_t)s;
-}
-
-// one round of pointer jumping from `in` to `out`
-__global__ void __launch_bounds__(256) sx_jump_kernel(int64_t nseg, const uint64_t* __restrict__ in, uint64_t* __restrict__ out)
-{
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= nseg) return;
-    const uint64_t v = in[s], w = in[(uint32_t)v];
-    out[s] = (((v >> 32) + (w >> 32)) << 32) | (uint64_t)(uint32_t)w;
-}
-
-// start[c] = the first sorted position of contour c, start[n_contours] = nseg
-__global__ void __launch_bounds__(256) sx_start_kernel(const uint32_t* __restrict__ skey, int64_t nseg, int64_t nc, int64_t* __restrict__ start)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nseg) return;
-    const uint32_t c = skey[i];
-    if (i == 0 || skey[i - 1] != c) start[c] = i;
-    if (i == 0) start[nc] = nseg;
-}
-
-// the output order: the stable sort left every contour in ascending segment id; a closed contour is laid out by rank instead
-// (rank 0 = the head, rank r = n - distance to the head along the successors)
-__global__ void __launch_bounds__(256) sx_place_kernel(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sseg, int64_t nseg,
-                                                        const int32_t* __restrict__ closed, const int64_t* __restrict__ counts,
-                                                        const int64_t* __restrict__ start, const uint64_t* __restrict__ pp,
-                                                        uint32_t* __restrict__ order)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nseg) return;
-    const uint32_t c = skey[i], s = sseg[i];
-    int64_t pos = i;
-    if (closed[c]) {
-        const int64_t n = counts[(int64_t)c * SX_NCNT + 2], d = (int64_t)(pp[s] >> 32);
-        const int64_t rank = d ? n - d : 0;
-        if (rank < 0 || rank >= n) return;   // (cannot happen on a cycle; keeps the store inside the contour's range)
-        pos = start[c] + rank;
-    }
-    order[pos] = s;
 }
 
 // the point of the node on the edge between corners u and w of a triangle at level ck, taken from the smaller vertex index
@@ -518,7 +458,7 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
         HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, keys, keys2, vals, vals2, (size_t)nh, 0u, ebits, st));
         sx_link_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, vals2, nh, ckey, h, levels, nl, offset, first, parent, succ);
         HIP_TRY(hipGetLastError());
-        sx_flatten_kernel<<<ms_blocks(nseg), 256, 0, st>>>(nseg, parent, rflag);
+        ms_flatten_kernel<false><<<ms_blocks(nseg), 256, 0, st>>>(nullptr, nseg, parent, rflag);
         HIP_TRY(hipGetLastError());
         HIP_TRY(rocprim::exclusive_scan(w.temp.p, tb2, rflag, num, (int32_t)0, (size_t)nseg, rocprim::plus<int32_t>(), st));
         int32_t last[2] = {0, 0};
@@ -557,22 +497,11 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
         HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
 
-        // the round count comes from the longest closed loop the device found: 2^rounds >= that length
-        uint64_t *pin = w.pp0.as<uint64_t>(), *pout = w.pp1.as<uint64_t>();
-        sx_rank_init_kernel<<<ms_blocks(nseg), 256, 0, st>>>(nseg, skey, w.closed.as<int32_t>(), counts, succ, pin);
-        HIP_TRY(hipGetLastError());
-        for (uint64_t reach = 1; reach < h_small[SX_MAXLOOP]; reach <<= 1) {
-            sx_jump_kernel<<<ms_blocks(nseg), 256, 0, st>>>(nseg, pin, pout);
-            HIP_TRY(hipGetLastError());
-            std::swap(pin, pout);
-        }
-        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb2, skey, skey2, sval, sval2, (size_t)nseg, 0u, sbits, st));
-        HIP_TRY(hipMemsetAsync(w.order.p, 0, sizeof(uint32_t) * (size_t)nseg, st));
-        sx_start_kernel<<<ms_blocks(nseg), 256, 0, st>>>(skey2, nseg, nc, w.start.as<int64_t>());
-        HIP_TRY(hipGetLastError());
-        sx_place_kernel<<<ms_blocks(nseg), 256, 0, st>>>(skey2, sval2, nseg, w.closed.as<int32_t>(), counts, w.start.as<int64_t>(), pin,
-                                                       w.order.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
+        // the round count comes from the longest closed loop the device found
+        if (const int rc = ms_order_loops<SX_NCNT, 2, false>(nseg, nc, h_small[SX_MAXLOOP], w.closed.as<int32_t>(), parent, succ, counts, skey,
+                                                             skey2, sval, sval2, w.pp0.as<uint64_t>(), w.pp1.as<uint64_t>(), w.temp.p, tb2,
+                                                             w.start.as<int64_t>(), nullptr, w.order.as<uint32_t>(), st))
+            return rc;
         sx_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, h, levels, skey2, w.order.as<uint32_t>(), w.tri_of.as<int32_t>(),
                                                           w.level_of.as<int32_t>(), nseg, nrm[0], nrm[1], nrm[2], r[0], r[1], r[2],
                                                           w.seg_tri.as<int32_t>(), w.points.as<double>(), w.partial.as<double>());
@@ -624,12 +553,6 @@ int table_args(const void* start, const void* counts, const void* sums, int64_t 
 }
 
 }  // namespace
-
-namespace r2s_int {
-
-void release_section_work() { g_section_work.release_all(); }
-
-}  // namespace r2s_int
 
 extern "C" {
 

@@ -7,13 +7,14 @@
 //   ms_union_kernel    one union per run member with the member before it (integer union-find: the larger root is hooked
 //                      under the smaller with a compare-and-swap, paths are halved with atomicMin, so the final root of a
 //                      component is its smallest triangle whatever the race)
-//   ms_flatten_kernel  label = root, root flags -> rocPRIM exclusive scan (integers) -> ms_number_kernel: shell numbers
+//   ms_flatten_kernel<true> (r2s_mesh_graph.hpp) parent = root, root flags -> rocPRIM exclusive scan (integers) ->
+//                      ms_number_kernel<false, true> (r2s_mesh_graph.hpp): shell numbers, the sort pairs
 //   -> stable radix sort of the triangle ids by shell number -> ms_segment_kernel (r2s_mesh_graph.hpp): where each shell starts
 //   ms_sum_kernel      blocks of 256 consecutive sorted triangles, the 11 terms per triangle -> ms_block_sum<11>
 //                      (r2s_mesh_graph.hpp): a segmented fixed tree in LDS, one partial per (block, shell) at slot block + shell
 //   ms_combine_kernel<11> (r2s_mesh_graph.hpp) one wavefront per shell: up to 64 equal runs of its block partials in ascending
 //                      order, then a fixed tree; n_tris of the shell
-//   ms_edge_kernel     the sorted edge runs again: class of each run, counted into the shell of its first half-edge
+//   ms_edge_kernel     the sorted edge runs again: class of each run (ms_run_class), counted into the shell of its first half-edge
 //   ms_vkey_kernel     (shell << 32) | vertex per corner -> radix sort of keys -> ms_vcount_kernel: distinct vertices per shell
 //   ms_totals_kernel   the column sums of the integer table and the number of referenced vertices
 // Integer counts use integer atomics (a workgroup whose entries all fall into one shell adds once per column); no
@@ -52,37 +53,6 @@ __global__ void __launch_bounds__(256) ms_union_kernel(const uint64_t* __restric
     const uint64_t k = keys[i];
     if (k >= ckey || (keys[i - 1] >> 1) != (k >> 1)) return;
     ms_union(parent, vals[i - 1] / 3u, vals[i] / 3u);
-}
-
-__global__ void __launch_bounds__(256) ms_flatten_kernel(const int32_t* __restrict__ tris, int64_t n, uint32_t* parent, int32_t* __restrict__ flag)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    int32_t i0, i1, i2;
-    if (ms_collapsed(tris, t, i0, i1, i2)) {
-        flag[t] = 0;
-        return;
-    }
-    const uint32_t r = ms_find(parent, (uint32_t)t);
-    if (r != (uint32_t)t) atomicMin(&parent[t], r);
-    flag[t] = r == (uint32_t)t ? 1 : 0;
-}
-
-// num = the exclusive scan of flag: shell_of[t], the sort key of t (collapsed: n_shells, behind every shell), n_shells
-__global__ void __launch_bounds__(256) ms_number_kernel(const int32_t* __restrict__ tris, int64_t n, const uint32_t* __restrict__ parent,
-                                                         const int32_t* __restrict__ num, const int32_t* __restrict__ flag,
-                                                         int32_t* __restrict__ shell_of, uint32_t* __restrict__ skey, uint32_t* __restrict__ sval,
-                                                         uint64_t* __restrict__ small)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    const int32_t nsh = num[n - 1] + flag[n - 1];
-    int32_t i0, i1, i2;
-    const int32_t s = ms_collapsed(tris, t, i0, i1, i2) ? -1 : num[parent[t]];   // (ms_flatten_kernel left parent = root)
-    shell_of[t] = s;
-    skey[t] = s < 0 ? (uint32_t)nsh : (uint32_t)s;
-    sval[t] = (uint32_t)t;
-    if (t == n - 1) small[MS_NSHELLS] = (uint64_t)nsh;
 }
 
 // the 11 terms of one triangle in the header's operation order
@@ -142,12 +112,11 @@ __global__ void __launch_bounds__(256) ms_edge_kernel(const uint64_t* __restrict
         const uint64_t k = keys[i];
         head = k < ckey && (i == 0 || (keys[i - 1] >> 1) != (k >> 1));
         if (head) {
-            const uint64_t k1 = i + 1 < nh ? keys[i + 1] : ~0ull, k2 = i + 2 < nh ? keys[i + 2] : ~0ull;
-            const bool two = (k1 >> 1) == (k >> 1), three = two && (k2 >> 1) == (k >> 1);
+            const int cls = ms_run_class(keys, i, nh);
             add[0] = true;
-            add[1] = !two;
-            add[2] = two && !three && ((k1 ^ k) & 1ull) == 0ull;
-            add[3] = three;
+            add[1] = cls == MS_RUN_SINGLE;
+            add[2] = cls == MS_RUN_SAME;
+            add[3] = cls == MS_RUN_MANY;
             shell = shell_of[vals[i] / 3u];
         }
     }
@@ -243,11 +212,12 @@ int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         if (rc) return rc;
         ms_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, parent);
         HIP_TRY(hipGetLastError());
-        ms_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.rflag.as<int32_t>());
+        ms_flatten_kernel<true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.rflag.as<int32_t>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(rocprim::exclusive_scan(w.temp.p, tb2, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
-        ms_number_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.num.as<int32_t>(), w.rflag.as<int32_t>(), w.shell.as<int32_t>(),
-                                                     w.skey.as<uint32_t>(), w.sval.as<uint32_t>(), small);
+        ms_number_kernel<false, true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.num.as<int32_t>(), w.rflag.as<int32_t>(),
+                                                                  w.shell.as<int32_t>(), w.skey.as<uint32_t>(), w.sval.as<uint32_t>(),
+                                                                  small + MS_NSHELLS);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
@@ -309,12 +279,6 @@ int shells_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_
 }
 
 }  // namespace
-
-namespace r2s_int {
-
-void release_shell_work() { g_shell_work.release_all(); }
-
-}  // namespace r2s_int
 
 extern "C" {
 

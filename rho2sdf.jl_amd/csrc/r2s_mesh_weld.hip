@@ -385,12 +385,6 @@ int weld_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tr
 
 }  // namespace
 
-namespace r2s_int {
-
-void release_weld_work() { g_weld_work.release_all(); }
-
-}  // namespace r2s_int
-
 extern "C" {
 
 int r2s_mesh_weld(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, double snap, int32_t flags, int32_t device,

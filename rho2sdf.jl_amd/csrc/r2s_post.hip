@@ -440,7 +440,6 @@ struct CclWork {
     DevBuf L, size, roots, cnt, blk, tab;
 };
 static r2s_int::PerDevice<CclWork> g_ccl_work;
-static void release_ccl_work() { g_ccl_work.release_all(); }
 
 // The labelling of {sdf >= threshold} shared by removal and analysis, on the device's work arrays (the caller holds
 // g_ccl_work.mu): afterwards L[v] is v's head (or root, or NOLABEL) and size[r] the size of every root r.  h[8] comes back
@@ -3205,6 +3204,12 @@ int rbf_fit_weights(const double* sdf, const r2s_grid* g, int is_interp, double 
 void rbf_coarse_axis(double mn, double mx, int n, std::vector<float>& c) { coarse_coords(mn, mx, n, c); }
 void* rbf_workspace_create() { return new RbfWork(); }
 void rbf_workspace_release(void* w) { delete (RbfWork*)w; }
+
+std::vector<PerDeviceCache*>& per_device_caches()
+{
+    static std::vector<PerDeviceCache*>& list = *new std::vector<PerDeviceCache*>;
+    return list;
+}
 }  // namespace r2s_int
 
 extern "C" {
@@ -3332,24 +3337,15 @@ void r2s_last_rbf_plan(int32_t out[12])
     if (out) memcpy(out, g_last_rbf_plan, sizeof g_last_rbf_plan);
 }
 
-/* frees the process-wide work buffers kept between calls (the materialised RBF matrix) */
+/* frees the process-wide work buffers kept between calls: the materialised RBF matrix, every per-device work cache (each
+ * PerDevice is on the list by its construction) and the host sessions */
 void r2s_release_cache(void)
 {
     {
         std::lock_guard<std::mutex> lock(g_rbf_kv_mutex);
         g_rbf_kv.release();
     }
-    release_ccl_work();
-    r2s_int::release_iso_work();
-    r2s_int::release_dist_work();
-    r2s_int::release_shell_work();
-    r2s_int::release_section_work();
-    r2s_int::release_weld_work();
-    r2s_int::release_orient_work();
-    r2s_int::release_fans_work();
-    r2s_int::release_holes_work();
-    r2s_int::release_intersect_work();
-    r2s_int::release_nesting_work();
+    for (r2s_int::PerDeviceCache* c : r2s_int::per_device_caches()) c->release_all();
     r2s_int::release_host_sessions();
 }
 

@@ -243,8 +243,6 @@ thread_local double g_dist_stats[8];
 
 namespace r2s_int {
 
-void release_dist_work() { g_dist_work.release_all(); }
-
 int lattice_args(const char* who, const int64_t dims[3], const double origin[3], double spacing, double band)
 {
     if (!dims || !origin) return fail(R2S_ERR_ARG, "%s: null dims / origin", who);

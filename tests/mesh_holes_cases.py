@@ -42,6 +42,12 @@ def tube_and_cube():
     return S.join(tube(), cube_minus_face())
 
 
+def loops_and_chain():
+    """closed rims of 3, 4, 5 and twice 300 edges (9 rounds of pointer jumping, each across a block edge of the sums) next to the
+    open chain of the fin"""
+    return S.join(tube(300), tet_minus_face(), cube_minus_face(), disk(5), fin())
+
+
 def bowtie():
     """two triangles sharing vertex 0 and nothing else: one rim of 6 edges through a branch node; two rims of 3 after the split"""
     return S._mesh([[0, 0, 0], [1, 1, 0], [1, -1, 0], [-1, 1, 0.5], [-1, -1, 0.5]], [[0, 1, 2], [0, 3, 4]])
@@ -159,9 +165,9 @@ HAND = {"empty": S.empty, "one_triangle": S.one_triangle, "all_collapsed": S.all
         "bowtie": bowtie, "ico_touching_holes": ico_touching_holes, "strip_one_reversed": strip_one_reversed, "moebius": O.moebius,
         "fin": fin, "three_on_edge": S.three_on_edge, "degenerate_mixed": degenerate_mixed, "disk255": lambda: disk(255),
         "disk256": lambda: disk(256), "disk257": lambda: disk(257), "disk16385": lambda: disk(16385), "ico_many_holes": ico_many_holes,
-        "sphere33_holes": sphere33_holes, "gyroid17": lambda: S.extracted("gyroid17")}
+        "sphere33_holes": sphere33_holes, "gyroid17": lambda: S.extracted("gyroid17"), "loops_and_chain": loops_and_chain}
 VARIED = ("cube_minus_face", "cube_far", "tube_and_cube", "degenerate_mixed", "disk255", "disk256", "disk257", "disk16385",
-          "ico_many_holes", "sphere33_holes", "gyroid17")
+          "ico_many_holes", "sphere33_holes", "gyroid17", "loops_and_chain")
 VARIANTS = (None, "permuted", "rotated")
 ALL = tuple(HAND)
 _cases = {}

@@ -5,6 +5,7 @@ are chosen so that each case reaches one way the kernels can go wrong (the table
 tests/test_mesh_sections_gpu.py)."""
 import numpy as np
 
+import mesh_holes_cases as H
 import mesh_shells_cases as S
 
 Z = (0.0, 0.0, 1.0)
@@ -46,6 +47,13 @@ def cones():
     sums and the powers of two of pointer jumping; the triangles shuffled so that no loop is in segment order"""
     mesh = S.join(*[cone(m, (3.0 * k, 0.0)) for k, m in enumerate(LOOP_SIZES)])
     return S.permuted(mesh, 7)[0]
+
+
+def loops_and_chain():
+    """cones of 3, 4 and 5 triangles, an open tube of 300 and a single triangle, cut by one plane: closed loops of 3, 4, 5 and
+    300 segments (9 rounds of pointer jumping, across a block edge of the sums) next to an open chain"""
+    mesh = S.join(cone(3), cone(4, (3.0, 0.0)), cone(5, (6.0, 0.0)), H.tube(150, -0.5), S.one_triangle())
+    return _case(mesh, Z, [0.125])
 
 
 def stacked_cubes():
@@ -90,6 +98,7 @@ HAND = {
     "torus_123": lambda: _case(S.torus(), (1.0, 2.0, 3.0), [-2.5, -0.4, 0.0, 0.3, 1.1, 4.0]),
     "band20000": lambda: _case(band(), Z, [0.0]),
     "cones": lambda: _case(cones(), Z, [-0.5, 0.25]),
+    "loops_and_chain": loops_and_chain,
 }
 EXTRACTED = ("sphere33", "gyroid17", "noise24_closed", "noise24_open")
 ALL = tuple(HAND) + EXTRACTED

@@ -1,6 +1,9 @@
-"""r2s_release_cache() against the nine per-device work caches (PerDevice in r2s_internal.hpp): shells, sections, weld, orient,
-fans, holes, intersections, the distance calls and the component labelling.  Every family is called once, the cache is released,
-and every family is called again on fresh buffers: the same bits."""
+"""r2s_release_cache() against the eleven per-device work caches (PerDevice in r2s_internal.hpp): shells, sections, weld, orient,
+fans, holes, intersections, nesting, the distance calls, the component labelling and the device extraction.  Every family is
+called once, the cache is released, and every family is called again on fresh buffers: the same bits.  r2s_live_device_bytes()
+grows with the calls and is back at its value from before them after the release (include/rho2sdf_hip.h)."""
+import gc
+
 import numpy as np
 import pytest
 
@@ -39,6 +42,11 @@ def _families(pkg):
     n = [int(k) + 1 for k in grid.c.N]
     c = np.indices(n[::-1]).reshape(3, -1).T / (np.array(n[::-1]) - 1.0)
     sdf = 0.3 - np.linalg.norm(c - 0.5, axis=1) + np.where((c < 0.1).all(1), 1.0, 0.0)   # a ball and a corner blob
+
+    def extracted():
+        import torch
+        return [x.cpu().numpy() for x in pkg.extract_isosurface_dev(torch.from_numpy(sdf).cuda(), grid)]
+
     return {
         "shells": lambda: pkg.mesh_shells(V, T),
         "sections": lambda: pkg.mesh_sections(Vx, Tx, normal, levels),
@@ -49,16 +57,26 @@ def _families(pkg):
         "intersect": lambda: pkg.mesh_intersections(V, T),
         "distance": lambda: pkg.mesh_distance(V, T, ((9, 9, 9), (-0.5, -0.5, -0.5), 0.375), 1.0, want_index=True),
         "components": lambda: pkg.analyze_sdf_components(sdf, grid),
+        "nesting": lambda: pkg.mesh_nesting(V, T, rewind=True),
+        "extraction": extracted,
     }
 
 
 def test_every_family_gives_the_same_bits_after_release_cache(pkg):
     calls = _families(pkg)
+    live = pkg._lib.lib().r2s_live_device_bytes
+    gc.collect()                                             # (no handle of an earlier test is freed in between)
+    pkg._lib.lib().r2s_release_cache()
+    b0 = live()
     before = {k: _flat(f()) for k, f in calls.items()}
     assert len(before["components"]) == 2 and before["shells"][".totals"] is not None
+    assert len(before["extraction"]["[1]"][2]) > 0 and before["nesting"][".totals"] is not None
+    assert live() > b0
     pkg._lib.lib().r2s_release_cache()
+    assert live() == b0
     for k, f in calls.items():
         assert _flat(f()) == before[k], k
     pkg._lib.lib().r2s_release_cache()                       # released twice in a row: nothing left to free
     pkg._lib.lib().r2s_release_cache()
+    assert live() == b0
     assert _flat(calls["shells"]()) == before["shells"]
