@@ -2,10 +2,13 @@
 // pre-stage and post-processing stages, used by the host-pointer entry points of their own files and by the
 // chained r2s_rho2sdf() in r2s_host.hip, and the seam between r2s_redistance.hip and r2s_mesh_index.hip.  All of them run on the CURRENT device and are synchronous on return.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "r2s_common.hpp"
@@ -199,9 +202,109 @@ inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + bbytes && b0 < a0 + abytes;
 }
+// a caller's array as a byte range, for the overlap checks of the tools with several outputs
+struct Span {
+    const void* p;
+    size_t bytes;
+};
+inline bool overlaps(const Span& a, const Span& b) { return overlaps(a.p, a.bytes, b.p, b.bytes); }
 // sizes dv / dt for the mesh (at least one element each) and copies it in: from the host with hipMemcpy, or
 // (from_device) from the current device on `st`
 int upload_mesh(DevBuf& dv, DevBuf& dt, const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, bool from_device,
                 hipStream_t st);
+
+// ---- one call of a mesh topology tool (shells, sections, weld, orient, fans, holes, nesting) ----------------------------------
+// What the host-pointer entry and the _dev entry of a tool do between their argument checks and the core, and how results go
+// back, so that each tool has one body (X_run) for both kinds of caller.  W is the tool's work struct, with DevBuf members
+// verts, tris and flag.  The call holds the lock of the tool's cache from open() until it is destroyed.
+template <class W>
+class MeshCall {
+public:
+    static constexpr bool STAGE_DEVICE_CALLER = true;   // (for staged)
+    MeshCall(const char* who, PerDevice<W>& cache, const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, int32_t device)
+        : who_(who), cache_(cache), verts_(verts), tris_(tris), n_verts_(n_verts), n_tris_(n_tris), host_(true), device_(device) {}
+    MeshCall(const char* who, PerDevice<W>& cache, const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n_tris, hipStream_t st)
+        : who_(who), cache_(cache), verts_(d_verts), tris_(d_tris), n_verts_(n_verts), n_tris_(n_tris), host_(false), st_(st) {}
+    // a host caller:   check_mesh_host, use_device(device), [before_lock], the lock, current(), upload_mesh into w.verts / w.tris
+    // a device caller: check_device(0), [before_lock], the lock, current(), check_mesh_dev with w.flag
+    // before_lock: a check of the tool's own that needs the device but not the work buffers (nesting: the index's device)
+    template <class F = std::nullptr_t>
+    int open(F before_lock = nullptr)
+    {
+        int rc = host_ ? check_mesh_host(who_, verts_, n_verts_, tris_, n_tris_) : 0;
+        if (rc || (rc = host_ ? use_device(device_) : check_device(0))) return rc;
+        if constexpr (!std::is_null_pointer_v<F>)
+            if ((rc = before_lock())) return rc;
+        lock_ = std::unique_lock<std::mutex>(cache_.mu);
+        w_ = cache_.current(rc);
+        if (rc) return rc;
+        if (!host_) return check_mesh_dev(who_, verts_, n_verts_, tris_, n_tris_, w_->flag, st_);
+        if ((rc = upload_mesh(w_->verts, w_->tris, verts_, n_verts_, tris_, n_tris_, false, nullptr))) return rc;
+        verts_ = w_->verts.template as<float>();
+        tris_ = tris_ ? w_->tris.template as<int32_t>() : nullptr;   // (weld: no triangle array is a soup, on the device too)
+        return 0;
+    }
+    bool is_host() const { return host_; }
+    const float* d_verts() const { return verts_; }
+    const int32_t* d_tris() const { return tris_; }
+    hipStream_t stream() const { return st_; }   // (a host caller's: the null stream)
+    W& work() { return *w_; }
+    // `bytes` from device memory to the caller's dst: a host caller's copy is done on return, a device caller's is queued on
+    // the stream.  No dst, no bytes, or dst is where the kernels wrote already (staged): nothing to do.
+    int deliver(void* dst, const void* src, size_t bytes)
+    {
+        if (!dst || !bytes || dst == src) return 0;
+        if (host_) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        if (!host_) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st_));
+        return 0;
+    }
+    // d_out = where the kernels write an output array of the caller's, delivered afterwards: a host caller's goes to `buf`, sized
+    // here.  A device caller's is written in place by orient, fans, holes and weld, so what a refusal behind those kernels leaves
+    // in it is unspecified; nesting alone passes STAGE_DEVICE_CALLER, so that its refusals leave the array untouched.
+    template <class T>
+    int staged(DevBuf& buf, T* caller, size_t bytes, T*& d_out, bool stage_device_caller = false)
+    {
+        d_out = caller;
+        if (!host_ && !stage_device_caller) return 0;
+        ENSURE(buf, bytes);
+        d_out = buf.as<T>();
+        return 0;
+    }
+    // one table of the result, `count` elements at src: a host caller keeps all of it in `kept` (for the tool's r2s_last_*), a
+    // device caller gets it at d_dst when the tool's capacity rule says it fits
+    template <class T>
+    int table(std::vector<T>& kept, T* d_dst, bool fits, const DevBuf& src, size_t count)
+    {
+        if (host_) kept.resize(count);
+        return host_ ? deliver(kept.data(), src.p, sizeof(T) * count) : fits ? deliver(d_dst, src.p, sizeof(T) * count) : 0;
+    }
+    // the cores are synchronous, the copies queued for a device caller are not
+    int finish()
+    {
+        HIP_TRY(hipStreamSynchronize(st_));
+        return 0;
+    }
+
+private:
+    const char* who_;
+    PerDevice<W>& cache_;
+    const float* verts_;
+    const int32_t* tris_;
+    int64_t n_verts_, n_tris_;
+    bool host_;
+    int32_t device_ = -1;
+    hipStream_t st_ = nullptr;
+    std::unique_lock<std::mutex> lock_;
+    W* w_ = nullptr;
+};
+
+// min(capacity, n) rows of `row` elements of a kept table to dst, which r2s_last_* has checked; the number copied
+template <class T>
+inline int64_t copy_rows(T* dst, const std::vector<T>& table, size_t row, int64_t capacity, int64_t n)
+{
+    const int64_t m = std::min(capacity, n);
+    if (m > 0) std::memcpy(dst, table.data(), sizeof(T) * row * (size_t)m);
+    return m;
+}
 
 }  // namespace r2s_int

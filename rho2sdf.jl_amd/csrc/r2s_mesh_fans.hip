@@ -358,12 +358,47 @@ int fans_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tr
     *split = tris_out || verts_out || vert_of_out;
     if (*split && ((n_tris > 0 && !tris_out) || !verts_out || !vert_of_out))
         return fail(R2S_ERR_ARG, "mesh_fans: the split needs tris_out, verts_out and vert_of_out together");
-    const struct { const void* p; size_t bytes; } in[2] = {{verts, vert_bytes(n_verts)}, {tris, tri_bytes(n_tris)}},
-        out[5] = {{fan_of_corner, tri_bytes(n_tris)}, {fans_of_vert, sizeof(int32_t) * (size_t)n_verts}, {tris_out, tri_bytes(n_tris)},
-                  {verts_out, vert_bytes(vert_capacity)}, {vert_of_out, sizeof(int32_t) * (size_t)vert_capacity}};
+    const Span in[2] = {{verts, vert_bytes(n_verts)}, {tris, tri_bytes(n_tris)}},
+               out[5] = {{fan_of_corner, tri_bytes(n_tris)}, {fans_of_vert, sizeof(int32_t) * (size_t)n_verts}, {tris_out, tri_bytes(n_tris)},
+                         {verts_out, vert_bytes(vert_capacity)}, {vert_of_out, sizeof(int32_t) * (size_t)vert_capacity}};
     for (const auto& o : out)
         for (const auto& i : in)
-            if (overlaps(o.p, o.bytes, i.p, i.bytes)) return fail(R2S_ERR_ARG, "mesh_fans: an output overlaps an input");
+            if (overlaps(o, i)) return fail(R2S_ERR_ARG, "mesh_fans: an output overlaps an input");
+    return 0;
+}
+
+// One call for both kinds of caller: the core, the split when it was asked for and vert_capacity holds n_verts_out vertices,
+// then fan_of_corner, fans_of_vert, the records and the scalars.  A host caller's records are kept whole for r2s_last_mesh_fans;
+// a device caller gets them when fan_capacity holds all of them, else none.
+int fans_run(MeshCall<FanWork>& c, int64_t n_verts, int64_t n_tris, int32_t* fan_of_corner, int32_t* fans_of_vert, int64_t* d_counts,
+             int64_t fan_capacity, bool split, int32_t* tris_out, float* verts_out, int32_t* vert_of_out, int64_t vert_capacity,
+             int64_t* n_fans, int64_t* n_verts_out, int64_t totals[8])
+{
+    int rc = c.open();
+    if (rc) return rc;
+    FanWork& w = c.work();
+    std::vector<int64_t> tab;
+    int64_t nf = 0, nvo = 0, tot[8];
+    if ((rc = fans_core(n_verts, c.d_tris(), n_tris, c.stream(), w, &nf, &nvo, tot))) return rc;
+    const bool room = split && vert_capacity >= nvo;
+    int32_t *d_tris_out = nullptr, *d_vert_of = nullptr;
+    float* d_verts_out = nullptr;
+    if (room &&
+        ((rc = c.staged(w.tris_out, tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)), d_tris_out)) ||
+         (rc = c.staged(w.verts_out, verts_out, vert_bytes(std::max<int64_t>(nvo, 1)), d_verts_out)) ||
+         (rc = c.staged(w.vert_of, vert_of_out, sizeof(int32_t) * (size_t)std::max<int64_t>(nvo, 1), d_vert_of)) ||
+         (rc = fans_apply(c.d_verts(), n_verts, c.d_tris(), n_tris, nf, c.stream(), w, d_tris_out, d_verts_out, d_vert_of))))
+        return rc;
+    if ((rc = c.table(tab, d_counts, fan_capacity >= nf, w.counts, (size_t)nf * MF_NCNT)) ||
+        (rc = c.deliver(fan_of_corner, w.foc.p, tri_bytes(n_tris))) || (rc = c.deliver(fans_of_vert, w.fov.p, sizeof(int32_t) * (size_t)n_verts)) ||
+        (rc = c.deliver(room ? tris_out : nullptr, d_tris_out, tri_bytes(n_tris))) ||
+        (rc = c.deliver(room ? verts_out : nullptr, d_verts_out, vert_bytes(nvo))) ||
+        (rc = c.deliver(room ? vert_of_out : nullptr, d_vert_of, sizeof(int32_t) * (size_t)nvo)) || (rc = c.finish()))
+        return rc;
+    if (c.is_host()) g_last_fans = std::move(tab);
+    *n_fans = nf;
+    *n_verts_out = nvo;
+    std::memcpy(totals, tot, sizeof tot);
     return 0;
 }
 
@@ -376,50 +411,19 @@ int r2s_mesh_fans(const float* verts, int64_t n_verts, const int32_t* tris, int6
                   int64_t* n_fans, int64_t* n_verts_out, int64_t totals[8])
 {
     bool split = false;
-    int rc = fans_args(verts, n_verts, tris, n_tris, fan_of_corner_out, fans_of_vert_out, tris_out, verts_out, vert_of_out, vert_capacity,
-                       n_fans, n_verts_out, totals, &split);
-    if (rc) return rc;
-    if ((rc = check_mesh_host("mesh_fans", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_fans_work.mu);
-    FanWork* w = g_fans_work.current(rc);
-    if (rc) return rc;
-    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
-    int64_t nf = 0, nvo = 0, tot[8];
-    if ((rc = fans_core(n_verts, w->tris.as<int32_t>(), n_tris, nullptr, *w, &nf, &nvo, tot))) return rc;
-    const bool room = split && vert_capacity >= nvo;
-    if (room) {
-        ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)));
-        ENSURE(w->verts_out, vert_bytes(std::max<int64_t>(nvo, 1)));
-        ENSURE(w->vert_of, sizeof(int32_t) * (size_t)std::max<int64_t>(nvo, 1));
-        if ((rc = fans_apply(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, nf, nullptr, *w, w->tris_out.as<int32_t>(),
-                             w->verts_out.as<float>(), w->vert_of.as<int32_t>())))
-            return rc;
-    }
-    std::vector<int64_t> tab((size_t)nf * MF_NCNT);
-    if (nf > 0) HIP_TRY(hipMemcpy(tab.data(), w->counts.p, sizeof(int64_t) * tab.size(), hipMemcpyDeviceToHost));
-    if (fan_of_corner_out && n_tris > 0) HIP_TRY(hipMemcpy(fan_of_corner_out, w->foc.p, tri_bytes(n_tris), hipMemcpyDeviceToHost));
-    if (fans_of_vert_out && n_verts > 0)
-        HIP_TRY(hipMemcpy(fans_of_vert_out, w->fov.p, sizeof(int32_t) * (size_t)n_verts, hipMemcpyDeviceToHost));
-    if (room) {
-        if (n_tris > 0) HIP_TRY(hipMemcpy(tris_out, w->tris_out.p, tri_bytes(n_tris), hipMemcpyDeviceToHost));
-        if (nvo > 0) {
-            HIP_TRY(hipMemcpy(verts_out, w->verts_out.p, vert_bytes(nvo), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(vert_of_out, w->vert_of.p, sizeof(int32_t) * (size_t)nvo, hipMemcpyDeviceToHost));
-        }
-    }
-    g_last_fans = std::move(tab);
-    *n_fans = nf;
-    *n_verts_out = nvo;
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (const int rc = fans_args(verts, n_verts, tris, n_tris, fan_of_corner_out, fans_of_vert_out, tris_out, verts_out, vert_of_out,
+                                 vert_capacity, n_fans, n_verts_out, totals, &split))
+        return rc;
+    MeshCall<FanWork> call("mesh_fans", g_fans_work, verts, n_verts, tris, n_tris, device);
+    return fans_run(call, n_verts, n_tris, fan_of_corner_out, fans_of_vert_out, nullptr, 0, split, tris_out, verts_out, vert_of_out, vert_capacity,
+                    n_fans, n_verts_out, totals);
 }
 
 int r2s_last_mesh_fans(int64_t* counts_out, int64_t capacity, int64_t* n_fans)
 {
     if (!n_fans || capacity < 0 || (capacity > 0 && !counts_out)) return fail(R2S_ERR_ARG, "last_mesh_fans: null output or negative capacity");
-    const int64_t n = (int64_t)(g_last_fans.size() / MF_NCNT), m = std::min(capacity, n);
-    *n_fans = n;
-    if (m > 0) std::memcpy(counts_out, g_last_fans.data(), sizeof(int64_t) * MF_NCNT * (size_t)m);
+    *n_fans = (int64_t)(g_last_fans.size() / MF_NCNT);
+    copy_rows(counts_out, g_last_fans, MF_NCNT, capacity, *n_fans);
     return 0;
 }
 
@@ -428,30 +432,13 @@ int r2s_mesh_fans_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tr
                       int32_t* d_vert_of_out, int64_t vert_capacity, int64_t* n_fans, int64_t* n_verts_out, int64_t totals[8], void* stream)
 {
     bool split = false;
-    int rc = fans_args(d_verts, n_verts, d_tris, n_tris, d_fan_of_corner, d_fans_of_vert, d_tris_out, d_verts_out, d_vert_of_out,
-                       vert_capacity, n_fans, n_verts_out, totals, &split);
-    if (rc) return rc;
-    if (fan_capacity < 0 || (fan_capacity > 0 && !d_counts)) return fail(R2S_ERR_ARG, "mesh_fans: null table or negative fan_capacity");
-    if ((rc = check_device(0))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_fans_work.mu);
-    FanWork* w = g_fans_work.current(rc);
-    if (rc) return rc;
-    if ((rc = check_mesh_dev("mesh_fans", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
-    int64_t nf = 0, nvo = 0, tot[8];
-    if ((rc = fans_core(n_verts, d_tris, n_tris, st, *w, &nf, &nvo, tot))) return rc;
-    if (d_fan_of_corner && n_tris > 0) HIP_TRY(hipMemcpyAsync(d_fan_of_corner, w->foc.p, tri_bytes(n_tris), hipMemcpyDeviceToDevice, st));
-    if (d_fans_of_vert && n_verts > 0)
-        HIP_TRY(hipMemcpyAsync(d_fans_of_vert, w->fov.p, sizeof(int32_t) * (size_t)n_verts, hipMemcpyDeviceToDevice, st));
-    if (nf > 0 && fan_capacity >= nf)
-        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MF_NCNT * (size_t)nf, hipMemcpyDeviceToDevice, st));
-    if (split && vert_capacity >= nvo && (rc = fans_apply(d_verts, n_verts, d_tris, n_tris, nf, st, *w, d_tris_out, d_verts_out, d_vert_of_out)))
+    if (const int rc = fans_args(d_verts, n_verts, d_tris, n_tris, d_fan_of_corner, d_fans_of_vert, d_tris_out, d_verts_out, d_vert_of_out,
+                                 vert_capacity, n_fans, n_verts_out, totals, &split))
         return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_fans = nf;
-    *n_verts_out = nvo;
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (fan_capacity < 0 || (fan_capacity > 0 && !d_counts)) return fail(R2S_ERR_ARG, "mesh_fans: null table or negative fan_capacity");
+    MeshCall<FanWork> call("mesh_fans", g_fans_work, d_verts, n_verts, d_tris, n_tris, (hipStream_t)stream);
+    return fans_run(call, n_verts, n_tris, d_fan_of_corner, d_fans_of_vert, d_counts, fan_capacity, split, d_tris_out, d_verts_out, d_vert_of_out,
+                    vert_capacity, n_fans, n_verts_out, totals);
 }
 
 }  // extern "C"

@@ -9,6 +9,9 @@
 //   the component numbering behind the unions: ms_flatten_kernel<false> (sections, holes) and <true> (shells, nesting: triangles)
 //     leave parent = root and flag the roots, the caller scans the flags, ms_number_kernel writes the group of every triangle
 //     (shells, orient, nesting), with the sort pairs where asked;
+//   the host stages around those kernels: ms_begin_small (shells, orient, holes, sections: the small array and the box),
+//     ms_group_triangles (shells, orient, nesting: half-edge table, the tool's unions, flatten, scan, numbering) and
+//     ms_sum_by_group (shells, orient: sort by group, segments, the tool's terms, combine);
 //   the loop ordering of sections and holes, ms_order_loops: pointer jumping (ms_rank_init_kernel, ms_jump_kernel), the stable
 //     sort by group, ms_start_kernel and ms_place_kernel;
 //   the segmented Float64 sum every Float64 table of these tools is defined by (include/rho2sdf_hip.h): ms_block_sum, the tree
@@ -19,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cstdint>
@@ -87,6 +91,22 @@ inline void ms_ref_point(const uint64_t* bb, int64_t n_verts, double r[3])
 {
     for (int k = 0; k < 3; ++k)
         r[k] = n_verts > 0 ? 0.5 * ((double)ms_unordered((uint32_t)bb[k]) + (double)ms_unordered((uint32_t)bb[3 + k])) : 0.0;
+}
+
+// How shells, orient, holes and sections open their cores on `st`: h_small = 0 but for the three minima of the box, which
+// start at the largest pattern, uploaded to `buf` (sized here), and ms_bounds_kernel over the vertices
+template <int N>
+int ms_begin_small(DevBuf& buf, uint64_t (&h_small)[N], const float* d_verts, int64_t n_verts, hipStream_t st)
+{
+    std::fill(h_small, h_small + N, (uint64_t)0);
+    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
+    ENSURE(buf, sizeof h_small);
+    HIP_TRY(hipMemcpyAsync(buf.p, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
+    if (n_verts > 0) {
+        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, buf.as<uint64_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
 }
 
 // parents are rewritten by other CUs during the kernel: bypass the per-CU L1
@@ -303,6 +323,35 @@ int ms_sort_half_edges(MsHalfEdgeBufs& b, const int32_t* d_tris, int64_t n, int6
     return 0;
 }
 
+// The component stage of shells, orient and nesting on `st`, for n > 0 device triangles: sizes parent (NPARENT nodes a triangle),
+// rflag, num, group and, with PAIRS, skey / sval; the sorted half-edge table (ms_sort_half_edges<NPARENT, VFLAG>, temp sized for
+// the sort and the scan together); the tool's unions over the sorted runs, launch_union(keys2, vals2, nh, ckey, parent); the
+// flatten, launch_flatten(parent, rflag): ms_flatten_kernel<true>, or the orient's own, which leaves the roots in `info`; the
+// exclusive scan of rflag into num; ms_number_kernel<DOUBLED, PAIRS> reading the roots from info (DOUBLED) or parent.
+template <int NPARENT, bool VFLAG, bool DOUBLED, bool PAIRS, class Union, class Flatten>
+int ms_group_triangles(MsHalfEdgeBufs& b, const int32_t* d_tris, int64_t n, int64_t n_verts, DevBuf& parent, int32_t* vflag, const uint32_t* info,
+                       DevBuf& rflag, DevBuf& num, DevBuf& group, DevBuf* skey, DevBuf* sval, uint64_t* n_collapsed, uint64_t* n_groups,
+                       Union launch_union, Flatten launch_flatten, hipStream_t st)
+{
+    ENSURE(parent, sizeof(uint32_t) * NPARENT * (size_t)n);
+    for (DevBuf* per_tri : {&rflag, &num, &group, skey, sval})   // (skey / sval: null without PAIRS)
+        if (per_tri) ENSURE(*per_tri, sizeof(int32_t) * (size_t)n);
+    uint32_t* root = parent.as<uint32_t>();
+    int32_t *flag = rflag.as<int32_t>(), *scan = num.as<int32_t>();
+    size_t scan_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flag, scan, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
+    if (const int rc = ms_sort_half_edges<NPARENT, VFLAG>(b, d_tris, n, n_verts, root, vflag, n_collapsed, scan_bytes, st)) return rc;
+    launch_union(b.keys2.as<uint64_t>(), b.vals2.as<uint32_t>(), 3 * n, ms_collapsed_key(n_verts), root);
+    HIP_TRY(hipGetLastError());
+    launch_flatten(root, flag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rocprim::exclusive_scan(b.temp.p, scan_bytes, flag, scan, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
+    ms_number_kernel<DOUBLED, PAIRS><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, DOUBLED ? info : root, scan, flag, group.as<int32_t>(),
+                                                                 PAIRS ? skey->as<uint32_t>() : nullptr, PAIRS ? sval->as<uint32_t>() : nullptr, n_groups);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- the segmented Float64 sum ---------------------------------------------------------------------------------------------
 constexpr int MS_BLOCK = 256;   // sorted items per block of the Float64 sums (the header's definition)
 
@@ -406,6 +455,30 @@ __global__ void __launch_bounds__(256) ms_combine_kernel(const int64_t* __restri
         for (int q = 0; q < NSUM; ++q) sums[s * NSUM + q] = v[q];
         if (n_items) n_items[s * item_stride] = end - first;
     }
+}
+
+// The Float64 table of shells and orient on `st`: the stable radix sort of the pairs ms_number_kernel left (skey = group, sval =
+// triangle, n of them, the nvalid real ones in front) into skey2 / sval2, ms_segment_kernel<NCNT>, the tool's terms
+// (launch_sum(blocks): its kernel around ms_block_sum<NSUM>, over skey2 / sval2 into partial) and ms_combine_kernel<NSUM> with
+// the groups' lengths in column count_col of counts.  temp is sized for the sort and for extra_temp bytes, what the caller runs
+// behind this on the same buffer; seg [n_groups + 1], partial [blocks + n_groups][NSUM], sums and counts are the caller's.
+template <int NCNT, int NSUM, class Sum>
+int ms_sum_by_group(DevBuf& temp, size_t extra_temp, int64_t n, int64_t nvalid, int64_t n_groups, uint32_t* skey, uint32_t* skey2,
+                    uint32_t* sval, uint32_t* sval2, int64_t* seg, const double* partial, double* sums, int64_t* counts, int count_col,
+                    Sum launch_sum, hipStream_t st)
+{
+    size_t tb = 0;
+    const unsigned sbits = ms_bits((uint64_t)n_groups);
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
+    ENSURE(temp, std::max<size_t>(std::max(tb, extra_temp), 16));
+    HIP_TRY(rocprim::radix_sort_pairs(temp.p, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
+    ms_segment_kernel<NCNT><<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, n_groups, seg, counts);
+    HIP_TRY(hipGetLastError());
+    launch_sum((unsigned)((nvalid + MS_BLOCK - 1) / MS_BLOCK));
+    HIP_TRY(hipGetLastError());
+    ms_combine_kernel<NSUM><<<(unsigned)((n_groups + 3) / 4), 256, 0, st>>>(seg, n_groups, partial, sums, counts + count_col, NCNT);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---- the loop ordering ------------------------------------------------------------------------------------------------------

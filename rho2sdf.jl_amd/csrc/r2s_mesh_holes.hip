@@ -319,15 +319,9 @@ struct HoleSizes {
 int holes_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, bool fill, int64_t max_edges, hipStream_t st,
                HoleWork& w, HoleSizes& out)
 {
-    uint64_t h_small[MH_SMALL] = {};
-    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
-    ENSURE(w.small, sizeof h_small);
+    uint64_t h_small[MH_SMALL];
+    if (const int rc = ms_begin_small(w.small, h_small, d_verts, n_verts, st)) return rc;
     uint64_t* small = w.small.as<uint64_t>();
-    HIP_TRY(hipMemcpyAsync(small, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
-    if (n_verts > 0) {
-        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, small);
-        HIP_TRY(hipGetLastError());
-    }
     const int64_t nh = 3 * n;
     const uint64_t ckey = ms_collapsed_key(n_verts);
     size_t tb = 0, sb = 0, sb2 = 0;
@@ -461,11 +455,6 @@ int holes_apply(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
     return 0;
 }
 
-struct Span {
-    const void* p;
-    size_t bytes;
-};
-
 // the checks that need no device; *fill: the fill was asked for
 int holes_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tris, const void* tris_out, const void* verts_out,
                int64_t vert_capacity, int64_t tri_capacity, const int64_t* n_rims, const int64_t* n_edges, const int64_t* n_verts_out,
@@ -483,9 +472,9 @@ int holes_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_t
     const Span out[2] = {{tris_out, tri_bytes(tri_capacity)}, {verts_out, vert_bytes(vert_capacity)}};
     for (const auto& i : in) {
         for (const auto& o : out)
-            if (overlaps(o.p, o.bytes, i.p, i.bytes)) return fail(R2S_ERR_ARG, "mesh_holes: an output overlaps an input");
+            if (overlaps(o, i)) return fail(R2S_ERR_ARG, "mesh_holes: an output overlaps an input");
         for (int k = 0; k < n_tables; ++k)
-            if (overlaps(tables[k].p, tables[k].bytes, i.p, i.bytes)) return fail(R2S_ERR_ARG, "mesh_holes: an output overlaps an input");
+            if (overlaps(tables[k], i)) return fail(R2S_ERR_ARG, "mesh_holes: an output overlaps an input");
     }
     return 0;
 }
@@ -498,12 +487,48 @@ int table_args(const char* who, const void* start, const void* counts, const voi
     return 0;
 }
 
-void holes_return(const HoleSizes& s, int64_t* n_rims, int64_t* n_edges, int64_t* n_verts_out, int64_t* n_tris_out, double ref_point[3],
-                  int64_t totals[8])
+// where a device caller wants the tables and the room it has for them (a host caller: none)
+struct HoleDevTables {
+    int64_t *start = nullptr, *counts = nullptr;
+    double* sums = nullptr;
+    int64_t rim_capacity = 0;
+    int32_t* rim_edge = nullptr;
+    int64_t edge_capacity = 0;
+};
+
+// One call for both kinds of caller: the core, the fill (the vertices when vert_capacity holds n_verts_out of them, the
+// triangles when tri_capacity holds n_tris_out), then the tables and the scalars.  A host caller's tables are kept whole for
+// r2s_last_mesh_holes; a device caller gets the three per-rim tables when rim_capacity holds all rims and rim_edge when
+// edge_capacity holds all edges.
+int holes_run(MeshCall<HoleWork>& c, int64_t n_verts, int64_t n_tris, int64_t max_edges, const HoleDevTables& d, bool fill, int32_t* tris_out,
+              float* verts_out, int64_t vert_capacity, int64_t tri_capacity, int64_t* n_rims, int64_t* n_edges, int64_t* n_verts_out,
+              int64_t* n_tris_out, double ref_point[3], int64_t totals[8])
 {
+    int rc = c.open();
+    if (rc) return rc;
+    HoleWork& w = c.work();
+    HoleTables tab;
+    HoleSizes s;
+    if ((rc = holes_core(c.d_verts(), n_verts, c.d_tris(), n_tris, fill, max_edges, c.stream(), w, s))) return rc;
+    const bool vroom = fill && vert_capacity >= s.n_verts_out, troom = fill && tri_capacity >= s.n_tris_out;
+    float* d_verts_out = nullptr;
+    int32_t* d_tris_out = nullptr;
+    if (vroom && (rc = c.staged(w.verts_out, verts_out, vert_bytes(std::max<int64_t>(s.n_verts_out, 1)), d_verts_out))) return rc;
+    if (troom && (rc = c.staged(w.tris_out, tris_out, tri_bytes(std::max<int64_t>(s.n_tris_out, 1)), d_tris_out))) return rc;
+    if ((vroom || troom) && (rc = holes_apply(c.d_verts(), n_verts, c.d_tris(), n_tris, s, c.stream(), w, d_tris_out, d_verts_out))) return rc;
+    const size_t nr = (size_t)s.n_rims;
+    const bool rims_fit = d.rim_capacity >= s.n_rims, edges_fit = d.edge_capacity >= s.n_edges;
+    if ((rc = c.table(tab.start, d.start, rims_fit, w.start, nr ? nr + 1 : 0)) ||
+        (rc = c.table(tab.counts, d.counts, rims_fit, w.counts, nr * MH_NCNT)) || (rc = c.table(tab.sums, d.sums, rims_fit, w.sums, nr * MH_NSUM)) ||
+        (rc = c.table(tab.rim_edge, d.rim_edge, edges_fit, w.rim_edge, nr ? (size_t)s.n_edges : 0)) ||
+        (rc = c.deliver(vroom ? verts_out : nullptr, d_verts_out, vert_bytes(s.n_verts_out))) ||
+        (rc = c.deliver(troom ? tris_out : nullptr, d_tris_out, tri_bytes(s.n_tris_out))) || (rc = c.finish()))
+        return rc;
+    if (c.is_host()) g_last_holes = std::move(tab);
     *n_rims = s.n_rims, *n_edges = s.n_edges, *n_verts_out = s.n_verts_out, *n_tris_out = s.n_tris_out;
     std::memcpy(ref_point, s.r, sizeof s.r);
     std::memcpy(totals, s.totals, sizeof s.totals);
+    return 0;
 }
 
 }  // namespace
@@ -515,38 +540,12 @@ int r2s_mesh_holes(const float* verts, int64_t n_verts, const int32_t* tris, int
                    int64_t* n_verts_out, int64_t* n_tris_out, double ref_point[3], int64_t totals[8])
 {
     bool fill = false;
-    int rc = holes_args(verts, n_verts, tris, n_tris, tris_out, verts_out, vert_capacity, tri_capacity, n_rims, n_edges, n_verts_out,
-                        n_tris_out, ref_point, totals, nullptr, 0, &fill);
-    if (rc) return rc;
-    if ((rc = check_mesh_host("mesh_holes", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_holes_work.mu);
-    HoleWork* w = g_holes_work.current(rc);
-    if (rc) return rc;
-    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
-    HoleSizes s;
-    if ((rc = holes_core(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, fill, max_edges, nullptr, *w, s))) return rc;
-    const bool vroom = fill && vert_capacity >= s.n_verts_out, troom = fill && tri_capacity >= s.n_tris_out;
-    if (vroom) ENSURE(w->verts_out, vert_bytes(std::max<int64_t>(s.n_verts_out, 1)));
-    if (troom) ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(s.n_tris_out, 1)));
-    if ((vroom || troom) && (rc = holes_apply(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, s, nullptr, *w,
-                                              troom ? w->tris_out.as<int32_t>() : nullptr, vroom ? w->verts_out.as<float>() : nullptr)))
+    if (const int rc = holes_args(verts, n_verts, tris, n_tris, tris_out, verts_out, vert_capacity, tri_capacity, n_rims, n_edges, n_verts_out,
+                                  n_tris_out, ref_point, totals, nullptr, 0, &fill))
         return rc;
-    HoleTables tab;
-    if (s.n_rims > 0) {
-        tab.start.resize((size_t)s.n_rims + 1);
-        tab.counts.resize((size_t)s.n_rims * MH_NCNT);
-        tab.sums.resize((size_t)s.n_rims * MH_NSUM);
-        tab.rim_edge.resize((size_t)s.n_edges);
-        HIP_TRY(hipMemcpy(tab.start.data(), w->start.p, sizeof(int64_t) * tab.start.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.sums.data(), w->sums.p, sizeof(double) * tab.sums.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.rim_edge.data(), w->rim_edge.p, sizeof(int32_t) * tab.rim_edge.size(), hipMemcpyDeviceToHost));
-    }
-    if (vroom && s.n_verts_out > 0) HIP_TRY(hipMemcpy(verts_out, w->verts_out.p, vert_bytes(s.n_verts_out), hipMemcpyDeviceToHost));
-    if (troom && s.n_tris_out > 0) HIP_TRY(hipMemcpy(tris_out, w->tris_out.p, tri_bytes(s.n_tris_out), hipMemcpyDeviceToHost));
-    g_last_holes = std::move(tab);
-    holes_return(s, n_rims, n_edges, n_verts_out, n_tris_out, ref_point, totals);
-    return 0;
+    MeshCall<HoleWork> call("mesh_holes", g_holes_work, verts, n_verts, tris, n_tris, device);
+    return holes_run(call, n_verts, n_tris, max_edges, {}, fill, tris_out, verts_out, vert_capacity, tri_capacity, n_rims, n_edges, n_verts_out,
+                     n_tris_out, ref_point, totals);
 }
 
 int r2s_last_mesh_holes(int64_t* rim_start_out, int64_t* counts_out, double* sums_out, int64_t rim_capacity, int32_t* rim_edge_out,
@@ -556,16 +555,11 @@ int r2s_last_mesh_holes(int64_t* rim_start_out, int64_t* counts_out, double* sum
     const int rc = table_args("last_mesh_holes", rim_start_out, counts_out, sums_out, rim_capacity, rim_edge_out, edge_capacity);
     if (rc) return rc;
     const HoleTables& t = g_last_holes;
-    const int64_t nr = (int64_t)(t.counts.size() / MH_NCNT), nb = (int64_t)t.rim_edge.size();
-    const int64_t mr = std::min(rim_capacity, nr), mb = std::min(edge_capacity, nb);
-    *n_rims = nr;
-    *n_edges = nb;
-    if (mr > 0) {
-        std::memcpy(rim_start_out, t.start.data(), sizeof(int64_t) * (size_t)(mr + 1));
-        std::memcpy(counts_out, t.counts.data(), sizeof(int64_t) * MH_NCNT * (size_t)mr);
-        std::memcpy(sums_out, t.sums.data(), sizeof(double) * MH_NSUM * (size_t)mr);
-    }
-    if (mb > 0) std::memcpy(rim_edge_out, t.rim_edge.data(), sizeof(int32_t) * (size_t)mb);
+    const int64_t nr = *n_rims = (int64_t)(t.counts.size() / MH_NCNT), nb = *n_edges = (int64_t)t.rim_edge.size();
+    const int64_t mr = copy_rows(counts_out, t.counts, MH_NCNT, rim_capacity, nr);
+    copy_rows(sums_out, t.sums, MH_NSUM, rim_capacity, nr);
+    if (mr > 0) copy_rows(rim_start_out, t.start, 1, mr + 1, nr + 1);   // (the end of the last rim copied with it)
+    copy_rows(rim_edge_out, t.rim_edge, 1, edge_capacity, nb);
     return 0;
 }
 
@@ -584,28 +578,9 @@ int r2s_mesh_holes_dev(const float* d_verts, int64_t n_verts, const int32_t* d_t
     if ((rc = holes_args(d_verts, n_verts, d_tris, n_tris, d_tris_out, d_verts_out, vert_capacity, tri_capacity, n_rims, n_edges, n_verts_out,
                          n_tris_out, ref_point, totals, tables, rim_capacity > 0 || edge_capacity > 0 ? 4 : 0, &fill)))
         return rc;
-    if ((rc = check_device(0))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_holes_work.mu);
-    HoleWork* w = g_holes_work.current(rc);
-    if (rc) return rc;
-    if ((rc = check_mesh_dev("mesh_holes", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
-    HoleSizes s;
-    if ((rc = holes_core(d_verts, n_verts, d_tris, n_tris, fill, max_edges, st, *w, s))) return rc;
-    if (s.n_rims > 0 && rim_capacity >= s.n_rims) {
-        HIP_TRY(hipMemcpyAsync(d_rim_start, w->start.p, sizeof(int64_t) * (size_t)(s.n_rims + 1), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MH_NCNT * (size_t)s.n_rims, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_sums, w->sums.p, sizeof(double) * MH_NSUM * (size_t)s.n_rims, hipMemcpyDeviceToDevice, st));
-    }
-    if (s.n_edges > 0 && edge_capacity >= s.n_edges)
-        HIP_TRY(hipMemcpyAsync(d_rim_edge, w->rim_edge.p, sizeof(int32_t) * (size_t)s.n_edges, hipMemcpyDeviceToDevice, st));
-    const bool vroom = fill && vert_capacity >= s.n_verts_out, troom = fill && tri_capacity >= s.n_tris_out;
-    if ((vroom || troom) &&
-        (rc = holes_apply(d_verts, n_verts, d_tris, n_tris, s, st, *w, troom ? d_tris_out : nullptr, vroom ? d_verts_out : nullptr)))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    holes_return(s, n_rims, n_edges, n_verts_out, n_tris_out, ref_point, totals);
-    return 0;
+    MeshCall<HoleWork> call("mesh_holes", g_holes_work, d_verts, n_verts, d_tris, n_tris, (hipStream_t)stream);
+    return holes_run(call, n_verts, n_tris, max_edges, {d_rim_start, d_counts, d_sums, rim_capacity, d_rim_edge, edge_capacity}, fill, d_tris_out,
+                     d_verts_out, vert_capacity, tri_capacity, n_rims, n_edges, n_verts_out, n_tris_out, ref_point, totals);
 }
 
 }  // extern "C"

@@ -331,26 +331,17 @@ int nesting_core(const MiTree* index, const float* d_verts, int64_t n_verts, con
     HIP_TRY(hipMemsetAsync(small, 0, sizeof h_small, st));
     const int64_t nh = 3 * n;
     const uint64_t ckey = ms_collapsed_key(n_verts);
-    ENSURE(w.parent, sizeof(uint32_t) * (size_t)n);
-    ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
-    ENSURE(w.num, sizeof(int32_t) * (size_t)n);
-    ENSURE(w.patch, sizeof(int32_t) * (size_t)n);
-    uint32_t* parent = w.parent.as<uint32_t>();
-    int32_t *rflag = w.rflag.as<int32_t>(), *num = w.num.as<int32_t>(), *patch = w.patch.as<int32_t>();
-    size_t scan_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, rflag, num, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
-    int rc = ms_sort_half_edges<1, false>(w, d_tris, n, n_verts, parent, nullptr, (uint64_t*)small + MN_COLLAPSED, scan_bytes, st);
+    int rc = ms_group_triangles<1, false, false, false>(
+        w, d_tris, n, n_verts, w.parent, nullptr, nullptr, w.rflag, w.num, w.patch, nullptr, nullptr, (uint64_t*)small + MN_COLLAPSED,
+        (uint64_t*)small + MN_NPATCHES,
+        [&](const uint64_t* keys2, const uint32_t* vals2, int64_t nhe, uint64_t ck, uint32_t* parent) {
+            mn_union_kernel<<<ms_blocks(nhe), 256, 0, st>>>(keys2, vals2, nhe, ck, parent);
+        },
+        [&](uint32_t* parent, int32_t* flag) { ms_flatten_kernel<true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, flag); }, st);
     if (rc) return rc;
     const uint64_t* hkeys = w.keys2.as<uint64_t>();
     const uint32_t* hvals = w.vals2.as<uint32_t>();
-    mn_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(hkeys, hvals, nh, ckey, parent);
-    HIP_TRY(hipGetLastError());
-    ms_flatten_kernel<true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, rflag);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(rocprim::exclusive_scan(w.temp.p, scan_bytes, rflag, num, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
-    ms_number_kernel<false, false><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, num, rflag, patch, nullptr, nullptr,
-                                                               (uint64_t*)small + MN_NPATCHES);
-    HIP_TRY(hipGetLastError());
+    int32_t *rflag = w.rflag.as<int32_t>(), *patch = w.patch.as<int32_t>();
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t np = (int64_t)h_small[MN_NPATCHES], ncol = (int64_t)h_small[MN_COLLAPSED];
@@ -463,6 +454,35 @@ int nesting_args(const void* verts, int64_t n_verts, const void* tris, int64_t n
     return 0;
 }
 
+// One call for both kinds of caller: the core, then the triangles (with the rewind flag), patch_of_tri, the two tables and the
+// scalars.  The triangles go to a work buffer first for either caller: a refusal behind the traversal leaves tris_out untouched.
+// A host caller's tables are kept whole for r2s_last_mesh_nesting; a device caller gets each one when its capacity holds all of it.
+int nesting_run(MeshCall<NestWork>& c, const r2s_mesh_index* index, int64_t n_verts, int64_t n_tris, int32_t ray, int32_t flags,
+                int32_t* tris_out, int32_t* patch_of_tri, int64_t* d_counts, int64_t patch_capacity, int64_t* d_pairs, int64_t pair_capacity,
+                int64_t* n_patches, int64_t* n_pairs, int64_t totals[8])
+{
+    int rc = c.open([&] { return index ? index_on_current_device("mesh_nesting", index) : 0; });
+    if (rc) return rc;
+    NestWork& w = c.work();
+    NestTables tab;
+    const bool rewind = (flags & MN_FLAGS) != 0;
+    int64_t np = 0, npairs = 0, tot[8];
+    int32_t* d_tris_out = nullptr;
+    if (rewind && (rc = c.staged(w.tris_out, tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)), d_tris_out, c.STAGE_DEVICE_CALLER))) return rc;
+    if ((rc = nesting_core(index ? &index->tree : nullptr, c.d_verts(), n_verts, c.d_tris(), n_tris, ray, flags, c.stream(), w, d_tris_out, &np,
+                           &npairs, tot)) ||
+        (rc = c.table(tab.counts, d_counts, patch_capacity >= np, w.counts, (size_t)np * MN_NCNT)) ||
+        (rc = c.table(tab.pairs, d_pairs, pair_capacity >= npairs, w.pairs, (size_t)npairs)) ||
+        (rc = c.deliver(rewind ? tris_out : nullptr, d_tris_out, tri_bytes(n_tris))) ||
+        (rc = c.deliver(patch_of_tri, w.patch.p, sizeof(int32_t) * (size_t)n_tris)) || (rc = c.finish()))
+        return rc;
+    if (c.is_host()) g_last_nest = std::move(tab);
+    *n_patches = np;
+    if (n_pairs) *n_pairs = npairs;
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -470,32 +490,9 @@ extern "C" {
 int r2s_mesh_nesting(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, int32_t ray, int32_t flags, int32_t device,
                      int32_t* tris_out, int32_t* patch_of_tri_out, int64_t* n_patches, int64_t totals[8])
 {
-    int rc = nesting_args(verts, n_verts, tris, n_tris, ray, flags, tris_out, n_patches, totals);
-    if (rc) return rc;
-    if ((rc = check_mesh_host("mesh_nesting", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_nest_work.mu);
-    NestWork* w = g_nest_work.current(rc);
-    if (rc) return rc;
-    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
-    const bool rewind = (flags & MN_FLAGS) != 0;
-    if (rewind) ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)));
-    int64_t np = 0, npairs = 0, tot[8];
-    if ((rc = nesting_core(nullptr, w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, ray, flags, nullptr, *w,
-                           rewind ? w->tris_out.as<int32_t>() : nullptr, &np, &npairs, tot)))
-        return rc;
-    NestTables tab;
-    tab.counts.resize((size_t)np * MN_NCNT);
-    tab.pairs.resize((size_t)npairs);
-    if (np > 0) HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
-    if (npairs > 0) HIP_TRY(hipMemcpy(tab.pairs.data(), w->pairs.p, sizeof(int64_t) * tab.pairs.size(), hipMemcpyDeviceToHost));
-    if (n_tris > 0) {
-        if (rewind) HIP_TRY(hipMemcpy(tris_out, w->tris_out.p, tri_bytes(n_tris), hipMemcpyDeviceToHost));
-        if (patch_of_tri_out) HIP_TRY(hipMemcpy(patch_of_tri_out, w->patch.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToHost));
-    }
-    g_last_nest = std::move(tab);
-    *n_patches = np;
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (const int rc = nesting_args(verts, n_verts, tris, n_tris, ray, flags, tris_out, n_patches, totals)) return rc;
+    MeshCall<NestWork> call("mesh_nesting", g_nest_work, verts, n_verts, tris, n_tris, device);
+    return nesting_run(call, nullptr, n_verts, n_tris, ray, flags, tris_out, patch_of_tri_out, nullptr, 0, nullptr, 0, n_patches, nullptr, totals);
 }
 
 int r2s_last_mesh_nesting(int64_t* counts_out, int64_t capacity, int64_t* pairs_out, int64_t pair_capacity, int64_t* n_patches,
@@ -503,11 +500,9 @@ int r2s_last_mesh_nesting(int64_t* counts_out, int64_t capacity, int64_t* pairs_
 {
     if (!n_patches || !n_pairs || capacity < 0 || pair_capacity < 0 || (capacity > 0 && !counts_out) || (pair_capacity > 0 && !pairs_out))
         return fail(R2S_ERR_ARG, "last_mesh_nesting: null output or negative capacity");
-    const int64_t n = (int64_t)(g_last_nest.counts.size() / MN_NCNT), m = (int64_t)g_last_nest.pairs.size();
-    *n_patches = n, *n_pairs = m;
-    const int64_t cn = std::min(capacity, n), cm = std::min(pair_capacity, m);
-    if (cn > 0) std::memcpy(counts_out, g_last_nest.counts.data(), sizeof(int64_t) * MN_NCNT * (size_t)cn);
-    if (cm > 0) std::memcpy(pairs_out, g_last_nest.pairs.data(), sizeof(int64_t) * (size_t)cm);
+    *n_patches = (int64_t)(g_last_nest.counts.size() / MN_NCNT), *n_pairs = (int64_t)g_last_nest.pairs.size();
+    copy_rows(counts_out, g_last_nest.counts, MN_NCNT, capacity, *n_patches);
+    copy_rows(pairs_out, g_last_nest.pairs, 1, pair_capacity, *n_pairs);
     return 0;
 }
 
@@ -515,38 +510,15 @@ int r2s_mesh_nesting_dev(const r2s_mesh_index* index, const float* d_verts, int6
                          int32_t flags, int32_t* d_tris_out, int32_t* d_patch_of_tri, int64_t* d_counts, int64_t patch_capacity,
                          int64_t* d_pairs, int64_t pair_capacity, int64_t* n_patches, int64_t* n_pairs, int64_t totals[8], void* stream)
 {
-    int rc = nesting_args(d_verts, n_verts, d_tris, n_tris, ray, flags, d_tris_out, n_patches, totals);
-    if (rc) return rc;
+    if (const int rc = nesting_args(d_verts, n_verts, d_tris, n_tris, ray, flags, d_tris_out, n_patches, totals)) return rc;
     if (!n_pairs) return fail(R2S_ERR_ARG, "mesh_nesting: null n_pairs");
     if (patch_capacity < 0 || pair_capacity < 0 || (patch_capacity > 0 && !d_counts) || (pair_capacity > 0 && !d_pairs))
         return fail(R2S_ERR_ARG, "mesh_nesting: null tables or a negative capacity");
     if (index && index->tree.n_tris != n_tris)
         return fail(R2S_ERR_ARG, "mesh_nesting: the index holds %lld triangles, the mesh %lld", (long long)index->tree.n_tris, (long long)n_tris);
-    if ((rc = check_device(0)) || (index && (rc = index_on_current_device("mesh_nesting", index)))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_nest_work.mu);
-    NestWork* w = g_nest_work.current(rc);
-    if (rc) return rc;
-    if ((rc = check_mesh_dev("mesh_nesting", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
-    const bool rewind = (flags & MN_FLAGS) != 0;
-    // (the triangles go to a work buffer first: a refusal behind the traversal leaves d_tris_out untouched)
-    if (rewind) ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)));
-    int64_t np = 0, npairs = 0, tot[8];
-    if ((rc = nesting_core(index ? &index->tree : nullptr, d_verts, n_verts, d_tris, n_tris, ray, flags, st, *w,
-                           rewind ? w->tris_out.as<int32_t>() : nullptr, &np, &npairs, tot)))
-        return rc;
-    if (n_tris > 0) {
-        if (rewind) HIP_TRY(hipMemcpyAsync(d_tris_out, w->tris_out.p, tri_bytes(n_tris), hipMemcpyDeviceToDevice, st));
-        if (d_patch_of_tri) HIP_TRY(hipMemcpyAsync(d_patch_of_tri, w->patch.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToDevice, st));
-    }
-    if (np > 0 && patch_capacity >= np)
-        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MN_NCNT * (size_t)np, hipMemcpyDeviceToDevice, st));
-    if (npairs > 0 && pair_capacity >= npairs)
-        HIP_TRY(hipMemcpyAsync(d_pairs, w->pairs.p, sizeof(int64_t) * (size_t)npairs, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_patches = np, *n_pairs = npairs;
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    MeshCall<NestWork> call("mesh_nesting", g_nest_work, d_verts, n_verts, d_tris, n_tris, (hipStream_t)stream);
+    return nesting_run(call, index, n_verts, n_tris, ray, flags, d_tris_out, d_patch_of_tri, d_counts, patch_capacity, d_pairs, pair_capacity,
+                       n_patches, n_pairs, totals);
 }
 
 }  // extern "C"

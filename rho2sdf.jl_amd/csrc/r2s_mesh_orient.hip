@@ -237,48 +237,29 @@ thread_local OrientTables g_last_orient;
 int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, int32_t flags, hipStream_t st, OrientWork& w,
                 int32_t* d_tris_out, int64_t* n_patches, double ref_point[3], int64_t totals[8])
 {
-    uint64_t h_small[MO_SMALL] = {};
-    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
-    ENSURE(w.small, sizeof h_small);
+    uint64_t h_small[MO_SMALL];
+    int rc = ms_begin_small(w.small, h_small, d_verts, n_verts, st);
+    if (rc) return rc;
     uint64_t* small = w.small.as<uint64_t>();
-    HIP_TRY(hipMemcpyAsync(small, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
-    if (n_verts > 0) {
-        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, small);
-        HIP_TRY(hipGetLastError());
-    }
     const int64_t nh = 3 * n;
     const uint64_t ckey = ms_collapsed_key(n_verts);
-    size_t scan_bytes = 0;
     if (n > 0) {
-        ENSURE(w.parent, sizeof(uint32_t) * 2 * (size_t)n);
         ENSURE(w.info, sizeof(uint32_t) * (size_t)n);
-        ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
-        ENSURE(w.num, sizeof(int32_t) * (size_t)n);
-        ENSURE(w.patch, sizeof(int32_t) * (size_t)n);
         ENSURE(w.flip, sizeof(int32_t) * (size_t)n);
-        ENSURE(w.skey, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.skey2, sizeof(uint32_t) * (size_t)n);
-        ENSURE(w.sval, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.sval2, sizeof(uint32_t) * (size_t)n);
-        uint32_t* parent = w.parent.as<uint32_t>();
-        HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n,
-                                        rocprim::plus<int32_t>(), st));
-        int rc = ms_sort_half_edges<2, false>(w, d_tris, n, n_verts, parent, nullptr, small + MO_COLLAPSED, scan_bytes, st);
+        uint32_t* info = w.info.as<uint32_t>();
+        rc = ms_group_triangles<2, false, true, true>(
+            w, d_tris, n, n_verts, w.parent, nullptr, info, w.rflag, w.num, w.patch, &w.skey, &w.sval, small + MO_COLLAPSED, small + MO_NPATCHES,
+            [&](const uint64_t* keys2, const uint32_t* vals2, int64_t nhe, uint64_t ck, uint32_t* parent) {
+                mo_union_kernel<<<ms_blocks(nhe), 256, 0, st>>>(keys2, vals2, nhe, ck, parent);
+            },
+            [&](uint32_t* parent, int32_t* rflag) { mo_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, info, rflag); }, st);
         if (rc) return rc;
-        mo_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, parent);
-        HIP_TRY(hipGetLastError());
-        mo_flatten_kernel<<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.info.as<uint32_t>(), w.rflag.as<int32_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(rocprim::exclusive_scan(w.temp.p, scan_bytes, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n,
-                                        rocprim::plus<int32_t>(), st));
-        ms_number_kernel<true, true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, w.info.as<uint32_t>(), w.num.as<int32_t>(), w.rflag.as<int32_t>(),
-                                                                 w.patch.as<int32_t>(), w.skey.as<uint32_t>(), w.sval.as<uint32_t>(),
-                                                                 small + MO_NPATCHES);
-        HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    double r[3];
+    double* r = ref_point;
     ms_ref_point(h_small, n_verts, r);
     const int64_t np = (int64_t)h_small[MO_NPATCHES], ncol = (int64_t)h_small[MO_COLLAPSED], nvalid = n - ncol;
     if (n > 0) {
@@ -293,20 +274,16 @@ int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         const int32_t* patch = w.patch.as<int32_t>();
         if (np > 0) {
             HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * MO_NCNT * (size_t)np, st));
-            uint32_t *skey = w.skey.as<uint32_t>(), *skey2 = w.skey2.as<uint32_t>(), *sval = w.sval.as<uint32_t>(), *sval2 = w.sval2.as<uint32_t>();
-            size_t tb = 0;
-            const unsigned sbits = ms_bits((uint64_t)np);
-            HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
-            ENSURE(w.temp, std::max<size_t>(tb, 16));
-            HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
-            ms_segment_kernel<MO_NCNT><<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, np, w.seg.as<int64_t>(), counts);
-            HIP_TRY(hipGetLastError());
-            mo_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, info, skey2, sval2, nvalid, r[0], r[1], r[2],
-                                                              w.partial.as<double>());
-            HIP_TRY(hipGetLastError());
-            ms_combine_kernel<1><<<(unsigned)((np + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), np, w.partial.as<double>(), w.vol.as<double>(),
-                                                                        counts + MO_NTRIS, MO_NCNT);
-            HIP_TRY(hipGetLastError());
+            uint32_t *skey2 = w.skey2.as<uint32_t>(), *sval2 = w.sval2.as<uint32_t>();
+            rc = ms_sum_by_group<MO_NCNT, 1>(
+                w.temp, 0, n, nvalid, np, w.skey.as<uint32_t>(), skey2, w.sval.as<uint32_t>(), sval2, w.seg.as<int64_t>(),
+                w.partial.as<double>(), w.vol.as<double>(), counts, MO_NTRIS,
+                [&](unsigned blocks) {
+                    mo_sum_kernel<<<blocks, MS_BLOCK, 0, st>>>(d_verts, d_tris, info, skey2, sval2, nvalid, r[0], r[1], r[2],
+                                                               w.partial.as<double>());
+                },
+                st);
+            if (rc) return rc;
             mo_parity_kernel<<<ms_blocks(n), 256, 0, st>>>(n, info, patch, counts);
             HIP_TRY(hipGetLastError());
             // (keys2 / vals2 still hold the sorted half-edges)
@@ -325,7 +302,6 @@ int orient_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         HIP_TRY(hipStreamSynchronize(st));
     }
     *n_patches = np;
-    for (int k = 0; k < 3; ++k) ref_point[k] = r[k];
     totals[0] = np, totals[1] = n, totals[2] = ncol;
     for (int k = 0; k < 5; ++k) totals[3 + k] = np > 0 ? (int64_t)h_small[MO_TOT + k] : 0;
     return 0;
@@ -343,6 +319,34 @@ int orient_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_
     return 0;
 }
 
+// One call for both kinds of caller: the core, then the triangles, flip, patch_of_tri, the tables and the scalars.  A host
+// caller's tables are kept whole for r2s_last_mesh_orient; a device caller gets them when patch_capacity holds all of them.
+int orient_run(MeshCall<OrientWork>& c, int64_t n_verts, int64_t n_tris, int32_t flags, int32_t* tris_out, int32_t* flip_out,
+               int32_t* patch_of_tri, int64_t* d_counts, double* d_volume, int64_t patch_capacity, int64_t* n_patches, double ref_point[3],
+               int64_t totals[8])
+{
+    int rc = c.open();
+    if (rc) return rc;
+    OrientWork& w = c.work();
+    OrientTables tab;
+    int64_t np = 0, tot[8];
+    double r[3];
+    int32_t* d_tris_out = nullptr;
+    if ((rc = c.staged(w.tris_out, tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)), d_tris_out)) ||
+        (rc = orient_core(c.d_verts(), n_verts, c.d_tris(), n_tris, flags, c.stream(), w, d_tris_out, &np, r, tot)))
+        return rc;
+    const bool fits = patch_capacity >= np;
+    if ((rc = c.table(tab.counts, d_counts, fits, w.counts, (size_t)np * MO_NCNT)) || (rc = c.table(tab.volume, d_volume, fits, w.vol, (size_t)np)) ||
+        (rc = c.deliver(tris_out, d_tris_out, tri_bytes(n_tris))) || (rc = c.deliver(flip_out, w.flip.p, sizeof(int32_t) * (size_t)n_tris)) ||
+        (rc = c.deliver(patch_of_tri, w.patch.p, sizeof(int32_t) * (size_t)n_tris)) || (rc = c.finish()))
+        return rc;
+    if (c.is_host()) g_last_orient = std::move(tab);
+    *n_patches = np;
+    std::memcpy(ref_point, r, sizeof r);
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -351,48 +355,18 @@ int r2s_mesh_orient(const float* verts, int64_t n_verts, const int32_t* tris, in
                     int32_t* tris_out, int32_t* flip_out, int32_t* patch_of_tri_out, int64_t* n_patches, double ref_point[3],
                     int64_t totals[8])
 {
-    int rc = orient_args(verts, n_verts, tris, n_tris, flags, tris_out, n_patches, ref_point, totals);
-    if (rc) return rc;
-    if ((rc = check_mesh_host("mesh_orient", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_orient_work.mu);
-    OrientWork* w = g_orient_work.current(rc);
-    if (rc) return rc;
-    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
-    ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(n_tris, 1)));
-    int64_t np = 0, tot[8];
-    double r[3];
-    if ((rc = orient_core(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, flags, nullptr, *w, w->tris_out.as<int32_t>(), &np, r,
-                          tot)))
-        return rc;
-    OrientTables tab;
-    tab.counts.resize((size_t)np * MO_NCNT);
-    tab.volume.resize((size_t)np);
-    if (np > 0) {
-        HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.volume.data(), w->vol.p, sizeof(double) * tab.volume.size(), hipMemcpyDeviceToHost));
-    }
-    if (n_tris > 0) {
-        HIP_TRY(hipMemcpy(tris_out, w->tris_out.p, tri_bytes(n_tris), hipMemcpyDeviceToHost));
-        if (flip_out) HIP_TRY(hipMemcpy(flip_out, w->flip.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToHost));
-        if (patch_of_tri_out) HIP_TRY(hipMemcpy(patch_of_tri_out, w->patch.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToHost));
-    }
-    g_last_orient = std::move(tab);
-    *n_patches = np;
-    std::memcpy(ref_point, r, sizeof r);
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (const int rc = orient_args(verts, n_verts, tris, n_tris, flags, tris_out, n_patches, ref_point, totals)) return rc;
+    MeshCall<OrientWork> call("mesh_orient", g_orient_work, verts, n_verts, tris, n_tris, device);
+    return orient_run(call, n_verts, n_tris, flags, tris_out, flip_out, patch_of_tri_out, nullptr, nullptr, 0, n_patches, ref_point, totals);
 }
 
 int r2s_last_mesh_orient(int64_t* counts_out, double* volume_out, int64_t capacity, int64_t* n_patches)
 {
     if (!n_patches || capacity < 0 || (capacity > 0 && (!counts_out || !volume_out)))
         return fail(R2S_ERR_ARG, "last_mesh_orient: null output or negative capacity");
-    const int64_t n = (int64_t)g_last_orient.volume.size(), m = std::min(capacity, n);
-    *n_patches = n;
-    if (m > 0) {
-        std::memcpy(counts_out, g_last_orient.counts.data(), sizeof(int64_t) * MO_NCNT * (size_t)m);
-        std::memcpy(volume_out, g_last_orient.volume.data(), sizeof(double) * (size_t)m);
-    }
+    const int64_t n = *n_patches = (int64_t)g_last_orient.volume.size();
+    copy_rows(counts_out, g_last_orient.counts, MO_NCNT, capacity, n);
+    copy_rows(volume_out, g_last_orient.volume, 1, capacity, n);
     return 0;
 }
 
@@ -400,32 +374,12 @@ int r2s_mesh_orient_dev(const float* d_verts, int64_t n_verts, const int32_t* d_
                         int32_t* d_flip_out, int32_t* d_patch_of_tri, int64_t* d_counts, double* d_volume, int64_t patch_capacity,
                         int64_t* n_patches, double ref_point[3], int64_t totals[8], void* stream)
 {
-    int rc = orient_args(d_verts, n_verts, d_tris, n_tris, flags, d_tris_out, n_patches, ref_point, totals);
-    if (rc) return rc;
+    if (const int rc = orient_args(d_verts, n_verts, d_tris, n_tris, flags, d_tris_out, n_patches, ref_point, totals)) return rc;
     if (patch_capacity < 0 || (patch_capacity > 0 && (!d_counts || !d_volume)))
         return fail(R2S_ERR_ARG, "mesh_orient: null tables or negative patch_capacity");
-    if ((rc = check_device(0))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_orient_work.mu);
-    OrientWork* w = g_orient_work.current(rc);
-    if (rc) return rc;
-    if ((rc = check_mesh_dev("mesh_orient", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
-    int64_t np = 0, tot[8];
-    double r[3];
-    if ((rc = orient_core(d_verts, n_verts, d_tris, n_tris, flags, st, *w, d_tris_out, &np, r, tot))) return rc;
-    if (n_tris > 0) {
-        if (d_flip_out) HIP_TRY(hipMemcpyAsync(d_flip_out, w->flip.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToDevice, st));
-        if (d_patch_of_tri) HIP_TRY(hipMemcpyAsync(d_patch_of_tri, w->patch.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToDevice, st));
-    }
-    if (np > 0 && patch_capacity >= np) {
-        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MO_NCNT * (size_t)np, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_volume, w->vol.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_patches = np;
-    std::memcpy(ref_point, r, sizeof r);
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    MeshCall<OrientWork> call("mesh_orient", g_orient_work, d_verts, n_verts, d_tris, n_tris, (hipStream_t)stream);
+    return orient_run(call, n_verts, n_tris, flags, d_tris_out, d_flip_out, d_patch_of_tri, d_counts, d_volume, patch_capacity, n_patches,
+                      ref_point, totals);
 }
 
 }  // extern "C"

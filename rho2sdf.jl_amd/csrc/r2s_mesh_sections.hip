@@ -380,15 +380,9 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
                   int64_t n_levels, hipStream_t st, SectionWork& w, int64_t* n_contours, int64_t* n_segments, double ref_point[3],
                   int64_t totals[8])
 {
-    uint64_t h_small[SX_SMALL] = {};
-    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
-    ENSURE(w.small, sizeof h_small);
+    uint64_t h_small[SX_SMALL];
+    if (const int rc = ms_begin_small(w.small, h_small, d_verts, n_verts, st)) return rc;
     uint64_t* small = w.small.as<uint64_t>();
-    HIP_TRY(hipMemcpyAsync(small, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
-    if (n_verts > 0) {
-        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, small);
-        HIP_TRY(hipGetLastError());
-    }
     const int64_t nh = 3 * n;
     const int32_t nl = (int32_t)n_levels;
     const uint64_t ckey = ms_collapsed_key(n_verts);
@@ -422,7 +416,7 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (nseg > SX_MAX_SEGS) return fail(R2S_ERR_UNSUPPORTED, "mesh_sections: %lld segments exceed 2^31 - 1", (long long)nseg);
-    double r[3];
+    double* r = ref_point;
     ms_ref_point(h_small, n_verts, r);
     const int64_t ncol = (int64_t)h_small[SX_COLLAPSED];
     int64_t nc = 0;
@@ -511,9 +505,7 @@ int sections_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, 
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
-    *n_contours = nc;
-    *n_segments = nseg;
-    for (int k = 0; k < 3; ++k) ref_point[k] = r[k];
+    *n_contours = nc, *n_segments = nseg;
     totals[0] = nc, totals[1] = nseg, totals[2] = ncol;
     for (int k = 0; k < 5; ++k) totals[3 + k] = nseg > 0 ? (int64_t)h_small[SX_TOT + k] : 0;
     return 0;
@@ -552,6 +544,42 @@ int table_args(const void* start, const void* counts, const void* sums, int64_t 
     return 0;
 }
 
+// where a device caller wants the tables and the room it has for them (a host caller: none)
+struct SectionDevTables {
+    int64_t *start = nullptr, *counts = nullptr;
+    double* sums = nullptr;
+    int64_t contour_capacity = 0;
+    int32_t* seg_tri = nullptr;
+    double* points = nullptr;
+    int64_t segment_capacity = 0;
+};
+
+// One call for both kinds of caller: the core, then the five tables and the scalars.  A host caller's tables are kept whole for
+// r2s_last_mesh_sections; a device caller gets them when both capacities hold everything, else none.
+int sections_run(MeshCall<SectionWork>& c, int64_t n_verts, int64_t n_tris, const double normal[3], const double* levels, int64_t n_levels,
+                 const SectionDevTables& d, int64_t* n_contours, int64_t* n_segments, double ref_point[3], int64_t totals[8])
+{
+    int rc = c.open();
+    if (rc) return rc;
+    SectionWork& w = c.work();
+    SectionTables tab;
+    int64_t nc = 0, nseg = 0, tot[8];
+    double r[3];
+    if ((rc = sections_core(c.d_verts(), n_verts, c.d_tris(), n_tris, normal, levels, n_levels, c.stream(), w, &nc, &nseg, r, tot))) return rc;
+    const size_t n = (size_t)nc, m = nc ? (size_t)nseg : 0;
+    const bool fits = d.contour_capacity >= nc && d.segment_capacity >= nseg;
+    if ((rc = c.table(tab.start, d.start, fits, w.start, n ? n + 1 : 0)) || (rc = c.table(tab.counts, d.counts, fits, w.counts, n * SX_NCNT)) ||
+        (rc = c.table(tab.sums, d.sums, fits, w.sums, n * SX_NSUM)) || (rc = c.table(tab.seg_tri, d.seg_tri, fits, w.seg_tri, m)) ||
+        (rc = c.table(tab.points, d.points, fits, w.points, m * 6)) || (rc = c.finish()))
+        return rc;
+    if (c.is_host()) g_last_sections = std::move(tab);
+    *n_contours = nc;
+    *n_segments = nseg;
+    std::memcpy(ref_point, r, sizeof r);
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -559,37 +587,9 @@ extern "C" {
 int r2s_mesh_sections(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, const double normal[3], const double* levels,
                       int64_t n_levels, int32_t device, int64_t* n_contours, int64_t* n_segments, double ref_point[3], int64_t totals[8])
 {
-    int rc = sections_args(verts, n_verts, tris, n_tris, normal, levels, n_levels, n_contours, n_segments, ref_point, totals);
-    if (rc) return rc;
-    if ((rc = check_mesh_host("mesh_sections", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_section_work.mu);
-    SectionWork* w = g_section_work.current(rc);
-    if (rc) return rc;
-    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
-    int64_t nc = 0, nseg = 0, tot[8];
-    double r[3];
-    if ((rc = sections_core(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, normal, levels, n_levels, nullptr, *w, &nc, &nseg, r,
-                            tot)))
-        return rc;
-    SectionTables tab;
-    if (nc > 0) {
-        tab.start.resize((size_t)nc + 1);
-        tab.counts.resize((size_t)nc * SX_NCNT);
-        tab.sums.resize((size_t)nc * SX_NSUM);
-        tab.seg_tri.resize((size_t)nseg);
-        tab.points.resize((size_t)nseg * 6);
-        HIP_TRY(hipMemcpy(tab.start.data(), w->start.p, sizeof(int64_t) * tab.start.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.sums.data(), w->sums.p, sizeof(double) * tab.sums.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.seg_tri.data(), w->seg_tri.p, sizeof(int32_t) * tab.seg_tri.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.points.data(), w->points.p, sizeof(double) * tab.points.size(), hipMemcpyDeviceToHost));
-    }
-    g_last_sections = std::move(tab);
-    *n_contours = nc;
-    *n_segments = nseg;
-    std::memcpy(ref_point, r, sizeof r);
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (const int rc = sections_args(verts, n_verts, tris, n_tris, normal, levels, n_levels, n_contours, n_segments, ref_point, totals)) return rc;
+    MeshCall<SectionWork> call("mesh_sections", g_section_work, verts, n_verts, tris, n_tris, device);
+    return sections_run(call, n_verts, n_tris, normal, levels, n_levels, {}, n_contours, n_segments, ref_point, totals);
 }
 
 int r2s_last_mesh_sections(int64_t* contour_start_out, int64_t* counts_out, double* sums_out, int64_t contour_capacity, int32_t* seg_tri_out,
@@ -599,19 +599,12 @@ int r2s_last_mesh_sections(int64_t* contour_start_out, int64_t* counts_out, doub
     const int rc = table_args(contour_start_out, counts_out, sums_out, contour_capacity, seg_tri_out, seg_points_out, segment_capacity);
     if (rc) return rc;
     const SectionTables& t = g_last_sections;
-    const int64_t nc = (int64_t)(t.counts.size() / SX_NCNT), nseg = (int64_t)t.seg_tri.size();
-    const int64_t mc = std::min(contour_capacity, nc), ms = std::min(segment_capacity, nseg);
-    *n_contours = nc;
-    *n_segments = nseg;
-    if (mc > 0) {
-        std::memcpy(contour_start_out, t.start.data(), sizeof(int64_t) * (size_t)(mc + 1));
-        std::memcpy(counts_out, t.counts.data(), sizeof(int64_t) * SX_NCNT * (size_t)mc);
-        std::memcpy(sums_out, t.sums.data(), sizeof(double) * SX_NSUM * (size_t)mc);
-    }
-    if (ms > 0) {
-        std::memcpy(seg_tri_out, t.seg_tri.data(), sizeof(int32_t) * (size_t)ms);
-        std::memcpy(seg_points_out, t.points.data(), sizeof(double) * 6 * (size_t)ms);
-    }
+    const int64_t nc = *n_contours = (int64_t)(t.counts.size() / SX_NCNT), nseg = *n_segments = (int64_t)t.seg_tri.size();
+    const int64_t mc = copy_rows(counts_out, t.counts, SX_NCNT, contour_capacity, nc);
+    copy_rows(sums_out, t.sums, SX_NSUM, contour_capacity, nc);
+    if (mc > 0) copy_rows(contour_start_out, t.start, 1, mc + 1, nc + 1);   // (the end of the last contour copied with it)
+    copy_rows(seg_tri_out, t.seg_tri, 1, segment_capacity, nseg);
+    copy_rows(seg_points_out, t.points, 6, segment_capacity, nseg);
     return 0;
 }
 
@@ -621,30 +614,11 @@ int r2s_mesh_sections_dev(const float* d_verts, int64_t n_verts, const int32_t* 
                           int64_t* n_segments, double ref_point[3], int64_t totals[8], void* stream)
 {
     int rc = sections_args(d_verts, n_verts, d_tris, n_tris, normal, levels, n_levels, n_contours, n_segments, ref_point, totals);
-    if (rc) return rc;
-    if ((rc = table_args(d_contour_start, d_counts, d_sums, contour_capacity, d_seg_tri, d_seg_points, segment_capacity))) return rc;
-    if ((rc = check_device(0))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_section_work.mu);
-    SectionWork* w = g_section_work.current(rc);
-    if (rc) return rc;
-    if ((rc = check_mesh_dev("mesh_sections", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
-    int64_t nc = 0, nseg = 0, tot[8];
-    double r[3];
-    if ((rc = sections_core(d_verts, n_verts, d_tris, n_tris, normal, levels, n_levels, st, *w, &nc, &nseg, r, tot))) return rc;
-    if (nc > 0 && contour_capacity >= nc && segment_capacity >= nseg) {
-        HIP_TRY(hipMemcpyAsync(d_contour_start, w->start.p, sizeof(int64_t) * (size_t)(nc + 1), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * SX_NCNT * (size_t)nc, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_sums, w->sums.p, sizeof(double) * SX_NSUM * (size_t)nc, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_seg_tri, w->seg_tri.p, sizeof(int32_t) * (size_t)nseg, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_seg_points, w->points.p, sizeof(double) * 6 * (size_t)nseg, hipMemcpyDeviceToDevice, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_contours = nc;
-    *n_segments = nseg;
-    std::memcpy(ref_point, r, sizeof r);
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (rc || (rc = table_args(d_contour_start, d_counts, d_sums, contour_capacity, d_seg_tri, d_seg_points, segment_capacity))) return rc;
+    MeshCall<SectionWork> call("mesh_sections", g_section_work, d_verts, n_verts, d_tris, n_tris, (hipStream_t)stream);
+    return sections_run(call, n_verts, n_tris, normal, levels, n_levels,
+                        {d_contour_start, d_counts, d_sums, contour_capacity, d_seg_tri, d_seg_points, segment_capacity}, n_contours, n_segments,
+                        ref_point, totals);
 }
 
 }  // extern "C"

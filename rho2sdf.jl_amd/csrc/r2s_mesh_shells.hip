@@ -183,46 +183,29 @@ thread_local ShellTables g_last_shells;
 int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n, hipStream_t st, ShellWork& w, int64_t* n_shells,
                 double ref_point[3], int64_t totals[8])
 {
-    uint64_t h_small[MS_SMALL] = {};
-    h_small[0] = h_small[1] = h_small[2] = 0xffffffffull;
-    ENSURE(w.small, sizeof h_small);
+    uint64_t h_small[MS_SMALL];
+    int rc = ms_begin_small(w.small, h_small, d_verts, n_verts, st);
+    if (rc) return rc;
     uint64_t* small = w.small.as<uint64_t>();
-    HIP_TRY(hipMemcpyAsync(small, h_small, sizeof h_small, hipMemcpyHostToDevice, st));
-    if (n_verts > 0) {
-        ms_bounds_kernel<<<ms_blocks(n_verts), 256, 0, st>>>(d_verts, n_verts, small);
-        HIP_TRY(hipGetLastError());
-    }
     const int64_t nh = 3 * n;
     const uint64_t ckey = ms_collapsed_key(n_verts);
     if (n > 0) {
-        ENSURE(w.parent, sizeof(uint32_t) * (size_t)n);
-        ENSURE(w.rflag, sizeof(int32_t) * (size_t)n);
-        ENSURE(w.num, sizeof(int32_t) * (size_t)n);
-        ENSURE(w.shell, sizeof(int32_t) * (size_t)n);
-        ENSURE(w.skey, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.skey2, sizeof(uint32_t) * (size_t)n);
-        ENSURE(w.sval, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.sval2, sizeof(uint32_t) * (size_t)n);
         ENSURE(w.vflag, sizeof(int32_t) * (size_t)std::max<int64_t>(n_verts, 1));
         HIP_TRY(hipMemsetAsync(w.vflag.p, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(n_verts, 1), st));
-        uint32_t* parent = w.parent.as<uint32_t>();
-        size_t tb2 = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, tb2, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
-        int rc = ms_sort_half_edges<1, true>(w, d_tris, n, n_verts, parent, w.vflag.as<int32_t>(), small + MS_COLLAPSED, tb2, st);
+        rc = ms_group_triangles<1, true, false, true>(
+            w, d_tris, n, n_verts, w.parent, w.vflag.as<int32_t>(), nullptr, w.rflag, w.num, w.shell, &w.skey, &w.sval, small + MS_COLLAPSED,
+            small + MS_NSHELLS,
+            [&](const uint64_t* keys2, const uint32_t* vals2, int64_t nhe, uint64_t ck, uint32_t* parent) {
+                ms_union_kernel<<<ms_blocks(nhe), 256, 0, st>>>(keys2, vals2, nhe, ck, parent);
+            },
+            [&](uint32_t* parent, int32_t* rflag) { ms_flatten_kernel<true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, rflag); }, st);
         if (rc) return rc;
-        ms_union_kernel<<<ms_blocks(nh), 256, 0, st>>>(w.keys2.as<uint64_t>(), w.vals2.as<uint32_t>(), nh, ckey, parent);
-        HIP_TRY(hipGetLastError());
-        ms_flatten_kernel<true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.rflag.as<int32_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(rocprim::exclusive_scan(w.temp.p, tb2, w.rflag.as<int32_t>(), w.num.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
-        ms_number_kernel<false, true><<<ms_blocks(n), 256, 0, st>>>(d_tris, n, parent, w.num.as<int32_t>(), w.rflag.as<int32_t>(),
-                                                                  w.shell.as<int32_t>(), w.skey.as<uint32_t>(), w.sval.as<uint32_t>(),
-                                                                  small + MS_NSHELLS);
-        HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    double r[3];
+    double* r = ref_point;
     ms_ref_point(h_small, n_verts, r);
     const int64_t nsh = (int64_t)h_small[MS_NSHELLS], ncol = (int64_t)h_small[MS_COLLAPSED], nvalid = n - ncol;
     if (nsh > 0) {
@@ -233,21 +216,20 @@ int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         ENSURE(w.sums, sizeof(double) * MS_NSUM * (size_t)nsh);
         int64_t* counts = w.counts.as<int64_t>();
         HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * MS_NCNT * (size_t)nsh, st));
-        uint32_t *skey = w.skey.as<uint32_t>(), *skey2 = w.skey2.as<uint32_t>(), *sval = w.sval.as<uint32_t>(), *sval2 = w.sval2.as<uint32_t>();
-        size_t tb = 0, tb2 = 0;
-        const unsigned sbits = ms_bits((uint64_t)nsh), vbits = 32u + ms_bits((uint64_t)nsh);
+        uint32_t *skey2 = w.skey2.as<uint32_t>(), *sval2 = w.sval2.as<uint32_t>();
+        size_t tb2 = 0;
+        const unsigned vbits = 32u + ms_bits((uint64_t)nsh);
         uint64_t *keys = w.keys.as<uint64_t>(), *keys2 = w.keys2.as<uint64_t>();
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
+        // (the vertex-key sort below shares temp with the sort by shell)
         HIP_TRY(rocprim::radix_sort_keys(nullptr, tb2, keys, keys2, (size_t)nh, 0u, vbits, st));
-        ENSURE(w.temp, std::max<size_t>(std::max(tb, tb2), 16));
-        HIP_TRY(rocprim::radix_sort_pairs(w.temp.p, tb, skey, skey2, sval, sval2, (size_t)n, 0u, sbits, st));
-        ms_segment_kernel<MS_NCNT><<<ms_blocks(nvalid), 256, 0, st>>>(skey2, sval2, nvalid, nsh, w.seg.as<int64_t>(), counts);
-        HIP_TRY(hipGetLastError());
-        ms_sum_kernel<<<(unsigned)nblk, MS_BLOCK, 0, st>>>(d_verts, d_tris, skey2, sval2, nvalid, r[0], r[1], r[2], w.partial.as<double>());
-        HIP_TRY(hipGetLastError());
-        ms_combine_kernel<MS_NSUM><<<(unsigned)((nsh + 3) / 4), 256, 0, st>>>(w.seg.as<int64_t>(), nsh, w.partial.as<double>(), w.sums.as<double>(),
-                                                                           counts + 1, MS_NCNT);
-        HIP_TRY(hipGetLastError());
+        rc = ms_sum_by_group<MS_NCNT, MS_NSUM>(
+            w.temp, tb2, n, nvalid, nsh, w.skey.as<uint32_t>(), skey2, w.sval.as<uint32_t>(), sval2, w.seg.as<int64_t>(),
+            w.partial.as<double>(), w.sums.as<double>(), counts, 1,
+            [&](unsigned blocks) {
+                ms_sum_kernel<<<blocks, MS_BLOCK, 0, st>>>(d_verts, d_tris, skey2, sval2, nvalid, r[0], r[1], r[2], w.partial.as<double>());
+            },
+            st);
+        if (rc) return rc;
         // (keys2 / vals2 still hold the sorted half-edges)
         ms_edge_kernel<<<ms_blocks(nh), 256, 0, st>>>(keys2, w.vals2.as<uint32_t>(), nh, ckey, w.shell.as<int32_t>(), counts);
         HIP_TRY(hipGetLastError());
@@ -262,7 +244,6 @@ int shells_core(const float* d_verts, int64_t n_verts, const int32_t* d_tris, in
         HIP_TRY(hipStreamSynchronize(st));
     }
     *n_shells = nsh;
-    for (int k = 0; k < 3; ++k) ref_point[k] = r[k];
     totals[0] = nsh, totals[1] = n, totals[2] = ncol;
     for (int k = 0; k < 5; ++k) totals[3 + k] = nsh > 0 ? (int64_t)h_small[MS_TOT + k] : 0;
     return 0;
@@ -278,6 +259,30 @@ int shells_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_
     return 0;
 }
 
+// One call for both kinds of caller: the core, then shell_of_tri, the tables and the scalars.  A host caller's tables are kept
+// whole for r2s_last_mesh_shells; a device caller gets them when shell_capacity holds all of them, else none.
+int shells_run(MeshCall<ShellWork>& c, int64_t n_verts, int64_t n_tris, int32_t* shell_of_tri, int64_t* d_counts, double* d_sums,
+               int64_t shell_capacity, int64_t* n_shells, double ref_point[3], int64_t totals[8])
+{
+    int rc = c.open();
+    if (rc) return rc;
+    ShellWork& w = c.work();
+    ShellTables tab;
+    int64_t nsh = 0, tot[8];
+    double r[3];
+    if ((rc = shells_core(c.d_verts(), n_verts, c.d_tris(), n_tris, c.stream(), w, &nsh, r, tot))) return rc;
+    const bool fits = shell_capacity >= nsh;
+    if ((rc = c.table(tab.counts, d_counts, fits, w.counts, (size_t)nsh * MS_NCNT)) ||
+        (rc = c.table(tab.sums, d_sums, fits, w.sums, (size_t)nsh * MS_NSUM)) ||
+        (rc = c.deliver(shell_of_tri, w.shell.p, sizeof(int32_t) * (size_t)n_tris)) || (rc = c.finish()))
+        return rc;
+    if (c.is_host()) g_last_shells = std::move(tab);
+    *n_shells = nsh;
+    std::memcpy(ref_point, r, sizeof r);
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -285,41 +290,18 @@ extern "C" {
 int r2s_mesh_shells(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, int32_t device, int32_t* shell_of_tri_out,
                     int64_t* n_shells, double ref_point[3], int64_t totals[8])
 {
-    int rc = shells_args(verts, n_verts, tris, n_tris, n_shells, ref_point, totals);
-    if (rc) return rc;
-    if ((rc = check_mesh_host("mesh_shells", verts, n_verts, tris, n_tris)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_shell_work.mu);
-    ShellWork* w = g_shell_work.current(rc);
-    if (rc) return rc;
-    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, n_tris, false, nullptr))) return rc;
-    int64_t nsh = 0, tot[8];
-    double r[3];
-    if ((rc = shells_core(w->verts.as<float>(), n_verts, w->tris.as<int32_t>(), n_tris, nullptr, *w, &nsh, r, tot))) return rc;
-    ShellTables tab;
-    tab.counts.resize((size_t)nsh * MS_NCNT);
-    tab.sums.resize((size_t)nsh * MS_NSUM);
-    if (nsh > 0) {
-        HIP_TRY(hipMemcpy(tab.counts.data(), w->counts.p, sizeof(int64_t) * tab.counts.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tab.sums.data(), w->sums.p, sizeof(double) * tab.sums.size(), hipMemcpyDeviceToHost));
-    }
-    if (shell_of_tri_out && n_tris > 0) HIP_TRY(hipMemcpy(shell_of_tri_out, w->shell.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToHost));
-    g_last_shells = std::move(tab);
-    *n_shells = nsh;
-    std::memcpy(ref_point, r, sizeof r);
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (const int rc = shells_args(verts, n_verts, tris, n_tris, n_shells, ref_point, totals)) return rc;
+    MeshCall<ShellWork> call("mesh_shells", g_shell_work, verts, n_verts, tris, n_tris, device);
+    return shells_run(call, n_verts, n_tris, shell_of_tri_out, nullptr, nullptr, 0, n_shells, ref_point, totals);
 }
 
 int r2s_last_mesh_shells(int64_t* counts_out, double* sums_out, int64_t capacity, int64_t* n_shells)
 {
     if (!n_shells || capacity < 0 || (capacity > 0 && (!counts_out || !sums_out)))
         return fail(R2S_ERR_ARG, "last_mesh_shells: null output or negative capacity");
-    const int64_t n = (int64_t)(g_last_shells.counts.size() / MS_NCNT), m = std::min(capacity, n);
-    *n_shells = n;
-    if (m > 0) {
-        std::memcpy(counts_out, g_last_shells.counts.data(), sizeof(int64_t) * MS_NCNT * (size_t)m);
-        std::memcpy(sums_out, g_last_shells.sums.data(), sizeof(double) * MS_NSUM * (size_t)m);
-    }
+    const int64_t n = *n_shells = (int64_t)(g_last_shells.counts.size() / MS_NCNT);
+    copy_rows(counts_out, g_last_shells.counts, MS_NCNT, capacity, n);
+    copy_rows(sums_out, g_last_shells.sums, MS_NSUM, capacity, n);
     return 0;
 }
 
@@ -327,30 +309,11 @@ int r2s_mesh_shells_dev(const float* d_verts, int64_t n_verts, const int32_t* d_
                         int64_t* d_counts, double* d_sums, int64_t shell_capacity, int64_t* n_shells, double ref_point[3],
                         int64_t totals[8], void* stream)
 {
-    int rc = shells_args(d_verts, n_verts, d_tris, n_tris, n_shells, ref_point, totals);
-    if (rc) return rc;
+    if (const int rc = shells_args(d_verts, n_verts, d_tris, n_tris, n_shells, ref_point, totals)) return rc;
     if (shell_capacity < 0 || (shell_capacity > 0 && (!d_counts || !d_sums)))
         return fail(R2S_ERR_ARG, "mesh_shells: null tables or negative shell_capacity");
-    if ((rc = check_device(0))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_shell_work.mu);
-    ShellWork* w = g_shell_work.current(rc);
-    if (rc) return rc;
-    if ((rc = check_mesh_dev("mesh_shells", d_verts, n_verts, d_tris, n_tris, w->flag, st))) return rc;
-    int64_t nsh = 0, tot[8];
-    double r[3];
-    if ((rc = shells_core(d_verts, n_verts, d_tris, n_tris, st, *w, &nsh, r, tot))) return rc;
-    if (d_shell_of_tri && n_tris > 0)
-        HIP_TRY(hipMemcpyAsync(d_shell_of_tri, w->shell.p, sizeof(int32_t) * (size_t)n_tris, hipMemcpyDeviceToDevice, st));
-    if (nsh > 0 && shell_capacity >= nsh) {
-        HIP_TRY(hipMemcpyAsync(d_counts, w->counts.p, sizeof(int64_t) * MS_NCNT * (size_t)nsh, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_sums, w->sums.p, sizeof(double) * MS_NSUM * (size_t)nsh, hipMemcpyDeviceToDevice, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_shells = nsh;
-    std::memcpy(ref_point, r, sizeof r);
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    MeshCall<ShellWork> call("mesh_shells", g_shell_work, d_verts, n_verts, d_tris, n_tris, (hipStream_t)stream);
+    return shells_run(call, n_verts, n_tris, d_shell_of_tri, d_counts, d_sums, shell_capacity, n_shells, ref_point, totals);
 }
 
 }  // extern "C"

@@ -383,6 +383,28 @@ int weld_args(const void* verts, int64_t n_verts, const void* tris, int64_t n_tr
     return 0;
 }
 
+// One call for both kinds of caller: the welded mesh (a host caller's through work buffers, tot[0] vertices and tot[1] triangles of
+// them copied out), then vert_map, tri_map and the totals.  nt: the number of triangles, of a soup too.
+int weld_run(MeshCall<WeldWork>& c, int64_t n_verts, int64_t nt, double snap, int32_t flags, float* verts_out, int32_t* tris_out,
+             int32_t* vert_map_out, int32_t* tri_map_out, int64_t totals[8])
+{
+    int rc = c.open();
+    if (rc) return rc;
+    WeldWork& w = c.work();
+    int64_t tot[8];
+    float* d_verts_out = nullptr;
+    int32_t* d_tris_out = nullptr;
+    if ((rc = c.staged(w.verts_out, verts_out, vert_bytes(std::max<int64_t>(n_verts, 1)), d_verts_out)) ||
+        (rc = c.staged(w.tris_out, tris_out, tri_bytes(std::max<int64_t>(nt, 1)), d_tris_out)) ||
+        (rc = weld_core(c.d_verts(), n_verts, c.d_tris(), nt, snap, flags, c.stream(), w, d_verts_out, d_tris_out, tot)) ||
+        (rc = c.deliver(verts_out, d_verts_out, vert_bytes(tot[0]))) || (rc = c.deliver(tris_out, d_tris_out, tri_bytes(tot[1]))) ||
+        (rc = c.deliver(vert_map_out, w.vert_map.p, sizeof(int32_t) * (size_t)n_verts)) ||
+        (rc = c.deliver(tri_map_out, w.tri_map.p, sizeof(int32_t) * (size_t)nt)) || (rc = c.finish()))
+        return rc;
+    std::memcpy(totals, tot, sizeof tot);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -391,25 +413,9 @@ int r2s_mesh_weld(const float* verts, int64_t n_verts, const int32_t* tris, int6
                   float* verts_out, int32_t* tris_out, int32_t* vert_map_out, int32_t* tri_map_out, int64_t totals[8])
 {
     int64_t nt = 0;
-    int rc = weld_args(verts, n_verts, tris, n_tris, snap, flags, verts_out, tris_out, totals, &nt);
-    if (rc) return rc;
-    if ((rc = check_mesh_host("mesh_weld", verts, n_verts, tris, tris ? nt : 0)) || (rc = use_device(device))) return rc;
-    std::lock_guard<std::mutex> lock(g_weld_work.mu);
-    WeldWork* w = g_weld_work.current(rc);
-    if (rc) return rc;
-    if ((rc = upload_mesh(w->verts, w->tris, verts, n_verts, tris, tris ? nt : 0, false, nullptr))) return rc;
-    ENSURE(w->verts_out, vert_bytes(std::max<int64_t>(n_verts, 1)));
-    ENSURE(w->tris_out, tri_bytes(std::max<int64_t>(nt, 1)));
-    int64_t tot[8];
-    if ((rc = weld_core(w->verts.as<float>(), n_verts, tris ? w->tris.as<int32_t>() : nullptr, nt, snap, flags, nullptr, *w,
-                        w->verts_out.as<float>(), w->tris_out.as<int32_t>(), tot)))
-        return rc;
-    if (tot[0] > 0) HIP_TRY(hipMemcpy(verts_out, w->verts_out.p, vert_bytes(tot[0]), hipMemcpyDeviceToHost));
-    if (tot[1] > 0) HIP_TRY(hipMemcpy(tris_out, w->tris_out.p, tri_bytes(tot[1]), hipMemcpyDeviceToHost));
-    if (vert_map_out && n_verts > 0) HIP_TRY(hipMemcpy(vert_map_out, w->vert_map.p, sizeof(int32_t) * (size_t)n_verts, hipMemcpyDeviceToHost));
-    if (tri_map_out && nt > 0) HIP_TRY(hipMemcpy(tri_map_out, w->tri_map.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost));
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (const int rc = weld_args(verts, n_verts, tris, n_tris, snap, flags, verts_out, tris_out, totals, &nt)) return rc;
+    MeshCall<WeldWork> call("mesh_weld", g_weld_work, verts, n_verts, tris, tris ? nt : 0, device);
+    return weld_run(call, n_verts, nt, snap, flags, verts_out, tris_out, vert_map_out, tri_map_out, totals);
 }
 
 int r2s_mesh_weld_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tris, int64_t n_tris, double snap, int32_t flags,
@@ -417,23 +423,9 @@ int r2s_mesh_weld_dev(const float* d_verts, int64_t n_verts, const int32_t* d_tr
                       void* stream)
 {
     int64_t nt = 0;
-    int rc = weld_args(d_verts, n_verts, d_tris, n_tris, snap, flags, d_verts_out, d_tris_out, totals, &nt);
-    if (rc) return rc;
-    if ((rc = check_device(0))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_weld_work.mu);
-    WeldWork* w = g_weld_work.current(rc);
-    if (rc) return rc;
-    if ((rc = check_mesh_dev("mesh_weld", d_verts, n_verts, d_tris, d_tris ? nt : 0, w->flag, st))) return rc;
-    int64_t tot[8];
-    if ((rc = weld_core(d_verts, n_verts, d_tris, nt, snap, flags, st, *w, d_verts_out, d_tris_out, tot))) return rc;
-    if (d_vert_map_out && n_verts > 0)
-        HIP_TRY(hipMemcpyAsync(d_vert_map_out, w->vert_map.p, sizeof(int32_t) * (size_t)n_verts, hipMemcpyDeviceToDevice, st));
-    if (d_tri_map_out && nt > 0)
-        HIP_TRY(hipMemcpyAsync(d_tri_map_out, w->tri_map.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::memcpy(totals, tot, sizeof tot);
-    return 0;
+    if (const int rc = weld_args(d_verts, n_verts, d_tris, n_tris, snap, flags, d_verts_out, d_tris_out, totals, &nt)) return rc;
+    MeshCall<WeldWork> call("mesh_weld", g_weld_work, d_verts, n_verts, d_tris, d_tris ? nt : 0, (hipStream_t)stream);
+    return weld_run(call, n_verts, nt, snap, flags, d_verts_out, d_tris_out, d_vert_map_out, d_tri_map_out, totals);
 }
 
 }  // extern "C"
