@@ -37,14 +37,14 @@
  *     r2s_plan_run_dev (every call ends with a wait for `stream`; the first call for a set of shapes also waits twice in
  *     the middle), r2s_remove_artifacts_dev, r2s_analyze_components_dev, r2s_rbf_smooth_dev, r2s_extract_isosurface_dev,
  *     r2s_mesh_distance_dev, r2s_redistance_dev, r2s_redistance_full_dev, r2s_mesh_index_build_dev, r2s_mesh_shells_dev,
- *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_orient_dev, r2s_mesh_fans_dev, r2s_mesh_holes_dev,
- *     r2s_mesh_nesting_dev.  A caller should still order its consumers on `stream`, not on that wait.
+ *     r2s_mesh_sections_dev, r2s_mesh_weld_dev, r2s_mesh_simplify_dev, r2s_mesh_orient_dev, r2s_mesh_fans_dev,
+ *     r2s_mesh_holes_dev, r2s_mesh_nesting_dev.  A caller should still order its consumers on `stream`, not on that wait.
  *   - sharing.  A plan serves one call at a time: successive calls on one stream need no host wait in between (each call
  *     has drained the stream when it returns), r2s_plan_pack_tiles*_dev read the tile lists of the plan's last run and belong
  *     on that run's stream before the plan's next run; different plans are independent and may be driven on different
  *     streams.  A field (r2s_rbf_field) and a mesh index are only read by their _dev entry points: one object may be used
  *     from several streams and threads at once.  The entry points that keep work buffers per device (removal and component
- *     analysis, smoothing, extraction, redistancing, shells, sections, weld, orient, fans, holes, intersections, nesting) take a lock
+ *     analysis, smoothing, extraction, redistancing, shells, sections, weld, simplify, orient, fans, holes, intersections, nesting) take a lock
  *     for the length of the call: concurrent calls are safe and run one after the other.  The host-pointer SDF entry points
  *     (r2s_eval_distances, r2s_sign_detection, r2s_sdf, r2s_rho2sdf) lock their device's session in the same way.  Results a
  *     call leaves behind for r2s_last_* and r2s_last_error belong to the calling thread.  tests/test_threads_gpu.py is the
@@ -924,7 +924,8 @@ int r2s_mesh_sections_dev(const float *d_verts, int64_t n_verts, const int32_t *
  * collapses the zero-area triangles between them and can leave non-manifold edges, which r2s_mesh_shells reports, and
  * non-manifold vertices, which only r2s_mesh_fans below reports (the shells join triangles over edges and cannot see a vertex
  * whose triangles fall into several fans); weld, then split with r2s_mesh_fans, gives a mesh whose every vertex is manifold.
- * Not here: distance-tolerance welding, hole filling, decimation; flipped triangles are re-oriented by r2s_mesh_orient below. */
+ * Not here: distance-tolerance welding; hole filling is r2s_mesh_holes, decimation r2s_mesh_simplify below; flipped triangles are
+ * re-oriented by r2s_mesh_orient below. */
 #define R2S_WELD_DROP_COLLAPSED 1
 #define R2S_WELD_DROP_DUPLICATES 2
 #define R2S_WELD_DROP_UNUSED 4
@@ -934,6 +935,74 @@ int r2s_mesh_weld(const float *verts, int64_t n_verts, const int32_t *tris, int6
 int r2s_mesh_weld_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, double snap, int32_t flags,
                       float *d_verts_out, int32_t *d_tris_out, int32_t *d_vert_map_out, int32_t *d_tri_map_out,
                       int64_t totals[8], void *stream);
+
+/* ---- mesh simplify: vertex-clustering decimation ------------------------------------------------
+ * The extractor makes one vertex per crossed lattice edge; this makes a mesh coarser.  The vertices are clustered by the weld's
+ * cells of edge `cell`, every cluster becomes ONE vertex at a computed position, and the triangles are remapped.
+ *   - input: an INDEXED mesh, verts float32 [n_verts][3], tris int32 [n_tris][3], 0-based.  tris == NULL is R2S_ERR_ARG: weld a
+ *     soup with r2s_mesh_weld(snap = 0) first.  cell must be positive and finite, else R2S_ERR_ARG.
+ *   - classes: the cell of a vertex is the weld's, q_a = floor((double)v_a / cell) per axis with the same division, floor and
+ *     -0 == +0; the partition of the vertices is by definition that of r2s_mesh_weld(snap = cell).  Every q_a must lie in
+ *     [-2^31, 2^31); otherwise R2S_ERR_ARG with the weld's message, outputs untouched.
+ *   - members: the vertices that a non-collapsed INPUT triangle references (collapsed: two equal indices).  Other vertices belong to
+ *     no class, count in totals[6] and have vert_map -1.
+ *   - triangles are remapped through the classes.  Collapsed ones (two corners in one class) are always dropped; flags takes
+ *     R2S_WELD_DROP_DUPLICATES with the weld's meaning and no other bit (else R2S_ERR_ARG); opposite pairs (two sheets pressed onto
+ *     each other) are counted and never dropped.  Survivors keep their order and corner order; tri_map[t] is the output index or -1.
+ *   - output vertices: one per class that a surviving triangle references, numbered in first-occurrence order of the class's first
+ *     (smallest-index) member.  A class none of whose triangles survives (a triangle inside one cell) gives no vertex; its members
+ *     have vert_map -1 and count in totals[2].
+ *   - ref_point: per axis 0.5 * (min + max) of all vertices, as in r2s_mesh_shells.  All sums are Float64 about ref_point and are
+ *     the segmented fixed-order sum of r2s_mesh_shells: the items sorted stably by output class, blocks of 256 consecutive items,
+ *     the in-block tree, then the block partials of a class in the combine order stated there.  No fma.
+ *   - mean: items = the members, ascending index inside a class, each once; terms (double)v_a - ref_a.  m = sum / count.
+ *   - quadric: items = (class, triangle) for every non-collapsed input triangle and every DISTINCT output class among its corners
+ *     (a triangle with two corners in one class counts once for it), ascending triangle inside a class.  With A, B, C the corners
+ *     about ref_point: e1 = B - A, e2 = C - A, n = e1 x e2 (n_x = e1_y e2_z - e1_z e2_y, cyclic), d = (n_x A_x + n_y A_y) + n_z A_z;
+ *     the ten terms n_x n_x, n_x n_y, n_x n_z, n_y n_y, n_y n_z, n_z n_z, d n_x, d n_y, d n_z, d d give the symmetric S, b and c of
+ *     E(p) = sum (n . p - d)^2 = p^T S p - 2 b . p + c.
+ *   - representative, rule R2S_SIMPLIFY_MEAN: m.  Rule R2S_SIMPLIFY_QUADRIC: S is eigen-decomposed by cyclic Jacobi; directions
+ *     with lambda < 1e-3 lambda_max are dropped (Lindstrom); x = m + sum over the kept (V_k . (b - S m) / lambda_k) V_k; if x leaves
+ *     the closed cell [q cell, (q + 1) cell] it is pulled back along the segment to m: x = m + s (x - m) with the largest s in
+ *     [0, 1] that stays inside (an axis along which |x - m| <= 2^-40 cell constrains nothing: a vertex that sits ON a cell face
+ *     must not be "pulled back" by the sign of a rounding error); lambda_max <= 0 (only zero-area triangles): m.  E is convex along that segment, so E(x) <= E(m)
+ *     up to rounding.  Then ref_point is added and the result is rounded ONCE to float32.
+ *   - per output vertex (r2s_last_mesh_simplify): members, the member count; error, E at the float32 representative as computed in
+ *     Float64, p^T (S p) - 2 (b . p) + c (under MEAN too: it says what QUADRIC would gain; it may come out slightly negative by
+ *     cancellation); solved, 0 = the mean, 1..3 = the rank kept by the quadric solve, + 4 if the point was pulled back.
+ *   - totals, int64[8]: [0] output vertices, [1] output triangles, [2] members minus output vertices (merged away), [3] triangles
+ *     collapsed by the clustering, [4] same-orientation duplicates, counted whether or not dropped, [5] opposite pairs, [6] input
+ *     vertices that are no member, [7] classes whose representative was pulled back to its cell.
+ *   - what clustering can break: manifoldness.  It can create non-manifold edges (r2s_mesh_shells reports them), non-manifold
+ *     vertices (r2s_mesh_fans reports and splits them), opposite pairs (totals[5]) and self-contact (r2s_mesh_intersections).  It
+ *     opens no hole where no triangle is dropped as a duplicate: a closed input gives a result without boundary edges when it
+ *     is consistently oriented or R2S_WELD_DROP_DUPLICATES is off (on a closed but inconsistently wound input, dropping a
+ *     same-orientation duplicate can leave an edge with one triangle).  Every vertex moves inside its cell, so every point of
+ *     a surviving triangle is within sqrt(3) * cell of its image.
+ * r2s_mesh_simplify: host arrays, `device` (-1 = current).  Outputs are sized by the caller to the INPUT counts; only the first
+ * totals[0] rows of verts_out and totals[1] rows of tris_out are written.  The two maps may be NULL.
+ * r2s_mesh_simplify_dev: the same with device pointers on the current device, read after the work queued on `stream`; totals is a
+ * host pointer.  Synchronous on return.  The outputs must not overlap the inputs.  Work buffers are kept per device behind a
+ * lock and freed by r2s_release_cache.
+ * r2s_last_mesh_simplify: the three tables of the calling thread's last successful call of EITHER variant; *n_verts_out is always
+ * the full count, the first min(capacity, n) rows are written; the arrays may be NULL only with capacity == 0.
+ * Refused before any output is touched, as by r2s_mesh_weld: R2S_ERR_ARG for NULL arrays with a count, NULL tris, NULL outputs
+ * with a count or NULL totals, a negative count, a bad cell, rule or flag bit, a triangle index outside [0, n_verts) or a
+ * non-finite vertex (checked before any kernel reads through the indices); 3 * n_tris >= 2^31 or n_verts >= 2^31:
+ * R2S_ERR_UNSUPPORTED.  No GPU: R2S_ERR_NO_DEVICE.  n_verts == 0 or n_tris == 0 succeed with nothing.
+ * The same input gives the same output bit for bit on every call, from both variants and with fresh work buffers (no result depends
+ * on an atomic's arrival order).  Under a permutation of the input the partition and every integer follow up to the renumbering;
+ * the positions do not (the order of the additions changes), the bounds above do.
+ * Not here: edge collapse, boundary or feature constraints, attribute transfer. */
+#define R2S_SIMPLIFY_MEAN 0
+#define R2S_SIMPLIFY_QUADRIC 1
+int r2s_mesh_simplify(const float *verts, int64_t n_verts, const int32_t *tris, int64_t n_tris, double cell, int32_t rule,
+                      int32_t flags, int32_t device, float *verts_out, int32_t *tris_out, int32_t *vert_map_out,
+                      int32_t *tri_map_out, int64_t totals[8]);
+int r2s_mesh_simplify_dev(const float *d_verts, int64_t n_verts, const int32_t *d_tris, int64_t n_tris, double cell, int32_t rule,
+                          int32_t flags, float *d_verts_out, int32_t *d_tris_out, int32_t *d_vert_map_out,
+                          int32_t *d_tri_map_out, int64_t totals[8], void *stream);
+int r2s_last_mesh_simplify(int64_t *members_out, double *error_out, int32_t *solved_out, int64_t capacity, int64_t *n_verts_out);
 
 /* ---- mesh orient: consistent, outward triangle winding ------------------------------------------
  * STL files from the wild have facets, or whole bodies, wound the wrong way; r2s_mesh_shells reads a shell's volume sign as

@@ -16,7 +16,7 @@ from .api import (DenseInNodes, analyze_sdf_components, DevicePlan, Grid, Mesh, 
                   vertex_normals, surface_thickness, surface_thickness_dev,
                   MeshShells, mesh_shells, mesh_shells_dev, select_shells,
                   MeshSections, mesh_sections, mesh_sections_dev,
-                  MeshWeld, mesh_weld, mesh_weld_dev, import_stl,
+                  MeshWeld, mesh_weld, mesh_weld_dev, import_stl, MeshSimplify, mesh_simplify, mesh_simplify_dev,
                   MeshOrient, mesh_orient, mesh_orient_dev, flip_patches,
                   MeshFans, mesh_fans, mesh_fans_dev,
                   MeshHoles, mesh_holes, mesh_holes_dev,
@@ -35,7 +35,7 @@ __all__ = ["DenseInNodes", "analyze_sdf_components", "DevicePlan", "Grid", "Mesh
            "vertex_normals", "surface_thickness", "surface_thickness_dev",
            "MeshShells", "mesh_shells", "mesh_shells_dev", "select_shells",
            "MeshSections", "mesh_sections", "mesh_sections_dev",
-           "MeshWeld", "mesh_weld", "mesh_weld_dev", "import_stl",
+           "MeshWeld", "mesh_weld", "mesh_weld_dev", "import_stl", "MeshSimplify", "mesh_simplify", "mesh_simplify_dev",
            "MeshOrient", "mesh_orient", "mesh_orient_dev", "flip_patches",
            "MeshFans", "mesh_fans", "mesh_fans_dev",
            "MeshHoles", "mesh_holes", "mesh_holes_dev",

@@ -232,6 +232,11 @@ SYMBOLS = [
                                      ctypes.c_int32, c_float_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p]),
     ("r2s_mesh_weld_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P,
                                          c_int64_p, _P]),
+    ("r2s_mesh_simplify", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_int32, c_float_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p]),
+    ("r2s_mesh_simplify_dev", ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _P, _P,
+                                             _P, _P, c_int64_p, _P]),
+    ("r2s_last_mesh_simplify", ctypes.c_int, [c_int64_p, c_double_p, c_int32_p, ctypes.c_int64, c_int64_p]),
     ("r2s_mesh_orient", ctypes.c_int, [c_float_p, ctypes.c_int64, c_int32_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_int32_p,
                                        c_int32_p, c_int32_p, c_int64_p, c_double_p, c_int64_p]),
     ("r2s_last_mesh_orient", ctypes.c_int, [c_int64_p, c_double_p, ctypes.c_int64, c_int64_p]),
@@ -267,6 +272,7 @@ SYMBOLS = [
 OUT_DIST, OUT_SIGN, OUT_SDF, OUT_XP = 1, 2, 4, 8
 HEX8, TET4 = 0, 1
 WELD_DROP_COLLAPSED, WELD_DROP_DUPLICATES, WELD_DROP_UNUSED = 1, 2, 4
+SIMPLIFY_MEAN, SIMPLIFY_QUADRIC = 0, 1
 ORIENT_OUTWARD = 1
 NESTING_REWIND = 1
 

@@ -1153,6 +1153,95 @@ def mesh_weld_dev(verts, tris=None, stream=None, *, snap=0.0, drop_collapsed=Tru
     return MeshWeld(vo[:tot[0]], to[:tot[1]], vm, tm, tot)
 
 
+class MeshSimplify:
+    """The result of mesh_simplify (include/rho2sdf_hip.h, r2s_mesh_simplify): `verts` (nv_out, 3) float32, one computed point per
+    cluster, in first-occurrence order of the cluster's first member; `tris` (nt_out, 3) int32 into them; `vert_map` (nv_in,) and
+    `tri_map` (nt_in,) int32, input index -> output index or -1; per output vertex `members` (int64, the size of the cluster),
+    `error` (float64, the summed squared plane distances, area-weighted, at the vertex) and `solved` (int32: 0 the mean, 1..3 the
+    rank the quadric solve kept, + 4 if the point was pulled back to its cell), always numpy; `totals` (8,) int64 (output vertices,
+    output triangles, members merged away, collapsed triangles, same-orientation duplicates, opposite pairs, vertices that are no
+    member, pulled-back clusters).  numpy arrays from mesh_simplify, device tensors for the first four from mesh_simplify_dev."""
+
+    def __init__(self, verts, tris, vert_map, tri_map, members, error, solved, totals):
+        self.verts, self.tris, self.vert_map, self.tri_map = verts, tris, vert_map, tri_map
+        self.members, self.error, self.solved, self.totals = members, error, solved, totals
+
+    n_verts = property(lambda s: int(s.totals[0]))
+    n_tris = property(lambda s: int(s.totals[1]))
+    n_merged = property(lambda s: int(s.totals[2]))
+    n_collapsed = property(lambda s: int(s.totals[3]))
+    n_duplicates = property(lambda s: int(s.totals[4]))
+    n_opposite = property(lambda s: int(s.totals[5]))
+    n_unused = property(lambda s: int(s.totals[6]))
+    n_pulled = property(lambda s: int(s.totals[7]))
+
+    @property
+    def ratio(self):
+        """output triangles / input triangles (1.0 for an input without triangles)"""
+        return self.n_tris / len(self.tri_map) if len(self.tri_map) else 1.0
+
+
+_SIMPLIFY_RULES = {"mean": L.SIMPLIFY_MEAN, "quadric": L.SIMPLIFY_QUADRIC}
+
+
+def _simplify_rule(rule):
+    if rule not in _SIMPLIFY_RULES:
+        raise L.R2SError('rule must be "mean" or "quadric"')
+    return _SIMPLIFY_RULES[rule]
+
+
+def _last_mesh_simplify():
+    """the calling thread's last tables (r2s_last_mesh_simplify): count, then copy"""
+    n = ctypes.c_int64(0)
+    L.check(L.lib().r2s_last_mesh_simplify(None, None, None, 0, ctypes.byref(n)))
+    members, error, solved = np.empty(n.value, np.int64), np.empty(n.value, np.float64), np.empty(n.value, np.int32)
+    L.check(L.lib().r2s_last_mesh_simplify(_i(members), _d(error), solved.ctypes.data_as(L.c_int32_p), n.value, ctypes.byref(n)))
+    return members, error, solved
+
+
+def mesh_simplify(verts, tris, cell, rule="quadric", drop_duplicates=True, *, device=-1):
+    """Vertex-clustering decimation of an indexed triangle mesh (verts (nv, 3) float32, tris (nt, 3) int32 0-based; weld a soup
+    first) -> MeshSimplify.  The vertices are clustered by the cells floor(v / cell) per axis, the cells of mesh_weld(snap=cell);
+    every cluster that keeps a triangle becomes one vertex: rule="mean" the Float64 mean of its members, rule="quadric" the point
+    of the cell that minimises the summed squared distances to the planes of the triangles around the cluster (Lindstrom), which
+    keeps edges and corners where the mean rounds them off.  Triangles with two corners in one cluster are dropped, duplicates
+    with drop_duplicates; every vertex moves inside its cell, so the result is within sqrt(3) * cell of the input.
+    Clustering does not preserve manifoldness: it can leave non-manifold edges (mesh_shells reports them), pinched vertices
+    (mesh_fans reports and splits them), opposite pairs (totals[5]) and self-contact (mesh_intersections).  It opens no hole in a
+    consistently oriented closed mesh (or with drop_duplicates=False).
+    Not here: edge collapse, boundary or feature constraints, attribute transfer."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    vo, to = np.empty((len(v), 3), np.float32), np.empty((len(t), 3), np.int32)
+    vm, tm = np.empty(len(v), np.int32), np.empty(len(t), np.int32)
+    tot = np.zeros(8, np.int64)
+    ip = lambda a: a.ctypes.data_as(L.c_int32_p)
+    pad = np.zeros(3, np.int32)   # (a non-NULL pointer for a mesh without triangles)
+    L.check(L.lib().r2s_mesh_simplify(_f(v) if len(v) else None, len(v), ip(t if len(t) else pad), len(t), float(cell), _simplify_rule(rule),
+                                      L.WELD_DROP_DUPLICATES if drop_duplicates else 0, int(device), _f(vo), ip(to), ip(vm), ip(tm),
+                                      _i(tot)))
+    return MeshSimplify(vo[:tot[0]].copy(), to[:tot[1]].copy(), vm, tm, *_last_mesh_simplify(), tot)
+
+
+def mesh_simplify_dev(verts, tris, cell, rule="quadric", drop_duplicates=True, *, stream=None):
+    """mesh_simplify on torch tensors on the current device (verts float32 (nv, 3), tris int32 (nt, 3), contiguous).  verts, tris
+    and the two maps of the MeshSimplify stay device tensors, verts and tris trimmed to the counts; the per-vertex tables and
+    totals are numpy."""
+    import torch
+    dev = verts.device
+    _mesh_tensors(verts, tris)
+    nv, nt = verts.numel() // 3, tris.numel() // 3
+    pad = torch.zeros(3, dtype=torch.int32, device=dev)   # (torch's empty tensors have a NULL pointer)
+    st = _stream(stream)
+    vo, to = torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    vm, tm = torch.empty(nv, dtype=torch.int32, device=dev), torch.empty(nt, dtype=torch.int32, device=dev)
+    tot = np.zeros(8, np.int64)
+    vp = lambda x: ctypes.c_void_p(x.data_ptr())
+    L.check(L.lib().r2s_mesh_simplify_dev(vp(verts), nv, vp(tris if nt else pad), nt, float(cell), _simplify_rule(rule),
+                                          L.WELD_DROP_DUPLICATES if drop_duplicates else 0, vp(vo), vp(to), vp(vm), vp(tm), _i(tot), st))
+    return MeshSimplify(vo[:tot[0]], to[:tot[1]], vm, tm, *_last_mesh_simplify(), tot)
+
+
 def select_shells(verts, tris, shells, keep):
     """The triangles of the shells where `keep` is true -> (verts, tris) with the vertices compacted (ascending old index) and the
     indices remapped; the mesh-level counterpart of remove_sdf_artifacts.  `shells` is the MeshShells of (verts, tris); `keep` a
@@ -2077,7 +2166,7 @@ def export_stl(filename, verts, tris):
 
 
 def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_intersections=False, split_vertices=False,
-               fill_holes=None):
+               fill_holes=None, simplify=None, simplify_rule="quadric"):
     """The triangles of a binary or ASCII STL file -> (verts (nv, 3) float32, tris (nt, 3) int32).  weld=True (needs the GPU): the
     vertices that are the same point are merged by mesh_weld(soup, snap=snap) with its defaults (collapsed triangles and unused
     vertices dropped), so the mesh tools see shared vertices; weld=False: the soup as the file holds it, 3 nt vertices and
@@ -2092,9 +2181,12 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     mesh_fans(split=True), so that every vertex of the result has a single fan unless it lies on a non-manifold edge.
     fill_holes=k (needs weld=True): after the weld, the orient and the split, the closed rims of the mesh are capped by
     mesh_holes(fill=k): -1 every hole, k > 0 the holes of at most k edges.  The intersections are those of the filled mesh.
+    simplify=cell (needs weld=True): directly after the weld, before the orient, the split and the fill, the mesh is decimated by
+    mesh_simplify(verts, tris, cell, simplify_rule); what clustering can leave behind (pinched vertices, non-manifold edges) is
+    what the later steps and checks are there for.
 
-    From an STL file to the signed-distance volume everything else here produces (the full repair recipe: weld -> orient ->
-    split pinched vertices -> fill holes -> check):
+    From an STL file to the signed-distance volume everything else here produces (the full repair recipe: weld -> simplify
+    (optional) -> orient -> split pinched vertices -> fill holes -> check with mesh_shells / mesh_intersections):
 
         verts, tris, x = import_stl("part.stl", orient="majority", split_vertices=True, fill_holes=-1, check_intersections=True)
         assert len(x) == 0                                        # the surface, caps included, does not pass through itself
@@ -2114,6 +2206,8 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
         raise L.R2SError("check_intersections needs weld=True: in a soup every neighbour touches under different indices")
     if fill_holes is not None and not weld:
         raise L.R2SError("fill_holes needs weld=True: in a soup every triangle is a hole of its own")
+    if simplify is not None and not weld:
+        raise L.R2SError("simplify needs weld=True: clustering works on an indexed mesh")
     m = L.R2SStlMesh()
     L.check(L.lib().r2s_import_stl(str(filename).encode(), ctypes.byref(m)))
     try:
@@ -2124,6 +2218,8 @@ def import_stl(filename, *, weld=True, snap=0.0, device=-1, orient=None, check_i
     if not weld:
         return soup, np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
     w = mesh_weld(soup, None, snap=snap, device=device)
+    if simplify is not None:
+        w = mesh_simplify(w.verts, w.tris, simplify, simplify_rule, device=device)
     verts = w.verts
     tris = w.tris if orient is None else mesh_orient(verts, w.tris, outward=orient != "majority", device=device).tris
     if orient == "nested":
@@ -2229,7 +2325,8 @@ class Rho2sdfOptions:
 
 def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, export_results=False, n_gpus=1,
             info=None, pinned_results=False, fine_out=None, dists_out=None, surface=False, redistance_cells=None,
-            signed_distance=False, deviation=False, thickness=False, shells=False, sections=None):
+            signed_distance=False, deviation=False, thickness=False, shells=False, sections=None, simplify_cells=None,
+            simplify_rule="quadric"):
     """rho2sdf(taskName, X, IEN, rho; options) -> (fine_sdf, fine_grid, sdf_grid, sdf_dists)
     src/RhoToSDF.jl:116-242.  ONE call into the library (r2s_rho2sdf): the mesh goes up once, mesh volume ->
     nodal densities -> threshold -> raw SDF -> artifact removal -> RBF smoothing run on HBM-resident data, the two
@@ -2246,6 +2343,10 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     surface=True: the library also extracts the iso-0 surface of fine_sdf on the device (r2s_options extract_surface);
     info["surface"] = (verts, tris) as extract_isosurface(fine_sdf, sdf_grid, smooth) returns them (bit-identical), and
     export_results=True also writes it next to the .vti as <same name>.stl.  The return values are unchanged.
+    simplify_cells=k (a positive number; needs surface=True): the extracted surface is decimated by mesh_simplify with cell = k
+    spacings of the fine lattice and simplify_rule, a further library call after the first; the simplified mesh is then THE
+    surface: info["surface"], what thickness / shells / sections read and what the .stl holds; info["simplify"] = the MeshSimplify.
+    (deviation=True still measures the surface as extracted, so that it does not include the decimation.)
     redistance_cells=k (a positive number; needs `info`): info["sdf_redistanced"] = redistance(fine_sdf, sdf_grid, smooth,
     band=k * spacing of the fine lattice) - the banded signed distance to the iso-0 surface of fine_sdf, a second library
     call after the first.  None: nothing is called.
@@ -2271,6 +2372,8 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     if sections is not None and info is None:
         raise L.R2SError("sections needs an `info` dict for the result")
     surface = bool(surface) or bool(thickness) or bool(shells) or sections is not None
+    if simplify_cells is not None and not (surface and float(simplify_cells) > 0.0):
+        raise L.R2SError("simplify_cells must be a positive number and needs surface=True")
     if redistance_cells is not None and (info is None or not (float(redistance_cells) > 0.0)):
         raise L.R2SError("redistance_cells must be a positive number and needs an `info` dict for the result")
     mesh = Mesh(X, IEN, options.element_type)
@@ -2313,6 +2416,12 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
         if analysis:
             info["components_before"] = _components_dict(lambda r, s, cap, n: L.lib().r2s_last_components(r, s, cap, n))
     mesh_out = _last_isosurface() if surface else None
+    extracted = mesh_out                                  # (the smoothing deviation reads the surface as extracted)
+    if simplify_cells is not None:
+        simplified = mesh_simplify(*mesh_out, float(simplify_cells) * _iso_lattice(sdf_grid, smooth)[2], simplify_rule, device=device)
+        mesh_out = (simplified.verts, simplified.tris)
+        if info is not None:
+            info["simplify"] = simplified
     if info is not None and surface:
         info["surface"] = mesh_out
     fine_sdf = fine.reshape(dims[2], dims[1], dims[0])
@@ -2325,7 +2434,7 @@ def rho2sdf(taskName, X, IEN, rho, *, options=None, sdf_grid=None, device=-1, ex
     if signed_distance:
         info["sdf_distance"] = redistance_full(fine_sdf, sdf_grid, smooth, device=device)
     if deviation:
-        smoothed = mesh_out if surface else extract_isosurface(fine_sdf, sdf_grid, smooth, device=device)
+        smoothed = extracted if surface else extract_isosurface(fine_sdf, sdf_grid, smooth, device=device)
         raw = extract_isosurface(sdf_dists, sdf_grid, None, device=device)
         info["smoothing_deviation"] = surface_deviation(*smoothed, *raw, device=device)
     if thickness:

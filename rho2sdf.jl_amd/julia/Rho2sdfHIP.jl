@@ -604,6 +604,58 @@ function mesh_weld_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cv
     return totals
 end
 
+# Vertex-clustering decimation of an indexed triangle mesh (include/rho2sdf_hip.h, r2s_mesh_simplify): verts 3 x nv Float32, tris
+# 3 x nt 1-based, cell > 0.  The clusters are the cells of mesh_weld_hip(snap = cell); rule :mean puts each at the Float64 mean
+# of its members, :quadric at the point of the cell that minimises the summed plane quadrics of the triangles around it.
+# -> (verts 3 x nv_out, tris 3 x nt_out 1-based, vert_map and tri_map 1-based with 0 for what was dropped, members, error, solved
+# per output vertex, totals).  Clustering does not preserve manifoldness: check with mesh_shells_hip / mesh_fans_hip /
+# mesh_intersections_hip.  Not here: edge collapse, boundary or feature constraints, attribute transfer.
+function mesh_simplify_hip(verts::AbstractMatrix{Float32}, tris::AbstractMatrix{<:Integer}, cell::Real; rule::Symbol = :quadric,
+                           drop_duplicates::Bool = true, device::Integer = -1)
+    size(verts, 1) == 3 && size(tris, 1) == 3 || error("verts and tris must be 3 x n")
+    rule in (:mean, :quadric) || error("rule must be :mean or :quadric")
+    nv = size(verts, 2)
+    t0 = Int32.(tris) .- Int32(1)
+    nt = size(t0, 2)
+    vout = Matrix{Float32}(undef, 3, nv); tout = Matrix{Int32}(undef, 3, nt)
+    vmap = Vector{Int32}(undef, nv); tmap = Vector{Int32}(undef, nt)
+    totals = zeros(Int64, 8)
+    pad = zeros(Int32, 3)                 # a mesh without triangles still passes a non-NULL tris
+    check(ccall((:r2s_mesh_simplify, LIB[]), Cint,
+                (Ptr{Float32}, Int64, Ptr{Int32}, Int64, Float64, Int32, Int32, Int32, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+                 Ptr{Int64}),
+                Matrix(verts), nv, nt == 0 ? pad : t0, nt, Float64(cell), Int32(rule == :mean ? 0 : 1), Int32(drop_duplicates ? 2 : 0),
+                Int32(device), vout, tout, vmap, tmap, totals))
+    members, err, solved = last_mesh_simplify_hip()
+    return (verts = vout[:, 1:totals[1]], tris = tout[:, 1:totals[2]] .+ Int32(1), vert_map = vmap .+ Int32(1),
+            tri_map = tmap .+ Int32(1), members = members, error = err, solved = solved, totals = totals)
+end
+
+# the per-vertex tables of the calling thread's last mesh_simplify_hip / mesh_simplify_dev_hip -> (members, error, solved)
+function last_mesh_simplify_hip()
+    n = Ref{Int64}(0)
+    check(ccall((:r2s_last_mesh_simplify, LIB[]), Cint, (Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Int64}),
+                C_NULL, C_NULL, C_NULL, 0, n))
+    members = Vector{Int64}(undef, n[]); err = Vector{Float64}(undef, n[]); solved = Vector{Int32}(undef, n[])
+    check(ccall((:r2s_last_mesh_simplify, LIB[]), Cint, (Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Int64}),
+                members, err, solved, n[], n))
+    return members, err, solved
+end
+
+# the same on device arrays of the current device (raw pointers); the outputs are sized to the input counts, the maps may be
+# C_NULL -> totals; indices stay 0-based on the device; the tables are read with last_mesh_simplify_hip()
+function mesh_simplify_dev_hip(d_verts::Ptr{Cvoid}, n_verts::Integer, d_tris::Ptr{Cvoid}, n_tris::Integer, cell::Real,
+                               d_verts_out::Ptr{Cvoid}, d_tris_out::Ptr{Cvoid}, d_vert_map::Ptr{Cvoid}, d_tri_map::Ptr{Cvoid};
+                               rule::Integer = 1, flags::Integer = 2, stream::Ptr{Cvoid} = C_NULL)
+    totals = zeros(Int64, 8)
+    check(ccall((:r2s_mesh_simplify_dev, LIB[]), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Float64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64},
+                 Ptr{Cvoid}),
+                d_verts, Int64(n_verts), d_tris, Int64(n_tris), Float64(cell), Int32(rule), Int32(flags), d_verts_out, d_tris_out,
+                d_vert_map, d_tri_map, totals, stream))
+    return totals
+end
+
 mutable struct R2SStlMesh              # mirrors r2s_stl_mesh
     n_tris::Int64
     verts::Ptr{Float32}
